@@ -15,9 +15,12 @@ Default workload (N=1): BASELINE.json configs[2] -- Criteo-1TB shaped table (177
 91.1 GB in pinned host DRAM), cache_ratio 0.01, B=16384, F=26, prefetch_num=8, DATASET eviction with an
 id-frequency map, per-table long-tail ids (baselines/data/custom.py generator, s=0.25).
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" for the dominant kernel (HIP-event timed in
-here; bytes are ALGORITHMIC bytes per launch) and "cpu_baseline" (stock torch CPU
-EmbeddingBag+SGD over the same host table, bounded sample, rank 0 / N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps consecutive steps as one
+region (value, ms_per_step) and prints the line; --dump-outputs DIR also writes what the last timed step computed.
+--full adds the rest: extra objects "roofline" for the dominant kernel (HIP-event timed in here; bytes are
+ALGORITHMIC bytes per launch), "cpu_baseline" (stock torch CPU EmbeddingBag+SGD over the same host
+table, bounded sample, rank 0 / N=1 only), "verified" (the end-of-run check), "box", the repeated region, the
+reference window semantics and the cache op's phases.
 """
 from __future__ import annotations
 
@@ -208,7 +211,21 @@ def parse():
                          "lookups) accumulated in fp64 (oracle/closed_form.py; `verified` in the JSON line)")
     ap.add_argument("--cpu_seconds", type=float, default=12.0)
     ap.add_argument("--seed", type=int, default=1024)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the box probe, the K-step block with the cache op's phase "
+                         "timers, the repeated region (reps x K steps, >= --min_time), the reference window semantics, "
+                         "the per-kernel passes and roofline, the end-of-run check and the CPU baseline.  Without it a "
+                         "run sets up, warms up, times exactly --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "a fixed, seeded sample of its forward output and of the embedding rows it looked up, as its "
+                         "SGD update left them")
+    args = ap.parse_args()
+    if not args.full:           # a plain run: the headline only (the flags below gate what --full adds)
+        args.no_verify = args.no_cpu_baseline = args.no_reference_semantics = True
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is implemented for the one-GPU path only")
+    return args
 
 
 def main():
@@ -309,7 +326,8 @@ def main():
     lottery = None
     out_static = None
     want_lottery = args.buffer_lottery and not args.unchanged_trainer and L == 1
-    grad = torch.randn(B, F, D, device=dev) * 1e-3                   # fixed upstream grad (benchmark_cache.py:64-65)
+    # fixed upstream grad (benchmark_cache.py:64-65), drawn from a generator of its own: the same every run
+    grad = torch.randn(B, F, D, device=dev, generator=torch.Generator(device=dev).manual_seed(args.seed)) * 1e-3
     # ... with zero mean over the batch, per feature and element.  The reference draws a fresh randn every iteration;
     # ONE tensor reused for thousands of steps at lr = 1 otherwise pushes the rows of the 3-row tables (a third of every
     # batch each) linearly to |w| ~ 460, where one fp32 ulp is 3e-5 and ANY summation order -- torch's included --
@@ -375,9 +393,28 @@ def main():
         gbuf.copy_(grad)
         grad = gbuf                                                  # (train_step reads the name when it is called)
 
+    # --dump-outputs: the forward outputs the captured steps write on every replay.  GraphedWindow captures, per slot
+    # buffer b, the whole window (steps 0..P-1) and then, for P > 1, every step alone; only the last step of a whole-window
+    # capture and the single-step captures are kept (a kept output of an earlier step would change where the window's
+    # later steps allocate).  run_range records which capture trained the last step.
+    dump = {"capturing": False, "calls": 0, "outs": {}, "last": None}
+
+    def keep_captured(slots_i, i, out):
+        n = dump["calls"]
+        dump["calls"] += 1
+        per_buf = 2 * P if P > 1 else P
+        b, r = divmod(n, per_buf)
+        if r == P - 1:
+            dump["outs"][("whole", b)] = (slots_i.data_ptr(), out)
+        elif r >= P:
+            dump["outs"][("step", b, r - P)] = (slots_i.data_ptr(), out)
+        assert r % P == i, "GraphedWindow captured its steps in another order than --dump-outputs expects"
+
     def train_step(slots_i, i, keys_i=None):
         out = embed(slots_i, offsets, hook_features=F, presorted=keys_i, out=out_static)
         out.backward(grad)
+        if dump["capturing"] and torch.cuda.is_current_stream_capturing():
+            keep_captured(slots_i, i, out.detach())
 
     def ref_step(slots_i):
         # recsys/models/dlrm.py:99-110 + recsys/dlrm_main.py:274-279: shape hook as a callable (a transposed VIEW),
@@ -386,6 +423,7 @@ def main():
         ref_opt.zero_grad()
         out.backward(grad)
         ref_opt.step()
+        return out
 
     gw = None
     if use_graph:
@@ -394,12 +432,18 @@ def main():
         can_switch = args.overlap and plan_ahead in (1, 2) and not args.graph_cache_op
         # the arrangement is the LIBRARY's choice (GraphedWindow(arrangement="auto"), its default): bench.py only says
         # which one it wants to see (--arrangement overlap / interleaved) and reports what the library chose
+        dump["capturing"] = bool(args.dump_outputs)
         gw = GraphedWindow(embed, P, B * F * L, train_step, overlap=args.overlap,
                            warmup_values=[windows[0][i] for i in range(P)], cache_cus=args.cache_cus, presort=presort,
                            transport=None, bag_layout=layout,
                            graph_cache_op=args.graph_cache_op and args.overlap,
                            plan_ahead=plan_ahead, interleaved=args.interleaved,
                            arrangement=args.arrangement if can_switch else None)
+        if dump["capturing"]:
+            dump["capturing"] = False
+            assert dump["calls"] == gw.nbuf * (2 * P if P > 1 else P), "unexpected number of captured steps"
+            assert P == 1 or all(dump["outs"][("whole", b)][0] == dump["outs"][("step", b, P - 1)][0]
+                                 for b in range(gw.nbuf)), "captured steps and slot buffers do not line up"
         trained(0, 0, P)          # GraphedWindow ran the window it was given once, eagerly, before capturing
         note("hipGraph of the window's training steps captured" +
              (" (+ the cache op as a graph of its own)" if gw._plan_graphs is not None else ""))
@@ -422,6 +466,7 @@ def main():
                 gw.run_and_submit(w % 2, [windows[w + 1][j] for j in range(P)])
                 state["submitted"] = w + 1
                 trained(w, 0, P)
+                dump["last"] = (("whole", w % 2), w, P - 1)
                 g += P
             elif use_graph:
                 nb, ahead = gw.nbuf, gw.plan_ahead
@@ -435,8 +480,10 @@ def main():
                 n = min(P - i, g1 - g)
                 if i == 0 and n == P:
                     gw.run(w % nb)
+                    dump["last"] = (("whole", w % nb), w, P - 1)
                 else:
                     gw.run_steps(w % nb, i, i + n)
+                    dump["last"] = (("step", w % nb, i + n - 1) if P > 1 else ("whole", w % nb), w, i + n - 1)
                 trained(w, i, i + n)
                 g += n
             else:
@@ -449,11 +496,13 @@ def main():
                     else:
                         state["slots"] = win.prepare([windows[w][j] for j in range(P)])
                 if ref_opt is not None:
-                    ref_step(state["slots"][i])
+                    out = ref_step(state["slots"][i])
                 else:
                     out = embed(state["slots"][i], offsets, hook_features=F,
                                 presorted=win.keys[i] if win.keys else None, out=out_static)
                     out.backward(grad)
+                if args.dump_outputs:
+                    dump["last"] = (out.detach(), w, i)
                 trained(w, i, i + 1)
                 g += 1
 
@@ -510,9 +559,11 @@ def main():
         return {"read_GBps": rd.value, "fill_GBps": fl.value}
 
     barrier()
-    box = {"what": "ce_box_probe: 20 streaming reads, then 20 fills, of a buffer the size of the forward's output "
-                   "(>= 64 MB), hipEvent-bracketed; `before` the warm-up, `after` the timed region",
-           "before": box_probe()}
+    box = None
+    if args.full:
+        box = {"what": "ce_box_probe: 20 streaming reads, then 20 fills, of a buffer the size of the forward's output "
+                       "(>= 64 MB), hipEvent-bracketed; `before` the warm-up, `after` the repeated region",
+               "before": box_probe()}
     # The launch thread is the clock of a `prefetch_num` 1 pipeline (~10 launches per 0.27 ms step), and the run keeps
     # tens of thousands of tensors alive (every window's ids, for the end-of-run check): a generation-2 pass of
     # Python's cycle collector over them is milliseconds in which the GPU runs dry.  No cycles are created in the
@@ -560,18 +611,92 @@ def main():
         arrangement["trial_windows"] = g_trial // P
         note(f"arrangement trial (library): {arrangement['trial_ms_per_window']} -> {gw.arrangement}")
         W = g
-    # ---- timed region.  K steps at the default sizes are 4-50 ms: a region that short measures pipeline fill and
-    # drain (one cache op of ~1 ms cannot overlap with anything when both ends are synchronised), not the pipeline.
-    # So: (1) one K-step block bracketed by barrier + synchronize on its own -- reported as block_ms.single, and used
-    # to size (2) the MEASUREMENT: `reps` x K consecutive steps (reps >= 3, region >= --min_time seconds) bracketed
-    # by barrier + synchronize ONCE; value = reps * K * lookups-per-step / that time.  Every cache op, presort and
-    # training step enqueued for those steps is inside the region.
-    # The phase timers of the cache op (8 hipEvent records per call + their read-back) run in block (1) ONLY: at
-    # prefetch_num 1 they cost the launch thread ~25 us of a 160 us step (Avazu B = 2048: 165 -> 19x M with them off),
-    # so the measurement (2) runs without them and cache_op_ms_by_phase comes from block (1).
+    # ---- the headline: exactly K = --steps consecutive steps bracketed by barrier + synchronize ONCE; value = K *
+    # lookups-per-step / that time, ms_per_step = that time / K.  Every cache op, presort and training step enqueued for
+    # those steps is inside the region, and so are the pipeline's fill and drain (one cache op of ~1 ms at each end that
+    # cannot overlap with anything): a K of a few windows reads slow for that reason, a K of thousands of steps does not.
+    # The cache op's phase timers are off here (at prefetch_num 1 they cost the launch thread ~25 us of a 160 us step).
+    g = W
+    need_windows(g + K, g)
+    barrier()
+    mgr.sync_stats()
+    t1 = time.perf_counter()
+    c1 = time.thread_time()
+    run_range(g, g + K)
+    enqueue_s = time.perf_counter() - t1
+    enqueue_cpu_s = time.thread_time() - c1      # CPU seconds of the launch thread: < enqueue_s means it waited
+    barrier()
+    elapsed = time.perf_counter() - t1           # seconds for the K steps
+    g += K
+    if not args.keep_gc and not args.full:
+        gc.enable()
+    note(f"timed region done: {K} steps in {elapsed:.4f}s = {1e3 * elapsed / K:.4f} ms/step; host enqueue "
+         f"{enqueue_s:.3f}s wall / {enqueue_cpu_s:.3f}s CPU")
+    st = mgr.sync_stats()
+    if st.status != 0:
+        raise AssertionError(f"cache op failed with status {st.status}: unique rows of a window exceed cuda_row_num={C}")
+    dumped = None
+    if args.dump_outputs:
+        last, w_last, i_last = dump["last"]
+        out_last = dump["outs"][last][1] if isinstance(last, tuple) else last
+        dumped = dump_outputs(args.dump_outputs, out_last, windows[w_last][i_last], mgr, B, F, L, D, args.seed)
+        note(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(dumped)}")
+
+    lookups = K * B * F * L
+    value = lookups / elapsed
+    hits, miss = sum(mgr.num_hits_history), sum(mgr.num_miss_history)
+    tot = mgr.totals()
+    result = {
+        "metric": "embedding lookups/sec (cache op + EmbeddingBag fwd + bwd/SGD), Criteo-1TB table @1% cache",
+        "value": value, "unit": "lookups/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
+        "warmup_steps_run": W,
+        "timing": "`steps` consecutive steps timed as ONE region bracketed by barrier + synchronize (pipeline fill and "
+                  "drain included); ms_per_step = region / steps",
+        "ms_per_step": 1e3 * elapsed / K, "it_per_s": K / elapsed,
+        "it_per_s_scope": "embedding operator only (cache op + EmbeddingBag forward + backward/SGD), no dense part: "
+                          "the whole-model it/s of examples/dlrm_main.py at this configuration is in profiles/ "
+                          "(r05_dlrm_main_criteo1tb_*.json)",
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload} table_scale={args.table_scale}", "num_embeddings": N,
+                   "embedding_dim": D, "features": F, "batch_size": B, "pooling": L, "cache_ratio": args.cache_ratio,
+                   "cuda_row_num": C, "prefetch_num": P, "evict": "LFU" if args.use_lfu else "DATASET",
+                   "id_dist": f"{args.dist}(s={args.skew})" + (f" + {args.uniform_frac:g} uniform" if args.uniform_frac else ""),
+                   "host_table_GB": N * D * 4 / 1e9,
+                   "transport": transport, "overlap": arrangement["mode"] == "overlap",
+                   "interleaved": arrangement["mode"] == "interleaved", "arrangement": arrangement,
+                   "plan_ahead_windows": (gw.plan_ahead if gw is not None else 1) if args.overlap else 0,
+                   "launch": "hipGraph per window" if use_graph else "python per step",
+                   "gc": "on" if args.keep_gc else "off during warm-up and timed region",
+                   **({"static_buffers": lottery} if lottery else {}),
+                   "bwd_duplicate_fold": "slots grouped by row per 16384-lookup segment, once per window "
+                                         "(ce_bag_presort_window%s)" % ("" if args.tile_keys else "_src: keys = row | grad_out row, streaming backward") if presort else "1024-lookup tiles sorted inside every backward",
+                   "update": ("torch.optim.SGD on the sparse COO gradient" if args.unchanged_trainer else
+                              "sorted" if args.deterministic else "atomic"), "lr": args.lr,
+                   "surface": ("unchanged trainer: recsys/dlrm_main.py:259-279 call sequence, none of this build's "
+                               "additions" if args.unchanged_trainer else "this build's additions (see launch / "
+                               "bwd_duplicate_fold / transport)")},
+        "cache": {"unique_hit_rate": hits / max(1, hits + miss), "lookup_miss_rate": tot["cache_miss"] / max(1, tot["total_cache"]),
+                  "rows_in": tot["cpu_to_cuda_numel"] // D, "rows_out": tot["cuda_to_cpu_numel"] // D,
+                  "prefill_cache_ops": prefill, "setup_s": setup_s},
+    }
+    if dumped is not None:
+        result["outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                             "what": "the last timed step: a seeded sample of its forward output and of the rows it "
+                                     "looked up after its SGD update (float32)"}
+    if not args.full:
+        if rank == 0:
+            emit(result)
+        return
+
+    # ---- --full: (1) one K-step block bracketed by barrier + synchronize on its own with the cache op's phase timers
+    # on -- reported as block_ms.single, and used to size (2) the repeated region: `reps` x K consecutive steps (reps >=
+    # 3, region >= --min_time seconds) bracketed by barrier + synchronize ONCE, where fill and drain are amortised --
+    # reported as `repeated_region`.  The phase timers (8 hipEvent records per call + their read-back) run in block (1)
+    # ONLY: at prefetch_num 1 they cost the launch thread ~25 us of a 160 us step (Avazu B = 2048: 165 -> 19x M with
+    # them off), so the region (2) runs without them and cache_op_ms_by_phase comes from block (1).
     mgr.set_profiling(True)
     mgr.phase_times(reset=True)
-    g = W
     need_windows(g + K, g)
     barrier()
     mgr.sync_stats()
@@ -594,16 +719,15 @@ def main():
     c1 = time.thread_time()
     run_range(g, g + reps * K)
     enqueue_s = time.perf_counter() - t1
-    enqueue_cpu_s = time.thread_time() - c1      # CPU seconds of the launch thread: < enqueue_s means it waited
+    enqueue_cpu_s = time.thread_time() - c1
     barrier()
     region = time.perf_counter() - t1
     if not args.keep_gc:
         gc.enable()
     g += reps * K
-    elapsed = region / reps                      # seconds per K steps
-    blocks = [single]
-    note(f"timed region done: {reps} x {K} steps in {region:.3f}s = {1e3 * elapsed / K:.4f} ms/step (one K-step block "
-         f"bracketed on its own: {1e3 * single:.3f} ms = {1e3 * single / K:.4f} ms/step); host enqueue {enqueue_s:.3f}s wall / {enqueue_cpu_s:.3f}s CPU")
+    elapsed_rep = region / reps                  # seconds per K steps in the repeated region
+    note(f"repeated region done: {reps} x {K} steps in {region:.3f}s = {1e3 * elapsed_rep / K:.4f} ms/step (one K-step "
+         f"block bracketed on its own: {1e3 * single:.3f} ms = {1e3 * single / K:.4f} ms/step); host enqueue {enqueue_s:.3f}s wall / {enqueue_cpu_s:.3f}s CPU")
     st = mgr.sync_stats()
     if st.status != 0:
         raise AssertionError(f"cache op failed with status {st.status}: unique rows of a window exceed cuda_row_num={C}")
@@ -631,8 +755,6 @@ def main():
         for k_ in tot_blk1:
             tot_blk1[k_] += tot_p1[k_] - tot_p0[k_]
 
-    lookups = K * B * F * L
-    value = lookups / elapsed
     hits, miss = sum(mgr.num_hits_history), sum(mgr.num_miss_history)
     tot = mgr.totals()
 
@@ -909,48 +1031,26 @@ def main():
     dominant, other = ranked[0], ranked[1:] + ([swap_roof] if transport == "worker" else [])
     cache_phases = {k: v / max(1, phases.get("calls", 0)) for k, v in phases.items() if k != "calls"}
 
-    result = {
-        "metric": "embedding lookups/sec (cache op + EmbeddingBag fwd + bwd/SGD), Criteo-1TB table @1% cache",
-        "value": value, "unit": "lookups/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-        "warmup_steps_run": W, "reps": reps,
-        "timing": "`reps` x `steps` consecutive steps timed as ONE region bracketed by barrier + synchronize (a "
-                  "region of `steps` steps alone is a few ms and measures pipeline fill/drain); ms_per_step = region / "
-                  "(reps * steps); block_ms.single = one `steps`-step block bracketed on its own",
-        "block_ms": {"single": 1e3 * single, "region": 1e3 * region},
-        "ms_per_step": 1e3 * elapsed / K, "it_per_s": K / elapsed,
-        "it_per_s_scope": "embedding operator only (cache op + EmbeddingBag forward + backward/SGD), no dense part: "
-                          "the whole-model it/s of examples/dlrm_main.py at this configuration is in profiles/ "
-                          "(r05_dlrm_main_criteo1tb_*.json)",
-        "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "box": box,
-        "config": {"workload": f"{args.workload} table_scale={args.table_scale}", "num_embeddings": N,
-                   "embedding_dim": D, "features": F, "batch_size": B, "pooling": L, "cache_ratio": args.cache_ratio,
-                   "cuda_row_num": C, "prefetch_num": P, "evict": "LFU" if args.use_lfu else "DATASET",
-                   "id_dist": f"{args.dist}(s={args.skew})" + (f" + {args.uniform_frac:g} uniform" if args.uniform_frac else ""),
-                   "distinct_rows_per_batch_frac": uniq_avg / (B * F * L), "host_table_GB": N * D * 4 / 1e9,
-                   "transport": transport, "overlap": arrangement["mode"] == "overlap",
-                   "interleaved": arrangement["mode"] == "interleaved", "arrangement": arrangement,
-                   "plan_ahead_windows": (gw.plan_ahead if gw is not None else 1) if args.overlap else 0,
-                   "launch": "hipGraph per window" if use_graph else "python per step",
-                   "gc": "on" if args.keep_gc else "off during warm-up and timed region",
-                   **({"static_buffers": lottery} if lottery else {}),
-                   "bwd_duplicate_fold": "slots grouped by row per 16384-lookup segment, once per window "
-                                         "(ce_bag_presort_window%s)" % ("" if args.tile_keys else "_src: keys = row | grad_out row, streaming backward") if presort else "1024-lookup tiles sorted inside every backward",
-                   "update": ("torch.optim.SGD on the sparse COO gradient" if args.unchanged_trainer else
-                              "sorted" if args.deterministic else "atomic"), "lr": args.lr,
-                   "surface": ("unchanged trainer: recsys/dlrm_main.py:259-279 call sequence, none of this build's "
-                               "additions" if args.unchanged_trainer else "this build's additions (see launch / "
-                               "bwd_duplicate_fold / transport)")},
-        "cache": {"unique_hit_rate": hits / max(1, hits + miss), "lookup_miss_rate": tot["cache_miss"] / max(1, tot["total_cache"]),
-                  "rows_in": tot["cpu_to_cuda_numel"] // D, "rows_out": tot["cuda_to_cpu_numel"] // D,
-                  "prefill_cache_ops": prefill, "setup_s": setup_s,
-                  "cache_op_ms_by_phase": cache_phases, "cache_ops_timed": phases.get("calls", 0),
-                  "cache_op_phases_measured_in": "the K-step block bracketed on its own (block_ms.single): the timed "
-                                                 "region runs without the phase timers"},
+    result["timing"] += ("; block_ms.single = one `steps`-step block bracketed on its own with the cache op's phase "
+                         "timers on; repeated_region = `reps` x `steps` consecutive steps timed as ONE region (fill and "
+                         "drain amortised)")
+    result.update({
+        "reps": reps,
+        "block_ms": {"headline": 1e3 * elapsed, "single": 1e3 * single, "region": 1e3 * region},
+        "repeated_region": {"reps": reps, "steps": reps * K, "ms_per_step": 1e3 * elapsed_rep / K,
+                            "lookups_per_s": lookups / elapsed_rep},
+        "box": box,
         "roofline": {k: dominant[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")} |
                     {k: dominant[k] for k in dominant if k not in ("bound", "achieved", "peak", "unit", "frac", "traffic")},
         "roofline_other": other,
-    }
+    })
+    result["config"]["distinct_rows_per_batch_frac"] = uniq_avg / (B * F * L)
+    result["cache"].update({
+        "unique_hit_rate": hits / max(1, hits + miss), "lookup_miss_rate": tot["cache_miss"] / max(1, tot["total_cache"]),
+        "rows_in": tot["cpu_to_cuda_numel"] // D, "rows_out": tot["cuda_to_cpu_numel"] // D,
+        "cache_op_ms_by_phase": cache_phases, "cache_ops_timed": phases.get("calls", 0),
+        "cache_op_phases_measured_in": "the K-step block bracketed on its own (block_ms.single): the timed "
+                                       "regions run without the phase timers"})
     if ref_semantics is not None:
         result["reference_window_semantics"] = ref_semantics
     # what a window is made of (VERDICT r4 #2c): its length in the timed region, the back-to-back durations of its 2 P
@@ -959,7 +1059,7 @@ def main():
     # stream's release, k_unpack_admitted / k_admit_maps behind it.  The launch thread is not what the GPU waits for:
     # host_enqueue_cpu_s is its CPU time for the whole region.
     chain_ms = sum(v for k_, v in cache_phases.items() if k_ != "admit_swap")
-    win_ms = 1e3 * elapsed / K * P
+    win_ms = 1e3 * elapsed_rep / K * P
     result["window"] = {"ms": win_ms, "bag_kernels_ms": P * (fwd_avg + bwd_avg), "cache_op_chain_ms": chain_ms,
                         "window_gap_ms": win_ms - P * (fwd_avg + bwd_avg) - chain_ms,
                         "arrangement": arrangement["mode"], "host_enqueue_wall_s": enqueue_s,
@@ -1070,6 +1170,43 @@ def quiet_stdout():
         sys.stdout.flush()
         _REAL_STDOUT = os.dup(1)
         os.dup2(2, 1)
+
+
+DUMP_BYTES = 48 << 20          # what --dump-outputs writes at most (both files together)
+
+
+def dump_outputs(out_dir, out, ids, mgr, B, F, L, D, seed):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files in out_dir --
+        forward_output.npy  [S, F, D]     rows `bags` of its forward output ([B, F, D], the hook-folded layout)
+        updated_rows.npy    [S, F, L, D]  the embedding rows those bags looked up, as the step's SGD update left them
+    for a fixed sample of S batch rows drawn from `seed` (every batch row when they fit DUMP_BYTES).  The rows are
+    read where the step updated them: the cache slot the manager's maps give for the id (checked both ways)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    per_row = F * D * 4 * (1 + L)
+    S = min(B, max(1, DUMP_BYTES // per_row))
+    bags = np.sort(np.random.default_rng(seed).choice(B, size=S, replace=False)) if S < B else np.arange(B)
+    dev = out.device
+    bags_t = torch.from_numpy(bags).to(dev)
+    fwd = out.detach().reshape(B, F, D)[bags_t].float().cpu().numpy()
+    # lookup j of bag (f, b) is ids[(f * B + b) * L + j]
+    pos = ((torch.arange(F, device=dev)[None, :, None] * B + bags_t[:, None, None]) * L
+           + torch.arange(L, device=dev)[None, None, :]).reshape(-1)
+    ids_s = ids.reshape(-1)[pos].long()
+    rows = ids_s if mgr._idx_map is None else mgr._idx_map[ids_s].long()
+    slots = mgr.inverted_cached_idx[rows].long()
+    slots_h = slots.cpu()
+    C = mgr.cuda_row_num
+    if not bool(((slots_h >= 0) & (slots_h < C)).all()):
+        raise AssertionError("--dump-outputs: a row of the last timed step is not resident in the cache")
+    if not torch.equal(mgr.cached_idx_map[slots].long(), rows):
+        raise AssertionError("--dump-outputs: the cache maps disagree about a row of the last timed step")
+    upd = mgr.cuda_cached_weight.detach()[slots].view(S, F, L, D).float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"forward_output": fwd, "updated_rows": upd}
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    return {name + ".npy": list(arr.shape) for name, arr in files.items()}
 
 
 def ids_budget_reps(steps_per_rep: int, ids_per_step: int) -> int:
@@ -1199,7 +1336,7 @@ def run_sharded(args, sizes, rank, world, dev):
 
     need_windows(W + K)
     offsets = gen.offsets
-    grad = torch.randn(B, F, D, device=dev) * 1e-3
+    grad = torch.randn(B, F, D, device=dev, generator=torch.Generator(device=dev).manual_seed(args.seed + 1000 * rank)) * 1e-3
     grad -= grad.mean(dim=0, keepdim=True)          # zero mean over the batch: see the unsharded path
 
     from cachedembedding_amd.parallel import GraphedShardedWindow, ShardedWindowPipeline
@@ -1235,9 +1372,9 @@ def run_sharded(args, sizes, rank, world, dev):
 
     run_steps(0, W)
     barrier()
-    # same timing as the one-GPU path: one K-step block bracketed on its own sizes the measurement, `reps` x K
-    # consecutive steps bracketed by barrier + synchronize once (max over ranks).  K is rounded to whole windows here:
-    # a window's plan is built as a unit.
+    # the headline: one block of K steps bracketed by barrier + synchronize (max over ranks).  K is rounded to whole
+    # windows here: a window's plan is built as a unit.  --full: that block also sizes the repeated region, `reps` x K
+    # consecutive steps bracketed once.
     Kw = max(P, (K // P) * P) if K >= P else K
     t1 = time.perf_counter()
     run_steps(W, Kw)
@@ -1245,6 +1382,14 @@ def run_sharded(args, sizes, rank, world, dev):
     single = torch.tensor([time.perf_counter() - t1], dtype=torch.float64, device=dev)
     allreduce(single, op=dist.ReduceOp.MAX)
     single = float(single.item())
+    if not args.full:
+        st = mgr.sync_stats()
+        bad = torch.tensor([int(st.status != 0)], device=dev)
+        allreduce(bad)
+        if int(bad.item()):
+            raise AssertionError("a shard's cache op overflowed cuda_row_num")
+        emit_sharded_headline(args, mgr, world, rank, single, Kw, W, N, D, F, B, L, P, P_req, prefill, setup_s)
+        return
     reps = int(min(args.max_reps, max(3, -(-args.min_time // max(single, 1e-6)))))
     reps = min(reps, ids_budget_reps(Kw, B * F * L))
     g0 = W + Kw
@@ -1268,7 +1413,7 @@ def run_sharded(args, sizes, rank, world, dev):
     elapsed = torch.tensor([time.perf_counter() - t1], dtype=torch.float64, device=dev)
     allreduce(elapsed, op=dist.ReduceOp.MAX)
     region = float(elapsed.item())
-    elapsed = region / (reps * Kw) * K            # seconds per K steps
+    elapsed = single / Kw * K                     # seconds per K steps in the headline block
     st = mgr.sync_stats()
     bad = torch.tensor([int(st.status != 0)], device=dev)
     allreduce(bad)
@@ -1280,10 +1425,12 @@ def run_sharded(args, sizes, rank, world, dev):
     result = {
         "metric": "embedding lookups/sec (cache op + EmbeddingBag fwd + bwd/SGD), Criteo-1TB table @1% cache",
         "value": lookups / elapsed, "unit": "lookups/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-        "warmup_steps_run": W, "reps": reps, "steps_per_rep": Kw,
-        "timing": "`reps` x `steps_per_rep` consecutive steps timed as ONE region bracketed by barrier + synchronize, "
-                  "max over ranks; block_ms.single = one block bracketed on its own",
+        "warmup_steps_run": W, "steps_timed": Kw, "reps": reps, "steps_per_rep": Kw,
+        "timing": "`steps_timed` consecutive steps timed as ONE block bracketed by barrier + synchronize, max over "
+                  "ranks; repeated_region = `reps` x `steps_per_rep` consecutive steps timed as one region",
         "block_ms": {"single": 1e3 * single, "region": 1e3 * region},
+        "repeated_region": {"reps": reps, "steps": reps * Kw, "ms_per_step": 1e3 * region / (reps * Kw),
+                            "lookups_per_s": B * F * L * world * reps * Kw / region},
         "ms_per_step": 1e3 * elapsed / K, "it_per_s": K / elapsed, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"{args.workload} table_scale={args.table_scale}", "num_embeddings": N,
@@ -1296,6 +1443,32 @@ def run_sharded(args, sizes, rank, world, dev):
         "cache": {"rank0_unique_hit_rate": hits / max(1, hits + miss), "rank0_rows_in": tot["cpu_to_cuda_numel"] // D,
                   "rank0_rows_out": tot["cuda_to_cpu_numel"] // D, "prefill_cache_ops": prefill, "setup_s": setup_s},
         "roofline": None, "cpu_baseline": None,
+    }
+    dist.destroy_process_group()
+    if rank == 0:
+        emit(result)
+
+
+def emit_sharded_headline(args, mgr, world, rank, secs, steps, W, N, D, F, B, L, P, P_req, prefill, setup_s, config=None):
+    """the line of a plain sharded run: `steps` consecutive steps in `secs` seconds (max over ranks), nothing else"""
+    hits, miss = sum(mgr.num_hits_history), sum(mgr.num_miss_history)
+    tot = mgr.totals()
+    result = {
+        "metric": "embedding lookups/sec (cache op + EmbeddingBag fwd + bwd/SGD), Criteo-1TB table @1% cache",
+        "value": B * F * L * world * steps / secs, "unit": "lookups/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "warmup_steps_run": W, "steps_timed": steps,
+        "timing": "`steps_timed` consecutive steps (--steps in whole windows) timed as ONE block bracketed by barrier + "
+                  "synchronize, max over ranks",
+        "ms_per_step": 1e3 * secs / steps, "it_per_s": steps / secs, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload} table_scale={args.table_scale}", "num_embeddings": N,
+                   "embedding_dim": D, "features": F, "batch_size_per_gpu": B, "global_batch": B * world,
+                   "pooling": L, "cache_ratio": args.cache_ratio, "cuda_row_num_per_gpu": mgr.cuda_row_num,
+                   "prefetch_num": P, "prefetch_num_requested": P_req, "evict": "LFU" if args.use_lfu else "DATASET",
+                   "id_dist": f"{args.dist}(s={args.skew})", "host_table_GB_per_gpu": mgr.num_embeddings * D * 4 / 1e9,
+                   "sharding": f"row-wise x{world} (row % W)", "update": "atomic", "lr": args.lr, **(config or {})},
+        "cache": {"rank0_unique_hit_rate": hits / max(1, hits + miss), "rank0_rows_in": tot["cpu_to_cuda_numel"] // D,
+                  "rank0_rows_out": tot["cuda_to_cpu_numel"] // D, "prefill_cache_ops": prefill, "setup_s": setup_s},
     }
     dist.destroy_process_group()
     if rank == 0:
@@ -1380,9 +1553,31 @@ def run_sharded_graphed(args, embed, gen, windows, need_windows, offsets, grad, 
         if gw.trial.decided is not None and gw.trial.decided != gw.arrangement:
             gw.set_arrangement(gw.trial.decided)
     Kw = max(1, K // P)                      # whole windows per block
+    # the headline: Kw windows bracketed by barrier + synchronize once (max over ranks), the phase timers off
     need_windows((Ww + Kw) * P, Ww * P)
-    mgr.set_profiling(True)                  # phase timers in the separately bracketed block only (their events cost
-                                             # the launch thread ~25 us per cache op: too much at a small prefetch_num)
+    barrier()
+    t1 = time.perf_counter()
+    run_windows(Ww, Ww + Kw)
+    barrier()
+    head = torch.tensor([time.perf_counter() - t1], dtype=torch.float64, device=dev)
+    allreduce(head, op=dist.ReduceOp.MAX)
+    head = float(head.item())
+    st = mgr.sync_stats()
+    bad = torch.tensor([int(st.status != 0)], device=dev)
+    allreduce(bad)
+    if int(bad.item()):
+        raise AssertionError("a shard's cache op overflowed cuda_row_num")
+    Ww += Kw
+    if not args.full:
+        emit_sharded_headline(args, mgr, world, rank, head, Kw * P, (Ww - Kw) * P, N, D, F, B, L, P, P_req, prefill, setup_s,
+                              {"transport": mgr.transport_name, "overlap": bool(args.overlap),
+                               "launch": "hipGraph per window" if gw._graphs is not None else
+                                         "fixed-capacity steps launched one by one"})
+        return
+    # --full: one block with the phase timers on (their events cost the launch thread ~25 us per cache op: too much at
+    # a small prefetch_num), which sizes the repeated region: `reps` x Kw windows bracketed once
+    need_windows((Ww + Kw) * P, Ww * P)
+    mgr.set_profiling(True)
     mgr.phase_times(reset=True)
     t1 = time.perf_counter()
     run_windows(Ww, Ww + Kw)
@@ -1405,7 +1600,8 @@ def run_sharded_graphed(args, embed, gen, windows, need_windows, offsets, grad, 
     allreduce(elapsed, op=dist.ReduceOp.MAX)
     region = float(elapsed.item())
     steps_timed = reps * Kw * P
-    ms_step = 1e3 * region / steps_timed
+    ms_rep = 1e3 * region / steps_timed
+    ms_step = 1e3 * head / (Kw * P)
     st = mgr.sync_stats()
     bad = torch.tensor([int(st.status != 0)], device=dev)
     allreduce(bad)
@@ -1417,10 +1613,14 @@ def run_sharded_graphed(args, embed, gen, windows, need_windows, offsets, grad, 
     result = {
         "metric": "embedding lookups/sec (cache op + EmbeddingBag fwd + bwd/SGD), Criteo-1TB table @1% cache",
         "value": B * F * L * world / (ms_step * 1e-3), "unit": "lookups/s", "n_gpus": world, "steps": K,
-        "warmup": args.warmup, "warmup_steps_run": Ww * P, "reps": reps, "steps_per_rep": Kw * P,
-        "timing": "`reps` x `steps_per_rep` consecutive steps timed as ONE region bracketed by barrier + synchronize, "
-                  "max over ranks; block_ms.single = one block bracketed on its own",
-        "block_ms": {"single": 1e3 * single, "region": 1e3 * region},
+        "warmup": args.warmup, "warmup_steps_run": (Ww - Kw) * P, "steps_timed": Kw * P, "reps": reps,
+        "steps_per_rep": Kw * P,
+        "timing": "`steps_timed` consecutive steps timed as ONE block bracketed by barrier + synchronize, max over "
+                  "ranks; block_ms.single = one such block with the phase timers on; repeated_region = `reps` x "
+                  "`steps_per_rep` consecutive steps timed as one region",
+        "block_ms": {"headline": 1e3 * head, "single": 1e3 * single, "region": 1e3 * region},
+        "repeated_region": {"reps": reps, "steps": steps_timed, "ms_per_step": ms_rep,
+                            "lookups_per_s": B * F * L * world / (ms_rep * 1e-3)},
         "ms_per_step": ms_step, "it_per_s": 1e3 / ms_step, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"{args.workload} table_scale={args.table_scale}", "num_embeddings": N,

@@ -8,16 +8,16 @@ mkdir -p $O
 NG=$(python -c "import torch; print(torch.cuda.device_count())")
 export GPU_MAX_HW_QUEUES=8
 timeout 900 python -m pytest tests/test_gpu_parallel.py -m gpu -x -q -k rccl 2>&1 | tail -3 > $O/pytest_rccl.txt
-python bench.py --gpus 1 --no_cpu_baseline 2>/dev/null | tail -1 > $O/bench_n1.json
+python bench.py --full --gpus 1 --no_cpu_baseline 2>/dev/null | tail -1 > $O/bench_n1.json
 for n in 2 4 8; do
   [ $n -le $NG ] || continue
   python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2951$n \
-    bench.py --gpus $n --steps 128 --warmup 32 2> $O/bench_n$n.err | tail -1 > $O/bench_n$n.json
+    bench.py --full --gpus $n --steps 128 --warmup 32 2> $O/bench_n$n.err | tail -1 > $O/bench_n$n.json
 done
 cd /tmp; export TMPDIR=/tmp
 N=$([ $NG -ge 8 ] && echo 8 || echo $NG)
 rocprofv3 --kernel-trace --stats -d $O/prof_n$N -o r02 -- python -m torch.distributed.run --nnodes=1 \
-  --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29520 $R/bench.py --gpus $N --steps 64 --warmup 16 \
+  --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29520 $R/bench.py --full --gpus $N --steps 64 --warmup 16 \
   > $O/prof_n$N.log 2>&1
 cd $R
 for db in $O/prof_n$N/*_results.db; do python profiles/rocpd_summary.py $db 30 > $O/stats_$(basename $db .db).txt; done

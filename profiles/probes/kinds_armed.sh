@@ -5,7 +5,7 @@ BUDGET=${1:-100}
 O=gpurun_out/final6; mkdir -p $O
 T0=$(date +%s)
 while [ $(( $(date +%s) - T0 )) -lt $BUDGET ]; do
-  timeout 17 python bench.py --arrangement overlap --steps 20 --warmup 5 --no_cpu_baseline 2>&1 >/dev/null | grep -E "timed region done|warmup done" | cut -c1-220 >> $O/armed.txt
+  timeout 17 python bench.py --full --arrangement overlap --steps 20 --warmup 5 --no_cpu_baseline 2>&1 >/dev/null | grep -E "timed region done|warmup done" | cut -c1-220 >> $O/armed.txt
   echo "--" >> $O/armed.txt
 done
 cat $O/armed.txt

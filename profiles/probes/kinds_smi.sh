@@ -11,7 +11,7 @@ i=0
 while [ $(( $(date +%s) - T0 )) -lt $BUDGET ]; do
   i=$((i+1))
   s=$(date +%s.%N)
-  python bench.py --arrangement overlap --steps 20 --warmup 5 --no_verify --no_cpu_baseline 2>$O/err.txt | tail -1 > $O/run_$i.json
+  python bench.py --full --arrangement overlap --steps 20 --warmup 5 --no_verify --no_cpu_baseline 2>$O/err.txt | tail -1 > $O/run_$i.json
   e=$(date +%s.%N)
   echo "$i $s $e" >> $O/runs.txt
 done

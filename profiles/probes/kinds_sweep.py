@@ -15,7 +15,7 @@ import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[2]
-BENCH = ["--arrangement", "overlap", "--steps", "20", "--warmup", "5", "--no_verify", "--no_cpu_baseline"]
+BENCH = ["--full", "--arrangement", "overlap", "--steps", "20", "--warmup", "5", "--no_verify", "--no_cpu_baseline"]
 
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     prio = sys.argv[2]

@@ -1,7 +1,7 @@
 #!/bin/bash
 cd /root/repo
 one() {
-env $2 python bench.py --no_cpu_baseline --no_verify 2>/dev/null | tail -1 | python -c "
+env $2 python bench.py --full --no_cpu_baseline --no_verify 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['roofline_other'][1]; r=d['roofline']; o=d['roofline_other'][0]
 print('$1', round(d['value']/1e9,3), 'box', int(d['box']['before']['read_GBps']), int(d['box']['after']['fill_GBps']), 'bwd', round(r['avg_ms_in_pipeline']*1e3,1), 'fwd', round(o['avg_ms_in_pipeline']*1e3,1),'out_busy', round(s.get('worker_out_busy_ms',0),3), 'in_busy', round(s.get('worker_in_busy_ms',0),3), {k:round(v,2) for k,v in d['cache']['cache_op_ms_by_phase'].items()})"

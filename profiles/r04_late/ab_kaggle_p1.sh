@@ -1,7 +1,7 @@
 #!/bin/bash
 cd /root/repo
 one() {
-env $2 python bench.py --no_cpu_baseline --no_verify --workload criteo_kaggle --cache_ratio 0.05 --prefetch_num 1 2>/dev/null | tail -1 | python -c "
+env $2 python bench.py --full --no_cpu_baseline --no_verify --workload criteo_kaggle --cache_ratio 0.05 --prefetch_num 1 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['roofline_other'][1]
 print('$1', round(d['value']/1e9,3), 'out_busy', round(s.get('worker_out_busy_ms',0),3), 'in_busy', round(s.get('worker_in_busy_ms',0),3), 'in_wait', round(s.get('worker_in_wait_ms',0),3), {k:round(v,3) for k,v in d['cache']['cache_op_ms_by_phase'].items()})"

@@ -10,7 +10,7 @@ R=$PWD
 O=$R/gpurun_out/sweep
 mkdir -p $O/pmc
 run() {   # tag workload dist skew uniform_frac prefetch_num
-  python bench.py --workload $2 --dist $3 --skew $4 --uniform_frac $5 --prefetch_num $6 --no_verify --no_cpu_baseline \
+  python bench.py --full --workload $2 --dist $3 --skew $4 --uniform_frac $5 --prefetch_num $6 --no_verify --no_cpu_baseline \
       --steps 64 --warmup 8 > $O/$1.json 2> $O/$1.err || tail -3 $O/$1.err
   [ -n "$NO_PMC" ] || ( cd /tmp; export TMPDIR=/tmp
     for c in FETCH_SIZE WRITE_SIZE; do

@@ -597,7 +597,7 @@ def test_bench_multi_rank_path_with_ranks_sharing_the_gpu(ranks, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(ranks), "--share_gpu",
            "--table_scale", "0.02", "--batch_size", "4096", "--steps", "16", "--warmup", "8", "--no_cpu_baseline",
-           "--min_time", "0.05"] + extra
+           "--min_time", "0.05", "--full"] + extra
     r = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -620,7 +620,7 @@ def test_bench_one_gpu_line_carries_roofline_box_and_a_passing_verification(extr
     import subprocess
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     cmd = [sys.executable, str(ROOT / "bench.py"), "--table_scale", "0.1", "--cache_ratio", "0.03", "--prefetch_num", "4",
-           "--steps", "20", "--warmup", "5", "--no_cpu_baseline", "--min_time", "0.05"] + extra
+           "--steps", "20", "--warmup", "5", "--no_cpu_baseline", "--min_time", "0.05", "--full"] + extra
     r = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -635,6 +635,40 @@ def test_bench_one_gpu_line_carries_roofline_box_and_a_passing_verification(extr
         assert out["config"]["id_windows"].startswith(("given back", "resident"))
         assert out["roofline"]["bound"] == "hbm" and 0 < out["roofline"]["frac"] < 1.2
         assert out["box"]["before"]["read_GBps"] > 1000 and out["it_per_s_scope"].startswith("embedding operator only")
+
+
+def test_bench_plain_line_times_exactly_the_steps_and_dumps_the_last_step(tmp_path):
+    """a plain run (no --full) on a scaled-down table: ONE JSON line with the headline alone -- `steps` timed steps,
+    ms_per_step consistent with value -- and --dump-outputs writes the last timed step's forward output and updated
+    rows as float32 files; the same command twice gives the same forward output (same inputs, same rows)"""
+    import json
+    import subprocess
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--table_scale", "0.1", "--cache_ratio", "0.03",
+               "--prefetch_num", "4", "--steps", "10", "--warmup", "5", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=str(ROOT), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 10 and out["unit"] == "lookups/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "f32" and out["ms_per_step"] > 0
+        lookups = out["config"]["batch_size"] * out["config"]["features"] * out["config"]["pooling"]
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 / lookups - 1) < 1e-6
+        for moved in ("roofline", "verified", "cpu_baseline", "box", "reference_window_semantics", "repeated_region"):
+            assert moved not in out, moved
+        fwd, upd = np.load(d / "forward_output.npy"), np.load(d / "updated_rows.npy")
+        assert fwd.dtype == np.float32 and upd.dtype == np.float32
+        assert fwd.shape[1:] == (26, 128) and upd.shape[:2] == fwd.shape[:2] and upd.shape[-1] == 128
+        assert fwd.nbytes + upd.nbytes <= 64 << 20 and np.isfinite(fwd).all() and np.abs(fwd).max() > 0
+        outs.append((fwd, upd))
+    # (the rows that sum thousands of gradients per step by atomics differ in the last bits from run to run: held to
+    # 1e-3 of the largest magnitude; other inputs would differ by the magnitude itself)
+    for a, b in zip(outs[0], outs[1]):
+        np.testing.assert_allclose(a, b, rtol=0, atol=1e-3 * float(np.abs(a).max()))
 
 
 @pytest.mark.parametrize("W,P,cap,n_rows,fill", [(2, 4, 64, 500, 0.8), (3, 8, 1100, 9000, 0.9), (8, 8, 2500, 40000, 0.95),
