@@ -120,6 +120,14 @@ SIGNATURES = {
     "ce_bag_backward_sgd_sorted": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
                                            c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_float,
                                            c_void_p, c_size_t, c_void_p]),
+    "ce_bag_backward_rowwise_adagrad_workspace": (c_size_t, [c_int64, c_int32]),
+    "ce_bag_backward_rowwise_adagrad": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
+                                                c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t,
+                                                c_void_p]),
+    "ce_bag_backward_rowwise_adagrad_src": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t,
+                                                    c_void_p]),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
-from .functional import FusedSGD, embedding_bag
+from .functional import FusedRowwiseAdagrad, FusedSGD, embedding_bag
 
 
 class CachedEmbeddingBag(nn.Module):
@@ -51,6 +51,7 @@ class CachedEmbeddingBag(nn.Module):
         self.pool_str = mode
         self.cache_op = True
         self.fused_sgd = FusedSGD(None)
+        self.fused_adagrad = FusedRowwiseAdagrad(None)
 
         if _weight is None:
             table = HostTable.allocate(num_embeddings, embedding_dim)
@@ -88,8 +89,29 @@ class CachedEmbeddingBag(nn.Module):
     def set_fused_sgd(self, lr: Optional[float], deterministic: bool = False):
         """Apply SGD(lr) to the cache rows inside backward (K13+K14 fused).  lr=None restores
         the plain autograd behaviour (grad handed to torch.optim)."""
+        if lr is not None and self.fused_adagrad.lr is not None:
+            raise ValueError("fused row-wise Adagrad is set: set_fused_rowwise_adagrad(None) before set_fused_sgd(lr)")
         self.fused_sgd.lr = lr
         self.fused_sgd.deterministic = deterministic
+
+    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8):
+        """Apply exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0; the reference's baseline
+        --adagrad) to the cache rows inside backward.  The state is one fp32 accumulator per row of the host table,
+        `cache_weight_mgr.momentum1` (device, zeroed when first enabled, indexed like `weight`); it stays in HBM and
+        never moves with the cache.  lr=None turns the update off (the state is kept).  Exclusive with
+        set_fused_sgd(lr)."""
+        if lr is not None and self.fused_sgd.lr is not None:
+            raise ValueError("fused SGD is set: set_fused_sgd(None) before set_fused_rowwise_adagrad(lr)")
+        mgr = self.cache_weight_mgr
+        if lr is not None and getattr(mgr, "momentum1", None) is None:
+            mgr.momentum1 = torch.zeros(mgr.num_embeddings, device=mgr.device, dtype=torch.float32)
+        self.fused_adagrad.lr = lr
+        self.fused_adagrad.eps = float(eps)
+        self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
+        self.fused_adagrad.row_of_slot = mgr.cached_idx_map
+
+    def _fused(self):
+        return self.fused_adagrad if self.fused_adagrad.lr is not None else self.fused_sgd
 
     def forward(self, input: torch.Tensor, offsets: Optional[torch.Tensor] = None,
                 per_sample_weights: Optional[torch.Tensor] = None, shape_hook: Optional[Callable] = None,
@@ -114,7 +136,7 @@ class CachedEmbeddingBag(nn.Module):
         out = embedding_bag(input, self.cache_weight_mgr.cuda_cached_weight, offsets, self.max_norm,
                             self.norm_type, self.scale_grad_by_freq, self.mode, self.sparse, per_sample_weights,
                             self.include_last_offset, None, hook_features=hook_features,
-                            fused_sgd=self.fused_sgd, presorted=presorted, masked_indices=masked, out=out)
+                            fused_sgd=self._fused(), presorted=presorted, masked_indices=masked, out=out)
         if shape_hook is not None:
             out = shape_hook(out)
         return out

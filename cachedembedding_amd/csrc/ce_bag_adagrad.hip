@@ -1,0 +1,229 @@
+// Fused exact row-wise Adagrad for the cached table (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0; the
+// reference's baseline maps --adagrad to it: baselines/dlrm_main.py:698-702).  Per step and per UNIQUE row r looked up:
+//   g = sum of the step's gradient rows of r ;  m[r] += sum_d g[d]^2 / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps)
+// "Exact": the non-linear update sees the row's whole gradient of the batch, so duplicate lookups are folded across
+// the whole batch first.  Three launches, no host synchronisation, no allocation, shapes fixed by the inputs (the
+// backward can be captured into a hipGraph):
+//   1. k_adagrad_mark_*: flags[slot] = 1 for every slot the step looks up (plain byte stores; racing writers all store
+//      the same value);
+//   2. the existing dense backward (ce_bag_backward_dense* / the key-streaming k_bag_bwd_stream) scatters the step's
+//      gradient into acc[slot] -- fp32 [num_rows, D], runs folded in registers and one atomic row update per run;
+//   3. k_adagrad_apply: a wave reads 64 flags at once, and a lane group per flagged slot reads acc, reduces sum g^2
+//      across its lanes, updates m[row_of_slot[slot]] and W[slot], and writes acc and the flag back to zero.
+// The workspace (acc + flags) is zero-filled by its owner once and left zero-filled by every call, so no memset runs
+// between steps.  The momentum is indexed by host-table row (row_of_slot = cached_idx_map) and never moves with the
+// cache; a slot maps to one row for the whole step, so folding by slot is folding by row.
+#include <algorithm>
+
+#include "ce_common.h"
+
+namespace ce {
+
+struct AdagradArgs {
+  float* weight;             // [num_rows, D]
+  float* acc;                // [num_rows, D], zero outside a call
+  uint8_t* flags;            // [num_rows], zero outside a call
+  const int32_t* row_of_slot;  // NULL: momentum is indexed by slot
+  float* momentum;           // [momentum_rows]
+  int64_t momentum_rows;
+  uint32_t num_rows;
+  int32_t rowlen;            // vector chunks per row
+  int32_t g_log2;            // log2(lanes per row)
+  int32_t dim;
+  float lr;
+  float eps;
+};
+
+__global__ __launch_bounds__(256) void k_adagrad_mark_slots(const int64_t* __restrict__ slots, int64_t n,
+                                                            uint32_t num_rows, uint8_t* __restrict__ flags) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t s = slots[i];
+    if (s >= 0 && s < (int64_t)num_rows) flags[s] = 1;
+  }
+}
+
+// source-row keys (row << 32 | grad_out row); row 0xffffffff = ignored lookup / padding of the last segment
+__global__ __launch_bounds__(256) void k_adagrad_mark_keys(const unsigned long long* __restrict__ keys, int64_t n,
+                                                           uint32_t num_rows, uint8_t* __restrict__ flags) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint32_t s = (uint32_t)(keys[i] >> 32);
+    if (s < num_rows) flags[s] = 1;
+  }
+}
+
+__device__ __forceinline__ float sq_sum(float v) { return v * v; }
+__device__ __forceinline__ float sq_sum(f32x4 v) { return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
+
+// one wave per 64 consecutive slots (grid-stride); the flagged ones are handed to the wave's lane groups in rounds
+template <typename VT, int NCH>
+__global__ __launch_bounds__(256) void k_adagrad_apply(AdagradArgs a) {
+  const int G = 1 << a.g_log2;
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> a.g_log2;            // lane group within the wave
+  const int gl = lane & (G - 1);
+  const int ngw = 64 >> a.g_log2;            // lane groups per wave
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  VT* W = (VT*)a.weight;
+  VT* A = (VT*)a.acc;
+  for (int64_t base = wave * 64; base < (int64_t)a.num_rows; base += nwaves * 64) {
+    const int64_t mine = base + lane;
+    const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
+    unsigned long long m = __ballot(flagged);
+    while (m) {
+      unsigned long long mm = m;
+      for (int k = 0; k < q; ++k) mm &= mm - 1;          // this group's slot: the q-th lowest flagged one
+      for (int k = 0; k < ngw; ++k) m &= m - 1;          // the round's slots leave the wave's mask
+      if (mm == 0) continue;
+      const int64_t s = base + (__ffsll((long long)mm) - 1);
+      VT g[NCH];
+      float ss = 0.f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        g[c] = idx < a.rowlen ? A[s * a.rowlen + idx] : vzero<VT>();
+        ss += sq_sum(g[c]);
+      }
+      for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, G);
+      const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
+      if (r >= 0 && r < a.momentum_rows) {
+        const float mr = a.momentum[r] + ss / (float)a.dim;
+        const float mult = a.lr / (sqrtf(mr) + a.eps);
+        if (gl == 0) a.momentum[r] = mr;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int idx = gl + c * G;
+          if (idx < a.rowlen) W[s * a.rowlen + idx] = W[s * a.rowlen + idx] - g[c] * mult;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        if (idx < a.rowlen) A[s * a.rowlen + idx] = vzero<VT>();
+      }
+    }
+    if (flagged) a.flags[mine] = 0;
+  }
+}
+
+struct AdagradWs {
+  float* acc;
+  uint8_t* flags;
+  size_t bytes;
+};
+
+static AdagradWs carve_adagrad(void* ws, int64_t num_rows, int32_t dim) {
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  AdagradWs w{};
+  char* p = (char*)ws;
+  size_t o = 0;
+  w.acc = (float*)(p + o);    o = al(o + (size_t)num_rows * dim * 4);
+  w.flags = (uint8_t*)(p + o); o = al(o + (size_t)num_rows);
+  w.bytes = o;
+  return w;
+}
+
+static int adagrad_check(float* weight, int64_t num_rows, int32_t dim, const float* grad_out, float* momentum,
+                         int64_t momentum_rows, float lr, float eps, void* workspace, size_t workspace_bytes) {
+  CE_REQUIRE(weight && grad_out && momentum && workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE(dim > 0, CE_ERR_INVALID, "dim must be positive");
+  CE_REQUIRE(momentum_rows > 0, CE_ERR_INVALID, "momentum_rows must be positive");
+  CE_REQUIRE(lr >= 0.f && eps > 0.f, CE_ERR_INVALID, "lr must be >= 0 and eps > 0");
+  CE_REQUIRE(workspace_bytes >= carve_adagrad(nullptr, num_rows, dim).bytes, CE_ERR_INVALID, "workspace too small");
+  CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
+  return CE_OK;
+}
+
+static int launch_apply(float* weight, int64_t num_rows, int32_t dim, const int32_t* row_of_slot, float* momentum,
+                        int64_t momentum_rows, float lr, float eps, const AdagradWs& ws, hipStream_t s) {
+  AdagradArgs a{};
+  a.weight = weight;
+  a.acc = ws.acc;
+  a.flags = ws.flags;
+  a.row_of_slot = row_of_slot;
+  a.momentum = momentum;
+  a.momentum_rows = momentum_rows;
+  a.num_rows = (uint32_t)num_rows;
+  a.dim = dim;
+  a.lr = lr;
+  a.eps = eps;
+  const bool vec = dim % 4 == 0 && (((uintptr_t)weight) & 15) == 0;
+  a.rowlen = vec ? dim / 4 : dim;
+  const int G = vec ? group_lanes_for_dim(dim) : std::min(64, group_lanes_for_dim(4 * dim));
+  int gl2 = 0;
+  while ((1 << gl2) < G) ++gl2;
+  a.g_log2 = gl2;
+  const int nch = (int)cdiv(a.rowlen, G);
+  CE_REQUIRE(nch <= 4, CE_ERR_UNSUPPORTED, "dim %d: at most %d", dim, vec ? 1024 : 256);
+  const dim3 g(grid_for(cdiv(num_rows, 64), 4)), b(256);
+  if (vec) {
+    if (nch == 1) hipLaunchKernelGGL((k_adagrad_apply<f32x4, 1>), g, b, 0, s, a);
+    else if (nch == 2) hipLaunchKernelGGL((k_adagrad_apply<f32x4, 2>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_adagrad_apply<f32x4, 4>), g, b, 0, s, a);
+  } else {
+    if (nch == 1) hipLaunchKernelGGL((k_adagrad_apply<float, 1>), g, b, 0, s, a);
+    else if (nch == 2) hipLaunchKernelGGL((k_adagrad_apply<float, 2>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_adagrad_apply<float, 4>), g, b, 0, s, a);
+  }
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
+}  // namespace ce
+
+using namespace ce;
+
+extern "C" size_t ce_bag_backward_rowwise_adagrad_workspace(int64_t num_rows, int32_t dim) {
+  if (num_rows < 0 || dim < 0) return 0;
+  return carve_adagrad(nullptr, num_rows, dim).bytes;
+}
+
+extern "C" int ce_bag_backward_rowwise_adagrad(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                               int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                               int64_t num_bags, int32_t include_last_offset,
+                                               const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                               const float* grad_out, const uint64_t* presorted,
+                                               const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
+                                               float lr, float eps, void* workspace, size_t workspace_bytes,
+                                               ce_stream_t stream) {
+  if (num_bags == 0 || nnz == 0) return CE_OK;
+  int rc = adagrad_check(weight, num_rows, dim, grad_out, momentum, momentum_rows, lr, eps, workspace, workspace_bytes);
+  if (rc) return rc;
+  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const AdagradWs ws = carve_adagrad(workspace, num_rows, dim);
+  hipLaunchKernelGGL(k_adagrad_mark_slots, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz,
+                     (uint32_t)num_rows, ws.flags);
+  CE_LAUNCH_CHECK();
+  rc = presorted ? ce_bag_backward_dense_presorted(ws.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64,
+                                                   num_bags, include_last_offset, per_sample_weights, mode,
+                                                   hook_features, grad_out, presorted, stream)
+                 : ce_bag_backward_dense(ws.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                                         include_last_offset, per_sample_weights, mode, hook_features, grad_out,
+                                         stream);
+  if (rc) return rc;
+  return launch_apply(weight, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps, ws, s);
+}
+
+extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                                   const float* grad_out, const uint64_t* src_keys,
+                                                   const int32_t* row_of_slot, float* momentum,
+                                                   int64_t momentum_rows, float lr, float eps, void* workspace,
+                                                   size_t workspace_bytes, ce_stream_t stream) {
+  if (nnz == 0) return CE_OK;
+  int rc = adagrad_check(weight, num_rows, dim, grad_out, momentum, momentum_rows, lr, eps, workspace, workspace_bytes);
+  if (rc) return rc;
+  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const AdagradWs ws = carve_adagrad(workspace, num_rows, dim);
+  const int64_t total = ce_bag_presort_len(nnz);
+  hipLaunchKernelGGL(k_adagrad_mark_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
+                     (const unsigned long long*)src_keys, total, (uint32_t)num_rows, ws.flags);
+  CE_LAUNCH_CHECK();
+  rc = ce_bag_backward_dense_presorted_src(ws.acc, num_rows, dim, nnz, grad_out, src_keys, stream);
+  if (rc) return rc;
+  return launch_apply(weight, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps, ws, s);
+}

@@ -5,8 +5,9 @@
 mode, sparse, per_sample_weights, include_last_offset, padding_idx)`` (SURVEY.md A.7;
 call sites recsys/models/dlrm.py:99-110, benchmark/benchmark_cache.py:62), with two
 additions the reference does not have: `hook_features` folds sparse_embedding_shape_hook
-(recsys/models/dlrm.py:26-27) into the output store, and `fused_sgd_lr` applies
-SGD.step (recsys/dlrm_main.py:279) inside the backward pass.
+(recsys/models/dlrm.py:26-27) into the output store, and `fused_sgd` applies
+SGD.step (recsys/dlrm_main.py:279) -- or, given a FusedRowwiseAdagrad, the exact row-wise
+Adagrad step of the reference's baseline (baselines/dlrm_main.py:698-702) -- inside the backward pass.
 """
 from __future__ import annotations
 
@@ -73,7 +74,8 @@ class _BagFn(torch.autograd.Function):
             # d loss / d per_sample_weights[j] = <grad_out[bag of j], weight[indices[j]]> needs the rows as the forward
             # saw them, and the fused update moves them inside backward: refused HERE, before any kernel has run (a
             # refusal inside backward would leave the caller with an exception AND an updated table)
-            raise NotImplementedError("gradient w.r.t. per_sample_weights with the fused SGD update")
+            raise NotImplementedError("gradient w.r.t. per_sample_weights with the fused SGD / row-wise Adagrad "
+                                      "update")
         num_bags = offsets.numel() - 1 if include_last else offsets.numel()
         dim = weight.shape[1]
         shape = (num_bags // hook_features, hook_features, dim) if hook_features else (num_bags, dim)
@@ -113,7 +115,25 @@ class _BagFn(torch.autograd.Function):
         off64 = int(offsets.dtype == torch.int64)
         nnz = indices.numel()
         gw = None
-        if fused is not None and fused.lr is not None:
+        if isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None:
+            # exact row-wise Adagrad inside backward (ce_bag_adagrad.hip): the optimizer sees grad=None
+            with torch.no_grad():
+                ws = fused.workspace(weight.shape[0], dim, weight.device)
+                mom = fused.momentum
+                rmap = fused.row_of_slot
+                if isinstance(ctx.presorted, SrcKeys):
+                    check(lib.ce_bag_backward_rowwise_adagrad_src(ptr(weight), weight.shape[0], dim, nnz, ptr(grad_out),
+                                                                  ptr(ctx.presorted.keys), ptr(rmap), ptr(mom),
+                                                                  mom.numel(), float(fused.lr), float(fused.eps),
+                                                                  ptr(ws), ws.numel(), stream_ptr()))
+                else:
+                    check(lib.ce_bag_backward_rowwise_adagrad(ptr(weight), weight.shape[0], dim, ptr(indices), nnz,
+                                                              ptr(offsets), off64, num_bags, int(include_last),
+                                                              ptr(psw), mode, hook_features, ptr(grad_out),
+                                                              ptr(ctx.presorted), ptr(rmap), ptr(mom), mom.numel(),
+                                                              float(fused.lr), float(fused.eps), ptr(ws), ws.numel(),
+                                                              stream_ptr()))
+        elif fused is not None and fused.lr is not None:
             # K13+K14 in one pass; the optimizer sees grad=None for the cache parameter
             with torch.no_grad():
                 if fused.deterministic:
@@ -274,11 +294,54 @@ class FusedSGD:
         return self._ws
 
 
+class FusedRowwiseAdagrad:
+    """Switch for the fused backward + exact row-wise Adagrad update of one embedding module (FBGEMM's
+    EXACT_ROWWISE_ADAGRAD, weight_decay = 0).  Per step and per UNIQUE row r the step looks up, with g the sum of the
+    row's gradient rows in the batch:  m[r] += sum(g * g) / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps).
+
+    momentum: fp32 [rows] on the device -- one accumulator per row of the table the momentum follows; row_of_slot:
+    int32 [rows of the weight] mapping a row of the weight the kernels update to its momentum index (a cache's
+    cached_idx_map), None = the weight row itself.  lr=None disables the update (the weight then gets a gradient)."""
+
+    def __init__(self, lr: Optional[float] = None, eps: float = 1e-8, momentum: Optional[torch.Tensor] = None,
+                 row_of_slot: Optional[torch.Tensor] = None):
+        self.lr = lr
+        self.eps = float(eps)
+        self.momentum = momentum
+        self.row_of_slot = row_of_slot
+        self._ws = None
+
+    def check(self, weight: torch.Tensor) -> None:
+        """refusals that must come before any kernel of the step has run"""
+        m = self.momentum
+        if m is None or not m.is_cuda or m.dtype != torch.float32 or not m.is_contiguous() or m.device != weight.device:
+            raise ValueError("row-wise Adagrad needs a contiguous fp32 momentum tensor on the weight's device")
+        rmap = self.row_of_slot
+        if rmap is None:
+            if m.numel() < weight.shape[0]:
+                raise ValueError("momentum must have a row for every row of the weight")
+        elif rmap.numel() != weight.shape[0]:
+            # a cache with rows behind it (CachedParamMgr.reserve_tail: the row-wise exchange's received rows) would
+            # hand the backward slots outside [0, C), which have no row of the table and so no state
+            raise NotImplementedError("fused row-wise Adagrad updates the cache rows only: slots outside [0, C) "
+                                      f"(a weight of {weight.shape[0]} rows over a cache of {rmap.numel()})")
+        elif rmap.dtype != torch.int32 or not rmap.is_contiguous() or rmap.device != weight.device:
+            raise ValueError("row_of_slot must be a contiguous int32 tensor on the weight's device")
+
+    def workspace(self, num_rows: int, dim: int, device) -> torch.Tensor:
+        # zero-filled once; every call of the kernels leaves it zero-filled again
+        need = lib.ce_bag_backward_rowwise_adagrad_workspace(num_rows, dim)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = None
+            self._ws = torch.zeros(need, dtype=torch.uint8, device=device)
+        return self._ws
+
+
 def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional[torch.Tensor] = None,
                   max_norm: Optional[float] = None, norm_type: float = 2.0, scale_grad_by_freq: bool = False,
                   mode: str = "mean", sparse: bool = False, per_sample_weights: Optional[torch.Tensor] = None,
                   include_last_offset: bool = False, padding_idx: Optional[int] = None, *,
-                  hook_features: int = 0, fused_sgd: Optional[FusedSGD] = None,
+                  hook_features: int = 0, fused_sgd: Union[FusedSGD, FusedRowwiseAdagrad, None] = None,
                   presorted: Union[torch.Tensor, SrcKeys, None] = None, masked_indices: bool = False,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     # out: write the pooled output into this tensor (contiguous fp32, the shape the call would allocate) and return it --
@@ -287,6 +350,11 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     # sparse=True backward then parks their (zero) gradient rows at index 0 so the COO tensor stays valid
     if mode not in _MODES and mode != "max":
         raise NotImplementedError(f"mode={mode!r}: 'sum', 'mean' and 'max' are implemented")
+    if isinstance(fused_sgd, FusedRowwiseAdagrad) and fused_sgd.lr is not None:
+        # fused_sgd may also carry the row-wise Adagrad switch; its refusals come before any kernel runs
+        if mode == "max":
+            raise NotImplementedError("fused row-wise Adagrad with mode='max'")
+        fused_sgd.check(weight)
     if per_sample_weights is not None:
         if mode != "sum":
             raise NotImplementedError("embedding_bag: per_sample_weights was not None. per_sample_weights is "

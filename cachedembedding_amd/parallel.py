@@ -572,6 +572,12 @@ class RowwiseShardedEmbeddingBag(nn.Module):
     def set_fused_sgd(self, lr: Optional[float]):
         self._lr[0] = lr
 
+    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8):
+        """Refused: the owner-side update of the row exchange is SGD only (GraphedShardedWindow replays it too)."""
+        if lr is not None:
+            raise NotImplementedError("fused row-wise Adagrad is not implemented for the row-wise sharded embedding "
+                                      "(RowwiseShardedEmbeddingBag / GraphedShardedWindow); use set_fused_sgd(lr)")
+
     def plan_window(self, ids_list: Sequence[torch.Tensor]) -> List[BatchPlan]:
         return self.exchange.plan_window(ids_list)
 

@@ -89,6 +89,10 @@ def parse_args(argv=None):
                         "of a whole model takes tens of milliseconds, so short blocks measure well)")
     # additions of this build
     p.add_argument("--fused_sgd", action="store_true", help="apply the embedding SGD inside backward")
+    p.add_argument("--adagrad", action="store_true",
+                   help="exact row-wise Adagrad for the embedding, fused into backward (FBGEMM's EXACT_ROWWISE_ADAGRAD, "
+                        "as baselines/dlrm_main.py:698-702 maps --adagrad), torch.optim.Adagrad for the dense part "
+                        "(:799-802); takes the place of --fused_sgd (one process)")
     p.add_argument("--fold_hook", action="store_true", help="write [B,F,D] from the gather kernel")
     p.add_argument("--window_keys", action="store_true",
                    help="the window's cache op also groups every batch's slots by row (source-row keys): the forward "
@@ -308,8 +312,8 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None):
     embed = model.sparse_modules.embed
     layout = None
     if args.window_keys:
-        if not (args.fused_sgd and args.fold_hook) or world > 1:
-            raise ValueError("--window_keys needs --fused_sgd --fold_hook (one process)")
+        if not ((args.fused_sgd or args.adagrad) and args.fold_hook) or world > 1:
+            raise ValueError("--window_keys needs --fused_sgd (or --adagrad) --fold_hook (one process)")
         F = model.sparse_modules.sparse_feature_num
         offsets = torch.arange(F * args.batch_size + 1, dtype=torch.int32, device=device)     # one id per bag (KJT lengths = 1)
         layout = (offsets, True, F)
@@ -319,8 +323,9 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None):
                          if (args.overlap_cache_op and args.arrangement == "auto") else None)
     train.window = win
     graphed = None
-    if args.graph_step and (world > 1 or not (args.fused_sgd and args.fold_hook)):
-        raise ValueError("--graph_step needs --fused_sgd --fold_hook and one process (DDP's bucket hooks and the sparse "
+    if args.graph_step and (world > 1 or not ((args.fused_sgd or args.adagrad) and args.fold_hook)):
+        raise ValueError("--graph_step needs --fused_sgd (or --adagrad) --fold_hook and one process (DDP's bucket hooks "
+                         "and the sparse "
                          "COO gradient of the unfused path are not captured)")
     elapsed, done, loss = 0.0, 0, None
     steady = {"t0": None, "done0": 0}
@@ -462,6 +467,14 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.adagrad:
+        if args.fused_sgd:
+            raise ValueError("--adagrad takes the place of --fused_sgd: pass one of them")
+        if world > 1 or args.use_tablewise:
+            # the row-wise accumulator needs the whole row's gradient on one device: the model-parallel layouts of
+            # this trainer split the rows' columns over the ranks (or the tables over them)
+            raise NotImplementedError("--adagrad is implemented for one process without --use_tablewise (sharded "
+                                      "embeddings keep the fused SGD only)")
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     if world > 1:
@@ -499,11 +512,13 @@ def main(argv=None):
     embed = model.sparse_modules.embed
     embed.set_cache_mgr_async_copy(args.use_cache_mgr_async_copy)
     groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world}]
-    if args.fused_sgd:
+    if args.adagrad:
+        embed.set_fused_rowwise_adagrad(args.learning_rate)
+    elif args.fused_sgd:
         embed.set_fused_sgd(args.learning_rate)
     else:
         groups.insert(0, {"params": list(model.sparse_modules.parameters()), "lr": args.learning_rate})
-    optimizer = torch.optim.SGD(groups)
+    optimizer = torch.optim.Adagrad(groups) if args.adagrad else torch.optim.SGD(groups)
     if loader is None:
         loader = SyntheticLoader(sizes, args.batch_size, args.num_dense_features, args.limit_train_batches,
                                  args.seed + 17)
@@ -557,7 +572,7 @@ def main(argv=None):
                     "cuda_row_num": int(mgr.cuda_row_num), "dense_arch": args.dense_arch_layer_sizes,
                     "over_arch": args.over_arch_layer_sizes, "dtype": "f32", "data": "synthetic",
                     "surface": {k: bool(getattr(args, k)) for k in ("use_overlap", "overlap_cache_op", "fused_sgd",
-                                                                    "fold_hook", "window_keys", "tunable_gemm", "graph_step",
+                                                                    "adagrad", "fold_hook", "window_keys", "tunable_gemm", "graph_step",
                                                                     "use_sparse_embed_grad", "use_lfu", "use_freq")},
                     "transport": mgr.transport_name, "iterations": done, "warmup_iterations": args.warmup_batches,
                     "it_per_s": train.steady_it_per_s, "it_per_s_scope": "whole model: data iterator + cache op + "

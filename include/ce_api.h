@@ -271,6 +271,29 @@ int ce_bag_backward_sgd_sorted(float* weight, int64_t num_rows, int32_t dim,
                                int32_t mode, int64_t hook_features, const float* grad_out, float lr,
                                void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
+/* Fused exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD with weight_decay = 0).  For every UNIQUE row of the
+ * call, g = the sum of its lookups' gradient rows (as the SGD entries scale them), then
+ *   momentum[m] += sum_d g[d]^2 / dim ;  weight[slot] -= lr * g / (sqrt(momentum[m]) + eps)
+ * with m = row_of_slot[slot] (row_of_slot: device int32[num_rows], the cache's cached_idx_map; NULL = the slot itself)
+ * and momentum device fp32[momentum_rows]; a slot whose m lies outside [0, momentum_rows) is not updated.  Lookups of
+ * rows outside [0, num_rows) are ignored.  The workspace (device, 256-byte aligned, at least
+ * ce_bag_backward_rowwise_adagrad_workspace(num_rows, dim) bytes) must be ZERO-FILLED before its first use; every call
+ * leaves it zero-filled again.  No host synchronisation, no allocation: the calls can be captured into a hipGraph.
+ * The general form takes slots + offsets (sum / mean, per-sample weights, hook_features; presorted: optional keys
+ * from ce_bag_presort* as for ce_bag_backward_dense_presorted); the _src form takes a batch's source-row keys
+ * (ce_bag_presort_window_src*). */
+size_t ce_bag_backward_rowwise_adagrad_workspace(int64_t num_rows, int32_t dim);
+int ce_bag_backward_rowwise_adagrad(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                    const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                    int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                    int64_t hook_features, const float* grad_out, const uint64_t* presorted,
+                                    const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                    float eps, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                        const float* grad_out, const uint64_t* src_keys, const int32_t* row_of_slot,
+                                        float* momentum, int64_t momentum_rows, float lr, float eps, void* workspace,
+                                        size_t workspace_bytes, ce_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6].  Device state arrays are owned by the caller (so the Python
  * mirror can expose them as tensors: cached_idx_map, inverted_cached_idx, idx_map,
