@@ -29,6 +29,9 @@ CE_EVICT_DATASET = 0
 CE_EVICT_LFU = 1
 CE_MODE_SUM = 0
 CE_MODE_MEAN = 1
+CE_ACT_F32 = 0
+CE_ACT_BF16 = 1
+CE_ACT_F16 = 2
 CE_TRANSPORT_ZEROCOPY = 0
 CE_TRANSPORT_STAGED = 1
 CE_TRANSPORT_WORKER = 2
@@ -128,6 +131,28 @@ SIGNATURES = {
     "ce_bag_backward_rowwise_adagrad_src": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
                                                     c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t,
                                                     c_void_p]),
+    # the hot-path bag entries with the output / incoming gradient as void* of an activation dtype (CE_ACT_*)
+    "ce_bag_forward_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
+                                   c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_void_p]),
+    "ce_bag_forward_src_keys_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int32,
+                                            c_void_p]),
+    "ce_bag_backward_dense_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
+                                          c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_void_p,
+                                          c_void_p]),
+    "ce_bag_backward_sgd_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
+                                        c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_float, c_void_p,
+                                        c_void_p]),
+    "ce_bag_backward_sgd_src_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32, c_float, c_void_p,
+                                            c_void_p, c_void_p]),
+    "ce_bag_backward_dense_src_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32, c_void_p,
+                                              c_void_p]),
+    "ce_bag_backward_rowwise_adagrad_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
+                                                    c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32,
+                                                    c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
+                                                    c_void_p, c_size_t, c_void_p]),
+    "ce_bag_backward_rowwise_adagrad_src_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32,
+                                                        c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
+                                                        c_void_p, c_size_t, c_void_p]),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),
@@ -243,6 +268,21 @@ def stream_ptr() -> int:
     if _RAW_STREAM is not None:
         return _RAW_STREAM(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+# torch dtype of an activation tensor -> CE_ACT_* (the table itself is always fp32)
+ACT_DTYPES = {torch.float32: CE_ACT_F32, torch.bfloat16: CE_ACT_BF16, torch.float16: CE_ACT_F16}
+
+
+def act_code(dtype) -> int:
+    """CE_ACT_* of an output / gradient dtype; None means fp32.  Anything else is refused by name."""
+    if dtype is None:
+        return CE_ACT_F32
+    try:
+        return ACT_DTYPES[dtype]
+    except (KeyError, TypeError):
+        raise NotImplementedError(f"output_dtype={dtype!r}: torch.float32, torch.bfloat16 and torch.float16 are "
+                                  "implemented") from None
 
 
 def ptr(t) -> int:

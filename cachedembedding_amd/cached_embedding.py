@@ -24,12 +24,16 @@ class CachedEmbeddingBag(nn.Module):
                  include_last_offset: bool = False, dtype=None, device=None, cache_ratio: float = 0.01,
                  ids_freq_mapping=None, warmup_ratio: float = 0.7, buffer_size: int = 0, pin_weight: bool = False,
                  evict_strategy: EvictionStrategy = EvictionStrategy.DATASET, *, cuda_row_num: Optional[int] = None,
-                 init_seed: int = 1024, strict: bool = True):
+                 init_seed: int = 1024, strict: bool = True, output_dtype: Optional[torch.dtype] = None):
         super().__init__()
+        # output_dtype (addition): dtype of the pooled output and of the gradient coming back -- None / torch.float32,
+        # torch.bfloat16 or torch.float16 (functional.embedding_bag(output_dtype=...)).  `dtype` is the TABLE's dtype.
+        if dtype not in (None, torch.float32):
+            raise NotImplementedError("only fp32 tables are implemented (dtype= is the table's dtype; a 16-bit "
+                                      "pooled output is output_dtype=)")
+        self.set_output_dtype(output_dtype)
         _lib.require_gpu()
         assert cache_ratio <= 1.0, f"cache ratio {cache_ratio} must less than 1.0"
-        if dtype not in (None, torch.float32):
-            raise NotImplementedError("only fp32 tables are implemented")
         self.num_embeddings = num_embeddings
         self.embedding_dim = embedding_dim
         if padding_idx is not None:
@@ -110,6 +114,13 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
 
+    def set_output_dtype(self, dtype: Optional[torch.dtype]):
+        """dtype of the pooled output, training and eval alike: None / torch.float32 (default), torch.bfloat16 or
+        torch.float16.  The table, the sums and the fused updates stay fp32; the forward kernels round once on the
+        store and the backward kernels read the 16-bit gradient autograd hands back in place."""
+        _lib.act_code(dtype)                 # NotImplementedError for anything else
+        self.output_dtype = torch.float32 if dtype is None else dtype
+
     def _fused(self):
         return self.fused_adagrad if self.fused_adagrad.lr is not None else self.fused_sgd
 
@@ -136,7 +147,8 @@ class CachedEmbeddingBag(nn.Module):
         out = embedding_bag(input, self.cache_weight_mgr.cuda_cached_weight, offsets, self.max_norm,
                             self.norm_type, self.scale_grad_by_freq, self.mode, self.sparse, per_sample_weights,
                             self.include_last_offset, None, hook_features=hook_features,
-                            fused_sgd=self._fused(), presorted=presorted, masked_indices=masked, out=out)
+                            fused_sgd=self._fused(), presorted=presorted, masked_indices=masked, out=out,
+                            output_dtype=self.output_dtype)
         if shape_hook is not None:
             out = shape_hook(out)
         return out

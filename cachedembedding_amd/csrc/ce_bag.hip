@@ -19,6 +19,8 @@
 //     registers + LDS itself, or walks presorted segments), k_bag_bwd_rows (COO values), k_rows_axpy (row-wise exchange).
 // Output stores are non-temporal (never re-read here); row loads use the default policy so hot rows stay in
 // L2 / Infinity Cache.
+// The table, the sums and the updates are fp32; the forward's output and the backward's grad_out have the activation
+// type AT (fp32, bf16, fp16: Act<AT, VT> in ce_common.h) the four bag kernels are templated on.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -38,8 +40,8 @@ namespace ce {
 
 struct BagParams {
   const float* weight;      // fwd: rows to gather from
-  float* dst;               // fwd: out; bwd: grad_weight / weight / grad_rows
-  const float* grad_out;    // bwd only
+  float* dst;               // fwd: out (elements of the activation type AT); bwd: grad_weight / weight / grad_rows
+  const void* grad_out;     // bwd only (elements of the activation type AT)
   const int64_t* indices;
   const void* offsets;
   const float* psw;
@@ -96,26 +98,34 @@ __device__ __forceinline__ int64_t out_row(const BagParams& p, int g) {
   return (int64_t)b * p.hookF + f;
 }
 
+// PAIR form of the two key-walking kernels for a 16-bit activation type (D % 8 == 0, 16-byte aligned tensor).  A lane
+// keeps its 4 elements of a row (8 bytes on the 16-bit side), and 8-byte accesses run at 0.5-0.7 of the 16-byte rate,
+// so the lanes of a pair (gl, gl ^ 1) work on TWO keys at once: the even lane moves the 16 bytes that the pair holds of
+// the first key's row, the odd lane the 16 bytes of the second key's row -- every lane moves 16 bytes, one access
+// serves two keys, and the halves change hands with one DPP-able __shfl_xor(., 1) of two dwords.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x2 swap_with_pair(u32x2 v) {
+  return u32x2{(uint32_t)__shfl_xor((int)v.x, 1), (uint32_t)__shfl_xor((int)v.y, 1)};
+}
+
 constexpr int kIdxStage = 2048;   // indices of one 64-bag tile staged in LDS (8 KB per wave)
 
 // Output store of the forward: non-temporal (SP = 1).  The output is written once and read by another kernel; what
 // matters is how much of the L2 / Infinity Cache it takes from the cache rows the gather wants to find there (the
 // sc1 / sc0 sc1 / sc1 nt forms measured the same or slower: profiles/r03_probe_fwd_xcd.txt, docs/history.md).
-template <int SP>
-__device__ __forceinline__ void store_out(f32x4* p, f32x4 v) {
-  if (SP == 0) *p = v;
-  else __builtin_nontemporal_store(v, p);
-}
-template <int SP>
-__device__ __forceinline__ void store_out(float* p, float v) {
+template <int SP, typename T>
+__device__ __forceinline__ void store_out(T* p, T v) {
   if (SP == 0) *p = v;
   else __builtin_nontemporal_store(v, p);
 }
 
 // STAGE: tiles with multi-id bags stage their indices in LDS (32 KB per workgroup); the launcher picks the
 // LDS-free variant when nnz == num_bags (single-id batches) so occupancy is set by registers alone.
-template <typename VT, int NCH, bool STAGE, int U, int NTS>
+// AT: the output's element type (Act<AT, VT>, ce_common.h): sums stay fp32, the store rounds.
+template <typename VT, int NCH, bool STAGE, int U, int NTS, typename AT>
 __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
+  using A = Act<AT, VT>;
   __shared__ int lds_idx[STAGE ? 4 : 1][STAGE ? kIdxStage : 1];
   const int lane = threadIdx.x & 63;
   const int G = 1 << p.g_log2;
@@ -126,7 +136,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   const int64_t wave = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * wpb;
   const VT* __restrict__ W = (const VT*)p.weight;
-  VT* __restrict__ O = (VT*)p.dst;
+  typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const int rowlen = p.rowlen;
   // tiles are dealt round-robin to the waves of an oversubscribed grid (an even contiguous split over a
   // resident-sized grid measured 15 % slower: 0.060 -> 0.069 ms)
@@ -173,7 +183,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
               const int ch = gl + c * G;
               if (ch < rowlen) {
                 VT val = p.psw ? v[u][c] * wi : v[u][c];
-                store_out<NTS>(&O[orow * rowlen + ch], val);
+                store_out<NTS>(&O[orow * rowlen + ch], A::down(val));
               }
             }
           }
@@ -241,7 +251,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
           for (int c = 0; c < NCH; ++c) {
             const int ch = gl + c * G;
             if (ch < rowlen) {
-              store_out<NTS>(&O[orow * rowlen + ch], acc[c]);
+              store_out<NTS>(&O[orow * rowlen + ch], A::down(acc[c]));
             }
           }
         }
@@ -704,9 +714,10 @@ __global__ __launch_bounds__(1024) void k_bag_presort_seg(const int64_t* __restr
   }
 }
 
-template <typename VT, int NCH, typename KT, int R>
+template <typename VT, int NCH, typename KT, int R, typename AT>
 __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
   using K = KeyOps<KT>;
+  using A = Act<AT, VT>;
   __shared__ KT keys[kBwdTile];
   __shared__ int bagl[kBwdTile];
   __shared__ float scl[kBwdTile];
@@ -718,7 +729,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
   const int gl = tid & (G - 1);
   const int rowlen = p.rowlen;
   const int dim = rowlen * (int)(sizeof(VT) / 4);
-  const VT* __restrict__ GO = (const VT*)p.grad_out;
+  const typename A::V* __restrict__ GO = (const typename A::V*)p.grad_out;
   // tile_len <= kBwdTile is chosen by the launcher so that the tile count is a multiple of the CU count
   // (425,984 lookups -> 512 tiles of 832: two per CU, instead of 416 tiles = 1 or 2 per CU).
   // presorted: the tiles are tile_len consecutive positions of the segment-padded key array (any alignment)
@@ -803,7 +814,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
           for (int c = 0; c < NCH; ++c) {
             const int ch = gl + c * G;
             v[t][c] = vzero<VT>();
-            if (on && ch < rowlen) v[t][c] = __builtin_nontemporal_load(&GO[orow * rowlen + ch]);
+            if (on && ch < rowlen) v[t][c] = A::up(__builtin_nontemporal_load(&GO[orow * rowlen + ch]));
           }
         }
         // one wait for all R gathers (see k_bag_bwd_stream): keeps the flushes' atomics fire-and-forget
@@ -854,8 +865,12 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
 // 512-byte store.  Everything else (long runs, rows of hot buckets, runs that straddle a block, batches whose
 // segments share ids) keeps the transposed fire-and-forget atomics.  Why: the L2 atomic units retire ~1 float per
 // clock and channel -- 6.3 M lane-ops per launch = 24 us that do not overlap with the gather (profiles/r03_probe_*).
-template <typename VT, int NCH, int R, bool NTG, bool EXCL>
+// AT: grad_out's element type -- only the gather changes; fold, old rows and update are fp32 whatever it is.
+// PAIR (16-bit AT, f32x4 lanes): the gather of two keys' gradient rows is ONE 16-byte load per lane (see u32x4 above).
+template <typename VT, int NCH, int R, bool NTG, bool EXCL, typename AT, bool PAIR = false>
 __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t total, const long long* __restrict__ seg_ranges) {
+  using A = Act<AT, VT>;
+  static_assert(!PAIR || (sizeof(typename A::V) == 8 && R % 2 == 0), "PAIR: 4 x 16 bit per lane, keys two at a time");
   __shared__ unsigned long long lk[256 * (R > 4 ? R : 4)];     // ngroups * kc, worst case G = 1
   const int tid = threadIdx.x;
   const int G = 1 << p.g_log2;
@@ -864,7 +879,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
   const int gl = tid & (G - 1);
   const int rowlen = p.rowlen;
   const int dim = rowlen * (int)(sizeof(VT) / 4);
-  const VT* __restrict__ GO = (const VT*)p.grad_out;
+  const typename A::V* __restrict__ GO = (const typename A::V*)p.grad_out;
   const VT* __restrict__ WV = (const VT*)p.dst;
   const unsigned long long* __restrict__ keys = p.presorted;
   bool excl = false;
@@ -903,6 +918,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
     for (int64_t q = c0; q < c1; q += R) {
       VT v[R][NCH];
       VT w2[EXCL ? R : 1][NCH];
+      u32x4 raw[PAIR ? R / 2 : 1][NCH];
       uint32_t rw[R];
       uint32_t heads = 0;
 #pragma unroll
@@ -914,11 +930,26 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
         const int64_t src = (int64_t)(low & ~kExclFlag);
         const bool head = EXCL && excl && on && (low & kExclFlag);
         if (head) heads |= 1u << t;
+        if constexpr (PAIR) if (!(t & 1)) {
+          // keys t, t + 1: even lanes fetch the pair's 16 bytes of key t's gradient row, odd lanes those of key t + 1's
+          const unsigned long long k1 = mylk[(int)(q - c0) + t + 1];
+          const bool on1 = k1 != ~0ull && (uint32_t)(k1 >> 32) < p.num_rows;
+          const bool mine = (gl & 1) ? on1 : on;
+          const int64_t msrc = (gl & 1) ? (int64_t)((uint32_t)k1 & ~kExclFlag) : src;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            const int ch = gl + c * G;
+            raw[PAIR ? t / 2 : 0][c] = u32x4{0u, 0u, 0u, 0u};
+            if (mine && ch < rowlen)
+              raw[PAIR ? t / 2 : 0][c] = __builtin_nontemporal_load((const u32x4*)p.grad_out + ((msrc * rowlen + ch) >> 1));
+          }
+        }
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const int ch = gl + c * G;
           v[t][c] = vzero<VT>();
-          if (on && ch < rowlen) v[t][c] = NTG ? __builtin_nontemporal_load(&GO[src * rowlen + ch]) : GO[src * rowlen + ch];
+          if (!PAIR && on && ch < rowlen)
+            v[t][c] = A::up(NTG ? __builtin_nontemporal_load(&GO[src * rowlen + ch]) : GO[src * rowlen + ch]);
           if (EXCL) {
             w2[t][c] = vzero<VT>();
             if (head && ch < rowlen) w2[t][c] = WV[(int64_t)rw[t] * rowlen + ch];
@@ -928,6 +959,21 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
       // ONE wait for all R gathers here: left to the compiler, the wait for v[t] lands after the flush of v[t-1]'s
       // row, where the vmcnt counter also holds the atomics just issued -- every flush would be synchronous
       __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt/lgkmcnt untouched
+      if constexpr (PAIR) {
+        // even lane: [key t: my chunk | key t: partner's chunk]; odd lane: [key t + 1: partner's | key t + 1: mine]
+#pragma unroll
+        for (int t = 0; t < R; t += 2) {
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            const u32x4 r = raw[PAIR ? t / 2 : 0][c];
+            const u32x2 lo{r.x, r.y}, hi{r.z, r.w};
+            const bool odd = gl & 1;
+            const u32x2 got = swap_with_pair(odd ? lo : hi);
+            v[t][c] = A::up(__builtin_bit_cast(typename A::V, odd ? got : lo));
+            v[t + 1][c] = A::up(__builtin_bit_cast(typename A::V, odd ? hi : got));
+          }
+        }
+      }
 #pragma unroll
       for (int t = 0; t < R; ++t) {
         if (rw[t] != 0xffffffffu) {            // group-uniform
@@ -976,8 +1022,12 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
 // its output).  Same walk as k_bag_bwd_stream: contiguous equal shares, keys staged through a group-private LDS slice,
 // R keys per step -- the loads of the step's run heads in flight together, one wait, then the stores.
 // An ignored lookup (row 0xffffffff, see k_bag_presort_seg) gets a zero row; padding keys (~0) are skipped.
-template <typename VT, int NCH, int R, int NTS>
+// AT: the output's element type; the row is rounded once per store, so `prev` stays the fp32 row.
+// PAIR (16-bit AT, f32x4 lanes): the stores of two keys are ONE 16-byte store per lane (see u32x4 above).
+template <typename VT, int NCH, int R, int NTS, typename AT, bool PAIR = false>
 __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t total) {      // 4 waves per SIMD: <= 128 VGPRs
+  using A = Act<AT, VT>;
+  static_assert(!PAIR || (sizeof(typename A::V) == 8 && R % 2 == 0), "PAIR: 4 x 16 bit per lane, keys two at a time");
   __shared__ unsigned long long lk[256 * (R > 4 ? R : 4)];
   const int tid = threadIdx.x;
   const int G = 1 << p.g_log2;
@@ -986,7 +1036,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
   const int gl = tid & (G - 1);
   const int rowlen = p.rowlen;
   const VT* __restrict__ W = (const VT*)p.weight;
-  VT* __restrict__ O = (VT*)p.dst;
+  typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const unsigned long long* __restrict__ keys = p.presorted;
   const int64_t all_groups = (int64_t)gridDim.x * ngroups;
   const int64_t round = R > 16 ? R : 16;
@@ -1023,6 +1073,40 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
         }
       }
       __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): every head of the step has arrived
+      if constexpr (PAIR) {
+        const bool odd = gl & 1;
+#pragma unroll
+        for (int t = 0; t < R; t += 2) {
+          const unsigned long long k0 = mylk[(int)(q - c0) + t], k1 = mylk[(int)(q - c0) + t + 1];
+          if (k0 == ~0ull && k1 == ~0ull) continue;               // padding (group-uniform)
+          // the rounded row of key t and of key t + 1 (the same row inside a run)
+          u32x2 r0[NCH], r1[NCH];
+          if ((heads >> t) & 1) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) prev[c] = v[t][c];
+          }
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) r0[c] = __builtin_bit_cast(u32x2, A::down(prev[c]));
+          if ((heads >> (t + 1)) & 1) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) prev[c] = v[t + 1][c];
+          }
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) r1[c] = __builtin_bit_cast(u32x2, A::down(prev[c]));
+          // even lanes write key t's output row, odd lanes key t + 1's: 16 bytes = my chunk and my partner's
+          const unsigned long long km = odd ? k1 : k0;
+          const int64_t orow = (int64_t)((uint32_t)km & ~kExclFlag);
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            const int ch = gl + c * G;
+            const u32x2 got = swap_with_pair(odd ? r0[c] : r1[c]);
+            const u32x4 o = odd ? u32x4{got.x, got.y, r1[c].x, r1[c].y} : u32x4{r0[c].x, r0[c].y, got.x, got.y};
+            if (km != ~0ull && ch < rowlen) store_out<NTS>((u32x4*)p.dst + ((orow * rowlen + ch) >> 1), o);
+          }
+        }
+        prev_row = last;
+        continue;
+      }
 #pragma unroll
       for (int t = 0; t < R; ++t) {
         // (the output row comes out of LDS again rather than out of 16 more registers: the kernel sits at the
@@ -1038,7 +1122,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const int ch = gl + c * G;
-          if (ch < rowlen) store_out<NTS>(&O[orow * rowlen + ch], prev[c]);
+          if (ch < rowlen) store_out<NTS>(&O[orow * rowlen + ch], A::down(prev[c]));
         }
       }
       prev_row = last;
@@ -1093,7 +1177,8 @@ __global__ __launch_bounds__(256) void k_rows_axpy(float* __restrict__ dst, uint
 
 static int fill_params(BagParams& p, int32_t dim, const int64_t* indices, int64_t nnz, const void* offsets,
                        int32_t off64, int64_t num_bags, int32_t include_last, const float* psw, int32_t mode,
-                       int64_t hookF, bool* vec, int* nch, const void* a0, const void* a1, const void* a2) {
+                       int64_t hookF, bool* vec, int* nch, const void* a0, const void* a1, const void* a2,
+                       const void* a16 = nullptr) {
   CE_REQUIRE(dim > 0, CE_ERR_INVALID, "embedding dim must be positive");
   CE_REQUIRE(num_bags >= 0 && nnz >= 0, CE_ERR_INVALID, "negative sizes");
   CE_REQUIRE(num_bags < (int64_t)INT32_MAX - 64 && nnz < (int64_t)INT32_MAX, CE_ERR_UNSUPPORTED,
@@ -1103,7 +1188,9 @@ static int fill_params(BagParams& p, int32_t dim, const int64_t* indices, int64_
   CE_REQUIRE(hookF >= 0 && (hookF == 0 || num_bags % hookF == 0), CE_ERR_INVALID,
              "hook_features must divide num_bags");
   auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  *vec = (dim % 4 == 0) && al16(a0) && al16(a1) && al16(a2);
+  // a16: an activation tensor of a 16-bit type -- a lane's 4 elements are 8 bytes there, and so is the alignment a row
+  // of dim % 4 == 0 elements keeps (dim = 20, 100 included)
+  *vec = (dim % 4 == 0) && al16(a0) && al16(a1) && al16(a2) && (((uintptr_t)a16) & 7) == 0;
   const int rowlen = *vec ? dim / 4 : dim;
   int g = 1, gl2 = 0;
   while (g < rowlen && g < 64) { g <<= 1; ++gl2; }
@@ -1130,6 +1217,25 @@ static int fill_params(BagParams& p, int32_t dim, const int64_t* indices, int64_
   return CE_OK;
 }
 
+// the activation type of a launch: CE_ACT(act, launch) compiles `launch` once per type with AT naming it
+#define CE_ACT(act, ...)                                          \
+  do {                                                            \
+    if ((act) == CE_ACT_F32) { using AT = float; __VA_ARGS__; }   \
+    else if ((act) == CE_ACT_BF16) { using AT = bf16_t; __VA_ARGS__; } \
+    else { using AT = f16_t; __VA_ARGS__; }                       \
+  } while (0)
+#define CE_REQUIRE_ACT(act)                                                                            \
+  CE_REQUIRE((act) == CE_ACT_F32 || (act) == CE_ACT_BF16 || (act) == CE_ACT_F16, CE_ERR_INVALID,       \
+             "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)(act))
+// the 16-bit activation pointer fill_params checks for 8-byte alignment (fp32 ones go with the 16-byte pointers)
+static inline const void* act16(const void* q, int act) { return act == CE_ACT_F32 ? nullptr : q; }
+static inline const void* act32(const void* q, int act) { return act == CE_ACT_F32 ? q : nullptr; }
+
+// the PAIR form of the key-walking kernels: a 16-bit tensor whose rows are whole 16-byte units
+static inline bool pair16(int act, int32_t dim, const void* q) {
+  return act != CE_ACT_F32 && dim % 8 == 0 && (((uintptr_t)q) & 15) == 0;
+}
+
 static int bag_grid(int64_t num_bags) {
   int64_t tiles = cdiv(num_bags, 64);
   return grid_for(tiles, 4);
@@ -1137,7 +1243,7 @@ static int bag_grid(int64_t num_bags) {
 
 // grad accumulation / fused SGD by target row: grouped segments (ce_bag_presort*) are walked as they are, otherwise
 // the kernel sorts 1024-lookup tiles itself
-static int launch_bwd_scatter(const BagParams& p, bool vec, int nch, hipStream_t s) {
+static int launch_bwd_scatter(const BagParams& p, bool vec, int nch, int act, hipStream_t s) {
   BagParams q = p;
 #ifdef CE_ABLATIONS
   { const char* dbg = getenv("CE_BWD_DEBUG"); q.debug = dbg ? atoi(dbg) : 0; }
@@ -1157,8 +1263,8 @@ static int launch_bwd_scatter(const BagParams& p, bool vec, int nch, hipStream_t
   const bool k32 = q.num_rows <= (1u << 22) - 2;
 #define CE_BWT(VT, N, R)                                                                              \
   do {                                                                                                \
-    if (k32) hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, uint32_t, R>), grid, block, 0, s, q);          \
-    else hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, unsigned long long, R>), grid, block, 0, s, q);    \
+    if (k32) CE_ACT(act, hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, uint32_t, R, AT>), grid, block, 0, s, q));          \
+    else CE_ACT(act, hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, unsigned long long, R, AT>), grid, block, 0, s, q));    \
   } while (0)
   if (vec) {
     if (nch == 1) CE_BWT(f32x4, 1, 16);
@@ -1189,10 +1295,11 @@ static int launch_bwd_rows(const BagParams& p, bool vec, int nch, hipStream_t s)
 
 using namespace ce;
 
-extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
-                              int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
-                              int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
-                              int64_t hook_features, float* out, ce_stream_t stream) {
+extern "C" int ce_bag_forward_act(const float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                  int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                  int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                  int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
   if (num_bags == 0) return CE_OK;
   CE_REQUIRE(weight && out && (indices || nnz == 0), CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(offsets || num_bags == nnz, CE_ERR_INVALID,
@@ -1201,10 +1308,11 @@ extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim
   bool vec;
   int nch;
   int rc = fill_params(p, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       per_sample_weights, mode, hook_features, &vec, &nch, weight, out, nullptr);
+                       per_sample_weights, mode, hook_features, &vec, &nch, weight, act32(out, act_dtype), nullptr,
+                       act16(out, act_dtype));
   if (rc) return rc;
   p.weight = weight;
-  p.dst = out;
+  p.dst = (float*)out;
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   p.num_rows = (uint32_t)num_rows;
   dim3 grid(bag_grid(num_bags)), block(256);
@@ -1212,8 +1320,8 @@ extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim
   const bool stage = nnz != num_bags;      // multi-id bags possible
 #define CE_FWD(VT, N, U)                                                                          \
   do {                                                                                            \
-    if (stage) hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, 1>), grid, block, 0, s, p);          \
-    else hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, 1>), grid, block, 0, s, p);               \
+    if (stage) CE_ACT(act_dtype, hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, 1, AT>), grid, block, 0, s, p));          \
+    else CE_ACT(act_dtype, hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, 1, AT>), grid, block, 0, s, p));               \
   } while (0)
   if (vec) {
     if (nch == 1) CE_FWD(f32x4, 1, 16);
@@ -1226,18 +1334,28 @@ extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim
   return CE_OK;
 }
 
+extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                              int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                              int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                              int64_t hook_features, float* out, ce_stream_t stream) {
+  return ce_bag_forward_act(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                            per_sample_weights, mode, hook_features, out, CE_ACT_F32, stream);
+}
+
 static int backward_dense_impl(float* grad_weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
                                const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
                                int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
-                               int64_t hook_features, const float* grad_out, const unsigned long long* presorted,
+                               int64_t hook_features, const void* grad_out, int act, const unsigned long long* presorted,
                                ce_stream_t stream) {
+  CE_REQUIRE_ACT(act);
   if (num_bags == 0 || nnz == 0) return CE_OK;
   CE_REQUIRE(grad_weight && grad_out && offsets && indices, CE_ERR_INVALID, "null pointer");
   BagParams p{};
   bool vec;
   int nch;
   int rc = fill_params(p, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       per_sample_weights, mode, hook_features, &vec, &nch, grad_weight, grad_out, nullptr);
+                       per_sample_weights, mode, hook_features, &vec, &nch, grad_weight, act32(grad_out, act), nullptr,
+                       act16(grad_out, act));
   if (rc) return rc;
   p.dst = grad_weight;
   p.grad_out = grad_out;
@@ -1245,7 +1363,7 @@ static int backward_dense_impl(float* grad_weight, int64_t num_rows, int32_t dim
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   p.num_rows = (uint32_t)num_rows;
   p.presorted = presorted;
-  return launch_bwd_scatter(p, vec, nch, (hipStream_t)stream);
+  return launch_bwd_scatter(p, vec, nch, act, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_backward_dense(float* grad_weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1254,7 +1372,19 @@ extern "C" int ce_bag_backward_dense(float* grad_weight, int64_t num_rows, int32
                                      const float* per_sample_weights, int32_t mode, int64_t hook_features,
                                      const float* grad_out, ce_stream_t stream) {
   return backward_dense_impl(grad_weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                             include_last_offset, per_sample_weights, mode, hook_features, grad_out, nullptr, stream);
+                             include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32, nullptr,
+                             stream);
+}
+
+extern "C" int ce_bag_backward_dense_act(float* grad_weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                         int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                         int64_t num_bags, int32_t include_last_offset,
+                                         const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                         const void* grad_out, int32_t act_dtype, const uint64_t* presorted_keys,
+                                         ce_stream_t stream) {
+  return backward_dense_impl(grad_weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                             include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                             (const unsigned long long*)presorted_keys, stream);
 }
 
 extern "C" int ce_bag_backward_dense_presorted(float* grad_weight, int64_t num_rows, int32_t dim,
@@ -1265,22 +1395,24 @@ extern "C" int ce_bag_backward_dense_presorted(float* grad_weight, int64_t num_r
                                                const uint64_t* presorted_keys, ce_stream_t stream) {
   CE_REQUIRE(presorted_keys, CE_ERR_INVALID, "null presorted_keys");
   return backward_dense_impl(grad_weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                             include_last_offset, per_sample_weights, mode, hook_features, grad_out,
+                             include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
                              (const unsigned long long*)presorted_keys, stream);
 }
 
 static int backward_sgd_impl(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
                              const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
                              int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
-                             int64_t hook_features, const float* grad_out, float lr,
+                             int64_t hook_features, const void* grad_out, int act, float lr,
                              const unsigned long long* presorted, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act);
   if (num_bags == 0 || nnz == 0) return CE_OK;
   CE_REQUIRE(weight && grad_out && offsets && indices, CE_ERR_INVALID, "null pointer");
   BagParams p{};
   bool vec;
   int nch;
   int rc = fill_params(p, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       per_sample_weights, mode, hook_features, &vec, &nch, weight, grad_out, nullptr);
+                       per_sample_weights, mode, hook_features, &vec, &nch, weight, act32(grad_out, act), nullptr,
+                       act16(grad_out, act));
   if (rc) return rc;
   p.dst = weight;
   p.grad_out = grad_out;
@@ -1288,7 +1420,7 @@ static int backward_sgd_impl(float* weight, int64_t num_rows, int32_t dim, const
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   p.num_rows = (uint32_t)num_rows;
   p.presorted = presorted;
-  return launch_bwd_scatter(p, vec, nch, (hipStream_t)stream);
+  return launch_bwd_scatter(p, vec, nch, act, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_backward_sgd(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1296,7 +1428,18 @@ extern "C" int ce_bag_backward_sgd(float* weight, int64_t num_rows, int32_t dim,
                                    int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
                                    int64_t hook_features, const float* grad_out, float lr, ce_stream_t stream) {
   return backward_sgd_impl(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, lr, nullptr, stream);
+                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32, lr, nullptr,
+                           stream);
+}
+
+extern "C" int ce_bag_backward_sgd_act(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                       int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                       int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                       int64_t hook_features, const void* grad_out, int32_t act_dtype, float lr,
+                                       const uint64_t* presorted_keys, ce_stream_t stream) {
+  return backward_sgd_impl(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype, lr,
+                           (const unsigned long long*)presorted_keys, stream);
 }
 
 extern "C" int ce_bag_backward_sgd_presorted(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1307,23 +1450,24 @@ extern "C" int ce_bag_backward_sgd_presorted(float* weight, int64_t num_rows, in
                                              ce_stream_t stream) {
   CE_REQUIRE(presorted_keys, CE_ERR_INVALID, "null presorted_keys");
   return backward_sgd_impl(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, lr,
+                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32, lr,
                            (const unsigned long long*)presorted_keys, stream);
 }
 
 // keys = row << 32 | grad_out row (ce_bag_presort_window_src); alpha * grad_out rows are folded into dst.
 // seg_ranges (fused SGD only): the batch's segment id ranges from ce_bag_presort_window_src_excl -> owner-exclusive
 // rows are updated with plain read-modify-writes (k_bag_bwd_stream<EXCL>)
-static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t nnz, const float* grad_out,
+static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int act,
                              float alpha, const unsigned long long* keys, const int64_t* seg_ranges, hipStream_t s) {
+  CE_REQUIRE_ACT(act);
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(dst && grad_out && keys, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   BagParams p{};
   bool vec;
   int nch;
-  int rc = fill_params(p, dim, nullptr, nnz, nullptr, 0, 0, 1, nullptr, CE_MODE_SUM, 0, &vec, &nch, dst, grad_out,
-                       nullptr);
+  int rc = fill_params(p, dim, nullptr, nnz, nullptr, 0, 0, 1, nullptr, CE_MODE_SUM, 0, &vec, &nch, dst,
+                       act32(grad_out, act), nullptr, act16(grad_out, act));
   if (rc) return rc;
   p.dst = dst;
   p.grad_out = grad_out;
@@ -1348,16 +1492,31 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
   dim3 g(grid), b(256);
   const long long* rg = (const long long*)seg_ranges;
   const bool excl = seg_ranges != nullptr && vec && nch == 1;
-  if (vec) {
-    if (nch == 1 && excl) hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, 1, 16, true, true>), g, b, 0, s, p, total, rg);
-    else if (nch == 1) hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, 1, 16, true, false>), g, b, 0, s, p, total, rg);
-    else if (nch == 2) hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, 2, 8, true, false>), g, b, 0, s, p, total, rg);
-    else hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, 4, 4, true, false>), g, b, 0, s, p, total, rg);
+#define CE_BWS(VT, N, R, EX) CE_ACT(act, hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, true, EX, AT>), g, b, 0, s, p, total, rg))
+#define CE_BWS2(N, R, EX)                                                                                              \
+  do {                                                                                                                 \
+    if (act == CE_ACT_BF16)                                                                                            \
+      hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, N, R, true, EX, bf16_t, true>), g, b, 0, s, p, total, rg);           \
+    else                                                                                                               \
+      hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, N, R, true, EX, f16_t, true>), g, b, 0, s, p, total, rg);            \
+  } while (0)
+  if (vec && pair16(act, dim, grad_out)) {       // 16-bit gradient, D % 8 == 0: 16 bytes per lane for two keys at a time
+    if (nch == 1 && excl) CE_BWS2(1, 16, true);
+    else if (nch == 1) CE_BWS2(1, 16, false);
+    else if (nch == 2) CE_BWS2(2, 8, false);
+    else CE_BWS2(4, 4, false);
+  } else if (vec) {
+    if (nch == 1 && excl) CE_BWS(f32x4, 1, 16, true);
+    else if (nch == 1) CE_BWS(f32x4, 1, 16, false);
+    else if (nch == 2) CE_BWS(f32x4, 2, 8, false);
+    else CE_BWS(f32x4, 4, 4, false);
   } else {
-    if (nch == 1) hipLaunchKernelGGL((k_bag_bwd_stream<float, 1, 16, true, false>), g, b, 0, s, p, total, rg);
-    else if (nch == 2) hipLaunchKernelGGL((k_bag_bwd_stream<float, 2, 8, true, false>), g, b, 0, s, p, total, rg);
-    else hipLaunchKernelGGL((k_bag_bwd_stream<float, 4, 4, true, false>), g, b, 0, s, p, total, rg);
+    if (nch == 1) CE_BWS(float, 1, 16, false);
+    else if (nch == 2) CE_BWS(float, 2, 8, false);
+    else CE_BWS(float, 4, 4, false);
   }
+#undef CE_BWS
+#undef CE_BWS2
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
@@ -1365,36 +1524,52 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
 extern "C" int ce_bag_backward_sgd_presorted_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                  const float* grad_out, float lr, const uint64_t* src_keys,
                                                  ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, -lr, (const unsigned long long*)src_keys, nullptr,
-                           (hipStream_t)stream);
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, (const unsigned long long*)src_keys,
+                           nullptr, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_backward_sgd_presorted_src_excl(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                       const float* grad_out, float lr, const uint64_t* src_keys,
                                                       const int64_t* seg_id_ranges, ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, -lr, (const unsigned long long*)src_keys,
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, (const unsigned long long*)src_keys,
                            seg_id_ranges, (hipStream_t)stream);
+}
+
+extern "C" int ce_bag_backward_sgd_src_act(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                           const void* grad_out, int32_t act_dtype, float lr, const uint64_t* src_keys,
+                                           const int64_t* seg_id_ranges, ce_stream_t stream) {
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, act_dtype, -lr, (const unsigned long long*)src_keys,
+                           seg_id_ranges, (hipStream_t)stream);
+}
+
+extern "C" int ce_bag_backward_dense_src_act(float* grad_weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                             const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                             ce_stream_t stream) {
+  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, act_dtype, 1.f,
+                           (const unsigned long long*)src_keys, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_backward_dense_presorted_src(float* grad_weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                    const float* grad_out, const uint64_t* src_keys,
                                                    ce_stream_t stream) {
-  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, 1.f, (const unsigned long long*)src_keys, nullptr,
-                           (hipStream_t)stream);
+  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, 1.f,
+                           (const unsigned long long*)src_keys, nullptr, (hipStream_t)stream);
 }
 
-extern "C" int ce_bag_forward_src_keys(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
-                                       const uint64_t* src_keys, float* out, ce_stream_t stream) {
+extern "C" int ce_bag_forward_src_keys_act(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                           const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   BagParams p{};
   bool vec;
   int nch;
-  int rc = fill_params(p, dim, nullptr, nnz, nullptr, 0, 0, 1, nullptr, CE_MODE_SUM, 0, &vec, &nch, weight, out, nullptr);
+  int rc = fill_params(p, dim, nullptr, nnz, nullptr, 0, 0, 1, nullptr, CE_MODE_SUM, 0, &vec, &nch, weight,
+                       act32(out, act_dtype), nullptr, act16(out, act_dtype));
   if (rc) return rc;
   p.weight = weight;
-  p.dst = out;
+  p.dst = (float*)out;
   p.num_rows = (uint32_t)num_rows;
   p.presorted = (const unsigned long long*)src_keys;
   p.interleave = 0;
@@ -1407,16 +1582,32 @@ extern "C" int ce_bag_forward_src_keys(const float* weight, int64_t num_rows, in
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)kNumCU * per_cu, cdiv(total, (int64_t)ngroups * 16)));
   dim3 g(grid), b(256);
   hipStream_t s = (hipStream_t)stream;
-#define CE_FWK(VT, N, R) hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1>), g, b, 0, s, p, total)
-  if (vec) {
+#define CE_FWK(VT, N, R) CE_ACT(act_dtype, hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT>), g, b, 0, s, p, total))
+#define CE_FWK2(N, R)                                                                                     \
+  do {                                                                                                    \
+    if (act_dtype == CE_ACT_BF16)                                                                         \
+      hipLaunchKernelGGL((k_bag_fwd_keys<f32x4, N, R, 1, bf16_t, true>), g, b, 0, s, p, total);           \
+    else                                                                                                  \
+      hipLaunchKernelGGL((k_bag_fwd_keys<f32x4, N, R, 1, f16_t, true>), g, b, 0, s, p, total);            \
+  } while (0)
+  if (vec && pair16(act_dtype, dim, out)) {      // 16-bit output, D % 8 == 0: 16 bytes per lane for two keys at a time
+    if (nch == 1) CE_FWK2(1, 16);
+    else if (nch == 2) CE_FWK2(2, 8); else CE_FWK2(4, 4);
+  } else if (vec) {
     if (nch == 1) CE_FWK(f32x4, 1, 16);
     else if (nch == 2) CE_FWK(f32x4, 2, 8); else CE_FWK(f32x4, 4, 4);
   } else {
     if (nch == 1) CE_FWK(float, 1, 16); else if (nch == 2) CE_FWK(float, 2, 8); else CE_FWK(float, 4, 4);
   }
 #undef CE_FWK
+#undef CE_FWK2
   CE_LAUNCH_CHECK();
   return CE_OK;
+}
+
+extern "C" int ce_bag_forward_src_keys(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                       const uint64_t* src_keys, float* out, ce_stream_t stream) {
+  return ce_bag_forward_src_keys_act(weight, num_rows, dim, nnz, src_keys, out, CE_ACT_F32, stream);
 }
 
 extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : cdiv(nnz, kSegLen) * kSegLen; }

@@ -125,7 +125,7 @@ static AdagradWs carve_adagrad(void* ws, int64_t num_rows, int32_t dim) {
   return w;
 }
 
-static int adagrad_check(float* weight, int64_t num_rows, int32_t dim, const float* grad_out, float* momentum,
+static int adagrad_check(float* weight, int64_t num_rows, int32_t dim, const void* grad_out, float* momentum,
                          int64_t momentum_rows, float lr, float eps, void* workspace, size_t workspace_bytes) {
   CE_REQUIRE(weight && grad_out && momentum && workspace, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
@@ -181,14 +181,17 @@ extern "C" size_t ce_bag_backward_rowwise_adagrad_workspace(int64_t num_rows, in
   return carve_adagrad(nullptr, num_rows, dim).bytes;
 }
 
-extern "C" int ce_bag_backward_rowwise_adagrad(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
-                                               int64_t nnz, const void* offsets, int32_t offsets_are_i64,
-                                               int64_t num_bags, int32_t include_last_offset,
-                                               const float* per_sample_weights, int32_t mode, int64_t hook_features,
-                                               const float* grad_out, const uint64_t* presorted,
-                                               const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
-                                               float lr, float eps, void* workspace, size_t workspace_bytes,
-                                               ce_stream_t stream) {
+// grad_out of the activation type act_dtype: step 2 reads it natively, acc and everything after it are fp32
+extern "C" int ce_bag_backward_rowwise_adagrad_act(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                                   int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                                   int64_t num_bags, int32_t include_last_offset,
+                                                   const float* per_sample_weights, int32_t mode,
+                                                   int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                                   const uint64_t* presorted, const int32_t* row_of_slot,
+                                                   float* momentum, int64_t momentum_rows, float lr, float eps,
+                                                   void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  CE_REQUIRE(act_dtype == CE_ACT_F32 || act_dtype == CE_ACT_BF16 || act_dtype == CE_ACT_F16, CE_ERR_INVALID,
+             "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)act_dtype);
   if (num_bags == 0 || nnz == 0) return CE_OK;
   int rc = adagrad_check(weight, num_rows, dim, grad_out, momentum, momentum_rows, lr, eps, workspace, workspace_bytes);
   if (rc) return rc;
@@ -198,21 +201,34 @@ extern "C" int ce_bag_backward_rowwise_adagrad(float* weight, int64_t num_rows, 
   hipLaunchKernelGGL(k_adagrad_mark_slots, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz,
                      (uint32_t)num_rows, ws.flags);
   CE_LAUNCH_CHECK();
-  rc = presorted ? ce_bag_backward_dense_presorted(ws.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64,
-                                                   num_bags, include_last_offset, per_sample_weights, mode,
-                                                   hook_features, grad_out, presorted, stream)
-                 : ce_bag_backward_dense(ws.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                                         include_last_offset, per_sample_weights, mode, hook_features, grad_out,
-                                         stream);
+  rc = ce_bag_backward_dense_act(ws.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                                 include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                                 presorted, stream);
   if (rc) return rc;
   return launch_apply(weight, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps, ws, s);
 }
 
-extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
-                                                   const float* grad_out, const uint64_t* src_keys,
-                                                   const int32_t* row_of_slot, float* momentum,
-                                                   int64_t momentum_rows, float lr, float eps, void* workspace,
-                                                   size_t workspace_bytes, ce_stream_t stream) {
+extern "C" int ce_bag_backward_rowwise_adagrad(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                               int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                               int64_t num_bags, int32_t include_last_offset,
+                                               const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                               const float* grad_out, const uint64_t* presorted,
+                                               const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
+                                               float lr, float eps, void* workspace, size_t workspace_bytes,
+                                               ce_stream_t stream) {
+  return ce_bag_backward_rowwise_adagrad_act(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                                             include_last_offset, per_sample_weights, mode, hook_features, grad_out,
+                                             CE_ACT_F32, presorted, row_of_slot, momentum, momentum_rows, lr, eps,
+                                             workspace, workspace_bytes, stream);
+}
+
+extern "C" int ce_bag_backward_rowwise_adagrad_src_act(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                                       const void* grad_out, int32_t act_dtype,
+                                                       const uint64_t* src_keys, const int32_t* row_of_slot,
+                                                       float* momentum, int64_t momentum_rows, float lr, float eps,
+                                                       void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  CE_REQUIRE(act_dtype == CE_ACT_F32 || act_dtype == CE_ACT_BF16 || act_dtype == CE_ACT_F16, CE_ERR_INVALID,
+             "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)act_dtype);
   if (nnz == 0) return CE_OK;
   int rc = adagrad_check(weight, num_rows, dim, grad_out, momentum, momentum_rows, lr, eps, workspace, workspace_bytes);
   if (rc) return rc;
@@ -223,7 +239,17 @@ extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_ro
   hipLaunchKernelGGL(k_adagrad_mark_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
                      (const unsigned long long*)src_keys, total, (uint32_t)num_rows, ws.flags);
   CE_LAUNCH_CHECK();
-  rc = ce_bag_backward_dense_presorted_src(ws.acc, num_rows, dim, nnz, grad_out, src_keys, stream);
+  rc = ce_bag_backward_dense_src_act(ws.acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
   if (rc) return rc;
   return launch_apply(weight, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps, ws, s);
+}
+
+extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                                   const float* grad_out, const uint64_t* src_keys,
+                                                   const int32_t* row_of_slot, float* momentum,
+                                                   int64_t momentum_rows, float lr, float eps, void* workspace,
+                                                   size_t workspace_bytes, ce_stream_t stream) {
+  return ce_bag_backward_rowwise_adagrad_src_act(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, src_keys,
+                                                 row_of_slot, momentum, momentum_rows, lr, eps, workspace,
+                                                 workspace_bytes, stream);
 }

@@ -37,6 +37,37 @@ template <typename VT> __device__ __forceinline__ VT vzero();
 template <> __device__ __forceinline__ float vzero<float>() { return 0.f; }
 template <> __device__ __forceinline__ f32x4 vzero<f32x4>() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
+// Activation type AT of the bag kernels (API 6 additions: CE_ACT_*): what the forward's output and the backward's
+// grad_out are stored as.  The table, the accumulation and the update stay fp32, and a lane keeps the same elements of
+// a row whatever AT is: Act<AT, VT>::V is the memory form of a lane's VT (VT itself for fp32; 4 x 16 bit = 8 bytes for
+// f32x4, one 16-bit scalar for float).  down() is the plain cast -- round-to-nearest-even, NaN stays NaN
+// (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32) --, up() is exact.
+typedef __bf16 bf16_t;
+typedef _Float16 f16_t;
+typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
+typedef f16_t f16x4 __attribute__((ext_vector_type(4)));
+
+template <typename AT, typename VT> struct Act;
+template <typename VT> struct Act<float, VT> {
+  typedef VT V;
+  static __device__ __forceinline__ VT up(V a) { return a; }
+  static __device__ __forceinline__ V down(VT v) { return v; }
+};
+#define CE_ACT16(AT, AT4)                                                                                     \
+  template <> struct Act<AT, float> {                                                                         \
+    typedef AT V;                                                                                             \
+    static __device__ __forceinline__ float up(V a) { return (float)a; }                                      \
+    static __device__ __forceinline__ V down(float v) { return (AT)v; }                                       \
+  };                                                                                                          \
+  template <> struct Act<AT, f32x4> {                                                                         \
+    typedef AT4 V;                                                                                            \
+    static __device__ __forceinline__ f32x4 up(V a) { return __builtin_convertvector(a, f32x4); }             \
+    static __device__ __forceinline__ V down(f32x4 v) { return __builtin_convertvector(v, AT4); }             \
+  };
+CE_ACT16(bf16_t, bf16x4)
+CE_ACT16(f16_t, f16x4)
+#undef CE_ACT16
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // MI355X: 256 CUs; memory-bound grid-stride kernels are capped at 8 blocks of 256 per CU.

@@ -67,7 +67,7 @@ class SrcKeys(NamedTuple):
 class _BagFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, indices, offsets, psw, mode, include_last, hook_features, sparse, fused, presorted,
-                bwd_scale=None, masked=False, out_box=None):
+                bwd_scale=None, masked=False, out_box=None, out_dtype=torch.float32):
         _lib.require_gpu()
         assert weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous()
         if psw is not None and ctx.needs_input_grad[3] and fused is not None and fused.lr is not None:
@@ -83,13 +83,26 @@ class _BagFn(torch.autograd.Function):
             # the caller's buffer (embedding_bag(out=...)): a static output for graph-captured steps, or one chosen by
             # pick_fast_buffer.  It comes in a box because it is no input of the autograd function.
             out = out_box[0]
-            if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or \
+            if tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous() or \
                     out.device != weight.device:
-                raise ValueError(f"out= must be a contiguous fp32 tensor of shape {shape} on {weight.device}")
+                raise ValueError(f"out= must be a contiguous {_DTYPE_NAMES[out_dtype]} tensor of shape {shape} on "
+                                 f"{weight.device}")
         else:
-            out = torch.empty(shape, device=weight.device, dtype=torch.float32)
-        if FORWARD_FROM_KEYS and isinstance(presorted, SrcKeys) and presorted.identity and psw is None \
-                and mode == _lib.CE_MODE_SUM and num_bags == indices.numel():
+            out = torch.empty(shape, device=weight.device, dtype=out_dtype)
+        from_keys = FORWARD_FROM_KEYS and isinstance(presorted, SrcKeys) and presorted.identity and psw is None \
+            and mode == _lib.CE_MODE_SUM and num_bags == indices.numel()
+        if out_dtype != torch.float32:
+            # 16-bit output: the same two kernels store the rounded row themselves (the ce_*_act entries)
+            act = _lib.ACT_DTYPES[out_dtype]
+            if from_keys:
+                check(lib.ce_bag_forward_src_keys_act(ptr(weight), weight.shape[0], dim, indices.numel(),
+                                                      ptr(presorted.keys), ptr(out), act, stream_ptr()))
+            else:
+                check(lib.ce_bag_forward_act(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(),
+                                             ptr(offsets), int(offsets.dtype == torch.int64), num_bags,
+                                             int(include_last), ptr(psw), mode, hook_features, ptr(out), act,
+                                             stream_ptr()))
+        elif from_keys:
             # one id per bag: out[bag] = W[slot], and the window's keys hold (slot, output row) grouped by slot
             check(lib.ce_bag_forward_src_keys(ptr(weight), weight.shape[0], dim, indices.numel(), ptr(presorted.keys),
                                               ptr(out), stream_ptr()))
@@ -115,7 +128,16 @@ class _BagFn(torch.autograd.Function):
         off64 = int(offsets.dtype == torch.int64)
         nnz = indices.numel()
         gw = None
-        if isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None:
+        act16 = False
+        if grad_out.dtype != torch.float32:
+            # a 16-bit gradient (what autograd delivers for a 16-bit output): the hot paths read it natively
+            # (_backward_act16); everything else takes its exact upcast through the fp32 entries below
+            act16, gw = _backward_act16(ctx, grad_out, indices, offsets, psw)
+            if not act16:
+                grad_out = grad_out.float()
+        if act16:
+            pass
+        elif isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None:
             # exact row-wise Adagrad inside backward (ce_bag_adagrad.hip): the optimizer sees grad=None
             with torch.no_grad():
                 ws = fused.workspace(weight.shape[0], dim, weight.device)
@@ -211,6 +233,8 @@ class _BagFn(torch.autograd.Function):
                                                 num_bags, int(include_last), ptr(psw), mode, hook_features,
                                                 ptr(grad_out), stream_ptr()))
         gpsw = None
+        if ctx.needs_input_grad[3] and grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()              # (off the hot path: ce_bag_backward_psw reads fp32)
         if ctx.needs_input_grad[3]:
             # d loss / d per_sample_weights[j] = <grad_out[bag of j], weight[indices[j]]> (the combination with the
             # fused update was refused in forward)
@@ -218,7 +242,68 @@ class _BagFn(torch.autograd.Function):
             check(lib.ce_bag_backward_psw(ptr(weight), weight.shape[0], dim, ptr(indices), nnz, ptr(offsets), off64,
                                           num_bags, int(include_last), hook_features, ptr(grad_out), ptr(gpsw),
                                           stream_ptr()))
-        return gw, None, None, gpsw, None, None, None, None, None, None, None, None, None
+        return gw, None, None, gpsw, None, None, None, None, None, None, None, None, None, None
+
+
+_DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
+
+
+def _backward_act16(ctx, grad_out, indices, offsets, psw):
+    """The hot backward paths with a bf16 / fp16 grad_out read in place by the kernels (the ce_*_act entries): row-wise
+    Adagrad (both entries), fused SGD (atomics: slots + offsets, presorted, source-row keys with and without owner
+    ranges) and the dense gradient (the same three).  Returns (True, grad_weight or None); (False, None): not one of
+    them -- deterministic fused SGD and the two sparse=True forms -- and nothing has run; the caller upcasts."""
+    weight = ctx.weight
+    mode, include_last, hook_features, sparse, fused, num_bags = ctx.args
+    act = _lib.ACT_DTYPES.get(grad_out.dtype)
+    if act is None:
+        raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
+    dim = weight.shape[1]
+    off64 = int(offsets.dtype == torch.int64)
+    nnz = indices.numel()
+    R = weight.shape[0]
+    pre = ctx.presorted
+    src = isinstance(pre, SrcKeys)
+    if isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None:
+        with torch.no_grad():
+            ws = fused.workspace(R, dim, weight.device)
+            mom = fused.momentum
+            if src:
+                check(lib.ce_bag_backward_rowwise_adagrad_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act,
+                                                                  ptr(pre.keys), ptr(fused.row_of_slot), ptr(mom),
+                                                                  mom.numel(), float(fused.lr), float(fused.eps),
+                                                                  ptr(ws), ws.numel(), stream_ptr()))
+            else:
+                check(lib.ce_bag_backward_rowwise_adagrad_act(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets),
+                                                              off64, num_bags, int(include_last), ptr(psw), mode,
+                                                              hook_features, ptr(grad_out), act, ptr(pre),
+                                                              ptr(fused.row_of_slot), ptr(mom), mom.numel(),
+                                                              float(fused.lr), float(fused.eps), ptr(ws), ws.numel(),
+                                                              stream_ptr()))
+        return True, None
+    if fused is not None and fused.lr is not None:
+        if fused.deterministic:
+            return False, None
+        with torch.no_grad():
+            if src:
+                check(lib.ce_bag_backward_sgd_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act, float(fused.lr),
+                                                      ptr(pre.keys), ptr(pre.ranges), stream_ptr()))
+            else:
+                check(lib.ce_bag_backward_sgd_act(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64,
+                                                  num_bags, int(include_last), ptr(psw), mode, hook_features,
+                                                  ptr(grad_out), act, float(fused.lr), ptr(pre), stream_ptr()))
+        return True, None
+    if sparse:
+        return False, None
+    gw = torch.zeros_like(weight)
+    if src:
+        check(lib.ce_bag_backward_dense_src_act(ptr(gw), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys),
+                                                stream_ptr()))
+    else:
+        check(lib.ce_bag_backward_dense_act(ptr(gw), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags,
+                                            int(include_last), ptr(psw), mode, hook_features, ptr(grad_out), act,
+                                            ptr(pre), stream_ptr()))
+    return True, gw
 
 
 # forward from the window's source-row keys when they were built for the one-id-per-bag layout (False: always the
@@ -343,9 +428,16 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                   include_last_offset: bool = False, padding_idx: Optional[int] = None, *,
                   hook_features: int = 0, fused_sgd: Union[FusedSGD, FusedRowwiseAdagrad, None] = None,
                   presorted: Union[torch.Tensor, SrcKeys, None] = None, masked_indices: bool = False,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    # out: write the pooled output into this tensor (contiguous fp32, the shape the call would allocate) and return it --
+                  out: Optional[torch.Tensor] = None, output_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    # out: write the pooled output into this tensor (contiguous, of the output dtype and the shape the call would
+    # allocate) and return it --
     # a static output buffer for steps replayed from a hipGraph, possibly one chosen by pick_fast_buffer
+    # output_dtype: None / torch.float32 (the default), torch.bfloat16 or torch.float16 -- the dtype of the pooled output
+    # and hence of the gradient autograd hands back; the weight, the sums and every update stay fp32, the kernels
+    # round once on the store and read the 16-bit gradient in place.  out= must then have that dtype.
+    _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
+    if output_dtype is None:
+        output_dtype = torch.float32
     # masked_indices: the caller already replaced ignored lookups (padding) by -1 -- the kernels skip them; the
     # sparse=True backward then parks their (zero) gradient rows at index 0 so the COO tensor stays valid
     if mode not in _MODES and mode != "max":
@@ -382,7 +474,9 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
             indices = torch.where(indices == padding_idx, torch.full_like(indices, -1), indices)
         if out is not None:
             raise NotImplementedError("out= with mode='max'")
-        return _BagMaxFn.apply(weight, indices, offsets, bool(include_last_offset), int(hook_features), fused_sgd)
+        res = _BagMaxFn.apply(weight, indices, offsets, bool(include_last_offset), int(hook_features), fused_sgd)
+        # (off the hot path: the fp32 kernel and one cast behind it; autograd upcasts the gradient on the way back)
+        return res if output_dtype == torch.float32 else res.to(output_dtype)
     if per_sample_weights is not None and per_sample_weights.numel() != indices.numel():
         raise ValueError("per_sample_weights must have the same number of elements as input")
     bwd_scale = None
@@ -455,7 +549,7 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                                   "the per-bag count of non-padding entries)")
     return _BagFn.apply(weight, indices, offsets, per_sample_weights, _MODES[mode], bool(include_last_offset),
                         int(hook_features), bool(sparse), fused_sgd, presorted, bwd_scale,
-                        padding_idx is not None or bool(masked_indices), None if out is None else [out])
+                        padding_idx is not None or bool(masked_indices), None if out is None else [out], output_dtype)
 
 
 def probe_rows(buf: torch.Tensor, fold: int, reps: int = 6):

@@ -17,6 +17,7 @@ from typing import Any, Iterable, List, Optional, Sequence, Union
 import torch
 import torch.nn as nn
 
+from . import _lib
 from .cache_mgr import EvictionStrategy
 from .parallel import KJTAllToAll, ParallelCachedEmbeddingBag
 
@@ -125,8 +126,14 @@ class FusedSparseModules(nn.Module):
                  reduction_mode: str = "sum", sparse: bool = False, output_device_type=None, use_cache: bool = False,
                  cache_ratio: float = 0.01, id_freq_map=None, warmup_ratio: float = 0.7, buffer_size: int = 50_000,
                  is_dist_dataloader: bool = True, use_lfu_eviction: bool = False, use_tablewise_parallel: bool = False,
-                 dataset: Optional[str] = None, fold_hook: bool = False, group=None):
+                 dataset: Optional[str] = None, fold_hook: bool = False, group=None,
+                 output_dtype: Optional[torch.dtype] = None):
         super().__init__()
+        # output_dtype (addition): dtype of the pooled embeddings (CachedEmbeddingBag(output_dtype=...)); single-rank
+        # column-wise operator only
+        if use_tablewise_parallel and _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"FusedSparseModules(use_tablewise_parallel=True, output_dtype={output_dtype}): "
+                                      "the table-wise all-to-all of the pooled output is fp32")
         self.sparse_feature_num = len(num_embeddings_per_feature)
         self.fold_hook = fold_hook
         if not use_cache:
@@ -146,7 +153,7 @@ class FusedSparseModules(nn.Module):
                                                     mode=reduction_mode, include_last_offset=True,
                                                     cache_ratio=cache_ratio, ids_freq_mapping=id_freq_map,
                                                     warmup_ratio=warmup_ratio, buffer_size=buffer_size,
-                                                    evict_strategy=strategy, group=group)
+                                                    evict_strategy=strategy, group=group, output_dtype=output_dtype)
             self.shape_hook = sparse_embedding_shape_hook
         dist_on = torch.distributed.is_initialized()
         self.kjt_collector = KJTAllToAll(group) if (is_dist_dataloader and dist_on) else None

@@ -526,8 +526,11 @@ class RowwiseShardedEmbeddingBag(nn.Module):
                  cache_ratio: float = 0.01, ids_freq_mapping=None, warmup_ratio: float = 0.7,
                  evict_strategy: EvictionStrategy = EvictionStrategy.DATASET, group=None,
                  _weight_shard: Optional[torch.Tensor] = None, init_seed: int = 1024,
-                 cuda_row_num: Optional[int] = None):
+                 cuda_row_num: Optional[int] = None, output_dtype: Optional[torch.dtype] = None):
         super().__init__()
+        if _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"RowwiseShardedEmbeddingBag with output_dtype={output_dtype}: the row-wise "
+                                      "exchange buffers are fp32")
         _lib.require_gpu()
         self.group = group if group is not None else dist.group.WORLD
         self.world = dist.get_world_size(self.group)
@@ -725,7 +728,10 @@ class GraphedShardedWindow:
                  transport: Optional[str] = None, warmup_ids: Optional[Sequence[torch.Tensor]] = None,
                  split: Optional[bool] = None, split_caps: Optional[Sequence[int]] = None,
                  arrangement: Optional[str] = None, arrangement_trial: Optional[dict] = None,
-                 static_out_candidates: int = 0, before_capture=None):
+                 static_out_candidates: int = 0, before_capture=None, output_dtype: Optional[torch.dtype] = None):
+        if _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"GraphedShardedWindow with output_dtype={output_dtype}: the row-wise exchange "
+                                      "buffers are fp32")
         # static_out_candidates > 0 (one-id-per-bag layouts; needs warmup_ids): the pooled output of every step is ONE
         # static buffer, the fastest of that many candidate allocations for this window's own forward
         # (functional.pick_fast_buffer(work=...): the same launch takes 37 or 45 us depending on how its output is
@@ -1394,6 +1400,7 @@ class ParallelCachedEmbeddingBag(CachedEmbeddingBag):
         self.group = group if group is not None else (dist.group.WORLD if dist.is_initialized() else None)
         self.rank = dist.get_rank(self.group) if self.group is not None else 0
         self.world_size = dist.get_world_size(self.group) if self.group is not None else 1
+        self._refuse_act16(kw.get("output_dtype"))            # before anything is allocated
         self.full_embedding_dim = embedding_dim
         lo, hi, _ = get_partition(embedding_dim, self.rank, self.world_size)
         self.partition_start_index, self.partition_end_index = lo, hi
@@ -1402,6 +1409,15 @@ class ParallelCachedEmbeddingBag(CachedEmbeddingBag):
         super().__init__(num_embeddings, hi - lo, padding_idx, max_norm, norm_type, scale_grad_by_freq, sparse,
                          _weight, mode, include_last_offset, dtype, device, cache_ratio, ids_freq_mapping,
                          warmup_ratio, buffer_size, pin_weight, evict_strategy, **kw)
+
+    def _refuse_act16(self, dtype):
+        if self.world_size > 1 and _lib.act_code(dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"ParallelCachedEmbeddingBag with output_dtype={dtype} on {self.world_size} "
+                                      "ranks: the all-to-all of the pooled output is fp32")
+
+    def set_output_dtype(self, dtype):
+        self._refuse_act16(dtype)
+        super().set_output_dtype(dtype)
 
     def forward(self, indices, offsets=None, per_sample_weights=None, shape_hook=None, scatter_dim=0, gather_dim=-1,
                 *, hook_features: int = 0, presorted=None):

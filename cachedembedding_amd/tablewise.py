@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import _lib
 from .cache_mgr import EvictionStrategy
 from .cached_embedding import CachedEmbeddingBag
 from .parallel import dual_all_to_all
@@ -67,8 +68,11 @@ class ParallelCachedEmbeddingBagTablewise(nn.Module):
                  padding_idx=None, max_norm=None, norm_type=2.0, scale_grad_by_freq=False, sparse=False,
                  mode: str = "mean", include_last_offset: bool = False, dtype=None, device=None,
                  warmup_ratio: float = 0.7, buffer_size: int = 50_000, pin_weight: bool = False,
-                 evict_strategy: EvictionStrategy = EvictionStrategy.LFU, group=None):
+                 evict_strategy: EvictionStrategy = EvictionStrategy.LFU, group=None, output_dtype=None):
         super().__init__()
+        if _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"ParallelCachedEmbeddingBagTablewise with output_dtype={output_dtype}: the "
+                                      "all-to-all of the pooled output is fp32")
         self.group = group if group is not None else (dist.group.WORLD if dist.is_initialized() else None)
         self.rank = dist.get_rank(self.group) if self.group is not None else 0
         self.world_size = dist.get_world_size(self.group) if self.group is not None else 1

@@ -113,8 +113,23 @@ def parse_args(argv=None):
                    help="the dense part's GEMMs through torch's TunableOp (stock torch: every GEMM shape of the two MLPs and "
                         "of the interaction is timed once over the rocBLAS / hipBLASLt solutions and the fastest kept; fp32 "
                         "as before, nothing hand-written) -- VERDICT r5 #6")
+    p.add_argument("--embedding_output_dtype", default="fp32", choices=["fp32", "bf16"],
+                   help="dtype of the pooled embeddings (CachedEmbeddingBag(output_dtype=...)).  bf16: the embedding "
+                        "kernels write bf16 and read the bf16 gradient in place (the table and its update stay fp32), "
+                        "and the dense part's forward runs under torch.autocast('cuda', torch.bfloat16).  One process, "
+                        "without --use_tablewise.  (fp16 is a library option only: a trainer would need loss scaling)")
     p.add_argument("--json_out", type=str, default=None, help="write the run's numbers as one JSON object")
     return p.parse_args(argv)
+
+
+_OUTPUT_DTYPES = {"fp32": None, "bf16": torch.bfloat16}
+
+
+def check_output_dtype(args, world: int) -> None:
+    """--embedding_output_dtype bf16 is refused, before anything is built, where the pooled output crosses ranks"""
+    if args.embedding_output_dtype != "fp32" and (world > 1 or args.use_tablewise):
+        raise NotImplementedError("--embedding_output_dtype bf16 is implemented for one process without "
+                                  "--use_tablewise (the all-to-all of the pooled output is fp32)")
 
 
 def mlp(sizes: List[int], last_activation: bool) -> nn.Sequential:
@@ -154,7 +169,9 @@ class HybridParallelDLRM(nn.Module):
             use_cache=args.use_cache, cache_ratio=args.cache_ratio, id_freq_map=id_freq_map,
             warmup_ratio=args.warmup_ratio, buffer_size=args.buffer_size,
             is_dist_dataloader=args.use_distributed_dataloader, use_lfu_eviction=args.use_lfu,
-            use_tablewise_parallel=args.use_tablewise, dataset=args.dataset, fold_hook=args.fold_hook)
+            use_tablewise_parallel=args.use_tablewise, dataset=args.dataset, fold_hook=args.fold_hook,
+            output_dtype=_OUTPUT_DTYPES[args.embedding_output_dtype])
+        self.autocast = args.embedding_output_dtype == "bf16"
         dense = DenseModules(args.num_dense_features, len(sizes), args.embedding_dim,
                              [int(x) for x in args.dense_arch_layer_sizes.split(",")],
                              [int(x) for x in args.over_arch_layer_sizes.split(",")]).to(device)
@@ -166,6 +183,10 @@ class HybridParallelDLRM(nn.Module):
 
     def forward(self, dense, sparse, cache_op: bool = True, presorted=None):
         emb = self.sparse_modules(sparse, cache_op=cache_op, presorted=presorted)     # [B(/W), F, D]
+        if self.autocast:
+            # bf16 pooled embeddings: the dense part's GEMMs in bf16 too; the logits go back to fp32 for the loss
+            with torch.autocast("cuda", torch.bfloat16):
+                return self.dense_modules(dense, emb).float()
         return self.dense_modules(dense, emb)
 
 
@@ -467,6 +488,7 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    check_output_dtype(args, world)
     if args.adagrad:
         if args.fused_sgd:
             raise ValueError("--adagrad takes the place of --fused_sgd: pass one of them")
@@ -570,7 +592,8 @@ def main(argv=None):
                     "num_embeddings": int(sum(sizes)), "embedding_dim": args.embedding_dim, "features": len(sizes),
                     "batch_size": args.batch_size, "prefetch_num": args.prefetch_num, "cache_ratio": args.cache_ratio,
                     "cuda_row_num": int(mgr.cuda_row_num), "dense_arch": args.dense_arch_layer_sizes,
-                    "over_arch": args.over_arch_layer_sizes, "dtype": "f32", "data": "synthetic",
+                    "over_arch": args.over_arch_layer_sizes, "dtype": "f32", "embedding_output_dtype": args.embedding_output_dtype,
+                    "data": "synthetic",
                     "surface": {k: bool(getattr(args, k)) for k in ("use_overlap", "overlap_cache_op", "fused_sgd",
                                                                     "adagrad", "fold_hook", "window_keys", "tunable_gemm", "graph_step",
                                                                     "use_sparse_embed_grad", "use_lfu", "use_freq")},

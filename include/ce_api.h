@@ -46,6 +46,12 @@ extern "C" {
 #define CE_MODE_SUM 0
 #define CE_MODE_MEAN 1
 
+/* Activation dtype of the bag kernels' output / incoming gradient (the ce_*_act entries; additions to API 6).  The
+ * table, the accumulation and every update stay fp32; only what the forward stores and the backward reads changes. */
+#define CE_ACT_F32 0
+#define CE_ACT_BF16 1    /* bfloat16: round-to-nearest-even on the store, NaN stays NaN */
+#define CE_ACT_F16 2     /* IEEE half: round-to-nearest-even, values beyond 65504 become inf */
+
 /* how missed / evicted rows move between the host table and the HBM cache */
 #define CE_TRANSPORT_ZEROCOPY 0  /* swap kernels read/write the mapped pinned host table over PCIe */
 #define CE_TRANSPORT_STAGED 1    /* host threads gather/scatter through pinned staging + hipMemcpyAsync */
@@ -293,6 +299,57 @@ int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_rows, int32_t
                                         const float* grad_out, const uint64_t* src_keys, const int32_t* row_of_slot,
                                         float* momentum, int64_t momentum_rows, float lr, float eps, void* workspace,
                                         size_t workspace_bytes, ce_stream_t stream);
+
+/* Half-precision activations (additions to API 6).  The entries below are the hot-path entries above with the
+ * pooled output / the incoming gradient as `void*` of act_dtype (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16) -- fp32
+ * weight, fp32 accumulation, ONE rounding on the forward's store, an exact upcast on the backward's gather; the 16-bit
+ * tensor is read / written by the kernel itself (no staging tensor, no extra launch, capture-safe as their fp32
+ * forms).  With CE_ACT_F32 each is its fp32 form, which now forwards here.  Fewer entries than there: `presorted_keys`
+ * (NULL = the kernel sorts its own tiles) merges ce_bag_backward_{dense,sgd} with their _presorted forms, and
+ * `seg_id_ranges` (NULL = atomics everywhere) merges ce_bag_backward_sgd_presorted_src with its _excl form.
+ * A 16-bit tensor must be 2-byte aligned; 8-byte aligned with dim % 4 == 0 takes the vector kernels (a lane moves its
+ * 4 elements as 8 bytes: dim = 20 or 100 qualify), anything else the scalar ones (dim <= 256).  The two key-driven
+ * kernels (ce_bag_forward_src_keys_act, the _src_act backwards) move 16 bytes per lane -- two keys per lane pair --
+ * when dim % 8 == 0 and the tensor is 16-byte aligned (what torch allocates).  An unknown act_dtype
+ * returns CE_ERR_INVALID and launches nothing.  Off the hot path (ce_bag_forward_max, ce_bag_backward_max / _psw /
+ * _rows / _sgd_sorted) there is no _act form: a caller converts. */
+int ce_bag_forward_act(const float* weight, int64_t num_rows, int32_t dim,
+                       const int64_t* indices, int64_t nnz,
+                       const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                       int32_t include_last_offset, const float* per_sample_weights,
+                       int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_forward_src_keys_act(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_backward_dense_act(float* grad_weight, int64_t num_rows, int32_t dim,
+                              const int64_t* indices, int64_t nnz,
+                              const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                              int32_t include_last_offset, const float* per_sample_weights,
+                              int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                              const uint64_t* presorted_keys, ce_stream_t stream);
+int ce_bag_backward_sgd_act(float* weight, int64_t num_rows, int32_t dim,
+                            const int64_t* indices, int64_t nnz,
+                            const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                            int32_t include_last_offset, const float* per_sample_weights,
+                            int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype, float lr,
+                            const uint64_t* presorted_keys, ce_stream_t stream);
+int ce_bag_backward_sgd_src_act(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                const void* grad_out, int32_t act_dtype, float lr, const uint64_t* src_keys,
+                                const int64_t* seg_id_ranges, ce_stream_t stream);
+int ce_bag_backward_dense_src_act(float* grad_weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                  const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                  ce_stream_t stream);
+int ce_bag_backward_rowwise_adagrad_act(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                        int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                        int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                        int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                        const uint64_t* presorted, const int32_t* row_of_slot, float* momentum,
+                                        int64_t momentum_rows, float lr, float eps, void* workspace,
+                                        size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_rowwise_adagrad_src_act(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                            const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                            const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
+                                            float lr, float eps, void* workspace, size_t workspace_bytes,
+                                            ce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6].  Device state arrays are owned by the caller (so the Python
