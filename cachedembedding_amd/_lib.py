@@ -76,7 +76,23 @@ class CeCallStats(Structure):
 
 
 # name -> (restype, argtypes); mirrors include/ce_api.h declaration by declaration
-_BAG_COMMON = [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int32, c_int64]
+# the pieces the ce_bag_* declarations are made of --
+# table, num_rows, dim | indices, nnz | offsets, offsets_are_i64, num_bags, include_last_offset
+_TABLE = [c_void_p, c_int64, c_int32]
+_LOOKUPS = _TABLE + [c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32]
+# ... per_sample_weights, mode, hook_features, out / grad_out: the slots + offsets entries
+_BAG = _LOOKUPS + [c_void_p, c_int32, c_int64, c_void_p]
+# table, num_rows, dim, nnz, grad_out: the backward entries that walk source-row keys
+_SRC = _TABLE + [c_int64, c_void_p]
+_ACT = [c_int32]                # act_dtype, right behind the out / grad_out it describes
+_KEYS = [c_void_p]              # presorted / source-row keys
+_STREAM = [c_void_p]
+# keys, row_of_slot, momentum, momentum_rows, lr, eps, workspace, workspace_bytes, stream
+_ADAGRAD_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t] + _STREAM
+# the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
+# num_bags, include_last_offset, hook_features
+_WINDOW = [c_void_p, c_int64, c_int64, c_int64]
+_WINDOW_SRC = _WINDOW + [c_void_p, c_int32, c_int64, c_int64, c_int32, c_int64]
 SIGNATURES = {
     "ce_version": (c_int, []),
     "ce_cpu_budget": (c_int32, []),
@@ -92,67 +108,37 @@ SIGNATURES = {
     "ce_host_rows_gather": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "ce_box_probe": (c_int, [c_void_p, c_size_t, c_int32, POINTER(c_double), POINTER(c_double), c_void_p]),
     "ce_probe_rows": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, POINTER(c_double), POINTER(c_double), c_void_p]),
-    "ce_bag_forward": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
-                               c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
-    "ce_bag_backward_dense": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
-                                      c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
-    "ce_bag_backward_dense_presorted": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
-                                      c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ce_bag_forward": (c_int, _BAG + _STREAM),
+    "ce_bag_backward_dense": (c_int, _BAG + _STREAM),
+    "ce_bag_backward_dense_presorted": (c_int, _BAG + _KEYS + _STREAM),
     "ce_bag_backward_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_int64, c_int32, c_void_p,
                                      c_int32, c_int64, c_void_p, c_void_p]),
-    "ce_bag_backward_sgd": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
-                                    c_int32, c_void_p, c_int32, c_int64, c_void_p, c_float, c_void_p]),
+    "ce_bag_backward_sgd": (c_int, _BAG + [c_float] + _STREAM),
     "ce_bag_presort_len": (c_int64, [c_int64]),
     "ce_bag_presort": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
-    "ce_bag_backward_sgd_presorted": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
-                                              c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_float,
-                                              c_void_p, c_void_p]),
-    "ce_bag_presort_window": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
-    "ce_bag_presort_window_src": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int64, c_int64,
-                                          c_int32, c_int64, c_void_p, c_void_p]),
-    "ce_bag_forward_src_keys": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
-    "ce_bag_backward_sgd_presorted_src": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_float, c_void_p,
-                                                  c_void_p]),
-    "ce_bag_presort_window_src_excl": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int64,
-                                               c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ce_bag_backward_sgd_presorted_src_excl": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_float,
-                                                       c_void_p, c_void_p, c_void_p]),
-    "ce_bag_backward_dense_presorted_src": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p,
-                                                    c_void_p]),
+    "ce_bag_backward_sgd_presorted": (c_int, _BAG + [c_float] + _KEYS + _STREAM),
+    "ce_bag_presort_window": (c_int, _WINDOW + _KEYS + _STREAM),
+    "ce_bag_presort_window_src": (c_int, _WINDOW_SRC + _KEYS + _STREAM),
+    "ce_bag_forward_src_keys": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _STREAM),
+    "ce_bag_backward_sgd_presorted_src": (c_int, _SRC + [c_float] + _KEYS + _STREAM),
+    # ... ids, keys_out, seg_id_ranges
+    "ce_bag_presort_window_src_excl": (c_int, _WINDOW_SRC + [c_void_p] + _KEYS + [c_void_p] + _STREAM),
+    "ce_bag_backward_sgd_presorted_src_excl": (c_int, _SRC + [c_float] + _KEYS + [c_void_p] + _STREAM),
+    "ce_bag_backward_dense_presorted_src": (c_int, _SRC + _KEYS + _STREAM),
     "ce_bag_backward_sgd_sorted_workspace": (c_size_t, [c_int64, c_int64]),
-    "ce_bag_backward_sgd_sorted": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
-                                           c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_float,
-                                           c_void_p, c_size_t, c_void_p]),
+    "ce_bag_backward_sgd_sorted": (c_int, _BAG + [c_float, c_void_p, c_size_t] + _STREAM),
     "ce_bag_backward_rowwise_adagrad_workspace": (c_size_t, [c_int64, c_int32]),
-    "ce_bag_backward_rowwise_adagrad": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
-                                                c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p,
-                                                c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t,
-                                                c_void_p]),
-    "ce_bag_backward_rowwise_adagrad_src": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
-                                                    c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t,
-                                                    c_void_p]),
+    "ce_bag_backward_rowwise_adagrad": (c_int, _BAG + _ADAGRAD_TAIL),
+    "ce_bag_backward_rowwise_adagrad_src": (c_int, _SRC + _ADAGRAD_TAIL),
     # the hot-path bag entries with the output / incoming gradient as void* of an activation dtype (CE_ACT_*)
-    "ce_bag_forward_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
-                                   c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_void_p]),
-    "ce_bag_forward_src_keys_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int32,
-                                            c_void_p]),
-    "ce_bag_backward_dense_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
-                                          c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_void_p,
-                                          c_void_p]),
-    "ce_bag_backward_sgd_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64,
-                                        c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_float, c_void_p,
-                                        c_void_p]),
-    "ce_bag_backward_sgd_src_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32, c_float, c_void_p,
-                                            c_void_p, c_void_p]),
-    "ce_bag_backward_dense_src_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32, c_void_p,
-                                              c_void_p]),
-    "ce_bag_backward_rowwise_adagrad_act": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
-                                                    c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int32,
-                                                    c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
-                                                    c_void_p, c_size_t, c_void_p]),
-    "ce_bag_backward_rowwise_adagrad_src_act": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32,
-                                                        c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
-                                                        c_void_p, c_size_t, c_void_p]),
+    "ce_bag_forward_act": (c_int, _BAG + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_act": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    "ce_bag_backward_dense_act": (c_int, _BAG + _ACT + _KEYS + _STREAM),
+    "ce_bag_backward_sgd_act": (c_int, _BAG + _ACT + [c_float] + _KEYS + _STREAM),
+    "ce_bag_backward_sgd_src_act": (c_int, _SRC + _ACT + [c_float] + _KEYS + [c_void_p] + _STREAM),
+    "ce_bag_backward_dense_src_act": (c_int, _SRC + _ACT + _KEYS + _STREAM),
+    "ce_bag_backward_rowwise_adagrad_act": (c_int, _BAG + _ACT + _ADAGRAD_TAIL),
+    "ce_bag_backward_rowwise_adagrad_src_act": (c_int, _SRC + _ACT + _ADAGRAD_TAIL),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),
@@ -208,12 +194,10 @@ SIGNATURES = {
     "ce_exchange_local_index_split": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                               c_int64, c_int64, c_int64, c_void_p, c_int32, c_int64, c_int64, c_int64,
                                               c_void_p, c_void_p, c_void_p]),
-    "ce_bag_forward_max": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32,
-                                   c_int64, c_void_p, c_void_p, c_void_p]),
+    "ce_bag_forward_max": (c_int, _LOOKUPS + [c_int64, c_void_p, c_void_p] + _STREAM),
     "ce_bag_backward_max": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                     c_float, c_void_p]),
-    "ce_bag_backward_psw": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32,
-                                    c_int64, c_void_p, c_void_p, c_void_p]),
+    "ce_bag_backward_psw": (c_int, _LOOKUPS + [c_int64, c_void_p, c_void_p] + _STREAM),
     "ce_rows_renorm_workspace": (c_size_t, [c_int64]),
     "ce_rows_renorm": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t,
                                c_void_p]),

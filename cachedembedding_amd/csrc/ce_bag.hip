@@ -1175,10 +1175,9 @@ __global__ __launch_bounds__(256) void k_rows_axpy(float* __restrict__ dst, uint
   }
 }
 
-static int fill_params(BagParams& p, int32_t dim, const int64_t* indices, int64_t nnz, const void* offsets,
-                       int32_t off64, int64_t num_bags, int32_t include_last, const float* psw, int32_t mode,
-                       int64_t hookF, bool* vec, int* nch, const void* a0, const void* a1, const void* a2,
-                       const void* a16 = nullptr) {
+static int fill_params(BagParams& p, RowGeom& r, int32_t dim, bool aligned, const int64_t* indices, int64_t nnz,
+                       const void* offsets, int32_t off64, int64_t num_bags, int32_t include_last, const float* psw,
+                       int32_t mode, int64_t hookF) {
   CE_REQUIRE(dim > 0, CE_ERR_INVALID, "embedding dim must be positive");
   CE_REQUIRE(num_bags >= 0 && nnz >= 0, CE_ERR_INVALID, "negative sizes");
   CE_REQUIRE(num_bags < (int64_t)INT32_MAX - 64 && nnz < (int64_t)INT32_MAX, CE_ERR_UNSUPPORTED,
@@ -1187,25 +1186,15 @@ static int fill_params(BagParams& p, int32_t dim, const int64_t* indices, int64_
   CE_REQUIRE(!(mode == CE_MODE_MEAN && psw), CE_ERR_INVALID, "per_sample_weights needs mode='sum'");
   CE_REQUIRE(hookF >= 0 && (hookF == 0 || num_bags % hookF == 0), CE_ERR_INVALID,
              "hook_features must divide num_bags");
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  // a16: an activation tensor of a 16-bit type -- a lane's 4 elements are 8 bytes there, and so is the alignment a row
-  // of dim % 4 == 0 elements keeps (dim = 20, 100 included)
-  *vec = (dim % 4 == 0) && al16(a0) && al16(a1) && al16(a2) && (((uintptr_t)a16) & 7) == 0;
-  const int rowlen = *vec ? dim / 4 : dim;
-  int g = 1, gl2 = 0;
-  while (g < rowlen && g < 64) { g <<= 1; ++gl2; }
-  const int need = (rowlen + g - 1) / g;
-  int n = 1;
-  while (n < need) n <<= 1;
-  CE_REQUIRE(n <= 4, CE_ERR_UNSUPPORTED, "embedding dim %d too large for this build", dim);
-  *nch = n;
+  int rc = row_geometry(dim, aligned, r);
+  if (rc) return rc;
   p.indices = indices;
   p.offsets = offsets;
   p.psw = psw;
   p.nnz = nnz;
   p.num_bags = (int32_t)num_bags;
-  p.rowlen = rowlen;
-  p.g_log2 = gl2;
+  p.rowlen = r.rowlen;
+  p.g_log2 = r.g_log2;
   p.off64 = off64;
   p.include_last = include_last;
   p.mode = mode;
@@ -1217,23 +1206,26 @@ static int fill_params(BagParams& p, int32_t dim, const int64_t* indices, int64_
   return CE_OK;
 }
 
-// the activation type of a launch: CE_ACT(act, launch) compiles `launch` once per type with AT naming it
-#define CE_ACT(act, ...)                                          \
-  do {                                                            \
-    if ((act) == CE_ACT_F32) { using AT = float; __VA_ARGS__; }   \
-    else if ((act) == CE_ACT_BF16) { using AT = bf16_t; __VA_ARGS__; } \
-    else { using AT = f16_t; __VA_ARGS__; }                       \
-  } while (0)
-#define CE_REQUIRE_ACT(act)                                                                            \
-  CE_REQUIRE((act) == CE_ACT_F32 || (act) == CE_ACT_BF16 || (act) == CE_ACT_F16, CE_ERR_INVALID,       \
-             "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)(act))
-// the 16-bit activation pointer fill_params checks for 8-byte alignment (fp32 ones go with the 16-byte pointers)
-static inline const void* act16(const void* q, int act) { return act == CE_ACT_F32 ? nullptr : q; }
-static inline const void* act32(const void* q, int act) { return act == CE_ACT_F32 ? q : nullptr; }
+// the key-walking kernels only: bags are one id each and the keys hold the layout
+static int fill_params_keys(BagParams& p, RowGeom& r, int32_t dim, bool aligned, int64_t nnz) {
+  return fill_params(p, r, dim, aligned, nullptr, nnz, nullptr, 0, 0, 1, nullptr, CE_MODE_SUM, 0);
+}
 
-// the PAIR form of the key-walking kernels: a 16-bit tensor whose rows are whole 16-byte units
-static inline bool pair16(int act, int32_t dim, const void* q) {
-  return act != CE_ACT_F32 && dim % 8 == 0 && (((uintptr_t)q) & 15) == 0;
+template <typename F> static void for_lanes_act(const RowGeom& r, int act, F&& f) {
+  for_lanes(r.vec, r.nch, [&](auto l) { for_act(act, [&](auto a) { f(l, a); }); });
+}
+
+// rows in flight per lane group, by lane shape: k_bag_fwd's U and k_bag_bwd_tile's R ...
+template <typename VT, int NCH> constexpr int tile_unroll() {
+  return NCH == 1 ? (sizeof(VT) == 16 ? 16 : 8) : (NCH == 2 ? 4 : 2);
+}
+// ... and the R of the two key-walking kernels (k_bag_fwd_keys, k_bag_bwd_stream)
+template <typename VT, int NCH> constexpr int keys_unroll() { return NCH == 1 ? 16 : (NCH == 2 ? 8 : 4); }
+
+// the PAIR form of the key-walking kernels: a 16-bit tensor whose rows are whole 16-byte units, vector lanes
+template <typename VT, typename AT> constexpr bool kHasPair = sizeof(VT) == 16 && sizeof(AT) == 2;
+static inline bool pair16(const RowGeom& r, int act, int32_t dim, const void* q) {
+  return r.vec && act != CE_ACT_F32 && dim % 8 == 0 && al16(q);
 }
 
 static int bag_grid(int64_t num_bags) {
@@ -1241,9 +1233,18 @@ static int bag_grid(int64_t num_bags) {
   return grid_for(tiles, 4);
 }
 
+// keys padded to whole segments, and the key-walking kernels' grid over them: per_cu workgroups per CU; small inputs:
+// one share of >= 16 keys per lane group
+static int64_t padded_keys(int64_t nnz) { return cdiv(nnz, kSegLen) * kSegLen; }
+static dim3 keys_grid(int64_t total, int g_log2, int per_cu) {
+  const int ngroups = 256 >> g_log2;
+  const int64_t shares = cdiv(total, (int64_t)ngroups * 16);
+  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)kNumCU * per_cu, shares)));
+}
+
 // grad accumulation / fused SGD by target row: grouped segments (ce_bag_presort*) are walked as they are, otherwise
 // the kernel sorts 1024-lookup tiles itself
-static int launch_bwd_scatter(const BagParams& p, bool vec, int nch, int act, hipStream_t s) {
+static int launch_bwd_scatter(const BagParams& p, const RowGeom& r, int act, hipStream_t s) {
   BagParams q = p;
 #ifdef CE_ABLATIONS
   { const char* dbg = getenv("CE_BWD_DEBUG"); q.debug = dbg ? atoi(dbg) : 0; }
@@ -1252,41 +1253,21 @@ static int launch_bwd_scatter(const BagParams& p, bool vec, int nch, int act, hi
   // instead of 416 tiles = one or two per CU): 80 -> 72.5 us.  More, smaller tiles lose to the per-tile prologue
   // (3/CU 77 us, 4/CU 85 us, 8/CU 94 us), and the self-sorting path does not gain (92 us either way).
   q.tile_len = kBwdTile;
+  const int64_t total = p.presorted ? padded_keys(p.nnz) : p.nnz;
   if (p.presorted) {
     constexpr int per_cu = 2;
-    const int64_t total = cdiv(p.nnz, kSegLen) * kSegLen;
-    if (per_cu > 0 && total > (int64_t)kNumCU * 256)
+    if (total > (int64_t)kNumCU * 256)
       q.tile_len = (int)std::min<int64_t>(kBwdTile, (cdiv(total, (int64_t)kNumCU * per_cu) + 15) & ~15ll);
   }
-  const int ntiles = (int)cdiv(p.presorted ? cdiv(p.nnz, kSegLen) * kSegLen : p.nnz, q.tile_len);
-  dim3 grid(std::min(ntiles, kMaxBlocks)), block(256);
+  dim3 grid(std::min((int)cdiv(total, q.tile_len), kMaxBlocks)), block(256);
   const bool k32 = q.num_rows <= (1u << 22) - 2;
-#define CE_BWT(VT, N, R)                                                                              \
-  do {                                                                                                \
-    if (k32) CE_ACT(act, hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, uint32_t, R, AT>), grid, block, 0, s, q));          \
-    else CE_ACT(act, hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, unsigned long long, R, AT>), grid, block, 0, s, q));    \
-  } while (0)
-  if (vec) {
-    if (nch == 1) CE_BWT(f32x4, 1, 16);
-    else if (nch == 2) CE_BWT(f32x4, 2, 4); else CE_BWT(f32x4, 4, 2);
-  } else {
-    if (nch == 1) CE_BWT(float, 1, 8); else if (nch == 2) CE_BWT(float, 2, 4); else CE_BWT(float, 4, 2);
-  }
-#undef CE_BWT
-  CE_LAUNCH_CHECK();
-  return CE_OK;
-}
-
-// per-lookup gradient rows (COO values of the sparse=True backward)
-static int launch_bwd_rows(const BagParams& p, bool vec, int nch, hipStream_t s) {
-  dim3 grid(bag_grid(p.num_bags)), block(256);
-#define CE_BWD(VT, N) hipLaunchKernelGGL((k_bag_bwd_rows<VT, N>), grid, block, 0, s, p)
-  if (vec) {
-    if (nch == 1) CE_BWD(f32x4, 1); else if (nch == 2) CE_BWD(f32x4, 2); else CE_BWD(f32x4, 4);
-  } else {
-    if (nch == 1) CE_BWD(float, 1); else if (nch == 2) CE_BWD(float, 2); else CE_BWD(float, 4);
-  }
-#undef CE_BWD
+  for_lanes_act(r, act, [&](auto l, auto a) {
+    using VT = typename decltype(l)::VT;
+    using AT = typename decltype(a)::AT;
+    constexpr int N = decltype(l)::NCH, R = tile_unroll<VT, N>();
+    if (k32) hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, uint32_t, R, AT>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, unsigned long long, R, AT>), grid, block, 0, s, q);
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
@@ -1305,11 +1286,9 @@ extern "C" int ce_bag_forward_act(const float* weight, int64_t num_rows, int32_t
   CE_REQUIRE(offsets || num_bags == nnz, CE_ERR_INVALID,
              "offsets == NULL states one id per bag (offsets = arange): num_bags must equal nnz");
   BagParams p{};
-  bool vec;
-  int nch;
-  int rc = fill_params(p, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       per_sample_weights, mode, hook_features, &vec, &nch, weight, act32(out, act_dtype), nullptr,
-                       act16(out, act_dtype));
+  RowGeom r;
+  int rc = fill_params(p, r, dim, al16(weight) && act_aligned(out, act_dtype), indices, nnz, offsets, offsets_are_i64,
+                       num_bags, include_last_offset, per_sample_weights, mode, hook_features);
   if (rc) return rc;
   p.weight = weight;
   p.dst = (float*)out;
@@ -1318,18 +1297,13 @@ extern "C" int ce_bag_forward_act(const float* weight, int64_t num_rows, int32_t
   dim3 grid(bag_grid(num_bags)), block(256);
   hipStream_t s = (hipStream_t)stream;
   const bool stage = nnz != num_bags;      // multi-id bags possible
-#define CE_FWD(VT, N, U)                                                                          \
-  do {                                                                                            \
-    if (stage) CE_ACT(act_dtype, hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, 1, AT>), grid, block, 0, s, p));          \
-    else CE_ACT(act_dtype, hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, 1, AT>), grid, block, 0, s, p));               \
-  } while (0)
-  if (vec) {
-    if (nch == 1) CE_FWD(f32x4, 1, 16);
-    else if (nch == 2) CE_FWD(f32x4, 2, 4); else CE_FWD(f32x4, 4, 2);
-  } else {
-    if (nch == 1) CE_FWD(float, 1, 8); else if (nch == 2) CE_FWD(float, 2, 4); else CE_FWD(float, 4, 2);
-  }
-#undef CE_FWD
+  for_lanes_act(r, act_dtype, [&](auto l, auto a) {
+    using VT = typename decltype(l)::VT;
+    using AT = typename decltype(a)::AT;
+    constexpr int N = decltype(l)::NCH, U = tile_unroll<VT, N>();
+    if (stage) hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, 1, AT>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, 1, AT>), grid, block, 0, s, p);
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
@@ -1342,28 +1316,28 @@ extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim
                             per_sample_weights, mode, hook_features, out, CE_ACT_F32, stream);
 }
 
-static int backward_dense_impl(float* grad_weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
-                               const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
-                               int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
-                               int64_t hook_features, const void* grad_out, int act, const unsigned long long* presorted,
-                               ce_stream_t stream) {
+// dst += alpha * (the lookups' gradient rows), by slots + offsets: the dense gradient (dst = grad_weight, alpha = 1)
+// and the fused SGD step (dst = the table, alpha = -lr)
+static int backward_scatter_impl(float* dst, float alpha, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                 int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                 int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                 int64_t hook_features, const void* grad_out, int act, const uint64_t* presorted,
+                                 ce_stream_t stream) {
   CE_REQUIRE_ACT(act);
   if (num_bags == 0 || nnz == 0) return CE_OK;
-  CE_REQUIRE(grad_weight && grad_out && offsets && indices, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(dst && grad_out && offsets && indices, CE_ERR_INVALID, "null pointer");
   BagParams p{};
-  bool vec;
-  int nch;
-  int rc = fill_params(p, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       per_sample_weights, mode, hook_features, &vec, &nch, grad_weight, act32(grad_out, act), nullptr,
-                       act16(grad_out, act));
+  RowGeom r;
+  int rc = fill_params(p, r, dim, al16(dst) && act_aligned(grad_out, act), indices, nnz, offsets, offsets_are_i64,
+                       num_bags, include_last_offset, per_sample_weights, mode, hook_features);
   if (rc) return rc;
-  p.dst = grad_weight;
+  p.dst = dst;
   p.grad_out = grad_out;
-  p.alpha = 1.f;
+  p.alpha = alpha;
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   p.num_rows = (uint32_t)num_rows;
-  p.presorted = presorted;
-  return launch_bwd_scatter(p, vec, nch, act, (hipStream_t)stream);
+  p.presorted = (const unsigned long long*)presorted;
+  return launch_bwd_scatter(p, r, act, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_backward_dense(float* grad_weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1371,9 +1345,9 @@ extern "C" int ce_bag_backward_dense(float* grad_weight, int64_t num_rows, int32
                                      int64_t num_bags, int32_t include_last_offset,
                                      const float* per_sample_weights, int32_t mode, int64_t hook_features,
                                      const float* grad_out, ce_stream_t stream) {
-  return backward_dense_impl(grad_weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                             include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32, nullptr,
-                             stream);
+  return backward_scatter_impl(grad_weight, 1.f, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
+                               nullptr, stream);
 }
 
 extern "C" int ce_bag_backward_dense_act(float* grad_weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1382,9 +1356,9 @@ extern "C" int ce_bag_backward_dense_act(float* grad_weight, int64_t num_rows, i
                                          const float* per_sample_weights, int32_t mode, int64_t hook_features,
                                          const void* grad_out, int32_t act_dtype, const uint64_t* presorted_keys,
                                          ce_stream_t stream) {
-  return backward_dense_impl(grad_weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                             include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
-                             (const unsigned long long*)presorted_keys, stream);
+  return backward_scatter_impl(grad_weight, 1.f, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                               presorted_keys, stream);
 }
 
 extern "C" int ce_bag_backward_dense_presorted(float* grad_weight, int64_t num_rows, int32_t dim,
@@ -1394,42 +1368,18 @@ extern "C" int ce_bag_backward_dense_presorted(float* grad_weight, int64_t num_r
                                                int32_t mode, int64_t hook_features, const float* grad_out,
                                                const uint64_t* presorted_keys, ce_stream_t stream) {
   CE_REQUIRE(presorted_keys, CE_ERR_INVALID, "null presorted_keys");
-  return backward_dense_impl(grad_weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                             include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
-                             (const unsigned long long*)presorted_keys, stream);
-}
-
-static int backward_sgd_impl(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
-                             const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
-                             int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
-                             int64_t hook_features, const void* grad_out, int act, float lr,
-                             const unsigned long long* presorted, ce_stream_t stream) {
-  CE_REQUIRE_ACT(act);
-  if (num_bags == 0 || nnz == 0) return CE_OK;
-  CE_REQUIRE(weight && grad_out && offsets && indices, CE_ERR_INVALID, "null pointer");
-  BagParams p{};
-  bool vec;
-  int nch;
-  int rc = fill_params(p, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       per_sample_weights, mode, hook_features, &vec, &nch, weight, act32(grad_out, act), nullptr,
-                       act16(grad_out, act));
-  if (rc) return rc;
-  p.dst = weight;
-  p.grad_out = grad_out;
-  p.alpha = -lr;
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  p.num_rows = (uint32_t)num_rows;
-  p.presorted = presorted;
-  return launch_bwd_scatter(p, vec, nch, act, (hipStream_t)stream);
+  return backward_scatter_impl(grad_weight, 1.f, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
+                               presorted_keys, stream);
 }
 
 extern "C" int ce_bag_backward_sgd(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
                                    int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
                                    int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
                                    int64_t hook_features, const float* grad_out, float lr, ce_stream_t stream) {
-  return backward_sgd_impl(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32, lr, nullptr,
-                           stream);
+  return backward_scatter_impl(weight, -lr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
+                               nullptr, stream);
 }
 
 extern "C" int ce_bag_backward_sgd_act(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1437,9 +1387,9 @@ extern "C" int ce_bag_backward_sgd_act(float* weight, int64_t num_rows, int32_t 
                                        int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
                                        int64_t hook_features, const void* grad_out, int32_t act_dtype, float lr,
                                        const uint64_t* presorted_keys, ce_stream_t stream) {
-  return backward_sgd_impl(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype, lr,
-                           (const unsigned long long*)presorted_keys, stream);
+  return backward_scatter_impl(weight, -lr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                               presorted_keys, stream);
 }
 
 extern "C" int ce_bag_backward_sgd_presorted(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1449,74 +1399,59 @@ extern "C" int ce_bag_backward_sgd_presorted(float* weight, int64_t num_rows, in
                                              const float* grad_out, float lr, const uint64_t* presorted_keys,
                                              ce_stream_t stream) {
   CE_REQUIRE(presorted_keys, CE_ERR_INVALID, "null presorted_keys");
-  return backward_sgd_impl(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                           include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32, lr,
-                           (const unsigned long long*)presorted_keys, stream);
+  return backward_scatter_impl(weight, -lr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
+                               presorted_keys, stream);
 }
 
 // keys = row << 32 | grad_out row (ce_bag_presort_window_src); alpha * grad_out rows are folded into dst.
 // seg_ranges (fused SGD only): the batch's segment id ranges from ce_bag_presort_window_src_excl -> owner-exclusive
 // rows are updated with plain read-modify-writes (k_bag_bwd_stream<EXCL>)
 static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int act,
-                             float alpha, const unsigned long long* keys, const int64_t* seg_ranges, hipStream_t s) {
+                             float alpha, const uint64_t* keys, const int64_t* seg_ranges, ce_stream_t stream) {
   CE_REQUIRE_ACT(act);
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(dst && grad_out && keys, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   BagParams p{};
-  bool vec;
-  int nch;
-  int rc = fill_params(p, dim, nullptr, nnz, nullptr, 0, 0, 1, nullptr, CE_MODE_SUM, 0, &vec, &nch, dst,
-                       act32(grad_out, act), nullptr, act16(grad_out, act));
+  RowGeom r;
+  int rc = fill_params_keys(p, r, dim, al16(dst) && act_aligned(grad_out, act), nnz);
   if (rc) return rc;
   p.dst = dst;
   p.grad_out = grad_out;
   p.alpha = alpha;
   p.num_rows = (uint32_t)num_rows;
-  p.presorted = keys;
+  p.presorted = (const unsigned long long*)keys;
 #ifdef CE_ABLATIONS
   { const char* dbg = getenv("CE_BWD_DEBUG"); p.debug = dbg ? atoi(dbg) : 0; }
 #endif
   p.interleave = 1;
-  const int64_t total = cdiv(nnz, kSegLen) * kSegLen;
+  const int64_t total = padded_keys(nnz);
   // 6 workgroups per CU, i.e. 12288 shares of ~35 keys at the bench shape.  Alone on the GPU the share size matters
   // little (2 / 3 / 4 / 5 / 6 / 8 / 12 per CU: 55.5 / 54 / 58.5 / 56 / 53.7 / 55.8 / 58.6 us); beside the cache op's
   // kernels it does -- a workgroup that gets its CU late holds the whole launch back by its share: 77 / 74 / 70.5 /
   // 67.5 / 67 / 68 / 70.5 us (profiles/r04_late/grid_sweep_*.txt: forward 16/CU + backward 6 or 8/CU take the bench
   // line from 2.91 to 3.02-3.03 G over 10 runs each; 6 is the one that is also fastest alone)
   // (re-checked in the one-stream arrangement: profiles/r05_ab_grid_interleaved.txt)
-  constexpr int per_cu = 6;
-  const int ngroups = 256 >> p.g_log2;
-  // small inputs: one share of >= 16 keys per lane group
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)kNumCU * per_cu, cdiv(total, (int64_t)ngroups * 16)));
-  dim3 g(grid), b(256);
+  const dim3 g = keys_grid(total, p.g_log2, 6), b(256);
+  hipStream_t s = (hipStream_t)stream;
   const long long* rg = (const long long*)seg_ranges;
-  const bool excl = seg_ranges != nullptr && vec && nch == 1;
-#define CE_BWS(VT, N, R, EX) CE_ACT(act, hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, true, EX, AT>), g, b, 0, s, p, total, rg))
-#define CE_BWS2(N, R, EX)                                                                                              \
-  do {                                                                                                                 \
-    if (act == CE_ACT_BF16)                                                                                            \
-      hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, N, R, true, EX, bf16_t, true>), g, b, 0, s, p, total, rg);           \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_bag_bwd_stream<f32x4, N, R, true, EX, f16_t, true>), g, b, 0, s, p, total, rg);            \
-  } while (0)
-  if (vec && pair16(act, dim, grad_out)) {       // 16-bit gradient, D % 8 == 0: 16 bytes per lane for two keys at a time
-    if (nch == 1 && excl) CE_BWS2(1, 16, true);
-    else if (nch == 1) CE_BWS2(1, 16, false);
-    else if (nch == 2) CE_BWS2(2, 8, false);
-    else CE_BWS2(4, 4, false);
-  } else if (vec) {
-    if (nch == 1 && excl) CE_BWS(f32x4, 1, 16, true);
-    else if (nch == 1) CE_BWS(f32x4, 1, 16, false);
-    else if (nch == 2) CE_BWS(f32x4, 2, 8, false);
-    else CE_BWS(f32x4, 4, 4, false);
-  } else {
-    if (nch == 1) CE_BWS(float, 1, 16, false);
-    else if (nch == 2) CE_BWS(float, 2, 8, false);
-    else CE_BWS(float, 4, 4, false);
-  }
-#undef CE_BWS
-#undef CE_BWS2
+  const bool excl = seg_ranges != nullptr;                // (taken by the one shape that has the form: f32x4, 1)
+  const bool pair = pair16(r, act, dim, grad_out);        // 16 bytes of a 16-bit gradient per lane: two keys at a time
+  for_lanes_act(r, act, [&](auto l, auto a) {
+    using VT = typename decltype(l)::VT;
+    using AT = typename decltype(a)::AT;
+    constexpr int N = decltype(l)::NCH, R = keys_unroll<VT, N>();
+    constexpr bool has_excl = sizeof(VT) == 16 && N == 1, has_pair = kHasPair<VT, AT>;
+    auto launch = [&](auto ex, auto pr) {
+      constexpr bool EX = decltype(ex)::value, PR = decltype(pr)::value;
+      hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, true, EX, AT, PR>), g, b, 0, s, p, total, rg);
+    };
+    if constexpr (has_excl && has_pair) { if (excl && pair) return launch(std::true_type{}, std::true_type{}); }
+    if constexpr (has_excl) { if (excl) return launch(std::true_type{}, std::false_type{}); }
+    if constexpr (has_pair) { if (pair) return launch(std::false_type{}, std::true_type{}); }
+    launch(std::false_type{}, std::false_type{});
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
@@ -1524,36 +1459,31 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
 extern "C" int ce_bag_backward_sgd_presorted_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                  const float* grad_out, float lr, const uint64_t* src_keys,
                                                  ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, (const unsigned long long*)src_keys,
-                           nullptr, (hipStream_t)stream);
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, src_keys, nullptr, stream);
 }
 
 extern "C" int ce_bag_backward_sgd_presorted_src_excl(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                       const float* grad_out, float lr, const uint64_t* src_keys,
                                                       const int64_t* seg_id_ranges, ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, (const unsigned long long*)src_keys,
-                           seg_id_ranges, (hipStream_t)stream);
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, src_keys, seg_id_ranges, stream);
 }
 
 extern "C" int ce_bag_backward_sgd_src_act(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                            const void* grad_out, int32_t act_dtype, float lr, const uint64_t* src_keys,
                                            const int64_t* seg_id_ranges, ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, act_dtype, -lr, (const unsigned long long*)src_keys,
-                           seg_id_ranges, (hipStream_t)stream);
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, act_dtype, -lr, src_keys, seg_id_ranges, stream);
 }
 
 extern "C" int ce_bag_backward_dense_src_act(float* grad_weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                              const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
                                              ce_stream_t stream) {
-  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, act_dtype, 1.f,
-                           (const unsigned long long*)src_keys, nullptr, (hipStream_t)stream);
+  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, act_dtype, 1.f, src_keys, nullptr, stream);
 }
 
 extern "C" int ce_bag_backward_dense_presorted_src(float* grad_weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                    const float* grad_out, const uint64_t* src_keys,
                                                    ce_stream_t stream) {
-  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, 1.f,
-                           (const unsigned long long*)src_keys, nullptr, (hipStream_t)stream);
+  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, 1.f, src_keys, nullptr, stream);
 }
 
 extern "C" int ce_bag_forward_src_keys_act(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
@@ -1563,44 +1493,33 @@ extern "C" int ce_bag_forward_src_keys_act(const float* weight, int64_t num_rows
   CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   BagParams p{};
-  bool vec;
-  int nch;
-  int rc = fill_params(p, dim, nullptr, nnz, nullptr, 0, 0, 1, nullptr, CE_MODE_SUM, 0, &vec, &nch, weight,
-                       act32(out, act_dtype), nullptr, act16(out, act_dtype));
+  RowGeom r;
+  int rc = fill_params_keys(p, r, dim, al16(weight) && act_aligned(out, act_dtype), nnz);
   if (rc) return rc;
   p.weight = weight;
   p.dst = (float*)out;
   p.num_rows = (uint32_t)num_rows;
   p.presorted = (const unsigned long long*)src_keys;
   p.interleave = 0;
-  const int64_t total = cdiv(nnz, kSegLen) * kSegLen;
+  const int64_t total = padded_keys(nnz);
   // 16 workgroups per CU: more than fit at once (97 VGPRs: 5), so the dispatcher hands the shares out as CUs free up
   // (measured at the bench shape beside the cache op: 4/CU 72-74 us per launch, 8/CU 66-70, 16/CU 63-64, 32/CU 62-65;
   // alone: 8/CU 48, 16/CU 46.7, 5/CU -- exactly resident -- 43 but 66 beside the cache op)
-  constexpr int per_cu = 16;
-  const int ngroups = 256 >> p.g_log2;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)kNumCU * per_cu, cdiv(total, (int64_t)ngroups * 16)));
-  dim3 g(grid), b(256);
+  const dim3 g = keys_grid(total, p.g_log2, 16), b(256);
   hipStream_t s = (hipStream_t)stream;
-#define CE_FWK(VT, N, R) CE_ACT(act_dtype, hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT>), g, b, 0, s, p, total))
-#define CE_FWK2(N, R)                                                                                     \
-  do {                                                                                                    \
-    if (act_dtype == CE_ACT_BF16)                                                                         \
-      hipLaunchKernelGGL((k_bag_fwd_keys<f32x4, N, R, 1, bf16_t, true>), g, b, 0, s, p, total);           \
-    else                                                                                                  \
-      hipLaunchKernelGGL((k_bag_fwd_keys<f32x4, N, R, 1, f16_t, true>), g, b, 0, s, p, total);            \
-  } while (0)
-  if (vec && pair16(act_dtype, dim, out)) {      // 16-bit output, D % 8 == 0: 16 bytes per lane for two keys at a time
-    if (nch == 1) CE_FWK2(1, 16);
-    else if (nch == 2) CE_FWK2(2, 8); else CE_FWK2(4, 4);
-  } else if (vec) {
-    if (nch == 1) CE_FWK(f32x4, 1, 16);
-    else if (nch == 2) CE_FWK(f32x4, 2, 8); else CE_FWK(f32x4, 4, 4);
-  } else {
-    if (nch == 1) CE_FWK(float, 1, 16); else if (nch == 2) CE_FWK(float, 2, 8); else CE_FWK(float, 4, 4);
-  }
-#undef CE_FWK
-#undef CE_FWK2
+  const bool pair = pair16(r, act_dtype, dim, out);       // 16 bytes of a 16-bit output per lane: two keys at a time
+  for_lanes_act(r, act_dtype, [&](auto l, auto a) {
+    using VT = typename decltype(l)::VT;
+    using AT = typename decltype(a)::AT;
+    constexpr int N = decltype(l)::NCH, R = keys_unroll<VT, N>();
+    if constexpr (kHasPair<VT, AT>) {
+      if (pair) {
+        hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT, true>), g, b, 0, s, p, total);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT>), g, b, 0, s, p, total);
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
@@ -1660,10 +1579,9 @@ int presort_window_from_rows(int64_t* slots_io, int64_t nnz_per_batch, int64_t n
     CE_REQUIRE(offsets || num_bags == nnz_per_batch, CE_ERR_INVALID,
                "offsets may only be NULL for the one-id-per-bag layout (num_bags == nnz_per_batch)");
     BagParams lay{};
-    bool vec;
-    int nch;
-    int rc = fill_params(lay, 4, nullptr, nnz_per_batch, offsets, offsets_are_i64, num_bags, include_last_offset, nullptr,
-                         CE_MODE_SUM, hook_features, &vec, &nch, nullptr, nullptr, nullptr);
+    RowGeom unused;
+    int rc = fill_params(lay, unused, 4, true, nullptr, nnz_per_batch, offsets, offsets_are_i64, num_bags,
+                         include_last_offset, nullptr, CE_MODE_SUM, hook_features);
     if (rc) return rc;
     hipLaunchKernelGGL((k_bag_presort_seg<true, false, true>), grid, block, 0, stream, (const int64_t*)nullptr,
                        nnz_per_batch, (int32_t)spb, nseg, (uint32_t)num_rows, (unsigned long long*)keys_out, lay,
@@ -1692,10 +1610,9 @@ static int presort_window_src_impl(const int64_t* indices, int64_t nnz_per_batch
   CE_REQUIRE(offsets || num_bags == nnz_per_batch, CE_ERR_INVALID,
              "offsets may only be NULL for the one-id-per-bag layout (num_bags == nnz_per_batch)");
   BagParams lay{};
-  bool vec;
-  int nch;
-  int rc = fill_params(lay, 4, indices, nnz_per_batch, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       nullptr, CE_MODE_SUM, hook_features, &vec, &nch, nullptr, nullptr, nullptr);
+  RowGeom unused;
+  int rc = fill_params(lay, unused, 4, true, indices, nnz_per_batch, offsets, offsets_are_i64, num_bags,
+                       include_last_offset, nullptr, CE_MODE_SUM, hook_features);
   if (rc) return rc;
 #ifdef CE_ABLATIONS
   { const char* dbg = getenv("CE_PRESORT_DEBUG"); lay.debug = dbg ? atoi(dbg) : 0; }
@@ -1735,32 +1652,23 @@ extern "C" int ce_rows_axpy(float* weight, int64_t num_rows, int32_t dim, const 
   CE_REQUIRE(weight && index && src_rows, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(dim > 0 && n > 0 && n < (int64_t)INT32_MAX, CE_ERR_INVALID, "bad sizes");
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  const bool vec = (dim % 4 == 0) && al16(weight) && al16(src_rows);
-  const int rowlen = vec ? dim / 4 : dim;
-  int g = 1, gl2 = 0;
-  while (g < rowlen && g < 64) { g <<= 1; ++gl2; }
-  const int need = (rowlen + g - 1) / g;
-  int nch = 1;
-  while (nch < need) nch <<= 1;
-  CE_REQUIRE(nch <= 4, CE_ERR_UNSUPPORTED, "embedding dim %d too large for this build", dim);
-  const int u = nch == 1 ? 8 : (nch == 2 ? 4 : 2);
-  const int64_t per_block = (int64_t)(64 / g) * u * 4;
+  RowGeom r;
+  int rc = row_geometry(dim, al16(weight) && al16(src_rows), r);
+  if (rc) return rc;
+  const int u = r.nch == 1 ? 8 : (r.nch == 2 ? 4 : 2);       // k_rows_axpy's U
+  const int64_t per_block = (int64_t)(64 >> r.g_log2) * u * 4;
   dim3 grid(grid_for(n, (int)per_block)), block(256);
   hipStream_t s = (hipStream_t)stream;
-#define CE_AXPY(VT, N)                                                                                      \
-  hipLaunchKernelGGL((k_rows_axpy<VT, N>), grid, block, 0, s, weight, (uint32_t)num_rows, index, n,         \
-                     (const VT*)src_rows, rowlen, gl2, dim, alpha)
-  if (vec) {
-    if (nch == 1) CE_AXPY(f32x4, 1); else if (nch == 2) CE_AXPY(f32x4, 2); else CE_AXPY(f32x4, 4);
-  } else {
-    if (nch == 1) CE_AXPY(float, 1); else if (nch == 2) CE_AXPY(float, 2); else CE_AXPY(float, 4);
-  }
-#undef CE_AXPY
+  for_lanes(r.vec, r.nch, [&](auto l) {
+    using VT = typename decltype(l)::VT;
+    hipLaunchKernelGGL((k_rows_axpy<VT, decltype(l)::NCH>), grid, block, 0, s, weight, (uint32_t)num_rows, index, n,
+                       (const VT*)src_rows, r.rowlen, r.g_log2, dim, alpha);
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
 
+// per-lookup gradient rows (COO values of the sparse=True backward)
 extern "C" int ce_bag_backward_rows(float* grad_rows, const int64_t* dest_index, int32_t dim, int64_t nnz,
                                     const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
                                     int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
@@ -1768,13 +1676,18 @@ extern "C" int ce_bag_backward_rows(float* grad_rows, const int64_t* dest_index,
   if (num_bags == 0 || nnz == 0) return CE_OK;
   CE_REQUIRE(grad_rows && grad_out && offsets, CE_ERR_INVALID, "null pointer");
   BagParams p{};
-  bool vec;
-  int nch;
-  int rc = fill_params(p, dim, dest_index, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
-                       per_sample_weights, mode, hook_features, &vec, &nch, grad_rows, grad_out, nullptr);
+  RowGeom r;
+  int rc = fill_params(p, r, dim, al16(grad_rows) && al16(grad_out), dest_index, nnz, offsets, offsets_are_i64,
+                       num_bags, include_last_offset, per_sample_weights, mode, hook_features);
   if (rc) return rc;
   p.dst = grad_rows;
   p.grad_out = grad_out;
   p.alpha = 1.f;
-  return launch_bwd_rows(p, vec, nch, (hipStream_t)stream);
+  dim3 grid(bag_grid(num_bags)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  for_lanes(r.vec, r.nch, [&](auto l) {
+    hipLaunchKernelGGL((k_bag_bwd_rows<typename decltype(l)::VT, decltype(l)::NCH>), grid, block, 0, s, p);
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
 }

@@ -13,8 +13,6 @@
 // The workspace (acc + flags) is zero-filled by its owner once and left zero-filled by every call, so no memset runs
 // between steps.  The momentum is indexed by host-table row (row_of_slot = cached_idx_map) and never moves with the
 // cache; a slot maps to one row for the whole step, so folding by slot is folding by row.
-#include <algorithm>
-
 #include "ce_common.h"
 
 namespace ce {
@@ -125,7 +123,10 @@ static AdagradWs carve_adagrad(void* ws, int64_t num_rows, int32_t dim) {
   return w;
 }
 
-static int adagrad_check(float* weight, int64_t num_rows, int32_t dim, const void* grad_out, float* momentum,
+// everything the two entries can refuse, BEFORE their first launch: the workspace stays zero-filled on every error.
+// The row geometry is asked for with the weakest alignment of the three launches' (weight, acc -- 256-byte aligned
+// by carve_adagrad -- and grad_out): a dim that fits the scalar form fits the vector form.
+static int adagrad_check(float* weight, int64_t num_rows, int32_t dim, const void* grad_out, int act, float* momentum,
                          int64_t momentum_rows, float lr, float eps, void* workspace, size_t workspace_bytes) {
   CE_REQUIRE(weight && grad_out && momentum && workspace, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
@@ -134,11 +135,15 @@ static int adagrad_check(float* weight, int64_t num_rows, int32_t dim, const voi
   CE_REQUIRE(lr >= 0.f && eps > 0.f, CE_ERR_INVALID, "lr must be >= 0 and eps > 0");
   CE_REQUIRE(workspace_bytes >= carve_adagrad(nullptr, num_rows, dim).bytes, CE_ERR_INVALID, "workspace too small");
   CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
-  return CE_OK;
+  RowGeom r;
+  return row_geometry(dim, al16(weight) && act_aligned(grad_out, act), r);
 }
 
 static int launch_apply(float* weight, int64_t num_rows, int32_t dim, const int32_t* row_of_slot, float* momentum,
                         int64_t momentum_rows, float lr, float eps, const AdagradWs& ws, hipStream_t s) {
+  RowGeom r;
+  int rc = row_geometry(dim, al16(weight), r);
+  if (rc) return rc;
   AdagradArgs a{};
   a.weight = weight;
   a.acc = ws.acc;
@@ -147,27 +152,15 @@ static int launch_apply(float* weight, int64_t num_rows, int32_t dim, const int3
   a.momentum = momentum;
   a.momentum_rows = momentum_rows;
   a.num_rows = (uint32_t)num_rows;
+  a.rowlen = r.rowlen;
+  a.g_log2 = r.g_log2;
   a.dim = dim;
   a.lr = lr;
   a.eps = eps;
-  const bool vec = dim % 4 == 0 && (((uintptr_t)weight) & 15) == 0;
-  a.rowlen = vec ? dim / 4 : dim;
-  const int G = vec ? group_lanes_for_dim(dim) : std::min(64, group_lanes_for_dim(4 * dim));
-  int gl2 = 0;
-  while ((1 << gl2) < G) ++gl2;
-  a.g_log2 = gl2;
-  const int nch = (int)cdiv(a.rowlen, G);
-  CE_REQUIRE(nch <= 4, CE_ERR_UNSUPPORTED, "dim %d: at most %d", dim, vec ? 1024 : 256);
   const dim3 g(grid_for(cdiv(num_rows, 64), 4)), b(256);
-  if (vec) {
-    if (nch == 1) hipLaunchKernelGGL((k_adagrad_apply<f32x4, 1>), g, b, 0, s, a);
-    else if (nch == 2) hipLaunchKernelGGL((k_adagrad_apply<f32x4, 2>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_adagrad_apply<f32x4, 4>), g, b, 0, s, a);
-  } else {
-    if (nch == 1) hipLaunchKernelGGL((k_adagrad_apply<float, 1>), g, b, 0, s, a);
-    else if (nch == 2) hipLaunchKernelGGL((k_adagrad_apply<float, 2>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_adagrad_apply<float, 4>), g, b, 0, s, a);
-  }
+  for_lanes(r.vec, r.nch, [&](auto l) {
+    hipLaunchKernelGGL((k_adagrad_apply<typename decltype(l)::VT, decltype(l)::NCH>), g, b, 0, s, a);
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
@@ -190,10 +183,10 @@ extern "C" int ce_bag_backward_rowwise_adagrad_act(float* weight, int64_t num_ro
                                                    const uint64_t* presorted, const int32_t* row_of_slot,
                                                    float* momentum, int64_t momentum_rows, float lr, float eps,
                                                    void* workspace, size_t workspace_bytes, ce_stream_t stream) {
-  CE_REQUIRE(act_dtype == CE_ACT_F32 || act_dtype == CE_ACT_BF16 || act_dtype == CE_ACT_F16, CE_ERR_INVALID,
-             "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)act_dtype);
+  CE_REQUIRE_ACT(act_dtype);
   if (num_bags == 0 || nnz == 0) return CE_OK;
-  int rc = adagrad_check(weight, num_rows, dim, grad_out, momentum, momentum_rows, lr, eps, workspace, workspace_bytes);
+  int rc = adagrad_check(weight, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps, workspace,
+                         workspace_bytes);
   if (rc) return rc;
   CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
   hipStream_t s = (hipStream_t)stream;
@@ -227,10 +220,10 @@ extern "C" int ce_bag_backward_rowwise_adagrad_src_act(float* weight, int64_t nu
                                                        const uint64_t* src_keys, const int32_t* row_of_slot,
                                                        float* momentum, int64_t momentum_rows, float lr, float eps,
                                                        void* workspace, size_t workspace_bytes, ce_stream_t stream) {
-  CE_REQUIRE(act_dtype == CE_ACT_F32 || act_dtype == CE_ACT_BF16 || act_dtype == CE_ACT_F16, CE_ERR_INVALID,
-             "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)act_dtype);
+  CE_REQUIRE_ACT(act_dtype);
   if (nnz == 0) return CE_OK;
-  int rc = adagrad_check(weight, num_rows, dim, grad_out, momentum, momentum_rows, lr, eps, workspace, workspace_bytes);
+  int rc = adagrad_check(weight, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps, workspace,
+                         workspace_bytes);
   if (rc) return rc;
   CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
   hipStream_t s = (hipStream_t)stream;

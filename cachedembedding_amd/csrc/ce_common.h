@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "ce_api.h"
 
 namespace ce {
@@ -99,12 +101,57 @@ void bind_thread_near_gpu();
 // the same CPU set for threads that have not selected the device themselves (taken by their creator); false = none
 bool near_gpu_cpus(cpu_set_t* out);
 
-// lanes cooperating on one embedding row: 16 B per lane, power of two, at most one wave
-static inline int group_lanes_for_dim(int dim) {
-  int v = (dim + 3) / 4;
+// How the lanes of a launch hold one embedding row.  Vector form: a lane's chunk is 16 B (f32x4); it needs dim % 4 == 0
+// and `aligned` -- every row pointer of the launch on its vector boundary.  Scalar form otherwise: one float per chunk.
+// A power-of-two group of at most 64 lanes works on a row and a lane holds nch = 1, 2 or 4 chunks of it (3 rounds up
+// to 4; the kernels mask chunks past rowlen), so the vector form ends at dim = 1024 and the scalar one at 256.
+struct RowGeom {
+  bool vec;
+  int rowlen;   // chunks per row
+  int g_log2;   // log2(lanes per row)
+  int nch;      // chunks per lane
+};
+
+static inline int row_geometry(int32_t dim, bool aligned, RowGeom& r) {
+  r.vec = dim % 4 == 0 && aligned;
+  r.rowlen = r.vec ? dim / 4 : dim;
   int g = 1;
-  while (g < v && g < 64) g <<= 1;
-  return g;
+  r.g_log2 = 0;
+  while (g < r.rowlen && g < 64) { g <<= 1; ++r.g_log2; }
+  const int need = (r.rowlen - 1) / g + 1;
+  r.nch = 1;
+  while (r.nch < need) r.nch <<= 1;
+  CE_REQUIRE(r.nch <= 4, CE_ERR_UNSUPPORTED, "embedding dim %d too large for this build", dim);
+  return CE_OK;
+}
+
+static inline bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
+// an activation tensor on its vector boundary: a lane's 4 elements are 16 bytes of fp32 and 8 bytes of a 16-bit type
+// (the alignment that rows of dim % 4 == 0 elements keep there: dim = 20, 100 included)
+static inline bool act_aligned(const void* q, int act) { return (((uintptr_t)q) & (act == CE_ACT_F32 ? 15 : 7)) == 0; }
+
+#define CE_REQUIRE_ACT(act)                                                                            \
+  CE_REQUIRE((act) == CE_ACT_F32 || (act) == CE_ACT_BF16 || (act) == CE_ACT_F16, CE_ERR_INVALID,       \
+             "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)(act))
+
+// The one place that turns the run-time lane shape and activation code into template arguments: f is a generic lambda
+// and gets a tag to read the types from (typename decltype(l)::VT, decltype(l)::NCH, typename decltype(a)::AT).
+template <typename VT_, int NCH_> struct Lanes {
+  typedef VT_ VT;
+  static constexpr int NCH = NCH_;
+};
+template <typename AT_> struct ActTag { typedef AT_ AT; };
+
+template <typename F> static inline void for_lanes(bool vec, int nch, F&& f) {
+  if (vec) {
+    if (nch == 1) f(Lanes<f32x4, 1>{}); else if (nch == 2) f(Lanes<f32x4, 2>{}); else f(Lanes<f32x4, 4>{});
+  } else {
+    if (nch == 1) f(Lanes<float, 1>{}); else if (nch == 2) f(Lanes<float, 2>{}); else f(Lanes<float, 4>{});
+  }
+}
+
+template <typename F> static inline void for_act(int act, F&& f) {
+  if (act == CE_ACT_F32) f(ActTag<float>{}); else if (act == CE_ACT_BF16) f(ActTag<bf16_t>{}); else f(ActTag<f16_t>{});
 }
 
 }  // namespace ce

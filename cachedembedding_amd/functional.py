@@ -91,25 +91,16 @@ class _BagFn(torch.autograd.Function):
             out = torch.empty(shape, device=weight.device, dtype=out_dtype)
         from_keys = FORWARD_FROM_KEYS and isinstance(presorted, SrcKeys) and presorted.identity and psw is None \
             and mode == _lib.CE_MODE_SUM and num_bags == indices.numel()
-        if out_dtype != torch.float32:
-            # 16-bit output: the same two kernels store the rounded row themselves (the ce_*_act entries)
-            act = _lib.ACT_DTYPES[out_dtype]
-            if from_keys:
-                check(lib.ce_bag_forward_src_keys_act(ptr(weight), weight.shape[0], dim, indices.numel(),
-                                                      ptr(presorted.keys), ptr(out), act, stream_ptr()))
-            else:
-                check(lib.ce_bag_forward_act(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(),
-                                             ptr(offsets), int(offsets.dtype == torch.int64), num_bags,
-                                             int(include_last), ptr(psw), mode, hook_features, ptr(out), act,
-                                             stream_ptr()))
-        elif from_keys:
+        # the ce_*_act entries for every dtype: the kernels store the output as `act` (CE_ACT_F32: the fp32 form)
+        act = _lib.ACT_DTYPES[out_dtype]
+        if from_keys:
             # one id per bag: out[bag] = W[slot], and the window's keys hold (slot, output row) grouped by slot
-            check(lib.ce_bag_forward_src_keys(ptr(weight), weight.shape[0], dim, indices.numel(), ptr(presorted.keys),
-                                              ptr(out), stream_ptr()))
+            check(lib.ce_bag_forward_src_keys_act(ptr(weight), weight.shape[0], dim, indices.numel(),
+                                                  ptr(presorted.keys), ptr(out), act, stream_ptr()))
         else:
-            check(lib.ce_bag_forward(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(), ptr(offsets),
-                                     int(offsets.dtype == torch.int64), num_bags, int(include_last), ptr(psw), mode,
-                                     hook_features, ptr(out), stream_ptr()))
+            check(lib.ce_bag_forward_act(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(),
+                                         ptr(offsets), int(offsets.dtype == torch.int64), num_bags, int(include_last),
+                                         ptr(psw), mode, hook_features, ptr(out), act, stream_ptr()))
         # bwd_scale (scale_grad_by_freq): per-lookup factor of the backward only; it takes the place of psw there
         ctx.save_for_backward(indices, offsets, psw if bwd_scale is None else bwd_scale.contiguous())
         ctx.weight = weight
@@ -127,61 +118,51 @@ class _BagFn(torch.autograd.Function):
         dim = weight.shape[1]
         off64 = int(offsets.dtype == torch.int64)
         nnz = indices.numel()
+        R = weight.shape[0]
         gw = None
-        act16 = False
-        if grad_out.dtype != torch.float32:
-            # a 16-bit gradient (what autograd delivers for a 16-bit output): the hot paths read it natively
-            # (_backward_act16); everything else takes its exact upcast through the fp32 entries below
-            act16, gw = _backward_act16(ctx, grad_out, indices, offsets, psw)
-            if not act16:
-                grad_out = grad_out.float()
-        if act16:
-            pass
-        elif isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None:
+        pre = ctx.presorted
+        src = isinstance(pre, SrcKeys)
+        rowwise = isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None
+        sgd = not rowwise and fused is not None and fused.lr is not None
+        # the hot paths -- row-wise Adagrad, fused SGD by atomics, the dense gradient -- read grad_out as it comes
+        # (fp32, bf16 or fp16: what autograd delivers for an output of that dtype) through the ce_*_act entries, from
+        # source-row keys or from slots + offsets (ptr(None) = 0: no presorted keys / no owner ranges).  Deterministic
+        # SGD and the two sparse=True forms have fp32 entries only and take the exact upcast of a 16-bit gradient.
+        act = _lib.ACT_DTYPES.get(grad_out.dtype)
+        if act is None:
+            raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
+        fp32_only = fused.deterministic if sgd else (sparse and not rowwise)
+        if fp32_only and act != _lib.CE_ACT_F32:
+            grad_out = grad_out.float()
+        slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
+                      hook_features, ptr(grad_out))
+        if rowwise:
             # exact row-wise Adagrad inside backward (ce_bag_adagrad.hip): the optimizer sees grad=None
             with torch.no_grad():
-                ws = fused.workspace(weight.shape[0], dim, weight.device)
+                ws = fused.workspace(R, dim, weight.device)
                 mom = fused.momentum
-                rmap = fused.row_of_slot
-                if isinstance(ctx.presorted, SrcKeys):
-                    check(lib.ce_bag_backward_rowwise_adagrad_src(ptr(weight), weight.shape[0], dim, nnz, ptr(grad_out),
-                                                                  ptr(ctx.presorted.keys), ptr(rmap), ptr(mom),
-                                                                  mom.numel(), float(fused.lr), float(fused.eps),
-                                                                  ptr(ws), ws.numel(), stream_ptr()))
+                tail = (ptr(fused.row_of_slot), ptr(mom), mom.numel(), float(fused.lr), float(fused.eps), ptr(ws),
+                        ws.numel(), stream_ptr())
+                if src:
+                    check(lib.ce_bag_backward_rowwise_adagrad_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act,
+                                                                      ptr(pre.keys), *tail))
                 else:
-                    check(lib.ce_bag_backward_rowwise_adagrad(ptr(weight), weight.shape[0], dim, ptr(indices), nnz,
-                                                              ptr(offsets), off64, num_bags, int(include_last),
-                                                              ptr(psw), mode, hook_features, ptr(grad_out),
-                                                              ptr(ctx.presorted), ptr(rmap), ptr(mom), mom.numel(),
-                                                              float(fused.lr), float(fused.eps), ptr(ws), ws.numel(),
-                                                              stream_ptr()))
-        elif fused is not None and fused.lr is not None:
+                    check(lib.ce_bag_backward_rowwise_adagrad_act(ptr(weight), R, dim, *slots_args, act, ptr(pre),
+                                                                  *tail))
+        elif sgd:
             # K13+K14 in one pass; the optimizer sees grad=None for the cache parameter
             with torch.no_grad():
                 if fused.deterministic:
-                    ws = fused.workspace(weight.shape[0], nnz, weight.device)
-                    check(lib.ce_bag_backward_sgd_sorted(ptr(weight), weight.shape[0], dim, ptr(indices), nnz,
-                                                         ptr(offsets), off64, num_bags, int(include_last), ptr(psw),
-                                                         mode, hook_features, ptr(grad_out), float(fused.lr),
-                                                         ptr(ws), ws.numel(), stream_ptr()))
-                elif isinstance(ctx.presorted, SrcKeys) and ctx.presorted.ranges is not None:
-                    check(lib.ce_bag_backward_sgd_presorted_src_excl(ptr(weight), weight.shape[0], dim, nnz,
-                                                                     ptr(grad_out), float(fused.lr),
-                                                                     ptr(ctx.presorted.keys),
-                                                                     ptr(ctx.presorted.ranges), stream_ptr()))
-                elif isinstance(ctx.presorted, SrcKeys):
-                    check(lib.ce_bag_backward_sgd_presorted_src(ptr(weight), weight.shape[0], dim, nnz,
-                                                                ptr(grad_out), float(fused.lr),
-                                                                ptr(ctx.presorted.keys), stream_ptr()))
-                elif ctx.presorted is not None:
-                    check(lib.ce_bag_backward_sgd_presorted(ptr(weight), weight.shape[0], dim, ptr(indices), nnz,
-                                                            ptr(offsets), off64, num_bags, int(include_last), ptr(psw),
-                                                            mode, hook_features, ptr(grad_out), float(fused.lr),
-                                                            ptr(ctx.presorted), stream_ptr()))
+                    ws = fused.workspace(R, nnz, weight.device)
+                    check(lib.ce_bag_backward_sgd_sorted(ptr(weight), R, dim, *slots_args, float(fused.lr), ptr(ws),
+                                                         ws.numel(), stream_ptr()))
+                elif src:
+                    check(lib.ce_bag_backward_sgd_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act,
+                                                          float(fused.lr), ptr(pre.keys), ptr(pre.ranges),
+                                                          stream_ptr()))
                 else:
-                    check(lib.ce_bag_backward_sgd(ptr(weight), weight.shape[0], dim, ptr(indices), nnz, ptr(offsets),
-                                                  off64, num_bags, int(include_last), ptr(psw), mode, hook_features,
-                                                  ptr(grad_out), float(fused.lr), stream_ptr()))
+                    check(lib.ce_bag_backward_sgd_act(ptr(weight), R, dim, *slots_args, act, float(fused.lr),
+                                                      ptr(pre), stream_ptr()))
         elif sparse and COALESCED_SPARSE_GRAD and nnz > 0 and not torch.cuda.is_current_stream_capturing():
             # sparse=True (scripts/kaggle.sh:71 --use_sparse_embed_grad): the COO gradient is handed over COALESCED --
             # unique rows (ce_dedupe_bucket_rows), ascending, each with the sum of its lookups' gradient rows (the dense
@@ -220,18 +201,11 @@ class _BagFn(torch.autograd.Function):
             gw = torch.sparse_coo_tensor(indices.view(1, -1), rows, weight.shape, check_invariants=False)
         else:
             gw = torch.zeros_like(weight)
-            if isinstance(ctx.presorted, SrcKeys):
-                check(lib.ce_bag_backward_dense_presorted_src(ptr(gw), weight.shape[0], dim, nnz, ptr(grad_out),
-                                                              ptr(ctx.presorted.keys), stream_ptr()))
-            elif ctx.presorted is not None:
-                check(lib.ce_bag_backward_dense_presorted(ptr(gw), weight.shape[0], dim, ptr(indices), nnz,
-                                                          ptr(offsets), off64, num_bags, int(include_last), ptr(psw),
-                                                          mode, hook_features, ptr(grad_out), ptr(ctx.presorted),
-                                                          stream_ptr()))
+            if src:
+                check(lib.ce_bag_backward_dense_src_act(ptr(gw), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys),
+                                                        stream_ptr()))
             else:
-                check(lib.ce_bag_backward_dense(ptr(gw), weight.shape[0], dim, ptr(indices), nnz, ptr(offsets), off64,
-                                                num_bags, int(include_last), ptr(psw), mode, hook_features,
-                                                ptr(grad_out), stream_ptr()))
+                check(lib.ce_bag_backward_dense_act(ptr(gw), R, dim, *slots_args, act, ptr(pre), stream_ptr()))
         gpsw = None
         if ctx.needs_input_grad[3] and grad_out.dtype != torch.float32:
             grad_out = grad_out.float()              # (off the hot path: ce_bag_backward_psw reads fp32)
@@ -246,64 +220,6 @@ class _BagFn(torch.autograd.Function):
 
 
 _DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
-
-
-def _backward_act16(ctx, grad_out, indices, offsets, psw):
-    """The hot backward paths with a bf16 / fp16 grad_out read in place by the kernels (the ce_*_act entries): row-wise
-    Adagrad (both entries), fused SGD (atomics: slots + offsets, presorted, source-row keys with and without owner
-    ranges) and the dense gradient (the same three).  Returns (True, grad_weight or None); (False, None): not one of
-    them -- deterministic fused SGD and the two sparse=True forms -- and nothing has run; the caller upcasts."""
-    weight = ctx.weight
-    mode, include_last, hook_features, sparse, fused, num_bags = ctx.args
-    act = _lib.ACT_DTYPES.get(grad_out.dtype)
-    if act is None:
-        raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
-    dim = weight.shape[1]
-    off64 = int(offsets.dtype == torch.int64)
-    nnz = indices.numel()
-    R = weight.shape[0]
-    pre = ctx.presorted
-    src = isinstance(pre, SrcKeys)
-    if isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None:
-        with torch.no_grad():
-            ws = fused.workspace(R, dim, weight.device)
-            mom = fused.momentum
-            if src:
-                check(lib.ce_bag_backward_rowwise_adagrad_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act,
-                                                                  ptr(pre.keys), ptr(fused.row_of_slot), ptr(mom),
-                                                                  mom.numel(), float(fused.lr), float(fused.eps),
-                                                                  ptr(ws), ws.numel(), stream_ptr()))
-            else:
-                check(lib.ce_bag_backward_rowwise_adagrad_act(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets),
-                                                              off64, num_bags, int(include_last), ptr(psw), mode,
-                                                              hook_features, ptr(grad_out), act, ptr(pre),
-                                                              ptr(fused.row_of_slot), ptr(mom), mom.numel(),
-                                                              float(fused.lr), float(fused.eps), ptr(ws), ws.numel(),
-                                                              stream_ptr()))
-        return True, None
-    if fused is not None and fused.lr is not None:
-        if fused.deterministic:
-            return False, None
-        with torch.no_grad():
-            if src:
-                check(lib.ce_bag_backward_sgd_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act, float(fused.lr),
-                                                      ptr(pre.keys), ptr(pre.ranges), stream_ptr()))
-            else:
-                check(lib.ce_bag_backward_sgd_act(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64,
-                                                  num_bags, int(include_last), ptr(psw), mode, hook_features,
-                                                  ptr(grad_out), act, float(fused.lr), ptr(pre), stream_ptr()))
-        return True, None
-    if sparse:
-        return False, None
-    gw = torch.zeros_like(weight)
-    if src:
-        check(lib.ce_bag_backward_dense_src_act(ptr(gw), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys),
-                                                stream_ptr()))
-    else:
-        check(lib.ce_bag_backward_dense_act(ptr(gw), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags,
-                                            int(include_last), ptr(psw), mode, hook_features, ptr(grad_out), act,
-                                            ptr(pre), stream_ptr()))
-    return True, gw
 
 
 # forward from the window's source-row keys when they were built for the one-id-per-bag layout (False: always the

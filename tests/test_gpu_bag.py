@@ -920,3 +920,96 @@ def test_out_argument_and_the_buffer_picker(hook):
     torch.testing.assert_close(w1.grad, w2.grad, rtol=0, atol=1e-6)
     with pytest.raises(ValueError):
         ce.embedding_bag(idx, w2, off, out=torch.empty(3, 3, device="cuda"), **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [128, 20, 260])
+def test_legacy_fp32_entries_equal_their_act_twins(D):
+    """The fp32 entries that the package itself no longer calls (bench.py, parallel.py and C callers do) against their
+    ce_*_act twins with CE_ACT_F32, through the C ABI, bit for bit: a wrapper that transposed or dropped an argument
+    would show here.  2048 lookups of DISTINCT rows, one id per bag, hook fold 4: every row gets exactly one update, so
+    both results are deterministic.  D = 260 (two chunks per lane) for the key-walking entries only."""
+    from cachedembedding_amd import _lib
+    from cachedembedding_amd._lib import check, lib, ptr, stream_ptr
+    from cachedembedding_amd.functional import presort_slots, presort_window
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(D)
+    C, B, F = 3000, 512, 4
+    n = B * F
+    slots = torch.randperm(C, generator=g)[:n].to(dev)
+    offs = torch.arange(n + 1, dtype=torch.int32, device=dev)
+    w0 = torch.randn(C, D, generator=g).to(dev)
+    go = (torch.randn(B, F, D, generator=g) * 0.1).to(dev)
+    keys = presort_slots(slots, C)
+    src = presort_window(slots.view(1, n), C, offsets=offs, include_last_offset=True, hook_features=F,
+                         ids=slots.view(1, n).clone())[0]
+    assert src.ranges is not None
+    f32, s = _lib.CE_ACT_F32, stream_ptr()
+    bag = (ptr(slots), n, ptr(offs), 0, n, 1, None, _lib.CE_MODE_SUM, F)      # indices ... hook_features
+    k, sk, rg, gp, w0p, lr = ptr(keys), ptr(src.keys), ptr(src.ranges), ptr(go), ptr(w0), 0.5
+
+    def out():
+        return [torch.zeros(n, D, device=dev)]
+
+    def grad():
+        return [torch.zeros(C, D, device=dev)]
+
+    def table():
+        return [w0.clone()]
+
+    def adagrad():          # table, momentum, workspace (zero-filled before and after)
+        ws = torch.zeros(lib.ce_bag_backward_rowwise_adagrad_workspace(C, D), dtype=torch.uint8, device=dev)
+        return [w0.clone(), torch.full((C,), 0.25, device=dev), ws]
+
+    # name, fresh destination, walks source-row keys, (legacy entry, its arguments, _act twin, its arguments) given
+    # d = the destination's pointer and a = the Adagrad tail (row_of_slot ... stream)
+    L = lib
+    pairs = [
+        ("forward", out, False, lambda d, a: (
+            L.ce_bag_forward, (w0p, C, D, *bag, d, s),
+            L.ce_bag_forward_act, (w0p, C, D, *bag, d, f32, s))),
+        ("forward_src_keys", out, True, lambda d, a: (
+            L.ce_bag_forward_src_keys, (w0p, C, D, n, sk, d, s),
+            L.ce_bag_forward_src_keys_act, (w0p, C, D, n, sk, d, f32, s))),
+        ("backward_dense", grad, False, lambda d, a: (
+            L.ce_bag_backward_dense, (d, C, D, *bag, gp, s),
+            L.ce_bag_backward_dense_act, (d, C, D, *bag, gp, f32, None, s))),
+        ("backward_dense_presorted", grad, False, lambda d, a: (
+            L.ce_bag_backward_dense_presorted, (d, C, D, *bag, gp, k, s),
+            L.ce_bag_backward_dense_act, (d, C, D, *bag, gp, f32, k, s))),
+        ("backward_sgd", table, False, lambda d, a: (
+            L.ce_bag_backward_sgd, (d, C, D, *bag, gp, lr, s),
+            L.ce_bag_backward_sgd_act, (d, C, D, *bag, gp, f32, lr, None, s))),
+        ("backward_sgd_presorted", table, False, lambda d, a: (
+            L.ce_bag_backward_sgd_presorted, (d, C, D, *bag, gp, lr, k, s),
+            L.ce_bag_backward_sgd_act, (d, C, D, *bag, gp, f32, lr, k, s))),
+        ("backward_sgd_presorted_src", table, True, lambda d, a: (
+            L.ce_bag_backward_sgd_presorted_src, (d, C, D, n, gp, lr, sk, s),
+            L.ce_bag_backward_sgd_src_act, (d, C, D, n, gp, f32, lr, sk, None, s))),
+        ("backward_sgd_presorted_src_excl", table, True, lambda d, a: (
+            L.ce_bag_backward_sgd_presorted_src_excl, (d, C, D, n, gp, lr, sk, rg, s),
+            L.ce_bag_backward_sgd_src_act, (d, C, D, n, gp, f32, lr, sk, rg, s))),
+        ("backward_dense_presorted_src", grad, True, lambda d, a: (
+            L.ce_bag_backward_dense_presorted_src, (d, C, D, n, gp, sk, s),
+            L.ce_bag_backward_dense_src_act, (d, C, D, n, gp, f32, sk, s))),
+        ("backward_rowwise_adagrad", adagrad, False, lambda d, a: (
+            L.ce_bag_backward_rowwise_adagrad, (d, C, D, *bag, gp, k, *a),
+            L.ce_bag_backward_rowwise_adagrad_act, (d, C, D, *bag, gp, f32, k, *a))),
+        ("backward_rowwise_adagrad_src", adagrad, True, lambda d, a: (
+            L.ce_bag_backward_rowwise_adagrad_src, (d, C, D, n, gp, sk, *a),
+            L.ce_bag_backward_rowwise_adagrad_src_act, (d, C, D, n, gp, f32, sk, *a))),
+    ]
+    for name, fresh, walks_keys, calls in pairs:
+        if D == 260 and not walks_keys:
+            continue
+        before = fresh()
+        res = []
+        for which in (0, 2):                                                  # the legacy entry, then its twin
+            t = fresh()
+            a = (None, ptr(t[1]), C, 0.1, 1e-8, ptr(t[2]), t[2].numel(), s) if fresh is adagrad else None
+            c = calls(ptr(t[0]), a)
+            check(c[which](*c[which + 1]))
+            res.append(t)
+        assert not torch.equal(res[0][0], before[0]), name                    # (the entry did run)
+        for x, y in zip(*res):
+            assert torch.equal(x, y), name

@@ -124,3 +124,28 @@ def test_refusals_before_any_kernel():
     with pytest.raises(ValueError, match="momentum"):                         # state on the host: refused
         embedding_bag(torch.zeros(2, dtype=torch.long), w, torch.arange(2), mode="sum",
                       fused_sgd=FusedRowwiseAdagrad(0.1, momentum=torch.zeros(4)))
+
+
+def test_adagrad_entries_refuse_an_unsupported_dim_before_their_first_launch():
+    """dim = 2048 (a multiple of 4 past the 1024 of the vector form) is refused by both entries, fp32 and _act, with the
+    code and message of every other bag entry -- before the mark kernel has set a flag in the workspace.  The pointers
+    are made-up addresses, which is why this runs only where nothing could be launched."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("passes made-up addresses: only for machines without a GPU")
+    import __graft_entry__ as g
+    g.build()
+    from cachedembedding_amd import _lib
+    lib = _lib.lib
+    R, D, n = 1000, 2048, 64
+    p = [0x7f0000000000 + 0x100000 * i for i in range(8)]            # non-null, 256-byte aligned
+    ws_bytes = lib.ce_bag_backward_rowwise_adagrad_workspace(R, D)
+    bag = (p[1], n, p[2], 0, n, 1, None, _lib.CE_MODE_SUM, 0)         # indices ... hook_features
+    tail = (None, p[5], R, 0.1, 1e-8, p[6], ws_bytes, None)           # row_of_slot ... stream
+    calls = [lambda: lib.ce_bag_backward_rowwise_adagrad(p[0], R, D, *bag, p[3], None, *tail),
+             lambda: lib.ce_bag_backward_rowwise_adagrad_act(p[0], R, D, *bag, p[3], _lib.CE_ACT_BF16, None, *tail),
+             lambda: lib.ce_bag_backward_rowwise_adagrad_src(p[0], R, D, n, p[3], p[4], *tail),
+             lambda: lib.ce_bag_backward_rowwise_adagrad_src_act(p[0], R, D, n, p[3], _lib.CE_ACT_F32, p[4], *tail)]
+    for call in calls:
+        assert call() == _lib.CE_ERR_UNSUPPORTED
+        assert "too large for this build" in _lib.last_error()
