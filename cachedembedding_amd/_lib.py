@@ -32,6 +32,10 @@ CE_MODE_MEAN = 1
 CE_ACT_F32 = 0
 CE_ACT_BF16 = 1
 CE_ACT_F16 = 2
+CE_OPT_SGD = 0
+CE_OPT_ROWWISE_ADAGRAD = 1
+CE_ROUND_NEAREST = 0
+CE_ROUND_STOCHASTIC = 1
 CE_TRANSPORT_ZEROCOPY = 0
 CE_TRANSPORT_STAGED = 1
 CE_TRANSPORT_WORKER = 2
@@ -89,6 +93,8 @@ _KEYS = [c_void_p]              # presorted / source-row keys
 _STREAM = [c_void_p]
 # keys, row_of_slot, momentum, momentum_rows, lr, eps, workspace, workspace_bytes, stream
 _ADAGRAD_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t] + _STREAM
+_W16 = [c_void_p, c_int32]      # the 16-bit table and its CE_ACT_* code
+_W16_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -139,6 +145,14 @@ SIGNATURES = {
     "ce_bag_backward_dense_src_act": (c_int, _SRC + _ACT + _KEYS + _STREAM),
     "ce_bag_backward_rowwise_adagrad_act": (c_int, _BAG + _ACT + _ADAGRAD_TAIL),
     "ce_bag_backward_rowwise_adagrad_src_act": (c_int, _SRC + _ACT + _ADAGRAD_TAIL),
+    # 16-bit table: weight, weight_dtype in front; the update's tail = keys, row_of_slot, momentum, momentum_rows, lr,
+    # eps, optimizer, rounding, seed, workspace, workspace_bytes, stream
+    "ce_host_fill_uniform_w16": (c_int, [c_void_p, c_int64, c_float, c_float, c_uint64, c_int32, c_int]),
+    "ce_bag_forward_w16": (c_int, _W16 + _BAG[1:] + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_w16": (c_int, _W16 + [c_int64, c_int32, c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    "ce_bag_backward_w16_workspace": (c_size_t, [c_int64, c_int32]),
+    "ce_bag_backward_update_w16": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL),
+    "ce_bag_backward_update_src_w16": (c_int, _W16 + _SRC[1:] + _ACT + _W16_TAIL),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),
@@ -254,7 +268,7 @@ def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-# torch dtype of an activation tensor -> CE_ACT_* (the table itself is always fp32)
+# torch dtype of an activation tensor (or of a 16-bit table's rows) -> CE_ACT_*
 ACT_DTYPES = {torch.float32: CE_ACT_F32, torch.bfloat16: CE_ACT_BF16, torch.float16: CE_ACT_F16}
 
 
@@ -267,6 +281,26 @@ def act_code(dtype) -> int:
     except (KeyError, TypeError):
         raise NotImplementedError(f"output_dtype={dtype!r}: torch.float32, torch.bfloat16 and torch.float16 are "
                                   "implemented") from None
+
+
+W16_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def table_code(dtype) -> int:
+    """CE_ACT_* of a table dtype (table_dtype=): None means fp32.  Anything else is refused by name."""
+    if dtype is None:
+        return CE_ACT_F32
+    try:
+        return ACT_DTYPES[dtype]
+    except (KeyError, TypeError):
+        raise NotImplementedError(f"table_dtype={dtype!r}: torch.float32, torch.bfloat16 and torch.float16 are "
+                                  "implemented") from None
+
+
+def check_w16_dim(dim: int) -> None:
+    """a 16-bit table's rows are whole 16-byte units, one lane group per row: refused before the GPU is asked for"""
+    if dim % 8 != 0 or dim > 1024 or dim <= 0:
+        raise NotImplementedError(f"a 16-bit table needs embedding_dim % 8 == 0 and embedding_dim <= 1024 (got {dim})")
 
 
 def ptr(t) -> int:

@@ -42,7 +42,8 @@ class _PinnedBlock:
 
 
 class HostTable:
-    """[N, D] fp32 table in pinned, device-mapped host DRAM (CachedParamMgr.weight, A.1)."""
+    """[N, D] fp32, bf16 or fp16 table in pinned, device-mapped host DRAM (CachedParamMgr.weight, A.1).  A 16-bit table
+    needs D % 8 == 0 and D <= 1024: its rows are whole 16-byte units, the bytes of an fp32 [N, D / 2] table."""
 
     def __init__(self, tensor: torch.Tensor, host_ptr: int, dev_ptr: int, registered: bool):
         self.tensor = tensor
@@ -59,28 +60,43 @@ class HostTable:
             pass
 
     @classmethod
-    def allocate(cls, num_embeddings: int, dim: int, threads: int = 0) -> "HostTable":
+    def allocate(cls, num_embeddings: int, dim: int, threads=0, dtype: torch.dtype = torch.float32) -> "HostTable":
+        if not isinstance(threads, int):              # allocate(N, D, dtype)
+            threads, dtype = 0, threads
+        w16 = _lib.table_code(dtype) != _lib.CE_ACT_F32
+        if w16:
+            _lib.check_w16_dim(dim)
         _lib.require_gpu()
-        nbytes = num_embeddings * dim * 4
+        nbytes = num_embeddings * dim * (2 if w16 else 4)
         hp, dp = ctypes.c_void_p(), ctypes.c_void_p()
         check(lib.ce_host_alloc(nbytes, threads or _default_threads(), ctypes.byref(hp), ctypes.byref(dp)))
-        carr = (ctypes.c_float * (num_embeddings * dim)).from_address(hp.value)
+        carr = ((ctypes.c_int16 if w16 else ctypes.c_float) * (num_embeddings * dim)).from_address(hp.value)
         # the pinned block lives exactly as long as the tensors over it: tensor -> numpy array -> ctypes array ->
         # block owner (a `.weight` view that outlives the module keeps the memory instead of dangling)
         carr._ce_block = _PinnedBlock(hp.value)
-        t = torch.from_numpy(np.ctypeslib.as_array(carr)).view(num_embeddings, dim)
-        return cls(t, hp.value, dp.value, registered=False)
+        t = torch.from_numpy(np.ctypeslib.as_array(carr))
+        if w16:
+            t = t.view(dtype)                         # the [N, D] 16-bit view of the pinned block
+        return cls(t.view(num_embeddings, dim), hp.value, dp.value, registered=False)
 
     @classmethod
     def wrap(cls, weight: torch.Tensor) -> "HostTable":
         """Pin + map a tensor the caller owns (the `_weight` / from_pretrained path)."""
+        if _lib.table_code(weight.dtype) != _lib.CE_ACT_F32:
+            _lib.check_w16_dim(weight.shape[-1])
         _lib.require_gpu()
-        assert weight.device.type == "cpu" and weight.dtype == torch.float32 and weight.is_contiguous()
+        assert weight.device.type == "cpu" and weight.is_contiguous()
         dp = ctypes.c_void_p()
-        check(lib.ce_host_register(ctypes.c_void_p(weight.data_ptr()), weight.numel() * 4, ctypes.byref(dp)))
+        check(lib.ce_host_register(ctypes.c_void_p(weight.data_ptr()), weight.numel() * weight.element_size(),
+                                   ctypes.byref(dp)))
         return cls(weight, weight.data_ptr(), dp.value, registered=True)
 
     def fill_uniform_(self, lo: float, hi: float, seed: int, threads: int = 0):
+        if self.tensor.dtype != torch.float32:
+            # the round-to-nearest-even cast of the fp32 fill of the same seed, element by element
+            check(lib.ce_host_fill_uniform_w16(ctypes.c_void_p(self.host_ptr), self.tensor.numel(), lo, hi, seed,
+                                               _lib.ACT_DTYPES[self.tensor.dtype], threads or _default_threads()))
+            return self
         check(lib.ce_host_fill_uniform(ctypes.c_void_p(self.host_ptr), self.tensor.numel(), lo, hi, seed,
                                        threads or _default_threads()))
         return self
@@ -94,7 +110,8 @@ def _default_threads() -> int:
 class CachedParamMgr(torch.nn.Module):
     """Manages a [cuda_row_num, D] HBM cache of rows of a host-resident [N, D] table.
 
-    Args mirror upstream: weight (CPU fp32 [N, D], or a HostTable), cuda_row_num,
+    Args mirror upstream: weight (CPU fp32 [N, D], or a HostTable -- possibly a bf16 / fp16 one: the cache then has the
+    table's dtype, and the library, which only moves rows, is driven with embedding_dim = D / 2), cuda_row_num,
     buffer_size (rows of staging the async_copy transport may use at a time -- upstream's
     LimitBuffIndexCopyer; 0 = stage a whole swap at once; the default zero-copy transport has no staging),
     pin_weight (the table is always pinned + mapped here), evict_strategy,
@@ -110,6 +127,9 @@ class CachedParamMgr(torch.nn.Module):
         self._table = weight if isinstance(weight, HostTable) else HostTable.wrap(weight)
         self._weight = self._table.tensor
         self.num_embeddings, self.embedding_dim = self._weight.shape
+        self.table_dtype = self._weight.dtype
+        # what the library is told a row is: fp32 elements (a 16-bit row of D elements = D / 2 of them, bit for bit)
+        self._lib_dim = self.embedding_dim // 2 if self.table_dtype in _lib.W16_DTYPES else self.embedding_dim
         self.cuda_row_num = int(cuda_row_num)
         self.buffer_size = buffer_size
         self.pin_weight = pin_weight
@@ -121,7 +141,7 @@ class CachedParamMgr(torch.nn.Module):
         assert N < 2 ** 31 - 1, "row ids are int32 on the device"
         dev = self.device
         # the only trainable parameter the optimiser sees (A.1)
-        self.cuda_cached_weight = torch.nn.Parameter(torch.zeros(C, D, device=dev, dtype=torch.float32))
+        self.cuda_cached_weight = torch.nn.Parameter(torch.zeros(C, D, device=dev, dtype=self.table_dtype))
         # DATASET+freq re-rank needs idx_map; identity otherwise (kept None = no array, no gather)
         self._idx_map: Optional[torch.Tensor] = None
         if use_idx_map:
@@ -146,14 +166,14 @@ class CachedParamMgr(torch.nn.Module):
     # ------------------------------------------------------------------ handle plumbing
     def _create_handle(self):
         N, C = self.num_embeddings, self.cuda_row_num
-        ws_bytes = lib.ce_cache_workspace_bytes(N, C, self._max_ids, self.embedding_dim)
+        ws_bytes = lib.ce_cache_workspace_bytes(N, C, self._max_ids, self._lib_dim)
         self._workspace = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=self.device)
         base = self._workspace.data_ptr()
         aligned = (base + 255) & ~255
         cfg = CeCacheConfig()
         cfg.num_embeddings = N
         cfg.cuda_row_num = C
-        cfg.embedding_dim = self.embedding_dim
+        cfg.embedding_dim = self._lib_dim
         cfg.evict_strategy = _lib.CE_EVICT_LFU if self._evict_strategy == EvictionStrategy.LFU else _lib.CE_EVICT_DATASET
         tr = getattr(self, "_transport", None)        # None = never set (CE_TRANSPORT_ZEROCOPY is 0: test identity)
         cfg.transport = tr if tr is not None else (
@@ -427,7 +447,7 @@ class CachedParamMgr(torch.nn.Module):
                f"lookups ({100.0 * t['cache_miss'] / max(1, t['total_cache']):.2f} %)")
         wb = self.writeback_stats()
         if wb["jobs"]:
-            row_b = self.embedding_dim * esz
+            row_b = self._lib_dim * esz
             def rate(nbytes, busy_s):
                 # (the chained admission is a kernel on the library's admission stream: no worker thread times it)
                 return f"{nbytes / busy_s / 1e9:.1f} GB/s" if busy_s > 0 else "a rate no worker thread timed"
@@ -464,7 +484,7 @@ class CachedParamMgr(torch.nn.Module):
         self._transport = self._TRANSPORTS[name]
 
     def reserve_tail(self, rows: int) -> torch.Tensor:
-        """fp32 [rows, D] lying right behind the cache in ONE allocation (the cache moves there, contents kept;
+        """[rows, D] of the table's dtype lying right behind the cache in ONE allocation (the cache moves there, contents kept;
         `cuda_cached_weight` stays the same Parameter object).  The row-wise exchange receives into it, so that
         "cache + received rows" is one table for the bag kernels (ce_exchange_local_index).  Blocks until the device
         is idle; call it before anything that captured the cache's address (hipGraphs) -- every address taken earlier
@@ -477,7 +497,7 @@ class CachedParamMgr(torch.nn.Module):
         if full is None or full.shape[0] < C + rows:
             with torch.cuda.device(self.device):
                 torch.cuda.synchronize(self.device)
-                full = torch.empty(C + rows, D, device=self.device, dtype=torch.float32)
+                full = torch.empty(C + rows, D, device=self.device, dtype=self.table_dtype)
                 full[:C].copy_(self.cuda_cached_weight.data)
                 full[C:].zero_()
                 check(lib.ce_cache_set_cache_weight(self._handle, full.data_ptr()))

@@ -24,14 +24,28 @@ class CachedEmbeddingBag(nn.Module):
                  include_last_offset: bool = False, dtype=None, device=None, cache_ratio: float = 0.01,
                  ids_freq_mapping=None, warmup_ratio: float = 0.7, buffer_size: int = 0, pin_weight: bool = False,
                  evict_strategy: EvictionStrategy = EvictionStrategy.DATASET, *, cuda_row_num: Optional[int] = None,
-                 init_seed: int = 1024, strict: bool = True, output_dtype: Optional[torch.dtype] = None):
+                 init_seed: int = 1024, strict: bool = True, output_dtype: Optional[torch.dtype] = None,
+                 table_dtype: Optional[torch.dtype] = None):
         super().__init__()
         # output_dtype (addition): dtype of the pooled output and of the gradient coming back -- None / torch.float32,
         # torch.bfloat16 or torch.float16 (functional.embedding_bag(output_dtype=...)).  `dtype` is the TABLE's dtype.
         if dtype not in (None, torch.float32):
             raise NotImplementedError("only fp32 tables are implemented (dtype= is the table's dtype; a 16-bit "
-                                      "pooled output is output_dtype=)")
-        self.set_output_dtype(output_dtype)
+                                      "pooled output is output_dtype=; for a 16-bit table see table_dtype=)")
+        # table_dtype (addition): None / torch.float32 -- today's module -- or torch.bfloat16 / torch.float16: the host
+        # table AND the cache hold 16-bit rows (half the host DRAM, half of every admission and write-back); sums and
+        # updates stay fp32 and a row is rounded once per step (set_weight_rounding).  The pooled output then defaults
+        # to the table's dtype.
+        self.table_dtype = torch.float32 if _lib.table_code(table_dtype) == _lib.CE_ACT_F32 else table_dtype
+        w16 = self.table_dtype != torch.float32
+        if w16:
+            _lib.check_w16_dim(embedding_dim)
+            for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
+                             ("sparse=True", bool(sparse))):
+                if on:
+                    raise NotImplementedError(f"{what} with a 16-bit table (table_dtype={table_dtype})")
+        self.set_output_dtype(self.table_dtype if (w16 and output_dtype is None) else output_dtype)
+        self.weight_rounding, self.weight_rounding_seed = "stochastic", 0
         _lib.require_gpu()
         assert cache_ratio <= 1.0, f"cache ratio {cache_ratio} must less than 1.0"
         self.num_embeddings = num_embeddings
@@ -58,19 +72,22 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_adagrad = FusedRowwiseAdagrad(None)
 
         if _weight is None:
-            table = HostTable.allocate(num_embeddings, embedding_dim)
+            table = HostTable.allocate(num_embeddings, embedding_dim, dtype=self.table_dtype)
             table.fill_uniform_(-1.0 / num_embeddings, 1.0 / num_embeddings, init_seed)
             if padding_idx is not None:
                 table.tensor[padding_idx].zero_()
         else:
             w = _weight.detach()
             assert tuple(w.shape) == (num_embeddings, embedding_dim)
-            if w.device.type != "cpu" or w.dtype != torch.float32 or not w.is_contiguous():
-                w = w.to("cpu", torch.float32).contiguous()
+            # (a _weight of another dtype is cast once, to nearest; one of the table's dtype is pinned in place)
+            if w.device.type != "cpu" or w.dtype != self.table_dtype or not w.is_contiguous():
+                w = w.to("cpu", self.table_dtype).contiguous()
             table = HostTable.wrap(w)
         self.cache_weight_mgr = CachedParamMgr(table, self.cuda_row_num, buffer_size, pin_weight,
                                                evict_strategy=evict_strategy, device=device, strict=strict)
         self.cache_weight_mgr.reorder(ids_freq_mapping, warmup_ratio)
+        if w16:
+            self.set_weight_rounding(self.weight_rounding, self.weight_rounding_seed)
 
     # -- the host table (upstream `.weight`) and the parameter protocol (A.7) ------------
     @property
@@ -95,6 +112,8 @@ class CachedEmbeddingBag(nn.Module):
         the plain autograd behaviour (grad handed to torch.optim)."""
         if lr is not None and self.fused_adagrad.lr is not None:
             raise ValueError("fused row-wise Adagrad is set: set_fused_rowwise_adagrad(None) before set_fused_sgd(lr)")
+        if lr is not None and deterministic and self.table_dtype != torch.float32:
+            raise NotImplementedError("FusedSGD(deterministic=True) with a 16-bit table")
         self.fused_sgd.lr = lr
         self.fused_sgd.deterministic = deterministic
 
@@ -113,6 +132,20 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_adagrad.eps = float(eps)
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
+
+    def set_weight_rounding(self, rounding: str = "stochastic", seed: int = 0):
+        """How the fused updates round a row of a 16-bit table: "nearest" (round-to-nearest-even) or "stochastic" (the
+        default: one of the two 16-bit neighbours, with probabilities that make the rounding unbiased; the random bits
+        are a hash of seed, step, host-table row and element).  A ValueError for an fp32 table."""
+        if self.table_dtype == torch.float32:
+            raise ValueError("set_weight_rounding is meaningful only with a 16-bit table (table_dtype=)")
+        if rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"rounding={rounding!r}: 'nearest' or 'stochastic'")
+        self.weight_rounding, self.weight_rounding_seed = rounding, int(seed)
+        for f in (self.fused_sgd, self.fused_adagrad):
+            f.rounding, f.seed = rounding, int(seed)
+        # the random bits follow the host-table row, not the slot it happens to sit in
+        self.fused_sgd.row_of_slot = self.cache_weight_mgr.cached_idx_map
 
     def set_output_dtype(self, dtype: Optional[torch.dtype]):
         """dtype of the pooled output, training and eval alike: None / torch.float32 (default), torch.bfloat16 or

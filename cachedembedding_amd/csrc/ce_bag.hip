@@ -19,8 +19,9 @@
 //     registers + LDS itself, or walks presorted segments), k_bag_bwd_rows (COO values), k_rows_axpy (row-wise exchange).
 // Output stores are non-temporal (never re-read here); row loads use the default policy so hot rows stay in
 // L2 / Infinity Cache.
-// The table, the sums and the updates are fp32; the forward's output and the backward's grad_out have the activation
-// type AT (fp32, bf16, fp16: Act<AT, VT> in ce_common.h) the four bag kernels are templated on.
+// The sums and the updates are fp32; the forward's output and the backward's grad_out have the activation
+// type AT (fp32, bf16, fp16: Act<AT, VT> in ce_common.h) the four bag kernels are templated on.  The table is fp32, or
+// -- the two forwards only (WT; ce_bag_forward_w16 / _src_keys_w16) -- bf16 / fp16; its update is ce_bag_adagrad.hip's.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -123,9 +124,12 @@ __device__ __forceinline__ void store_out(T* p, T v) {
 // STAGE: tiles with multi-id bags stage their indices in LDS (32 KB per workgroup); the launcher picks the
 // LDS-free variant when nnz == num_bags (single-id batches) so occupancy is set by registers alone.
 // AT: the output's element type (Act<AT, VT>, ce_common.h): sums stay fp32, the store rounds.
-template <typename VT, int NCH, bool STAGE, int U, int NTS, typename AT>
+// WT: the table's element type (float, or bf16 / fp16 with f32x4 lanes: a lane's chunk is then 8 bytes of the row,
+// up-converted exactly on load).
+template <typename VT, int NCH, bool STAGE, int U, int NTS, typename AT, typename WT = float>
 __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   using A = Act<AT, VT>;
+  using T = Act<WT, VT>;
   __shared__ int lds_idx[STAGE ? 4 : 1][STAGE ? kIdxStage : 1];
   const int lane = threadIdx.x & 63;
   const int G = 1 << p.g_log2;
@@ -135,7 +139,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   const int wpb = blockDim.x >> 6;
   const int64_t wave = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * wpb;
-  const VT* __restrict__ W = (const VT*)p.weight;
+  const typename T::V* __restrict__ W = (const typename T::V*)p.weight;
   typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const int rowlen = p.rowlen;
   // tiles are dealt round-robin to the waves of an oversubscribed grid (an even contiguous split over a
@@ -169,7 +173,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
           for (int c = 0; c < NCH; ++c) {
             const int ch = gl + c * G;
             v[u][c] = vzero<VT>();
-            if (bi < nb && ch < rowlen && (uint32_t)ri < p.num_rows) v[u][c] = W[(int64_t)ri * rowlen + ch];
+            if (bi < nb && ch < rowlen && (uint32_t)ri < p.num_rows) v[u][c] = T::up(W[(int64_t)ri * rowlen + ch]);
           }
         }
 #pragma unroll
@@ -229,7 +233,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
             for (int c = 0; c < NCH; ++c) {
               const int ch = gl + c * G;
               v[t][c] = vzero<VT>();
-              if (ch < rowlen && (uint32_t)r[t] < p.num_rows) v[t][c] = W[(int64_t)r[t] * rowlen + ch];
+              if (ch < rowlen && (uint32_t)r[t] < p.num_rows) v[t][c] = T::up(W[(int64_t)r[t] * rowlen + ch]);
             }
           }
 #pragma unroll
@@ -1024,9 +1028,11 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
 // An ignored lookup (row 0xffffffff, see k_bag_presort_seg) gets a zero row; padding keys (~0) are skipped.
 // AT: the output's element type; the row is rounded once per store, so `prev` stays the fp32 row.
 // PAIR (16-bit AT, f32x4 lanes): the stores of two keys are ONE 16-byte store per lane (see u32x4 above).
-template <typename VT, int NCH, int R, int NTS, typename AT, bool PAIR = false>
+// WT: the table's element type (a 16-bit table whose type differs from AT: the row is up-converted on load).
+template <typename VT, int NCH, int R, int NTS, typename AT, bool PAIR = false, typename WT = float>
 __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t total) {      // 4 waves per SIMD: <= 128 VGPRs
   using A = Act<AT, VT>;
+  using T = Act<WT, VT>;
   static_assert(!PAIR || (sizeof(typename A::V) == 8 && R % 2 == 0), "PAIR: 4 x 16 bit per lane, keys two at a time");
   __shared__ unsigned long long lk[256 * (R > 4 ? R : 4)];
   const int tid = threadIdx.x;
@@ -1035,7 +1041,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
   const int grp = tid >> p.g_log2;
   const int gl = tid & (G - 1);
   const int rowlen = p.rowlen;
-  const VT* __restrict__ W = (const VT*)p.weight;
+  const typename T::V* __restrict__ W = (const typename T::V*)p.weight;
   typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const unsigned long long* __restrict__ keys = p.presorted;
   const int64_t all_groups = (int64_t)gridDim.x * ngroups;
@@ -1069,7 +1075,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
         for (int c = 0; c < NCH; ++c) {
           const int ch = gl + c * G;
           v[t][c] = vzero<VT>();
-          if (head && ch < rowlen && rw < p.num_rows) v[t][c] = W[(int64_t)rw * rowlen + ch];
+          if (head && ch < rowlen && rw < p.num_rows) v[t][c] = T::up(W[(int64_t)rw * rowlen + ch]);
         }
       }
       __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): every head of the step has arrived
@@ -1527,6 +1533,92 @@ extern "C" int ce_bag_forward_src_keys_act(const float* weight, int64_t num_rows
 extern "C" int ce_bag_forward_src_keys(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                        const uint64_t* src_keys, float* out, ce_stream_t stream) {
   return ce_bag_forward_src_keys_act(weight, num_rows, dim, nnz, src_keys, out, CE_ACT_F32, stream);
+}
+
+// ---- forward from a 16-bit table: the same kernels with the row type WT; only the vector lane shape exists
+// (dim % 8 == 0), a lane's chunk is 8 bytes of the row
+extern "C" int ce_bag_forward_w16(const void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                  const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                  int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                  int32_t mode, int64_t hook_features, void* out, int32_t act_dtype,
+                                  ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  int rc = w16_check(weight_dtype, dim);
+  if (rc) return rc;
+  if (num_bags == 0) return CE_OK;
+  CE_REQUIRE(weight && out && (indices || nnz == 0), CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(offsets || num_bags == nnz, CE_ERR_INVALID,
+             "offsets == NULL states one id per bag (offsets = arange): num_bags must equal nnz");
+  CE_REQUIRE(al16(weight) && act_aligned(out, act_dtype), CE_ERR_INVALID,
+             "a 16-bit table must be 16-byte aligned and its output on the vector boundary");
+  BagParams p{};
+  RowGeom r;
+  rc = fill_params(p, r, dim, true, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                   per_sample_weights, mode, hook_features);
+  if (rc) return rc;
+  p.weight = (const float*)weight;
+  p.dst = (float*)out;
+  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  p.num_rows = (uint32_t)num_rows;
+  dim3 grid(bag_grid(num_bags)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  const bool stage = nnz != num_bags;      // multi-id bags possible
+  for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
+    for_act(act_dtype, [&](auto a) {
+      using VT = typename decltype(l)::VT;
+      using AT = typename decltype(a)::AT;
+      using WT = typename decltype(w)::AT;
+      constexpr int N = decltype(l)::NCH, U = tile_unroll<VT, N>();
+      if (stage) hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, 1, AT, WT>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, 1, AT, WT>), grid, block, 0, s, p);
+    });
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
+// Output type == table type: the forward moves bits, so it IS the fp32 key-driven forward over the same bytes seen as
+// an fp32 [num_rows, dim / 2] table (nothing converts, an ignored lookup's row is zero).  Other pairs: the converting
+// instantiation (exact up-conversion, one rounding on the store).
+extern "C" int ce_bag_forward_src_keys_w16(const void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                           int64_t nnz, const uint64_t* src_keys, void* out, int32_t act_dtype,
+                                           ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  int rc = w16_check(weight_dtype, dim);
+  if (rc) return rc;
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE(al16(weight) && act_aligned(out, act_dtype), CE_ERR_INVALID,
+             "a 16-bit table must be 16-byte aligned and its output on the vector boundary");
+  if (act_dtype == weight_dtype) {
+    CE_REQUIRE(al16(out), CE_ERR_INVALID, "the bit-copying forward needs a 16-byte aligned output");
+    return ce_bag_forward_src_keys_act((const float*)weight, num_rows, dim / 2, nnz, src_keys, out, CE_ACT_F32, stream);
+  }
+  BagParams p{};
+  RowGeom r;
+  rc = fill_params_keys(p, r, dim, true, nnz);
+  if (rc) return rc;
+  p.weight = (const float*)weight;
+  p.dst = (float*)out;
+  p.num_rows = (uint32_t)num_rows;
+  p.presorted = (const unsigned long long*)src_keys;
+  p.interleave = 0;
+  const int64_t total = padded_keys(nnz);
+  const dim3 g = keys_grid(total, p.g_log2, 16), b(256);
+  hipStream_t s = (hipStream_t)stream;
+  for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
+    for_act(act_dtype, [&](auto a) {
+      using VT = typename decltype(l)::VT;
+      using AT = typename decltype(a)::AT;
+      using WT = typename decltype(w)::AT;
+      constexpr int N = decltype(l)::NCH, R = keys_unroll<VT, N>();
+      if constexpr (!std::is_same<AT, WT>::value)       // (equal types left above)
+        hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT, false, WT>), g, b, 0, s, p, total);
+    });
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
 }
 
 extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : cdiv(nnz, kSegLen) * kSegLen; }

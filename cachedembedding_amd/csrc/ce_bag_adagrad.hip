@@ -165,6 +165,229 @@ static int launch_apply(float* weight, int64_t num_rows, int32_t dim, const int3
   return CE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// 16-bit table (bf16 / fp16 rows): the same three launches for SGD as well.  fp32 atomics cannot land on 16-bit rows
+// and a 16-bit atomic per partial sum would round once per lookup, so the step's gradient is folded into the fp32
+// accumulator and k_rows_apply_w16 rounds the row ONCE: w = up(W16[s]) (exact), x = the fp32 update, W16[s] = round(x).
+// The workspace is carve_adagrad's plus one 64-bit step counter: one thread of the mark kernel -- the first launch of
+// the sequence -- adds one to it, the apply pass reads it, so a replayed graph draws fresh random bits every step.
+
+struct W16Args {
+  void* weight;              // [num_rows, D] of WT
+  float* acc;
+  uint8_t* flags;
+  const unsigned long long* counter;
+  const int32_t* row_of_slot;
+  float* momentum;
+  int64_t momentum_rows;
+  uint64_t seed;
+  uint32_t num_rows;
+  int32_t rowlen;            // f32x4 chunks per row
+  int32_t g_log2;
+  int32_t dim;
+  float lr;
+  float eps;
+};
+
+__global__ __launch_bounds__(256) void k_w16_mark_slots(const int64_t* __restrict__ slots, int64_t n, uint32_t num_rows,
+                                                        uint8_t* __restrict__ flags, unsigned long long* counter) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t s = slots[i];
+    if (s >= 0 && s < (int64_t)num_rows) flags[s] = 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_w16_mark_keys(const unsigned long long* __restrict__ keys, int64_t n,
+                                                       uint32_t num_rows, uint8_t* __restrict__ flags,
+                                                       unsigned long long* counter) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint32_t s = (uint32_t)(keys[i] >> 32);
+    if (s < num_rows) flags[s] = 1;
+  }
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// Stochastic rounding in integer arithmetic on the fp32 bit pattern: a uniform integer below the dropped bits is added
+// to the magnitude and the sum truncated -- the neighbour farther from zero is taken with probability
+// (dropped bits) / 2^k, a representable x (dropped bits zero) never moves.  Everything else takes the nearest cast.
+__device__ __forceinline__ bf16_t round_stochastic(float x, uint32_t rnd, bf16_t) {
+  const uint32_t b = __float_as_uint(x);
+  const uint32_t t = b + (rnd & 0xffffu);
+  // NaN / inf, or a carry past the largest finite value
+  if ((b & 0x7f800000u) == 0x7f800000u || (t & 0x7f800000u) == 0x7f800000u) return (bf16_t)x;
+  return __builtin_bit_cast(bf16_t, (uint16_t)(t >> 16));
+}
+__device__ __forceinline__ f16_t round_stochastic(float x, uint32_t rnd, f16_t) {
+  const uint32_t b = __float_as_uint(x);
+  const uint32_t mag = b & 0x7fffffffu;
+  // fp16 normals below the largest finite value: 2^-14 <= |x| < 65504 (NaN / inf / subnormal results: nearest)
+  if (mag < 0x38800000u || mag >= 0x477fe000u) return (f16_t)x;
+  const uint32_t t = (b + (rnd & 0x1fffu)) & ~0x1fffu;       // 13 dropped bits; at most 65504: exact in fp16
+  return (f16_t)__uint_as_float(t);
+}
+
+// the same walk over the flags as k_adagrad_apply: one wave per 64 slots, a ballot, one lane group per flagged slot
+template <typename WT, int NCH, bool ADAGRAD, bool STOCH>
+__global__ __launch_bounds__(256) void k_rows_apply_w16(W16Args a) {
+  using T = Act<WT, f32x4>;
+  const int G = 1 << a.g_log2;
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> a.g_log2;
+  const int gl = lane & (G - 1);
+  const int ngw = 64 >> a.g_log2;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  typename T::V* W = (typename T::V*)a.weight;
+  f32x4* A = (f32x4*)a.acc;
+  uint64_t step_key = 0;
+  if (STOCH) step_key = mix64(a.seed + 0xD6E8FEB86659FD93ull * *a.counter);
+  for (int64_t base = wave * 64; base < (int64_t)a.num_rows; base += nwaves * 64) {
+    const int64_t mine = base + lane;
+    const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
+    unsigned long long m = __ballot(flagged);
+    while (m) {
+      unsigned long long mm = m;
+      for (int k = 0; k < q; ++k) mm &= mm - 1;
+      for (int k = 0; k < ngw; ++k) m &= m - 1;
+      if (mm == 0) continue;
+      const int64_t s = base + (__ffsll((long long)mm) - 1);
+      f32x4 g[NCH];
+      float ss = 0.f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        g[c] = idx < a.rowlen ? A[s * a.rowlen + idx] : vzero<f32x4>();
+        ss += sq_sum(g[c]);
+      }
+      const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
+      float mult = a.lr;
+      bool update = true;
+      if (ADAGRAD) {
+        for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, G);
+        update = r >= 0 && r < a.momentum_rows;
+        if (update) {
+          const float mr = a.momentum[r] + ss / (float)a.dim;
+          mult = a.lr / (sqrtf(mr) + a.eps);
+          if (gl == 0) a.momentum[r] = mr;
+        }
+      }
+      if (update) {
+        uint64_t row_key = 0;
+        if (STOCH) row_key = mix64(step_key ^ (uint64_t)r);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int idx = gl + c * G;
+          if (idx < a.rowlen) {
+            const f32x4 x = T::up(W[s * a.rowlen + idx]) - g[c] * mult;
+            if (STOCH) {
+              const uint64_t h = mix64(row_key + (uint64_t)idx);     // 16 bits for each of the chunk's 4 elements
+              typename T::V o;
+              o.x = round_stochastic(x.x, (uint32_t)h, WT{});
+              o.y = round_stochastic(x.y, (uint32_t)(h >> 16), WT{});
+              o.z = round_stochastic(x.z, (uint32_t)(h >> 32), WT{});
+              o.w = round_stochastic(x.w, (uint32_t)(h >> 48), WT{});
+              W[s * a.rowlen + idx] = o;
+            } else {
+              W[s * a.rowlen + idx] = T::down(x);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        if (idx < a.rowlen) A[s * a.rowlen + idx] = vzero<f32x4>();
+      }
+    }
+    if (flagged) a.flags[mine] = 0;
+  }
+}
+
+struct W16Ws {
+  AdagradWs base;
+  unsigned long long* counter;
+  size_t bytes;
+};
+
+static W16Ws carve_w16(void* ws, int64_t num_rows, int32_t dim) {
+  W16Ws w{};
+  w.base = carve_adagrad(ws, num_rows, dim);
+  w.counter = (unsigned long long*)((char*)ws + w.base.bytes);
+  w.bytes = w.base.bytes + 256;
+  return w;
+}
+
+// everything the two update entries can refuse, before their first launch (arguments alone: no launch, no HIP call)
+static int w16_update_check(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, const void* grad_out,
+                            int act, float* momentum, int64_t momentum_rows, float lr, float eps, int32_t optimizer,
+                            int32_t rounding, void* workspace, size_t workspace_bytes) {
+  CE_REQUIRE_ACT(act);
+  int rc = w16_check(weight_dtype, dim);
+  if (rc) return rc;
+  CE_REQUIRE(optimizer == CE_OPT_SGD || optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_INVALID,
+             "unknown optimizer %d (CE_OPT_SGD / CE_OPT_ROWWISE_ADAGRAD)", (int)optimizer);
+  CE_REQUIRE(rounding == CE_ROUND_NEAREST || rounding == CE_ROUND_STOCHASTIC, CE_ERR_INVALID,
+             "unknown rounding %d (CE_ROUND_NEAREST / CE_ROUND_STOCHASTIC)", (int)rounding);
+  CE_REQUIRE(weight && grad_out && workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE(lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
+  if (optimizer == CE_OPT_ROWWISE_ADAGRAD) {
+    CE_REQUIRE(momentum && momentum_rows > 0, CE_ERR_INVALID, "row-wise Adagrad needs its momentum");
+    CE_REQUIRE(eps > 0.f, CE_ERR_INVALID, "eps must be > 0");
+  }
+  CE_REQUIRE(workspace_bytes >= carve_w16(nullptr, num_rows, dim).bytes, CE_ERR_INVALID, "workspace too small");
+  CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
+  CE_REQUIRE(al16(weight), CE_ERR_INVALID, "a 16-bit table must be 16-byte aligned");
+  // the scatter into acc takes the vector or the scalar form by grad_out's alignment; both must fit the dim
+  RowGeom r;
+  return row_geometry(dim, act_aligned(grad_out, act), r);
+}
+
+static int launch_apply_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                            const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr, float eps,
+                            int32_t optimizer, int32_t rounding, uint64_t seed, const W16Ws& ws, hipStream_t s) {
+  RowGeom r;
+  int rc = row_geometry(dim, true, r);
+  if (rc) return rc;
+  W16Args a{};
+  a.weight = weight;
+  a.acc = ws.base.acc;
+  a.flags = ws.base.flags;
+  a.counter = ws.counter;
+  a.row_of_slot = row_of_slot;
+  a.momentum = momentum;
+  a.momentum_rows = momentum_rows;
+  a.seed = seed;
+  a.num_rows = (uint32_t)num_rows;
+  a.rowlen = r.rowlen;
+  a.g_log2 = r.g_log2;
+  a.dim = dim;
+  a.lr = lr;
+  a.eps = eps;
+  const dim3 g(grid_for(cdiv(num_rows, 64), 4)), b(256);
+  const bool ada = optimizer == CE_OPT_ROWWISE_ADAGRAD, st = rounding == CE_ROUND_STOCHASTIC;
+  for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
+    using WT = typename decltype(w)::AT;
+    constexpr int N = decltype(l)::NCH;
+    if (ada && st) hipLaunchKernelGGL((k_rows_apply_w16<WT, N, true, true>), g, b, 0, s, a);
+    else if (ada) hipLaunchKernelGGL((k_rows_apply_w16<WT, N, true, false>), g, b, 0, s, a);
+    else if (st) hipLaunchKernelGGL((k_rows_apply_w16<WT, N, false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_rows_apply_w16<WT, N, false, false>), g, b, 0, s, a);
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
 }  // namespace ce
 
 using namespace ce;
@@ -245,4 +468,66 @@ extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_ro
   return ce_bag_backward_rowwise_adagrad_src_act(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, src_keys,
                                                  row_of_slot, momentum, momentum_rows, lr, eps, workspace,
                                                  workspace_bytes, stream);
+}
+
+// ---- 16-bit table: mark (+ step counter), the dense backward into acc, k_rows_apply_w16
+
+extern "C" size_t ce_bag_backward_w16_workspace(int64_t num_rows, int32_t dim) {
+  if (num_rows < 0 || dim < 0) return 0;
+  return carve_w16(nullptr, num_rows, dim).bytes;
+}
+
+extern "C" int ce_bag_backward_update_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                          const int64_t* indices, int64_t nnz, const void* offsets,
+                                          int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                          const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                          const void* grad_out, int32_t act_dtype, const uint64_t* presorted,
+                                          const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                          float eps, int32_t optimizer, int32_t rounding, uint64_t seed,
+                                          void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  int rc = w16_update_check(weight, weight_dtype, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps,
+                            optimizer, rounding, workspace, workspace_bytes);
+  if (rc) return rc;
+  if (num_bags == 0 || nnz == 0) return CE_OK;
+  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(num_bags > 0 && nnz > 0 && num_bags < (int64_t)INT32_MAX - 64 && nnz < (int64_t)INT32_MAX, CE_ERR_INVALID,
+             "sizes out of range");
+  CE_REQUIRE(mode == CE_MODE_SUM || (mode == CE_MODE_MEAN && !per_sample_weights), CE_ERR_INVALID,
+             "mode must be sum, or mean without per_sample_weights");
+  CE_REQUIRE(hook_features >= 0 && (hook_features == 0 || num_bags % hook_features == 0), CE_ERR_INVALID,
+             "hook_features must divide num_bags");
+  hipStream_t s = (hipStream_t)stream;
+  const W16Ws ws = carve_w16(workspace, num_rows, dim);
+  hipLaunchKernelGGL(k_w16_mark_slots, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz, (uint32_t)num_rows,
+                     ws.base.flags, ws.counter);
+  CE_LAUNCH_CHECK();
+  rc = ce_bag_backward_dense_act(ws.base.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                                 include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                                 presorted, stream);
+  if (rc) return rc;
+  return launch_apply_w16(weight, weight_dtype, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps,
+                          optimizer, rounding, seed, ws, s);
+}
+
+extern "C" int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                              int64_t nnz, const void* grad_out, int32_t act_dtype,
+                                              const uint64_t* src_keys, const int32_t* row_of_slot, float* momentum,
+                                              int64_t momentum_rows, float lr, float eps, int32_t optimizer,
+                                              int32_t rounding, uint64_t seed, void* workspace,
+                                              size_t workspace_bytes, ce_stream_t stream) {
+  int rc = w16_update_check(weight, weight_dtype, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps,
+                            optimizer, rounding, workspace, workspace_bytes);
+  if (rc) return rc;
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(src_keys && nnz > 0 && nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "null keys or nnz out of range");
+  hipStream_t s = (hipStream_t)stream;
+  const W16Ws ws = carve_w16(workspace, num_rows, dim);
+  const int64_t total = ce_bag_presort_len(nnz);
+  hipLaunchKernelGGL(k_w16_mark_keys, dim3(grid_for(total, 256)), dim3(256), 0, s, (const unsigned long long*)src_keys,
+                     total, (uint32_t)num_rows, ws.base.flags, ws.counter);
+  CE_LAUNCH_CHECK();
+  rc = ce_bag_backward_dense_src_act(ws.base.acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
+  if (rc) return rc;
+  return launch_apply_w16(weight, weight_dtype, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps,
+                          optimizer, rounding, seed, ws, s);
 }

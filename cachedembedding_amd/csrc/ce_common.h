@@ -134,6 +134,16 @@ static inline bool act_aligned(const void* q, int act) { return (((uintptr_t)q) 
   CE_REQUIRE((act) == CE_ACT_F32 || (act) == CE_ACT_BF16 || (act) == CE_ACT_F16, CE_ERR_INVALID,       \
              "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)(act))
 
+// A 16-bit TABLE (ce_*_w16): bf16 / fp16 rows that are whole 16-byte units, vector lanes only.  Arguments alone decide.
+static inline int w16_check(int32_t weight_dtype, int32_t dim) {
+  CE_REQUIRE(weight_dtype == CE_ACT_BF16 || weight_dtype == CE_ACT_F16, CE_ERR_INVALID,
+             "weight_dtype %d: a 16-bit table is CE_ACT_BF16 or CE_ACT_F16", (int)weight_dtype);
+  CE_REQUIRE(dim > 0, CE_ERR_INVALID, "embedding dim must be positive");
+  CE_REQUIRE(dim % 8 == 0 && dim <= 1024, CE_ERR_UNSUPPORTED,
+             "a 16-bit table needs dim %% 8 == 0 and dim <= 1024 (got %d)", (int)dim);
+  return CE_OK;
+}
+
 // The one place that turns the run-time lane shape and activation code into template arguments: f is a generic lambda
 // and gets a tag to read the types from (typename decltype(l)::VT, decltype(l)::NCH, typename decltype(a)::AT).
 template <typename VT_, int NCH_> struct Lanes {
@@ -152,6 +162,14 @@ template <typename F> static inline void for_lanes(bool vec, int nch, F&& f) {
 
 template <typename F> static inline void for_act(int act, F&& f) {
   if (act == CE_ACT_F32) f(ActTag<float>{}); else if (act == CE_ACT_BF16) f(ActTag<bf16_t>{}); else f(ActTag<f16_t>{});
+}
+
+// a 16-bit table's lanes (always f32x4 chunks) and row type: f(Lanes<f32x4, N>, ActTag<WT>)
+template <typename F> static inline void for_w16(int nch, int weight_dtype, F&& f) {
+  auto lanes = [&](auto w) {
+    if (nch == 1) f(Lanes<f32x4, 1>{}, w); else if (nch == 2) f(Lanes<f32x4, 2>{}, w); else f(Lanes<f32x4, 4>{}, w);
+  };
+  if (weight_dtype == CE_ACT_BF16) lanes(ActTag<bf16_t>{}); else lanes(ActTag<f16_t>{});
 }
 
 }  // namespace ce

@@ -260,6 +260,52 @@ extern "C" int ce_host_fill_uniform(float* dst, int64_t n, float lo, float hi, u
   return CE_OK;
 }
 
+// round-to-nearest-even casts of a finite or non-finite fp32 value, in integer arithmetic (host code)
+static inline uint16_t f32_to_bf16_rne(float f) {
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  if ((x & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((x >> 16) | 0x40u);   // NaN stays NaN
+  return (uint16_t)((x + 0x7fffu + ((x >> 16) & 1u)) >> 16);
+}
+static inline uint16_t f32_to_f16_rne(float f) {
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
+  x &= 0x7fffffffu;
+  if (x >= 0x7f800000u) return sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u);
+  if (x >= 0x477ff000u) return sign | 0x7c00u;               // from 65520 on: inf
+  if (x < 0x38800000u) {                                     // below 2^-14: a subnormal half, in units of 2^-24
+    float m;
+    memcpy(&m, &x, 4);
+    m += 0.5f;                                               // the fp32 addition rounds to 2^-24, to nearest even
+    uint32_t r;
+    memcpy(&r, &m, 4);
+    return sign | (uint16_t)(r - 0x3f000000u);
+  }
+  uint32_t r = x - 0x38000000u;                              // exponent re-biased; 13 bits to drop
+  r += 0x0fffu + ((r >> 13) & 1u);
+  return sign | (uint16_t)(r >> 13);
+}
+
+extern "C" int ce_host_fill_uniform_w16(void* dst, int64_t n, float lo, float hi, uint64_t seed, int32_t dtype,
+                                        int threads) {
+  CE_REQUIRE(dst && n >= 0, CE_ERR_INVALID, "bad arguments");
+  CE_REQUIRE(dtype == CE_ACT_BF16 || dtype == CE_ACT_F16, CE_ERR_INVALID,
+             "dtype %d: CE_ACT_BF16 or CE_ACT_F16", (int)dtype);
+  const float span = hi - lo;
+  uint16_t* out = (uint16_t*)dst;
+  const bool bf = dtype == CE_ACT_BF16;
+  parallel_for(n, threads, [=](int64_t a, int64_t b) {
+    for (int64_t i = a; i < b; ++i) {
+      const uint64_t r = splitmix64(seed * 0xD6E8FEB86659FD93ull + (uint64_t)i);
+      const float u = (float)(r >> 40) * (1.0f / 16777216.0f);   // as ce_host_fill_uniform
+      const float v = lo + span * u;
+      out[i] = bf ? f32_to_bf16_rne(v) : f32_to_f16_rne(v);
+    }
+  });
+  return CE_OK;
+}
+
 // ---- rows of the host table by number: regenerated from the seed, or read back through the device mapping ----------
 
 namespace ce {

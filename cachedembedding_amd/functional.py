@@ -69,7 +69,8 @@ class _BagFn(torch.autograd.Function):
     def forward(ctx, weight, indices, offsets, psw, mode, include_last, hook_features, sparse, fused, presorted,
                 bwd_scale=None, masked=False, out_box=None, out_dtype=torch.float32):
         _lib.require_gpu()
-        assert weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous()
+        w16 = weight.dtype in _lib.W16_DTYPES
+        assert weight.is_cuda and (w16 or weight.dtype == torch.float32) and weight.is_contiguous()
         if psw is not None and ctx.needs_input_grad[3] and fused is not None and fused.lr is not None:
             # d loss / d per_sample_weights[j] = <grad_out[bag of j], weight[indices[j]]> needs the rows as the forward
             # saw them, and the fused update moves them inside backward: refused HERE, before any kernel has run (a
@@ -93,7 +94,18 @@ class _BagFn(torch.autograd.Function):
             and mode == _lib.CE_MODE_SUM and num_bags == indices.numel()
         # the ce_*_act entries for every dtype: the kernels store the output as `act` (CE_ACT_F32: the fp32 form)
         act = _lib.ACT_DTYPES[out_dtype]
-        if from_keys:
+        if w16:
+            # a 16-bit table: the same two kernels with the row type as a further argument (rows up-converted exactly,
+            # fp32 sums, one rounding on the store; from keys with out_dtype == the table's dtype: a bit copy)
+            wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], weight.shape[0], dim)
+            if from_keys:
+                check(lib.ce_bag_forward_src_keys_w16(*wd, indices.numel(), ptr(presorted.keys), ptr(out), act,
+                                                      stream_ptr()))
+            else:
+                check(lib.ce_bag_forward_w16(*wd, ptr(indices), indices.numel(), ptr(offsets),
+                                             int(offsets.dtype == torch.int64), num_bags, int(include_last), ptr(psw),
+                                             mode, hook_features, ptr(out), act, stream_ptr()))
+        elif from_keys:
             # one id per bag: out[bag] = W[slot], and the window's keys hold (slot, output row) grouped by slot
             check(lib.ce_bag_forward_src_keys_act(ptr(weight), weight.shape[0], dim, indices.numel(),
                                                   ptr(presorted.keys), ptr(out), act, stream_ptr()))
@@ -136,6 +148,32 @@ class _BagFn(torch.autograd.Function):
             grad_out = grad_out.float()
         slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
                       hook_features, ptr(grad_out))
+        if weight.dtype in _lib.W16_DTYPES:
+            # 16-bit table (the combinations it does not take were refused in embedding_bag, before the forward)
+            wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
+            if rowwise or sgd:
+                # mark + the dense backward into an fp32 accumulator + one apply pass that rounds every row once
+                with torch.no_grad():
+                    ws = fused.workspace_w16(R, dim, weight.device)
+                    mom = fused.momentum if rowwise else None
+                    tail = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), float(fused.lr),
+                            float(fused.eps) if rowwise else 0.0,
+                            _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
+                            _lib.CE_ROUND_STOCHASTIC if fused.rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
+                            int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr())
+                    if src:
+                        check(lib.ce_bag_backward_update_src_w16(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                    else:
+                        check(lib.ce_bag_backward_update_w16(*wd, *slots_args, act, ptr(pre), *tail))
+                return (None,) * 14
+            # no fused optimizer: the dense gradient is accumulated in fp32 and cast once to the parameter's dtype
+            g32 = torch.zeros(R, dim, device=weight.device, dtype=torch.float32)
+            if src:
+                check(lib.ce_bag_backward_dense_src_act(ptr(g32), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys),
+                                                        stream_ptr()))
+            else:
+                check(lib.ce_bag_backward_dense_act(ptr(g32), R, dim, *slots_args, act, ptr(pre), stream_ptr()))
+            return (g32.to(weight.dtype),) + (None,) * 13
         if rowwise:
             # exact row-wise Adagrad inside backward (ce_bag_adagrad.hip): the optimizer sees grad=None
             with torch.no_grad():
@@ -277,6 +315,16 @@ def renorm_rows_(weight: torch.Tensor, indices: torch.Tensor, max_norm: float, n
                                  float(norm_type), ptr(ws), ws.numel(), stream_ptr()))
 
 
+def _workspace_w16(self, num_rows: int, dim: int, device) -> torch.Tensor:
+    """workspace of the 16-bit table's update (fp32 accumulator [num_rows, dim] -- twice the 16-bit rows it serves --,
+    byte flags, the step counter): zero-filled once; every call leaves it zero-filled except the counter"""
+    need = lib.ce_bag_backward_w16_workspace(num_rows, dim)
+    if self._ws16 is None or self._ws16.numel() < need or self._ws16.device != device:
+        self._ws16 = None
+        self._ws16 = torch.zeros(need, dtype=torch.uint8, device=device)
+    return self._ws16
+
+
 class FusedSGD:
     """Switch for the fused backward+SGD path of one embedding module.
 
@@ -287,6 +335,12 @@ class FusedSGD:
         self.lr = lr
         self.deterministic = deterministic
         self._ws = None
+        # a 16-bit table only: how the update rounds a row ("nearest" / "stochastic"), the seed of the random bits and
+        # the host-table row of every slot they are drawn for (None: the slot itself)
+        self.rounding, self.seed, self.row_of_slot = "stochastic", 0, None
+        self._ws16 = None
+
+    workspace_w16 = _workspace_w16
 
     def workspace(self, num_rows: int, nnz: int, device) -> torch.Tensor:
         need = lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz)
@@ -311,6 +365,10 @@ class FusedRowwiseAdagrad:
         self.momentum = momentum
         self.row_of_slot = row_of_slot
         self._ws = None
+        self.rounding, self.seed = "stochastic", 0          # a 16-bit table only (see FusedSGD)
+        self._ws16 = None
+
+    workspace_w16 = _workspace_w16
 
     def check(self, weight: torch.Tensor) -> None:
         """refusals that must come before any kernel of the step has run"""
@@ -352,6 +410,20 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     # and hence of the gradient autograd hands back; the weight, the sums and every update stay fp32, the kernels
     # round once on the store and read the 16-bit gradient in place.  out= must then have that dtype.
     _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
+    if weight.dtype in _lib.W16_DTYPES:
+        # a 16-bit table (bf16 / fp16 weight): rows up-converted exactly, fp32 sums, the output defaults to the
+        # weight's dtype.  What it does not take is refused here, before any kernel has run.
+        _lib.check_w16_dim(weight.shape[1])
+        sgd16 = isinstance(fused_sgd, FusedSGD) and fused_sgd.lr is not None
+        for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
+                         ("FusedSGD(deterministic=True)", sgd16 and fused_sgd.deterministic),
+                         ("a gradient w.r.t. per_sample_weights",
+                          per_sample_weights is not None and per_sample_weights.requires_grad
+                          and torch.is_grad_enabled())):
+            if on:
+                raise NotImplementedError(f"{what} with a 16-bit table ({weight.dtype})")
+        if output_dtype is None:
+            output_dtype = weight.dtype
     if output_dtype is None:
         output_dtype = torch.float32
     # masked_indices: the caller already replaced ignored lookups (padding) by -1 -- the kernels skip them; the

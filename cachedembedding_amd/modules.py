@@ -127,8 +127,13 @@ class FusedSparseModules(nn.Module):
                  cache_ratio: float = 0.01, id_freq_map=None, warmup_ratio: float = 0.7, buffer_size: int = 50_000,
                  is_dist_dataloader: bool = True, use_lfu_eviction: bool = False, use_tablewise_parallel: bool = False,
                  dataset: Optional[str] = None, fold_hook: bool = False, group=None,
-                 output_dtype: Optional[torch.dtype] = None):
+                 output_dtype: Optional[torch.dtype] = None, table_dtype: Optional[torch.dtype] = None):
         super().__init__()
+        # table_dtype (addition): torch.bfloat16 / torch.float16 rows in the host table and in the cache
+        # (CachedEmbeddingBag(table_dtype=...)); single-rank column-wise operator only
+        if use_tablewise_parallel and _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"FusedSparseModules(use_tablewise_parallel=True, table_dtype={table_dtype}): "
+                                      "the table-wise module keeps fp32 tables")
         # output_dtype (addition): dtype of the pooled embeddings (CachedEmbeddingBag(output_dtype=...)); single-rank
         # column-wise operator only
         if use_tablewise_parallel and _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
@@ -153,7 +158,8 @@ class FusedSparseModules(nn.Module):
                                                     mode=reduction_mode, include_last_offset=True,
                                                     cache_ratio=cache_ratio, ids_freq_mapping=id_freq_map,
                                                     warmup_ratio=warmup_ratio, buffer_size=buffer_size,
-                                                    evict_strategy=strategy, group=group, output_dtype=output_dtype)
+                                                    evict_strategy=strategy, group=group, output_dtype=output_dtype,
+                                                    table_dtype=table_dtype)
             self.shape_hook = sparse_embedding_shape_hook
         dist_on = torch.distributed.is_initialized()
         self.kjt_collector = KJTAllToAll(group) if (is_dist_dataloader and dist_on) else None

@@ -526,8 +526,12 @@ class RowwiseShardedEmbeddingBag(nn.Module):
                  cache_ratio: float = 0.01, ids_freq_mapping=None, warmup_ratio: float = 0.7,
                  evict_strategy: EvictionStrategy = EvictionStrategy.DATASET, group=None,
                  _weight_shard: Optional[torch.Tensor] = None, init_seed: int = 1024,
-                 cuda_row_num: Optional[int] = None, output_dtype: Optional[torch.dtype] = None):
+                 cuda_row_num: Optional[int] = None, output_dtype: Optional[torch.dtype] = None,
+                 table_dtype: Optional[torch.dtype] = None):
         super().__init__()
+        if _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"RowwiseShardedEmbeddingBag with table_dtype={table_dtype}: the row-wise "
+                                      "exchange buffers and the owner-side update are fp32")
         if _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"RowwiseShardedEmbeddingBag with output_dtype={output_dtype}: the row-wise "
                                       "exchange buffers are fp32")
@@ -728,7 +732,11 @@ class GraphedShardedWindow:
                  transport: Optional[str] = None, warmup_ids: Optional[Sequence[torch.Tensor]] = None,
                  split: Optional[bool] = None, split_caps: Optional[Sequence[int]] = None,
                  arrangement: Optional[str] = None, arrangement_trial: Optional[dict] = None,
-                 static_out_candidates: int = 0, before_capture=None, output_dtype: Optional[torch.dtype] = None):
+                 static_out_candidates: int = 0, before_capture=None, output_dtype: Optional[torch.dtype] = None,
+                 table_dtype: Optional[torch.dtype] = None):
+        if _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"GraphedShardedWindow with table_dtype={table_dtype}: the row-wise exchange "
+                                      "buffers and the owner-side update are fp32")
         if _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"GraphedShardedWindow with output_dtype={output_dtype}: the row-wise exchange "
                                       "buffers are fp32")
@@ -1401,6 +1409,9 @@ class ParallelCachedEmbeddingBag(CachedEmbeddingBag):
         self.rank = dist.get_rank(self.group) if self.group is not None else 0
         self.world_size = dist.get_world_size(self.group) if self.group is not None else 1
         self._refuse_act16(kw.get("output_dtype"))            # before anything is allocated
+        if self.world_size > 1 and _lib.table_code(kw.get("table_dtype")) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"ParallelCachedEmbeddingBag with table_dtype={kw.get('table_dtype')} on "
+                                      f"{self.world_size} ranks: the all-to-all of the pooled output is fp32")
         self.full_embedding_dim = embedding_dim
         lo, hi, _ = get_partition(embedding_dim, self.rank, self.world_size)
         self.partition_start_index, self.partition_end_index = lo, hi

@@ -68,8 +68,12 @@ class ParallelCachedEmbeddingBagTablewise(nn.Module):
                  padding_idx=None, max_norm=None, norm_type=2.0, scale_grad_by_freq=False, sparse=False,
                  mode: str = "mean", include_last_offset: bool = False, dtype=None, device=None,
                  warmup_ratio: float = 0.7, buffer_size: int = 50_000, pin_weight: bool = False,
-                 evict_strategy: EvictionStrategy = EvictionStrategy.LFU, group=None, output_dtype=None):
+                 evict_strategy: EvictionStrategy = EvictionStrategy.LFU, group=None, output_dtype=None,
+                 table_dtype=None):
         super().__init__()
+        if _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
+            raise NotImplementedError(f"ParallelCachedEmbeddingBagTablewise with table_dtype={table_dtype}: the "
+                                      "table-wise module keeps fp32 tables")
         if _lib.act_code(output_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"ParallelCachedEmbeddingBagTablewise with output_dtype={output_dtype}: the "
                                       "all-to-all of the pooled output is fp32")

@@ -118,11 +118,20 @@ def parse_args(argv=None):
                         "kernels write bf16 and read the bf16 gradient in place (the table and its update stay fp32), "
                         "and the dense part's forward runs under torch.autocast('cuda', torch.bfloat16).  One process, "
                         "without --use_tablewise.  (fp16 is a library option only: a trainer would need loss scaling)")
+    p.add_argument("--table_dtype", default="fp32", choices=["fp32", "bf16", "fp16"],
+                   help="dtype of the embedding table's rows, in host DRAM and in the cache "
+                        "(CachedEmbeddingBag(table_dtype=...)).  bf16 / fp16: half the host memory and half of every "
+                        "admission and write-back; sums and updates stay fp32 and the fused update (--fused_sgd or "
+                        "--adagrad) rounds a row once per step.  One process, without --use_tablewise; the pooled "
+                        "embeddings keep --embedding_output_dtype")
+    p.add_argument("--weight_rounding", default="stochastic", choices=["nearest", "stochastic"],
+                   help="--table_dtype bf16 / fp16: how the fused update rounds a row (set_weight_rounding)")
     p.add_argument("--json_out", type=str, default=None, help="write the run's numbers as one JSON object")
     return p.parse_args(argv)
 
 
 _OUTPUT_DTYPES = {"fp32": None, "bf16": torch.bfloat16}
+_TABLE_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
 
 
 def check_output_dtype(args, world: int) -> None:
@@ -130,6 +139,11 @@ def check_output_dtype(args, world: int) -> None:
     if args.embedding_output_dtype != "fp32" and (world > 1 or args.use_tablewise):
         raise NotImplementedError("--embedding_output_dtype bf16 is implemented for one process without "
                                   "--use_tablewise (the all-to-all of the pooled output is fp32)")
+    if args.table_dtype != "fp32" and (world > 1 or args.use_tablewise):
+        raise NotImplementedError(f"--table_dtype {args.table_dtype} is implemented for one process without "
+                                  "--use_tablewise")
+    if args.table_dtype != "fp32" and args.use_sparse_embed_grad:
+        raise NotImplementedError(f"--table_dtype {args.table_dtype} with --use_sparse_embed_grad")
 
 
 def mlp(sizes: List[int], last_activation: bool) -> nn.Sequential:
@@ -170,7 +184,10 @@ class HybridParallelDLRM(nn.Module):
             warmup_ratio=args.warmup_ratio, buffer_size=args.buffer_size,
             is_dist_dataloader=args.use_distributed_dataloader, use_lfu_eviction=args.use_lfu,
             use_tablewise_parallel=args.use_tablewise, dataset=args.dataset, fold_hook=args.fold_hook,
-            output_dtype=_OUTPUT_DTYPES[args.embedding_output_dtype])
+            # (a 16-bit table's output would default to the table's dtype: the flag's fp32 stays fp32)
+            output_dtype=_OUTPUT_DTYPES[args.embedding_output_dtype] or
+            (torch.float32 if args.table_dtype != "fp32" else None),
+            table_dtype=_TABLE_DTYPES[args.table_dtype])
         self.autocast = args.embedding_output_dtype == "bf16"
         dense = DenseModules(args.num_dense_features, len(sizes), args.embedding_dim,
                              [int(x) for x in args.dense_arch_layer_sizes.split(",")],
@@ -533,6 +550,8 @@ def main(argv=None):
     model = HybridParallelDLRM(sizes, args, freq, device)
     embed = model.sparse_modules.embed
     embed.set_cache_mgr_async_copy(args.use_cache_mgr_async_copy)
+    if args.table_dtype != "fp32":
+        embed.set_weight_rounding(args.weight_rounding, seed=args.seed)
     groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world}]
     if args.adagrad:
         embed.set_fused_rowwise_adagrad(args.learning_rate)
@@ -593,6 +612,7 @@ def main(argv=None):
                     "batch_size": args.batch_size, "prefetch_num": args.prefetch_num, "cache_ratio": args.cache_ratio,
                     "cuda_row_num": int(mgr.cuda_row_num), "dense_arch": args.dense_arch_layer_sizes,
                     "over_arch": args.over_arch_layer_sizes, "dtype": "f32", "embedding_output_dtype": args.embedding_output_dtype,
+                    "table_dtype": args.table_dtype,
                     "data": "synthetic",
                     "surface": {k: bool(getattr(args, k)) for k in ("use_overlap", "overlap_cache_op", "fused_sgd",
                                                                     "adagrad", "fold_hook", "window_keys", "tunable_gemm", "graph_step",

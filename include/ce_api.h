@@ -351,6 +351,58 @@ int ce_bag_backward_rowwise_adagrad_src_act(float* weight, int64_t num_rows, int
                                             float lr, float eps, void* workspace, size_t workspace_bytes,
                                             ce_stream_t stream);
 
+/* 16-bit table (additions to API 6).  The TABLE's rows are bf16 / fp16: weight_dtype = CE_ACT_BF16 / CE_ACT_F16
+ * (CE_ACT_F32 and unknown codes: CE_ERR_INVALID before any launch).  dim % 8 == 0 and dim <= 1024 -- rows are whole
+ * 16-byte units, so a [N, dim] 16-bit table has the bytes of an fp32 [N, dim / 2] table and the cache op, which only
+ * moves rows, is driven with embedding_dim = dim / 2 -- and the table 16-byte aligned; any other dim is
+ * CE_ERR_UNSUPPORTED before any launch.  Rows are up-converted exactly on load and summed in fp32; the forward rounds
+ * once, on the store to act_dtype.  ce_bag_forward_src_keys_w16 with act_dtype == weight_dtype copies the row's bits
+ * (nothing is rounded or canonicalised; an ignored lookup's output row is zero).
+ *
+ * The update: fp32 atomics cannot land on 16-bit rows, so the step's gradient is folded into an fp32 accumulator first
+ * and the row is rounded ONCE, after its whole gradient is known.  Three launches, no host synchronisation, no
+ * allocation (capture-safe): mark the looked-up slots (one thread also adds 1 to the step counter), the dense backward
+ * (ce_bag_backward_dense_act / _dense_src_act) into acc[slot], then one apply pass over the flagged slots:
+ *   CE_OPT_SGD:             x = w - lr * g                                  (row_of_slot / momentum may be NULL, eps ignored)
+ *   CE_OPT_ROWWISE_ADAGRAD: m[row] += sum_d g[d]^2 / dim ;  x = w - lr * g / (sqrt(m[row]) + eps)
+ *   W16[slot] = round(x), acc[slot] = 0, flag = 0       (w = the exact up-conversion of the old row, all in fp32)
+ * CE_ROUND_NEAREST: the plain cast (round-to-nearest-even, NaN kept).  CE_ROUND_STOCHASTIC: one of the two 16-bit
+ * neighbours of x (x itself when representable), the one farther from zero with probability (distance to the nearer
+ * one) / (their spacing); NaN, infinities, fp16 results below 2^-14 or from 65504 on, and bf16 values beyond the largest
+ * finite one take the nearest cast.  The random bits are a counter-based hash of (seed, step counter, row_of_slot[slot]
+ * or the slot when NULL, element): independent of the slot a row sits in, of the grid and of timing; a replayed graph
+ * draws fresh bits each step because the counter lives in the workspace.
+ * Workspace (ce_bag_backward_w16_workspace bytes, 256-byte aligned): fp32 acc [num_rows, dim], byte flags [num_rows],
+ * one 64-bit step counter.  Zero-filled by its owner once; every call leaves it zero-filled except the counter, which
+ * counts the calls.  Everything the entries can refuse is refused before the first launch. */
+#define CE_OPT_SGD 0
+#define CE_OPT_ROWWISE_ADAGRAD 1
+#define CE_ROUND_NEAREST 0
+#define CE_ROUND_STOCHASTIC 1
+/* element i = the round-to-nearest-even cast to `dtype` (CE_ACT_BF16 / CE_ACT_F16) of what ce_host_fill_uniform writes
+ * at element i for the same arguments */
+int ce_host_fill_uniform_w16(void* dst, int64_t n, float lo, float hi, uint64_t seed, int32_t dtype, int threads);
+int ce_bag_forward_w16(const void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                       const int64_t* indices, int64_t nnz,
+                       const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                       int32_t include_last_offset, const float* per_sample_weights,
+                       int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_forward_src_keys_w16(const void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
+                                const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+size_t ce_bag_backward_w16_workspace(int64_t num_rows, int32_t dim);
+int ce_bag_backward_update_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                               const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                               int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                               int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                               const uint64_t* presorted, const int32_t* row_of_slot, float* momentum,
+                               int64_t momentum_rows, float lr, float eps, int32_t optimizer, int32_t rounding,
+                               uint64_t seed, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
+                                   const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                   const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                   float eps, int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                   size_t workspace_bytes, ce_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6].  Device state arrays are owned by the caller (so the Python
  * mirror can expose them as tensors: cached_idx_map, inverted_cached_idx, idx_map,
