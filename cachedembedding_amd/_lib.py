@@ -36,6 +36,7 @@ CE_OPT_SGD = 0
 CE_OPT_ROWWISE_ADAGRAD = 1
 CE_ROUND_NEAREST = 0
 CE_ROUND_STOCHASTIC = 1
+CE_SORTED_CHUNK = 64
 CE_TRANSPORT_ZEROCOPY = 0
 CE_TRANSPORT_STAGED = 1
 CE_TRANSPORT_WORKER = 2
@@ -153,6 +154,9 @@ SIGNATURES = {
     "ce_bag_backward_w16_workspace": (c_size_t, [c_int64, c_int32]),
     "ce_bag_backward_update_w16": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL),
     "ce_bag_backward_update_src_w16": (c_int, _W16 + _SRC[1:] + _ACT + _W16_TAIL),
+    # the deterministic, accumulator-free update: the w16 update's arguments without the presorted keys
+    "ce_bag_backward_update_sorted_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
+    "ce_bag_backward_update_sorted": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL[1:]),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),

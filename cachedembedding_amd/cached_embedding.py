@@ -117,12 +117,14 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_sgd.lr = lr
         self.fused_sgd.deterministic = deterministic
 
-    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8):
+    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8, deterministic: bool = False):
         """Apply exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0; the reference's baseline
         --adagrad) to the cache rows inside backward.  The state is one fp32 accumulator per row of the host table,
         `cache_weight_mgr.momentum1` (device, zeroed when first enabled, indexed like `weight`); it stays in HBM and
         never moves with the cache.  lr=None turns the update off (the state is kept).  Exclusive with
-        set_fused_sgd(lr)."""
+        set_fused_sgd(lr).  deterministic=True: the sorted, bit-reproducible fold (FusedRowwiseAdagrad), fp32 and
+        16-bit tables alike; the host table and the state then do not depend on the cache size or eviction strategy.
+        A 16-bit table needs set_weight_rounding("nearest") with it: the sorted fold does not round stochastically."""
         if lr is not None and self.fused_sgd.lr is not None:
             raise ValueError("fused SGD is set: set_fused_sgd(None) before set_fused_rowwise_adagrad(lr)")
         mgr = self.cache_weight_mgr
@@ -130,6 +132,7 @@ class CachedEmbeddingBag(nn.Module):
             mgr.momentum1 = torch.zeros(mgr.num_embeddings, device=mgr.device, dtype=torch.float32)
         self.fused_adagrad.lr = lr
         self.fused_adagrad.eps = float(eps)
+        self.fused_adagrad.deterministic = bool(deterministic)
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
 

@@ -388,6 +388,267 @@ static int launch_apply_w16(void* weight, int32_t weight_dtype, int64_t num_rows
   return CE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Deterministic, accumulator-free form (ce_bag_backward_update_sorted).  The lookups are stably sorted
+// by row (sorted_rows, ce_sort.hip), so a row's lookups are one run in ascending lookup position.  The run is cut into
+// chunks of CE_SORTED_CHUNK positions counted from the START OF THE RUN; a lane group folds one chunk sequentially from
+// zero in registers (k_sorted_fold).  A run of one chunk is applied right there; the chunks of a longer run go to a
+// partial row each and a second launch (k_sorted_combine) adds a run's partials in ascending chunk order and applies
+// the row once.  Nothing depends on the grid, on the slot a row sits in or on timing.
+// Partial rows: the chunk that starts at sorted position p takes row 2 * (p / 64) + (first chunk of its run).  Runs
+// that own partial rows are longer than 64, so an aligned block of 64 positions holds at most one run start of that
+// kind and at most one later chunk start: 2 * ceil(nnz / 64) rows, no compaction, no counter.
+// The update is k_adagrad_apply's / k_rows_apply_w16's: the same lane-group shape, the same reduction tree, the same
+// expressions, so a row looked up once gets the same bits.  A 16-bit row is stored with the nearest cast;
+// CE_ROUND_STOCHASTIC on a 16-bit table is refused by the entry.
+static_assert(CE_SORTED_CHUNK == 64, "the partial-row numbering and the wave walk assume 64 positions per chunk");
+
+struct SortedArgs {
+  void* weight;                // [num_rows, D] of WT
+  const void* grad_out;        // of AT
+  float* partials;             // [2 * ceil(nnz / 64), D]
+  const int32_t* rows_sorted;
+  const int32_t* lookup_sorted;
+  const int32_t* bag_of;
+  const void* offsets;
+  const float* psw;
+  const int32_t* row_of_slot;
+  float* momentum;
+  int64_t momentum_rows;
+  int64_t nnz;
+  int64_t num_bags;
+  int32_t num_rows;
+  int32_t rowlen, g_log2, dim, off64, include_last, mode, hookF, hookB, adagrad;
+  float lr;
+  float eps;
+};
+
+// first position of the run of `row` that holds position p (rows ascending, rows[p] == row): gallop back, then bisect
+__device__ __forceinline__ int64_t run_start(const int32_t* __restrict__ rows, int64_t p, int32_t row) {
+  int64_t hi = p, lo = p - 1, step = 1;
+  while (lo >= 0 && rows[lo] == row) {
+    hi = lo;
+    step <<= 1;
+    lo = p - step;
+  }
+  if (lo < 0) lo = -1;
+  while (hi - lo > 1) {                          // rows[hi] == row, lo == -1 or rows[lo] != row
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (rows[mid] == row) hi = mid; else lo = mid;
+  }
+  return hi;
+}
+
+// sum of a lane's squares, SPELLED OUT.  `ss += sq_sum(g[c])` is one expression in k_adagrad_apply and k_rows_apply_w16,
+// but under -ffp-contract=fast the compiler rounds it differently per instantiation: a chunk's four squares are either
+// rounded one by one and added ("plain": ((x^2 + y^2) + z^2) + w^2) or folded into a chain of fused multiply-adds
+// ("chain": fma(w, w, fma(z, z, fma(x, x, y * y)))).  A row looked up once must get the bits of those kernels, so the
+// form each of them compiled to (read off their ISA) is written here with contraction off and explicit
+// fmas, which also keeps the two kernels below from drifting apart.  fp32 table: the lane's LAST chunk plain, the
+// chunks before it chains; 16-bit table: chains only; scalar lanes: one chain over the lane's elements, started by the
+// second one (g1 * g1, then fma g0, g2, g3).  Chunk sums
+// are added in chunk order.
+__device__ __forceinline__ float sq_plain(f32x4 v) {
+#pragma clang fp contract(off)
+  const float xx = v.x * v.x, yy = v.y * v.y, zz = v.z * v.z, ww = v.w * v.w;
+  return ((xx + yy) + zz) + ww;
+}
+__device__ __forceinline__ float sq_chain(f32x4 v) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(v.w, v.w, __builtin_fmaf(v.z, v.z, __builtin_fmaf(v.x, v.x, v.y * v.y)));
+}
+template <typename WT, int NCH>
+__device__ __forceinline__ float sorted_sq_sum(const f32x4 (&g)[NCH]) {
+#pragma clang fp contract(off)
+  constexpr bool w32 = std::is_same<WT, float>::value;
+  float ss = (w32 && NCH == 1) ? sq_plain(g[0]) : sq_chain(g[0]);
+#pragma unroll
+  for (int c = 1; c < NCH; ++c) ss = ss + ((w32 && c == NCH - 1) ? sq_plain(g[c]) : sq_chain(g[c]));
+  return ss;
+}
+template <typename WT, int NCH>
+__device__ __forceinline__ float sorted_sq_sum(const float (&g)[NCH]) {
+#pragma clang fp contract(off)
+  // as in sq_chain, the SECOND square is the one rounded on its own and the first is fused onto it
+  if (NCH == 1) return g[0] * g[0];
+  float ss = __builtin_fmaf(g[0], g[0], g[NCH > 1 ? 1 : 0] * g[NCH > 1 ? 1 : 0]);
+#pragma unroll
+  for (int c = 2; c < NCH; ++c) ss = __builtin_fmaf(g[c], g[c], ss);
+  return ss;
+}
+
+// the update of one row by its lane group: g = the row's whole gradient of the step (zero in chunks past rowlen)
+template <typename VT, typename WT, int NCH>
+__device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s, const VT (&g)[NCH], int gl, int G) {
+  using T = Act<WT, VT>;
+  typename T::V* W = (typename T::V*)a.weight;
+  float ss = sorted_sq_sum<WT, NCH>(g);
+  const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
+  float mult = a.lr;
+  bool update = true;
+  if (a.adagrad) {
+    for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, G);
+    update = r >= 0 && r < a.momentum_rows;
+    if (update) {
+      const float mr = a.momentum[r] + ss / (float)a.dim;
+      mult = a.lr / (sqrtf(mr) + a.eps);
+      if (gl == 0) a.momentum[r] = mr;
+    }
+  }
+  if (!update) return;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int idx = gl + c * G;
+    if (idx < a.rowlen) W[s * a.rowlen + idx] = T::down(T::up(W[s * a.rowlen + idx]) - g[c] * mult);
+  }
+}
+
+// one wave per 64 consecutive sorted positions (grid-stride): every lane finds out whether its position starts a chunk,
+// the chunk heads are handed to the wave's lane groups in rounds (the walk of k_adagrad_apply)
+template <typename VT, typename AT, typename WT, int NCH>
+__global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
+  using TA = Act<AT, VT>;
+  const int G = 1 << a.g_log2;
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> a.g_log2;
+  const int gl = lane & (G - 1);
+  const int ngw = 64 >> a.g_log2;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const typename TA::V* GO = (const typename TA::V*)a.grad_out;
+  VT* P = (VT*)a.partials;
+  const int32_t* __restrict__ rows = a.rows_sorted;
+  for (int64_t base = wave * 64; base < a.nnz; base += nwaves * 64) {
+    const int64_t mine = base + lane;
+    bool head = false;
+    if (mine < a.nnz) {
+      const int32_t row = rows[mine];
+      // ignored lookups carry the key num_rows and lie behind every valid row: they start nothing
+      if ((uint32_t)row < (uint32_t)a.num_rows)
+        head = ((mine - run_start(rows, mine, row)) & (CE_SORTED_CHUNK - 1)) == 0;
+    }
+    unsigned long long m = __ballot(head);
+    while (m) {
+      unsigned long long mm = m;
+      for (int k = 0; k < q; ++k) mm &= mm - 1;          // this group's chunk: the q-th lowest head
+      for (int k = 0; k < ngw; ++k) m &= m - 1;
+      if (mm == 0) continue;
+      const int64_t p = base + (__ffsll((long long)mm) - 1);
+      const int32_t row = rows[p];
+      const bool first = p == 0 || rows[p - 1] != row;                                   // first chunk of its run
+      const bool more = p + CE_SORTED_CHUNK < a.nnz && rows[p + CE_SORTED_CHUNK] == row;   // a chunk follows
+      VT g[NCH];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) g[c] = vzero<VT>();
+      const int64_t end = p + CE_SORTED_CHUNK < a.nnz ? p + CE_SORTED_CHUNK : a.nnz;
+      for (int64_t t = p; t < end && rows[t] == row; ++t) {
+        const int32_t j = a.lookup_sorted[t];
+        const int64_t bag = a.bag_of[j];
+        if (bag < 0 || bag >= a.num_bags) continue;        // a lookup no bag covers
+        float sc = a.psw ? a.psw[j] : 1.f;
+        if (a.mode == CE_MODE_MEAN) {
+          const int64_t lo = a.off64 ? ((const int64_t*)a.offsets)[bag] : ((const int32_t*)a.offsets)[bag];
+          const int64_t hi = (a.include_last || bag + 1 < a.num_bags)
+                                 ? (a.off64 ? ((const int64_t*)a.offsets)[bag + 1] : ((const int32_t*)a.offsets)[bag + 1])
+                                 : a.nnz;
+          if (hi - lo > 1) sc = sc / (float)(hi - lo);
+        }
+        int64_t orow = bag;
+        if (a.hookF) {
+          const int64_t f = bag / a.hookB;
+          orow = (bag - f * a.hookB) * a.hookF + f;
+        }
+        {
+#pragma clang fp contract(off)      // the specification: the term s_j g_j is rounded before it is added
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            const int idx = gl + c * G;
+            if (idx < a.rowlen) {
+              const VT v = TA::up(GO[orow * a.rowlen + idx]);
+              g[c] = (sc == 1.f) ? g[c] + v : g[c] + v * sc;
+            }
+          }
+        }
+      }
+      if (first && !more) {
+        sorted_apply_row<VT, WT, NCH>(a, (int64_t)row, g, gl, G);
+      } else {
+        const int64_t prow = 2 * (p >> 6) + (first ? 1 : 0);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int idx = gl + c * G;
+          if (idx < a.rowlen) P[prow * a.rowlen + idx] = g[c];
+        }
+      }
+    }
+  }
+}
+
+// the runs of more than one chunk: the head of such a run adds its partial rows in ascending chunk order and applies
+template <typename VT, typename WT, int NCH>
+__global__ __launch_bounds__(256) void k_sorted_combine(SortedArgs a) {
+  const int G = 1 << a.g_log2;
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> a.g_log2;
+  const int gl = lane & (G - 1);
+  const int ngw = 64 >> a.g_log2;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const VT* P = (const VT*)a.partials;
+  const int32_t* __restrict__ rows = a.rows_sorted;
+  for (int64_t base = wave * 64; base < a.nnz; base += nwaves * 64) {
+    const int64_t mine = base + lane;
+    bool head = false;
+    if (mine + CE_SORTED_CHUNK < a.nnz) {
+      const int32_t row = rows[mine];
+      head = (uint32_t)row < (uint32_t)a.num_rows && (mine == 0 || rows[mine - 1] != row) &&
+             rows[mine + CE_SORTED_CHUNK] == row;
+    }
+    unsigned long long m = __ballot(head);
+    while (m) {
+      unsigned long long mm = m;
+      for (int k = 0; k < q; ++k) mm &= mm - 1;
+      for (int k = 0; k < ngw; ++k) m &= m - 1;
+      if (mm == 0) continue;
+      const int64_t p = base + (__ffsll((long long)mm) - 1);
+      const int32_t row = rows[p];
+      VT g[NCH];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        g[c] = idx < a.rowlen ? P[(2 * (p >> 6) + 1) * a.rowlen + idx] : vzero<VT>();
+      }
+      for (int64_t t = p + CE_SORTED_CHUNK; t < a.nnz && rows[t] == row; t += CE_SORTED_CHUNK) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int idx = gl + c * G;
+          if (idx < a.rowlen) g[c] = g[c] + P[(2 * (t >> 6)) * a.rowlen + idx];
+        }
+      }
+      sorted_apply_row<VT, WT, NCH>(a, (int64_t)row, g, gl, G);
+    }
+  }
+}
+
+// workspace: the sort arrays, then the partial rows; nothing in it needs initialising
+struct SortedWs {
+  void* sort;
+  float* partials;
+  size_t bytes;
+};
+
+static SortedWs carve_sorted(void* ws, int64_t nnz, int32_t dim) {
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const int64_t n = nnz < 1 ? 1 : nnz;
+  SortedWs w{};
+  char* p = (char*)ws;
+  size_t o = 0;
+  w.sort = p + o;                           o = al(o + sorted_rows_bytes(n));
+  w.partials = (float*)(p + o);             o = al(o + (size_t)(2 * cdiv(n, CE_SORTED_CHUNK)) * (size_t)dim * 4);
+  w.bytes = o;
+  return w;
+}
+
 }  // namespace ce
 
 using namespace ce;
@@ -530,4 +791,118 @@ extern "C" int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype
   if (rc) return rc;
   return launch_apply_w16(weight, weight_dtype, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps,
                           optimizer, rounding, seed, ws, s);
+}
+
+// ---- deterministic, accumulator-free: sort, fold + apply, combine + apply
+
+extern "C" size_t ce_bag_backward_update_sorted_workspace(int64_t num_rows, int64_t nnz, int32_t dim) {
+  (void)num_rows;
+  if (nnz < 0 || nnz >= (int64_t)INT32_MAX || dim <= 0) return 0;
+  return carve_sorted(nullptr, nnz, dim).bytes;
+}
+
+extern "C" int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                             const int64_t* indices, int64_t nnz, const void* offsets,
+                                             int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                             const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                             const void* grad_out, int32_t act_dtype, const int32_t* row_of_slot,
+                                             float* momentum, int64_t momentum_rows, float lr, float eps,
+                                             int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                             size_t workspace_bytes, ce_stream_t stream) {
+  // everything that can be refused, from the arguments alone: no launch, no HIP call before the last check
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE(weight_dtype == CE_ACT_F32 || weight_dtype == CE_ACT_BF16 || weight_dtype == CE_ACT_F16, CE_ERR_INVALID,
+             "unknown weight_dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)weight_dtype);
+  const bool w16 = weight_dtype != CE_ACT_F32;
+  if (w16) {
+    int rc = w16_check(weight_dtype, dim);
+    if (rc) return rc;
+  }
+  CE_REQUIRE(optimizer == CE_OPT_SGD || optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_INVALID,
+             "unknown optimizer %d (CE_OPT_SGD / CE_OPT_ROWWISE_ADAGRAD)", (int)optimizer);
+  CE_REQUIRE(rounding == CE_ROUND_NEAREST || rounding == CE_ROUND_STOCHASTIC, CE_ERR_INVALID,
+             "unknown rounding %d (CE_ROUND_NEAREST / CE_ROUND_STOCHASTIC)", (int)rounding);
+  (void)seed;     // part of the update entries' common tail; only stochastic rounding would read it
+  CE_REQUIRE(!w16 || rounding == CE_ROUND_NEAREST, CE_ERR_UNSUPPORTED,
+             "CE_ROUND_STOCHASTIC on a 16-bit table: the sorted update rounds to nearest only");
+  CE_REQUIRE(weight && grad_out && workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(dim > 0, CE_ERR_INVALID, "dim must be positive");
+  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX && nnz >= 0 && nnz < (int64_t)INT32_MAX && num_bags >= 0 &&
+                 num_bags < (int64_t)INT32_MAX,
+             CE_ERR_UNSUPPORTED, "sizes beyond 2^31");
+  CE_REQUIRE(lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
+  if (optimizer == CE_OPT_ROWWISE_ADAGRAD) {
+    CE_REQUIRE(momentum && momentum_rows > 0, CE_ERR_INVALID, "row-wise Adagrad needs its momentum");
+    CE_REQUIRE(eps > 0.f, CE_ERR_INVALID, "eps must be > 0");
+  }
+  CE_REQUIRE(mode == CE_MODE_SUM || mode == CE_MODE_MEAN, CE_ERR_UNSUPPORTED, "mode must be sum or mean");
+  CE_REQUIRE(hook_features >= 0 && hook_features < (int64_t)INT32_MAX &&
+                 (hook_features == 0 || num_bags % hook_features == 0),
+             CE_ERR_INVALID, "hook_features must divide num_bags");
+  CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
+  CE_REQUIRE(workspace_bytes >= ce_bag_backward_update_sorted_workspace(num_rows, nnz, dim), CE_ERR_INVALID,
+             "workspace too small");
+  const bool aligned = al16(weight) && act_aligned(grad_out, act_dtype);
+  CE_REQUIRE(!w16 || aligned, CE_ERR_INVALID,
+             "a 16-bit table must be 16-byte aligned and its gradient on the vector boundary");
+  RowGeom r;
+  int rc = row_geometry(dim, aligned, r);
+  if (rc) return rc;
+  if (num_bags == 0 || nnz == 0) return CE_OK;
+  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
+
+  hipStream_t s = (hipStream_t)stream;
+  const SortedWs ws = carve_sorted(workspace, nnz, dim);
+  SortedRows sr{};
+  rc = sorted_rows(indices, nnz, num_rows, offsets, offsets_are_i64, num_bags, include_last_offset, ws.sort,
+                   s, sr);
+  if (rc) return rc;
+  SortedArgs a{};
+  a.weight = weight;
+  a.grad_out = grad_out;
+  a.partials = ws.partials;
+  a.rows_sorted = sr.rows;
+  a.lookup_sorted = sr.lookups;
+  a.bag_of = sr.bag_of;
+  a.offsets = offsets;
+  a.psw = per_sample_weights;
+  a.row_of_slot = row_of_slot;
+  a.momentum = momentum;
+  a.momentum_rows = momentum_rows;
+  a.nnz = nnz;
+  a.num_bags = num_bags;
+  a.num_rows = (int32_t)num_rows;
+  a.rowlen = r.rowlen;
+  a.g_log2 = r.g_log2;
+  a.dim = dim;
+  a.off64 = offsets_are_i64;
+  a.include_last = include_last_offset;
+  a.mode = mode;
+  a.hookF = (int)hook_features;
+  a.hookB = hook_features ? (int)(num_bags / hook_features) : 0;
+  a.adagrad = optimizer == CE_OPT_ROWWISE_ADAGRAD;
+  a.lr = lr;
+  a.eps = eps;
+  const dim3 g(grid_for(cdiv(nnz, 64), 4)), b(256);
+  if (w16) {
+    for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
+      using WT = typename decltype(w)::AT;
+      constexpr int N = decltype(l)::NCH;
+      for_act(act_dtype, [&](auto at) {
+        hipLaunchKernelGGL((k_sorted_fold<f32x4, typename decltype(at)::AT, WT, N>), g, b, 0, s, a);
+      });
+      hipLaunchKernelGGL((k_sorted_combine<f32x4, WT, N>), g, b, 0, s, a);
+    });
+  } else {
+    for_lanes(r.vec, r.nch, [&](auto l) {
+      using VT = typename decltype(l)::VT;
+      constexpr int N = decltype(l)::NCH;
+      for_act(act_dtype, [&](auto at) {
+        hipLaunchKernelGGL((k_sorted_fold<VT, typename decltype(at)::AT, float, N>), g, b, 0, s, a);
+      });
+      hipLaunchKernelGGL((k_sorted_combine<VT, float, N>), g, b, 0, s, a);
+    });
+  }
+  CE_LAUNCH_CHECK();
+  return CE_OK;
 }

@@ -101,6 +101,21 @@ void bind_thread_near_gpu();
 // the same CPU set for threads that have not selected the device themselves (taken by their creator); false = none
 bool near_gpu_cpus(cpu_set_t* out);
 
+// ce_sort.hip, for the sorted fused update (ce_bag_adagrad.hip): the call's lookups stably radix-sorted by row.
+// rows[t] ascending, a valid row's lookups in ascending lookup position, every ignored lookup (slot outside
+// [0, num_rows)) behind them with rows[t] == num_rows; lookups[t] = position of the lookup in the call, bag_of[j] = bag
+// of lookup j (-1: no bag covers it).  The arrays live in `workspace` (sorted_rows_bytes(nnz) bytes, 256-byte
+// aligned, nothing in it needs initialising).
+struct SortedRows {
+  const int32_t* rows;
+  const int32_t* lookups;
+  const int32_t* bag_of;
+};
+size_t sorted_rows_bytes(int64_t nnz);
+int sorted_rows(const int64_t* indices, int64_t nnz, int64_t num_rows, const void* offsets, int off64,
+                int64_t num_bags, int include_last, void* workspace, hipStream_t s,
+                SortedRows& out);
+
 // How the lanes of a launch hold one embedding row.  Vector form: a lane's chunk is 16 B (f32x4); it needs dim % 4 == 0
 // and `aligned` -- every row pointer of the launch on its vector boundary.  Scalar form otherwise: one float per chunk.
 // A power-of-two group of at most 64 lanes works on a row and a lane holds nch = 1, 2 or 4 chunks of it (3 rounds up

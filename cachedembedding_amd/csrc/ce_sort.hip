@@ -621,6 +621,62 @@ static SortWs carve(void* ws, int64_t nnz) {
   return s;
 }
 
+// ---- the sorted fused update (ce_bag_backward_update_sorted, ce_bag_adagrad.hip): lookups stably sorted by row with
+// every ignored lookup (a slot outside [0, num_rows): the -1 of padding) behind all valid rows.  The split above sorts
+// only as many bits as the rows need, so a raw -1 key would share all of them with the last row of a power-of-two
+// table and interleave with it; the first launch therefore writes key = num_rows for such lookups and the passes sort
+// bits(num_rows + 1) bits.
+__global__ __launch_bounds__(256) void k_sorted_keys(const int64_t* __restrict__ ids, int64_t n, int64_t num_rows,
+                                                     int32_t* __restrict__ keys, int32_t* __restrict__ vals) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t id = ids[i];
+    keys[i] = (unsigned long long)id < (unsigned long long)num_rows ? (int32_t)id : (int32_t)num_rows;
+    vals[i] = (int32_t)i;
+  }
+}
+
+size_t sorted_rows_bytes(int64_t nnz) { return carve(nullptr, std::max<int64_t>(nnz, 1)).bytes; }
+
+// nnz in [1, 2^31 - 1), num_rows in [1, 2^31 - 1): checked by the caller.  bag_of is -1 for a lookup no bag covers.
+int sorted_rows(const int64_t* indices, int64_t nnz, int64_t num_rows, const void* offsets, int off64,
+                int64_t num_bags, int include_last, void* workspace, hipStream_t s,
+                SortedRows& out) {
+  SortWs ws = carve(workspace, nnz);
+  const int ntiles = (int)cdiv(nnz, kTile);
+  int bits = 1;
+  while ((1ll << bits) <= num_rows) ++bits;            // the sentinel key num_rows itself must fit
+  const int passes = (bits + 7) / 8;
+  hipLaunchKernelGGL(k_sorted_keys, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz, num_rows, ws.keys[0],
+                     ws.vals[0]);
+  CE_HIP_CHECK(hipMemsetAsync(ws.bag_of, 0xff, (size_t)nnz * 4, s));
+  hipLaunchKernelGGL(k_expand_bags, dim3(grid_for(num_bags, 256)), dim3(256), 0, s, offsets, off64, num_bags, nnz,
+                     include_last, ws.bag_of);
+  int cur = 0;
+  for (int p = 0; p < passes; ++p) {
+    SplitArgs a{};
+    a.n = nnz;
+    a.ntiles = ntiles;
+    a.shift = 8 * p;
+    a.world = 1;
+    a.nb = 256;
+    a.hist = ws.hist;
+    a.keys_in = ws.keys[cur];
+    a.vals_in = ws.vals[cur];
+    a.keys_out = ws.keys[cur ^ 1];
+    a.vals_out = ws.vals[cur ^ 1];
+    hipLaunchKernelGGL((k_split_hist<0, 0>), dim3(ntiles), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_scan1024, dim3(1), dim3(1024), 0, s, a.hist, (int64_t)256 * ntiles, ws.total);
+    hipLaunchKernelGGL((k_split_scatter<0, 0, false>), dim3(ntiles), dim3(256), 0, s, a);
+    cur ^= 1;
+  }
+  CE_LAUNCH_CHECK();
+  out.rows = ws.keys[cur];
+  out.lookups = ws.vals[cur];
+  out.bag_of = ws.bag_of;
+  return CE_OK;
+}
+
 }  // namespace ce
 
 using namespace ce;

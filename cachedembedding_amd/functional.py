@@ -148,6 +148,19 @@ class _BagFn(torch.autograd.Function):
             grad_out = grad_out.float()
         slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
                       hook_features, ptr(grad_out))
+        if rowwise and fused.deterministic:
+            # bit-reproducible row-wise Adagrad without the [rows, D] accumulator (ce_bag_backward_update_sorted): fp32
+            # and 16-bit tables (rounded to nearest: stochastic rounding was refused before the forward), always from
+            # slots + offsets -- presorted keys of either kind are not needed and ignored
+            with torch.no_grad():
+                ws = fused.workspace_sorted(R, nnz, dim, weight.device)
+                mom = fused.momentum
+                check(lib.ce_bag_backward_update_sorted(
+                    ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim, *slots_args, act, ptr(fused.row_of_slot),
+                    ptr(mom), mom.numel(), float(fused.lr), float(fused.eps), _lib.CE_OPT_ROWWISE_ADAGRAD,
+                    _lib.CE_ROUND_STOCHASTIC if fused.rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
+                    int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr()))
+            return (None,) * 14
         if weight.dtype in _lib.W16_DTYPES:
             # 16-bit table (the combinations it does not take were refused in embedding_bag, before the forward)
             wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
@@ -356,11 +369,19 @@ class FusedRowwiseAdagrad:
 
     momentum: fp32 [rows] on the device -- one accumulator per row of the table the momentum follows; row_of_slot:
     int32 [rows of the weight] mapping a row of the weight the kernels update to its momentum index (a cache's
-    cached_idx_map), None = the weight row itself.  lr=None disables the update (the weight then gets a gradient)."""
+    cached_idx_map), None = the weight row itself.  lr=None disables the update (the weight then gets a gradient).
+
+    deterministic=True: the step's lookups are sorted by row and a row's gradient is folded in lookup order (in chunks of
+    CE_SORTED_CHUNK for a hot row, the partial sums added in chunk order) instead of by atomics -- bit-reproducible
+    from run to run and independent of which slot a row sits in.  It needs no [rows, D] accumulator: its workspace
+    grows with the lookups of a step, not with the table.  A 16-bit table is rounded to nearest on this path: set
+    rounding = "nearest" (the default, "stochastic", is a NotImplementedError there before any kernel runs)."""
 
     def __init__(self, lr: Optional[float] = None, eps: float = 1e-8, momentum: Optional[torch.Tensor] = None,
-                 row_of_slot: Optional[torch.Tensor] = None):
+                 row_of_slot: Optional[torch.Tensor] = None, deterministic: bool = False):
         self.lr = lr
+        self.deterministic = bool(deterministic)
+        self._ws_sorted = None
         self.eps = float(eps)
         self.momentum = momentum
         self.row_of_slot = row_of_slot
@@ -386,6 +407,14 @@ class FusedRowwiseAdagrad:
                                       f"(a weight of {weight.shape[0]} rows over a cache of {rmap.numel()})")
         elif rmap.dtype != torch.int32 or not rmap.is_contiguous() or rmap.device != weight.device:
             raise ValueError("row_of_slot must be a contiguous int32 tensor on the weight's device")
+
+    def workspace_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
+        """workspace of the deterministic path (sort arrays, partial rows): nothing in it needs initialising"""
+        need = lib.ce_bag_backward_update_sorted_workspace(num_rows, nnz, dim)
+        if self._ws_sorted is None or self._ws_sorted.numel() < need or self._ws_sorted.device != device:
+            self._ws_sorted = None
+            self._ws_sorted = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._ws_sorted
 
     def workspace(self, num_rows: int, dim: int, device) -> torch.Tensor:
         # zero-filled once; every call of the kernels leaves it zero-filled again
@@ -415,8 +444,11 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
         # weight's dtype.  What it does not take is refused here, before any kernel has run.
         _lib.check_w16_dim(weight.shape[1])
         sgd16 = isinstance(fused_sgd, FusedSGD) and fused_sgd.lr is not None
+        det16 = isinstance(fused_sgd, FusedRowwiseAdagrad) and fused_sgd.lr is not None and fused_sgd.deterministic
         for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
                          ("FusedSGD(deterministic=True)", sgd16 and fused_sgd.deterministic),
+                         ("FusedRowwiseAdagrad(deterministic=True) with rounding='stochastic' (set rounding='nearest')",
+                          det16 and fused_sgd.rounding == "stochastic"),
                          ("a gradient w.r.t. per_sample_weights",
                           per_sample_weights is not None and per_sample_weights.requires_grad
                           and torch.is_grad_enabled())):

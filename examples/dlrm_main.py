@@ -93,6 +93,9 @@ def parse_args(argv=None):
                    help="exact row-wise Adagrad for the embedding, fused into backward (FBGEMM's EXACT_ROWWISE_ADAGRAD, "
                         "as baselines/dlrm_main.py:698-702 maps --adagrad), torch.optim.Adagrad for the dense part "
                         "(:799-802); takes the place of --fused_sgd (one process)")
+    p.add_argument("--adagrad_deterministic", action="store_true",
+                   help="with --adagrad: fold a row's gradient in lookup order over the step's sorted lookups instead "
+                        "of by atomics -- bit-reproducible, and without the [cache rows, D] fp32 accumulator")
     p.add_argument("--fold_hook", action="store_true", help="write [B,F,D] from the gather kernel")
     p.add_argument("--window_keys", action="store_true",
                    help="the window's cache op also groups every batch's slots by row (source-row keys): the forward "
@@ -500,6 +503,10 @@ def _evaluate(model, loader, stage, args, device, rank, world):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.adagrad_deterministic and not args.adagrad:
+        raise ValueError("--adagrad_deterministic chooses how --adagrad folds the gradient: pass --adagrad as well")
+    if args.adagrad_deterministic and args.table_dtype != "fp32" and args.weight_rounding == "stochastic":
+        raise NotImplementedError("--adagrad_deterministic rounds a 16-bit table to nearest: pass --weight_rounding nearest")
     if not args.use_cache:
         raise NotImplementedError("Other EmbeddingBags are under development")   # recsys/models/dlrm.py:83-84
     rank = int(os.environ.get("RANK", "0"))
@@ -554,7 +561,7 @@ def main(argv=None):
         embed.set_weight_rounding(args.weight_rounding, seed=args.seed)
     groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world}]
     if args.adagrad:
-        embed.set_fused_rowwise_adagrad(args.learning_rate)
+        embed.set_fused_rowwise_adagrad(args.learning_rate, deterministic=args.adagrad_deterministic)
     elif args.fused_sgd:
         embed.set_fused_sgd(args.learning_rate)
     else:

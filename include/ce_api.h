@@ -403,6 +403,40 @@ int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype, int64_t n
                                    float eps, int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
                                    size_t workspace_bytes, ce_stream_t stream);
 
+/* Deterministic, accumulator-free fused update (additions to API 6): the update of the entries above -- row-wise
+ * Adagrad or SGD, on an fp32 (weight_dtype = CE_ACT_F32), bf16 or fp16 table, grad_out read in place as act_dtype --
+ * with a bit-reproducible gradient fold and a workspace proportional to the LOOKUPS, not to the table.
+ * The lookups are stably radix-sorted by row, so a row's lookups form a run in ascending lookup position.  Fold order:
+ *   - a run of n <= CE_SORTED_CHUNK lookups: g = (...((s_0 g_0) + s_1 g_1) + ...) in fp32, strictly in lookup order
+ *     (s_j: per-sample weight, 1 / len for mean; for s_j == 1 the term is the gradient row itself);
+ *   - a longer run is cut into chunks of CE_SORTED_CHUNK consecutive positions counted from the start of the run, each
+ *     chunk is folded sequentially from zero by a lane group of its own, and the partial sums are added in ascending
+ *     chunk order.
+ * The result depends on the batch alone -- not on the grid, on the slot a row sits in, or on timing.  The row is then
+ * updated once, with the arithmetic of ce_bag_backward_rowwise_adagrad* / ce_bag_backward_update_w16: a row looked up
+ * once gets the same bits on either path.  The term s_j g_j is rounded to fp32 before it is added (no fused
+ * multiply-add).  A 16-bit row is stored with CE_ROUND_NEAREST; CE_ROUND_STOCHASTIC on a 16-bit table is refused
+ * (CE_ERR_UNSUPPORTED).  `rounding` is ignored for an fp32 table; `seed`, which only stochastic rounding would read,
+ * is ignored.
+ * Lookups outside [0, num_rows) (the -1 of padding) take no part; a slot whose momentum index lies outside
+ * [0, momentum_rows) is not updated.  CE_OPT_SGD: row_of_slot / momentum may be NULL, eps is ignored.
+ * Workspace: ce_bag_backward_update_sorted_workspace bytes (independent of num_rows), 256-byte aligned: the sort arrays
+ * (5 int32 per lookup + the digit histograms), then 2 * ceil(nnz / CE_SORTED_CHUNK) fp32 partial rows.  Nothing in it
+ * needs initialising and nothing in it outlives the call (no step counter: without stochastic rounding no state passes
+ * from one call to the next).  No host synchronisation, no allocation, launch shapes fixed by the arguments
+ * (capture-safe).  Everything that can be refused -- null pointers, sizes beyond 2^31, unknown dtype / optimizer /
+ * rounding codes, stochastic rounding, a 16-bit table's dim rule or alignment, a workspace that is too small -- is
+ * refused before the first launch. */
+#define CE_SORTED_CHUNK 64
+size_t ce_bag_backward_update_sorted_workspace(int64_t num_rows, int64_t nnz, int32_t dim);
+int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                  const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                  int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                  int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                  const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr, float eps,
+                                  int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                  size_t workspace_bytes, ce_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6].  Device state arrays are owned by the caller (so the Python
  * mirror can expose them as tensors: cached_idx_map, inverted_cached_idx, idx_map,
