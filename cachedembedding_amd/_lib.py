@@ -37,6 +37,7 @@ CE_OPT_ROWWISE_ADAGRAD = 1
 CE_ROUND_NEAREST = 0
 CE_ROUND_STOCHASTIC = 1
 CE_SORTED_CHUNK = 64
+CE_COMPACT_BLOCK = 4096
 CE_TRANSPORT_ZEROCOPY = 0
 CE_TRANSPORT_STAGED = 1
 CE_TRANSPORT_WORKER = 2
@@ -157,6 +158,10 @@ SIGNATURES = {
     # the deterministic, accumulator-free update: the w16 update's arguments without the presorted keys
     "ce_bag_backward_update_sorted_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
     "ce_bag_backward_update_sorted": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL[1:]),
+    # the atomic updates with a step-sized accumulator: the w16 update's arguments, weight_dtype may be CE_ACT_F32
+    "ce_bag_backward_update_compact_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
+    "ce_bag_backward_update_compact": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL),
+    "ce_bag_backward_update_compact_src": (c_int, _W16 + _SRC[1:] + _ACT + _W16_TAIL),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),

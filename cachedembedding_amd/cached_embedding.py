@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
-from .functional import FusedRowwiseAdagrad, FusedSGD, embedding_bag
+from .functional import FusedRowwiseAdagrad, FusedSGD, check_accumulator, embedding_bag
 
 
 class CachedEmbeddingBag(nn.Module):
@@ -107,24 +107,35 @@ class CachedEmbeddingBag(nn.Module):
     def set_cache_mgr_async_copy(self, flag: bool):
         self.cache_weight_mgr.set_async_copy(flag)
 
-    def set_fused_sgd(self, lr: Optional[float], deterministic: bool = False):
+    def set_fused_sgd(self, lr: Optional[float], deterministic: bool = False, accumulator: str = "cache"):
         """Apply SGD(lr) to the cache rows inside backward (K13+K14 fused).  lr=None restores
-        the plain autograd behaviour (grad handed to torch.optim)."""
+        the plain autograd behaviour (grad handed to torch.optim).  accumulator="step" (a 16-bit table only): the
+        update's fp32 accumulator has a row per lookup of the step at most instead of one per cache row."""
+        if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
+            check_accumulator("sgd", self.table_dtype, accumulator, bool(deterministic), self.weight_rounding)
         if lr is not None and self.fused_adagrad.lr is not None:
             raise ValueError("fused row-wise Adagrad is set: set_fused_rowwise_adagrad(None) before set_fused_sgd(lr)")
         if lr is not None and deterministic and self.table_dtype != torch.float32:
             raise NotImplementedError("FusedSGD(deterministic=True) with a 16-bit table")
         self.fused_sgd.lr = lr
         self.fused_sgd.deterministic = deterministic
+        self.fused_sgd.accumulator = accumulator
 
-    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8, deterministic: bool = False):
+    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8, deterministic: bool = False,
+                                  accumulator: str = "cache"):
         """Apply exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0; the reference's baseline
         --adagrad) to the cache rows inside backward.  The state is one fp32 accumulator per row of the host table,
         `cache_weight_mgr.momentum1` (device, zeroed when first enabled, indexed like `weight`); it stays in HBM and
         never moves with the cache.  lr=None turns the update off (the state is kept).  Exclusive with
         set_fused_sgd(lr).  deterministic=True: the sorted, bit-reproducible fold (FusedRowwiseAdagrad), fp32 and
         16-bit tables alike; the host table and the state then do not depend on the cache size or eviction strategy.
-        A 16-bit table needs set_weight_rounding("nearest") with it: the sorted fold does not round stochastically."""
+        A 16-bit table needs set_weight_rounding("nearest") with it: the sorted fold does not round stochastically.
+        accumulator="step": the atomic update with an fp32 accumulator of min(lookups of a step, cache rows) rows
+        instead of one as large as the cache (FusedRowwiseAdagrad); not with deterministic=True, and a 16-bit table
+        needs set_weight_rounding("nearest") first."""
+        if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
+            check_accumulator("rowwise_adagrad", self.table_dtype, accumulator, bool(deterministic),
+                              self.weight_rounding)
         if lr is not None and self.fused_sgd.lr is not None:
             raise ValueError("fused SGD is set: set_fused_sgd(None) before set_fused_rowwise_adagrad(lr)")
         mgr = self.cache_weight_mgr
@@ -133,6 +144,7 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_adagrad.lr = lr
         self.fused_adagrad.eps = float(eps)
         self.fused_adagrad.deterministic = bool(deterministic)
+        self.fused_adagrad.accumulator = accumulator
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
 

@@ -649,6 +649,353 @@ static SortedWs carve_sorted(void* ws, int64_t nnz, int32_t dim) {
   return w;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Step-sized accumulator (ce_bag_backward_update_compact*).  The atomic updates above fold the step's
+// gradient into acc[num_rows, D]; a step touches at most cap = min(nnz, num_rows) distinct slots, so here the flagged
+// slots are numbered 0 .. U-1 in ascending order and the SAME dense backward scatters into acc[cap, D] through the
+// renumbered indices / keys.  One stream, no host synchronisation, no allocation, launch shapes fixed by the arguments
+// (U stays on the device and is read by the apply kernel):
+//   1. k_adagrad_mark_* / k_w16_mark_* (unchanged): flags[slot] = 1, the 16-bit path's step counter += 1;
+//   2. k_compact_count + k_compact_emit: list[u] = the u-th flagged slot, cidx[slot] = u, U; the flags go back to zero;
+//   3. k_compact_remap_slots / _keys: slots -> cidx[slot] (-1 outside [0, num_rows)), row << 32 | x -> cidx[row] << 32 | x;
+//   4. ce_bag_backward_dense_act / _dense_src_act (unchanged) into acc[cap, D] with num_rows = cap;
+//   5. k_compact_apply: a lane group per u < U updates W[list[u]] / momentum[row_of_slot[list[u]]] and zeroes acc[u].
+// cidx is written for flagged slots only and read for flagged slots only (a lookup the remap reads was marked in this
+// call), so it is never initialised and never cleared; list and the remap buffer likewise.
+constexpr int kCompactRounds = 16;                                   // 64-slot ballots per wave
+constexpr int kCompactWave = 64 * kCompactRounds;                    // consecutive slots per wave
+static_assert(CE_COMPACT_BLOCK == 4 * kCompactWave, "a scan workgroup is four waves of kCompactRounds ballots");
+
+__device__ __forceinline__ int compact_wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// flagged slots of every scan workgroup (CE_COMPACT_BLOCK consecutive slots): one lane per slot and round
+__global__ __launch_bounds__(256) void k_compact_count(const uint8_t* __restrict__ flags, uint32_t num_rows,
+                                                       int32_t* __restrict__ blk_count) {
+  __shared__ int wcnt[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * CE_COMPACT_BLOCK + w * kCompactWave + lane;
+  int n = 0;
+#pragma unroll
+  for (int r = 0; r < kCompactRounds; ++r) {
+    const int64_t s = base + r * 64;
+    n += __popcll(__ballot(s < (int64_t)num_rows && flags[s] != 0));
+  }
+  if (lane == 0) wcnt[w] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) blk_count[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+}
+
+// every workgroup adds up the counts of the workgroups before its own (k_free_emit's cross-block prefix: a few KB out
+// of L2, no scan launch), the waves' totals go through LDS, a lane's place in its round is a popcount of the ballot
+// below it.  Nothing returns from an atomic.  u < cap always holds when the flags came from this call's mark (at most
+// min(nnz, num_rows) distinct slots); a slot past it -- a workspace that was not zero -- is dropped, never written.
+__global__ __launch_bounds__(256) void k_compact_emit(uint8_t* __restrict__ flags, uint32_t num_rows,
+                                                      const int32_t* __restrict__ blk_count, int32_t* __restrict__ cidx,
+                                                      int32_t* __restrict__ list, uint32_t cap, int32_t* __restrict__ n_out) {
+  __shared__ int wbefore[4];
+  __shared__ int wcnt[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int part = 0;
+  for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) part += blk_count[i];
+  part = compact_wave_sum(part);
+  const int64_t base = (int64_t)blockIdx.x * CE_COMPACT_BLOCK + w * kCompactWave + lane;
+  unsigned long long b[kCompactRounds];
+  int n = 0;
+#pragma unroll
+  for (int r = 0; r < kCompactRounds; ++r) {
+    const int64_t s = base + r * 64;
+    const bool f = s < (int64_t)num_rows && flags[s] != 0;
+    b[r] = __ballot(f);
+    n += __popcll(b[r]);
+    if (f) flags[s] = 0;
+  }
+  if (lane == 0) {
+    wbefore[w] = part;
+    wcnt[w] = n;
+  }
+  __syncthreads();
+  const long long before = (long long)wbefore[0] + wbefore[1] + wbefore[2] + wbefore[3];
+  long long pos = before;
+  for (int k = 0; k < w; ++k) pos += wcnt[k];
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int r = 0; r < kCompactRounds; ++r) {
+    if ((b[r] >> lane) & 1ull) {
+      const int64_t s = base + r * 64;
+      const long long u = pos + __popcll(b[r] & below);
+      if (u < (long long)cap) list[u] = (int32_t)s;
+      cidx[s] = u < (long long)cap ? (int32_t)u : -1;
+    }
+    pos += __popcll(b[r]);
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    const long long total = before + wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    *n_out = (int32_t)(total < (long long)cap ? total : (long long)cap);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_compact_remap_slots(const int64_t* __restrict__ slots, int64_t n,
+                                                             uint32_t num_rows, const int32_t* __restrict__ cidx,
+                                                             uint32_t cap, int64_t* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t s = slots[i];
+    int64_t c = -1;
+    if (s >= 0 && s < (int64_t)num_rows) c = cidx[s];
+    out[i] = (uint64_t)c < (uint64_t)cap ? c : -1;          // (a number outside [0, cap) is never handed on)
+  }
+}
+
+// keys = row << 32 | low word (the lookup's place in its segment, or the row of grad_out it reads): the low word and
+// the order stay, so rows that were adjacent stay adjacent (the map is injective on flagged slots).  Padding (~0) and
+// ignored rows stay what they are; a row outside [0, num_rows) -- which no presort writes -- becomes ignored: all ones
+// in the segment-sorted form (whole_key), 0xffffffff in the row half of a source-row key.
+__global__ __launch_bounds__(256) void k_compact_remap_keys(const unsigned long long* __restrict__ keys, int64_t n,
+                                                            uint32_t num_rows, const int32_t* __restrict__ cidx,
+                                                            uint32_t cap, int whole_key,
+                                                            unsigned long long* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const unsigned long long k = keys[i];
+    const uint32_t row = (uint32_t)(k >> 32);
+    unsigned long long o = whole_key ? ~0ull : (k | 0xffffffff00000000ull);
+    if (k == ~0ull) {
+      o = k;
+    } else if (row < num_rows) {
+      const uint32_t c = (uint32_t)cidx[row];
+      if (c < cap) o = ((unsigned long long)c << 32) | (k & 0xffffffffull);
+    }
+    out[i] = o;
+  }
+}
+
+struct CompactArgs {
+  void* weight;              // [num_rows, D] of WT
+  float* acc;                // [cap, D], zero outside a call
+  const int32_t* list;       // [cap]: list[u] = the u-th flagged slot
+  const int32_t* n_list;     // U, written by k_compact_emit
+  const unsigned long long* counter;
+  const int32_t* row_of_slot;
+  float* momentum;
+  int64_t momentum_rows;
+  uint64_t seed;
+  int32_t rowlen;
+  int32_t g_log2;
+  int32_t dim;
+  int32_t adagrad;
+  float lr;
+  float eps;
+};
+
+// one lane group per list entry (grid-stride over u < U; the grid is sized by cap).  The update is k_adagrad_apply's /
+// k_rows_apply_w16's: the same lane-group shape and reduction tree, the sum of squares in the form those kernels
+// compiled to (sorted_sq_sum), the same expressions for the row and the random bits of a stochastically rounded SGD
+// step -- given the same acc row, the same bits.
+template <typename VT, typename WT, int NCH, bool STOCH>
+__global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
+  using T = Act<WT, VT>;
+  static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
+  const int G = 1 << a.g_log2;
+  const int gl = threadIdx.x & (G - 1);
+  const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.g_log2;
+  const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) >> a.g_log2;
+  typename T::V* W = (typename T::V*)a.weight;
+  VT* A = (VT*)a.acc;
+  const int64_t n = *a.n_list;
+  uint64_t step_key = 0;
+  if (STOCH) step_key = mix64(a.seed + 0xD6E8FEB86659FD93ull * *a.counter);
+  for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
+    const int64_t s = a.list[u];
+    VT g[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      g[c] = idx < a.rowlen ? A[u * a.rowlen + idx] : vzero<VT>();
+    }
+    const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
+    float mult = a.lr;
+    bool update = true;
+    if (a.adagrad) {
+      float ss = sorted_sq_sum<WT, NCH>(g);
+      for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, G);
+      update = r >= 0 && r < a.momentum_rows;
+      if (update) {
+        const float mr = a.momentum[r] + ss / (float)a.dim;
+        mult = a.lr / (sqrtf(mr) + a.eps);
+        if (gl == 0) a.momentum[r] = mr;
+      }
+    }
+    if (update) {
+      uint64_t row_key = 0;
+      if (STOCH) row_key = mix64(step_key ^ (uint64_t)r);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        if (idx < a.rowlen) {
+          const VT x = T::up(W[s * a.rowlen + idx]) - g[c] * mult;
+          if constexpr (STOCH) {
+            const uint64_t h = mix64(row_key + (uint64_t)idx);       // 16 bits for each of the chunk's 4 elements
+            typename T::V o;
+            o.x = round_stochastic(x.x, (uint32_t)h, WT{});
+            o.y = round_stochastic(x.y, (uint32_t)(h >> 16), WT{});
+            o.z = round_stochastic(x.z, (uint32_t)(h >> 32), WT{});
+            o.w = round_stochastic(x.w, (uint32_t)(h >> 48), WT{});
+            W[s * a.rowlen + idx] = o;
+          } else {
+            W[s * a.rowlen + idx] = T::down(x);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      if (idx < a.rowlen) A[u * a.rowlen + idx] = vzero<VT>();
+    }
+  }
+}
+
+// workspace: what must be zero outside a call (flags, acc) and the step counter, then what needs no initialising.
+// The layout depends on num_rows, nnz and dim: a workspace serves ONE such triple (its owner zero-fills it again,
+// counter apart, before it serves another).
+struct CompactWs {
+  unsigned long long* counter;
+  int32_t* n_list;
+  uint8_t* flags;            // [num_rows]
+  float* acc;                // [cap, dim]
+  int32_t* cidx;             // [num_rows]
+  int32_t* blk_count;        // [ceil(num_rows / CE_COMPACT_BLOCK)]
+  int32_t* list;             // [cap]
+  void* remap;               // [ce_bag_presort_len(nnz)] x 8 bytes
+  int64_t cap;
+  size_t bytes;
+};
+
+static CompactWs carve_compact(void* ws, int64_t num_rows, int64_t nnz, int32_t dim) {
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  CompactWs w{};
+  w.cap = nnz < num_rows ? nnz : num_rows;
+  char* p = (char*)ws;
+  size_t o = 0;
+  w.counter = (unsigned long long*)(p + o);  o += 256;
+  w.n_list = (int32_t*)(p + o);              o += 256;
+  w.flags = (uint8_t*)(p + o);               o = al(o + (size_t)num_rows);
+  w.acc = (float*)(p + o);                   o = al(o + (size_t)w.cap * dim * 4);
+  w.cidx = (int32_t*)(p + o);                o = al(o + (size_t)num_rows * 4);
+  w.blk_count = (int32_t*)(p + o);           o = al(o + (size_t)cdiv(num_rows, CE_COMPACT_BLOCK) * 4);
+  w.list = (int32_t*)(p + o);                o = al(o + (size_t)w.cap * 4);
+  w.remap = p + o;                           o = al(o + (size_t)ce_bag_presort_len(nnz) * 8);
+  w.bytes = o;
+  return w;
+}
+
+// everything the two entries can refuse, from the arguments alone: no launch and no HIP call before the last check
+static int compact_check(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
+                         const void* grad_out, int act, float* momentum, int64_t momentum_rows, float lr, float eps,
+                         int32_t optimizer, int32_t rounding, void* workspace, size_t workspace_bytes, RowGeom& r) {
+  CE_REQUIRE_ACT(act);
+  CE_REQUIRE(weight_dtype == CE_ACT_F32 || weight_dtype == CE_ACT_BF16 || weight_dtype == CE_ACT_F16, CE_ERR_INVALID,
+             "unknown weight_dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)weight_dtype);
+  const bool w16 = weight_dtype != CE_ACT_F32;
+  if (w16) {
+    int rc = w16_check(weight_dtype, dim);
+    if (rc) return rc;
+  }
+  CE_REQUIRE(optimizer == CE_OPT_SGD || optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_INVALID,
+             "unknown optimizer %d (CE_OPT_SGD / CE_OPT_ROWWISE_ADAGRAD)", (int)optimizer);
+  CE_REQUIRE(rounding == CE_ROUND_NEAREST || rounding == CE_ROUND_STOCHASTIC, CE_ERR_INVALID,
+             "unknown rounding %d (CE_ROUND_NEAREST / CE_ROUND_STOCHASTIC)", (int)rounding);
+  CE_REQUIRE(w16 || optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_UNSUPPORTED,
+             "CE_OPT_SGD on an fp32 table folds straight into the rows: it has no accumulator to compact");
+  CE_REQUIRE(!(w16 && optimizer == CE_OPT_ROWWISE_ADAGRAD && rounding == CE_ROUND_STOCHASTIC), CE_ERR_UNSUPPORTED,
+             "row-wise Adagrad with CE_ROUND_STOCHASTIC on a 16-bit table is not taken with the step-sized accumulator");
+  CE_REQUIRE(weight && grad_out && workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(dim > 0, CE_ERR_INVALID, "dim must be positive");
+  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE(nnz >= 0 && nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "nnz out of range");
+  CE_REQUIRE(lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
+  if (optimizer == CE_OPT_ROWWISE_ADAGRAD) {
+    CE_REQUIRE(momentum && momentum_rows > 0, CE_ERR_INVALID, "row-wise Adagrad needs its momentum");
+    CE_REQUIRE(eps > 0.f, CE_ERR_INVALID, "eps must be > 0");
+  }
+  CE_REQUIRE(workspace_bytes >= carve_compact(nullptr, num_rows, nnz, dim).bytes, CE_ERR_INVALID,
+             "workspace too small");
+  CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
+  CE_REQUIRE(!w16 || al16(weight), CE_ERR_INVALID, "a 16-bit table must be 16-byte aligned");
+  // the scatter into acc takes the vector or the scalar form by grad_out's alignment, the apply pass by the table's
+  // (a 16-bit table: vector lanes only); a dim that fits the scalar form fits the vector form
+  RowGeom weakest;
+  int rc = row_geometry(dim, (w16 || al16(weight)) && act_aligned(grad_out, act), weakest);
+  if (rc) return rc;
+  return row_geometry(dim, w16 || al16(weight), r);
+}
+
+static void launch_compact_mark(bool w16, const void* src, bool keys, int64_t n, int64_t num_rows, const CompactWs& ws,
+                                hipStream_t s) {
+  const dim3 g(grid_for(n, 256)), b(256);
+  const uint32_t R = (uint32_t)num_rows;
+  if (keys) {
+    const unsigned long long* k = (const unsigned long long*)src;
+    if (w16) hipLaunchKernelGGL(k_w16_mark_keys, g, b, 0, s, k, n, R, ws.flags, ws.counter);
+    else hipLaunchKernelGGL(k_adagrad_mark_keys, g, b, 0, s, k, n, R, ws.flags);
+  } else {
+    const int64_t* i = (const int64_t*)src;
+    if (w16) hipLaunchKernelGGL(k_w16_mark_slots, g, b, 0, s, i, n, R, ws.flags, ws.counter);
+    else hipLaunchKernelGGL(k_adagrad_mark_slots, g, b, 0, s, i, n, R, ws.flags);
+  }
+}
+
+static int launch_compact_scan(int64_t num_rows, const CompactWs& ws, hipStream_t s) {
+  const dim3 g((unsigned)cdiv(num_rows, CE_COMPACT_BLOCK)), b(256);
+  hipLaunchKernelGGL(k_compact_count, g, b, 0, s, ws.flags, (uint32_t)num_rows, ws.blk_count);
+  hipLaunchKernelGGL(k_compact_emit, g, b, 0, s, ws.flags, (uint32_t)num_rows, ws.blk_count, ws.cidx, ws.list,
+                     (uint32_t)ws.cap, ws.n_list);
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
+static int launch_compact_apply(void* weight, int32_t weight_dtype, int32_t dim, const RowGeom& r,
+                                const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr, float eps,
+                                int32_t optimizer, int32_t rounding, uint64_t seed, const CompactWs& ws, hipStream_t s) {
+  CompactArgs a{};
+  a.weight = weight;
+  a.acc = ws.acc;
+  a.list = ws.list;
+  a.n_list = ws.n_list;
+  a.counter = ws.counter;
+  a.row_of_slot = row_of_slot;
+  a.momentum = momentum;
+  a.momentum_rows = momentum_rows;
+  a.seed = seed;
+  a.rowlen = r.rowlen;
+  a.g_log2 = r.g_log2;
+  a.dim = dim;
+  a.adagrad = optimizer == CE_OPT_ROWWISE_ADAGRAD;
+  a.lr = lr;
+  a.eps = eps;
+  const dim3 g(grid_for(ws.cap, 256 >> r.g_log2)), b(256);
+  if (weight_dtype == CE_ACT_F32) {
+    for_lanes(r.vec, r.nch, [&](auto l) {
+      hipLaunchKernelGGL((k_compact_apply<typename decltype(l)::VT, float, decltype(l)::NCH, false>), g, b, 0, s, a);
+    });
+  } else {
+    const bool st = rounding == CE_ROUND_STOCHASTIC;
+    for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
+      using WT = typename decltype(w)::AT;
+      constexpr int N = decltype(l)::NCH;
+      if (st) hipLaunchKernelGGL((k_compact_apply<f32x4, WT, N, true>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_compact_apply<f32x4, WT, N, false>), g, b, 0, s, a);
+    });
+  }
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
 }  // namespace ce
 
 using namespace ce;
@@ -791,6 +1138,88 @@ extern "C" int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype
   if (rc) return rc;
   return launch_apply_w16(weight, weight_dtype, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps,
                           optimizer, rounding, seed, ws, s);
+}
+
+// ---- step-sized accumulator: mark, compact, remap, the dense backward into acc[cap, D], apply over the list
+
+extern "C" size_t ce_bag_backward_update_compact_workspace(int64_t num_rows, int64_t nnz, int32_t dim) {
+  if (num_rows < 0 || num_rows >= (int64_t)INT32_MAX || nnz < 0 || nnz >= (int64_t)INT32_MAX || dim < 0) return 0;
+  return carve_compact(nullptr, num_rows, nnz, dim).bytes;
+}
+
+extern "C" int ce_bag_backward_update_compact(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                              const int64_t* indices, int64_t nnz, const void* offsets,
+                                              int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                              const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                              const void* grad_out, int32_t act_dtype, const uint64_t* presorted,
+                                              const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
+                                              float lr, float eps, int32_t optimizer, int32_t rounding, uint64_t seed,
+                                              void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  RowGeom r;
+  int rc = compact_check(weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, momentum, momentum_rows, lr,
+                         eps, optimizer, rounding, workspace, workspace_bytes, r);
+  if (rc) return rc;
+  if (num_bags == 0 || nnz == 0) return CE_OK;
+  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(num_bags > 0 && num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "sizes out of range");
+  CE_REQUIRE(mode == CE_MODE_SUM || (mode == CE_MODE_MEAN && !per_sample_weights), CE_ERR_INVALID,
+             "mode must be sum, or mean without per_sample_weights");
+  CE_REQUIRE(hook_features >= 0 && (hook_features == 0 || num_bags % hook_features == 0), CE_ERR_INVALID,
+             "hook_features must divide num_bags");
+  hipStream_t s = (hipStream_t)stream;
+  const CompactWs ws = carve_compact(workspace, num_rows, nnz, dim);
+  launch_compact_mark(weight_dtype != CE_ACT_F32, indices, false, nnz, num_rows, ws, s);
+  rc = launch_compact_scan(num_rows, ws, s);
+  if (rc) return rc;
+  // segment-sorted keys hold the rows themselves: with them the scatter never reads `indices`, so only they are remapped
+  const int64_t* idx = indices;
+  const uint64_t* keys = nullptr;
+  if (presorted) {
+    const int64_t total = ce_bag_presort_len(nnz);
+    hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
+                       (const unsigned long long*)presorted, total, (uint32_t)num_rows, ws.cidx, (uint32_t)ws.cap, 1,
+                       (unsigned long long*)ws.remap);
+    keys = (const uint64_t*)ws.remap;
+  } else {
+    hipLaunchKernelGGL(k_compact_remap_slots, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz,
+                       (uint32_t)num_rows, ws.cidx, (uint32_t)ws.cap, (int64_t*)ws.remap);
+    idx = (const int64_t*)ws.remap;
+  }
+  CE_LAUNCH_CHECK();
+  rc = ce_bag_backward_dense_act(ws.acc, ws.cap, dim, idx, nnz, offsets, offsets_are_i64, num_bags,
+                                 include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                                 keys, stream);
+  if (rc) return rc;
+  return launch_compact_apply(weight, weight_dtype, dim, r, row_of_slot, momentum, momentum_rows, lr, eps, optimizer,
+                              rounding, seed, ws, s);
+}
+
+extern "C" int ce_bag_backward_update_compact_src(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                                  int64_t nnz, const void* grad_out, int32_t act_dtype,
+                                                  const uint64_t* src_keys, const int32_t* row_of_slot,
+                                                  float* momentum, int64_t momentum_rows, float lr, float eps,
+                                                  int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                                  size_t workspace_bytes, ce_stream_t stream) {
+  RowGeom r;
+  int rc = compact_check(weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, momentum, momentum_rows, lr,
+                         eps, optimizer, rounding, workspace, workspace_bytes, r);
+  if (rc) return rc;
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const CompactWs ws = carve_compact(workspace, num_rows, nnz, dim);
+  const int64_t total = ce_bag_presort_len(nnz);
+  launch_compact_mark(weight_dtype != CE_ACT_F32, src_keys, true, total, num_rows, ws, s);
+  rc = launch_compact_scan(num_rows, ws, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
+                     (const unsigned long long*)src_keys, total, (uint32_t)num_rows, ws.cidx, (uint32_t)ws.cap, 0,
+                     (unsigned long long*)ws.remap);
+  CE_LAUNCH_CHECK();
+  rc = ce_bag_backward_dense_src_act(ws.acc, ws.cap, dim, nnz, grad_out, act_dtype, (const uint64_t*)ws.remap, stream);
+  if (rc) return rc;
+  return launch_compact_apply(weight, weight_dtype, dim, r, row_of_slot, momentum, momentum_rows, lr, eps, optimizer,
+                              rounding, seed, ws, s);
 }
 
 // ---- deterministic, accumulator-free: sort, fold + apply, combine + apply

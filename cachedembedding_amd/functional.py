@@ -148,6 +148,26 @@ class _BagFn(torch.autograd.Function):
             grad_out = grad_out.float()
         slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
                       hook_features, ptr(grad_out))
+        if (rowwise or sgd) and fused.accumulator == "step":
+            # the atomic update with an accumulator of min(nnz, rows) rows (ce_bag_backward_update_compact*): mark, an
+            # ordered compaction of the flagged slots, the slots / keys renumbered, the same dense backward, one apply
+            # pass over the list.  fp32 tables (row-wise Adagrad) and 16-bit tables alike, from slots + offsets, from
+            # presorted keys and from source-row keys; what it does not take was refused before the forward.
+            with torch.no_grad():
+                ws = fused.workspace_step(R, nnz, dim, weight.device)
+                mom = fused.momentum if rowwise else None
+                stoch = fused.rounding == "stochastic" and weight.dtype in _lib.W16_DTYPES
+                wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
+                tail = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), float(fused.lr),
+                        float(fused.eps) if rowwise else 0.0,
+                        _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
+                        _lib.CE_ROUND_STOCHASTIC if stoch else _lib.CE_ROUND_NEAREST,
+                        int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr())
+                if src:
+                    check(lib.ce_bag_backward_update_compact_src(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                else:
+                    check(lib.ce_bag_backward_update_compact(*wd, *slots_args, act, ptr(pre), *tail))
+            return (None,) * 14
         if rowwise and fused.deterministic:
             # bit-reproducible row-wise Adagrad without the [rows, D] accumulator (ce_bag_backward_update_sorted): fp32
             # and 16-bit tables (rounded to nearest: stochastic rounding was refused before the forward), always from
@@ -338,15 +358,64 @@ def _workspace_w16(self, num_rows: int, dim: int, device) -> torch.Tensor:
     return self._ws16
 
 
+ACCUMULATORS = ("cache", "step")
+
+
+def check_accumulator(optimizer: str, table_dtype, accumulator: str, deterministic: bool = False,
+                      rounding: str = "nearest") -> None:
+    """Refusals of accumulator= ("cache": the fp32 accumulator of the atomic updates has a row per row of the weight;
+    "step": a row per lookup of the step at most).  optimizer: "sgd" or "rowwise_adagrad"; table_dtype: the weight's
+    (None: not known yet -- what depends on it is asked again before the forward).
+    Host logic only -- it is asked before the forward, so that nothing is refused after a kernel has run."""
+    if accumulator not in ACCUMULATORS:
+        raise ValueError(f"accumulator={accumulator!r}: 'cache' or 'step'")
+    if accumulator == "cache":
+        return
+    if deterministic:
+        raise NotImplementedError("accumulator='step' with deterministic=True: the sorted update has no accumulator")
+    w16 = table_dtype in _lib.W16_DTYPES
+    if optimizer == "sgd" and table_dtype is not None and not w16:
+        raise NotImplementedError("accumulator='step' with fused SGD on an fp32 table: that update folds straight "
+                                  "into the rows and has no accumulator")
+    if optimizer == "rowwise_adagrad" and w16 and rounding == "stochastic":
+        raise NotImplementedError("accumulator='step' with row-wise Adagrad and rounding='stochastic' on a 16-bit "
+                                  "table (set rounding='nearest')")
+
+
+def _workspace_step(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
+    """workspace of accumulator="step" (step counter, byte flags, fp32 accumulator [min(nnz, num_rows), dim], the
+    compaction's arrays): zero-filled once; every call leaves it zero-filled except the counter and what needs no
+    initialising.  Its layout belongs to one (num_rows, nnz, dim): for another one it is zero-filled again, the
+    counter -- the first 8 bytes -- kept, so stochastic rounding goes on drawing fresh bits."""
+    need = lib.ce_bag_backward_update_compact_workspace(num_rows, nnz, dim)
+    key = (int(num_rows), int(nnz), int(dim))
+    ws = self._ws_step
+    if ws is None or ws.numel() < need or ws.device != device:
+        counter = None if ws is None or ws.device != device else ws[:8].clone()
+        self._ws_step = ws = None                       # (the old one goes before the new one comes)
+        self._ws_step = ws = torch.zeros(need, dtype=torch.uint8, device=device)
+        if counter is not None:
+            ws[:8].copy_(counter)
+    elif self._ws_step_key != key:
+        ws[256:].zero_()
+    self._ws_step_key = key
+    return ws
+
+
 class FusedSGD:
     """Switch for the fused backward+SGD path of one embedding module.
 
     lr=None disables fusion (the module behaves exactly like nn.EmbeddingBag under
-    torch.optim.SGD); deterministic=True uses the sorted segmented update instead of atomics."""
+    torch.optim.SGD); deterministic=True uses the sorted segmented update instead of atomics.
+    accumulator="step" (a 16-bit table only; an fp32 table's SGD has no accumulator): the update's fp32 accumulator has
+    min(lookups of the step, rows) rows instead of one per row of the weight."""
 
-    def __init__(self, lr: Optional[float] = None, deterministic: bool = False):
+    def __init__(self, lr: Optional[float] = None, deterministic: bool = False, accumulator: str = "cache"):
+        check_accumulator("sgd", None, accumulator, bool(deterministic))
         self.lr = lr
         self.deterministic = deterministic
+        self.accumulator = accumulator
+        self._ws_step, self._ws_step_key = None, None
         self._ws = None
         # a 16-bit table only: how the update rounds a row ("nearest" / "stochastic"), the seed of the random bits and
         # the host-table row of every slot they are drawn for (None: the slot itself)
@@ -354,6 +423,7 @@ class FusedSGD:
         self._ws16 = None
 
     workspace_w16 = _workspace_w16
+    workspace_step = _workspace_step
 
     def workspace(self, num_rows: int, nnz: int, device) -> torch.Tensor:
         need = lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz)
@@ -375,12 +445,20 @@ class FusedRowwiseAdagrad:
     CE_SORTED_CHUNK for a hot row, the partial sums added in chunk order) instead of by atomics -- bit-reproducible
     from run to run and independent of which slot a row sits in.  It needs no [rows, D] accumulator: its workspace
     grows with the lookups of a step, not with the table.  A 16-bit table is rounded to nearest on this path: set
-    rounding = "nearest" (the default, "stochastic", is a NotImplementedError there before any kernel runs)."""
+    rounding = "nearest" (the default, "stochastic", is a NotImplementedError there before any kernel runs).
+
+    accumulator="step": the atomic update keeps its speed but folds into an fp32 accumulator of min(lookups of the
+    step, rows) rows -- the flagged slots are compacted and the lookups renumbered first -- instead of one as large as
+    the weight ("cache", the default).  Not with deterministic=True, and on a 16-bit table with rounding="nearest"
+    only: both are refused before any kernel runs."""
 
     def __init__(self, lr: Optional[float] = None, eps: float = 1e-8, momentum: Optional[torch.Tensor] = None,
-                 row_of_slot: Optional[torch.Tensor] = None, deterministic: bool = False):
+                 row_of_slot: Optional[torch.Tensor] = None, deterministic: bool = False, accumulator: str = "cache"):
+        check_accumulator("rowwise_adagrad", None, accumulator, bool(deterministic))
         self.lr = lr
         self.deterministic = bool(deterministic)
+        self.accumulator = accumulator
+        self._ws_step, self._ws_step_key = None, None
         self._ws_sorted = None
         self.eps = float(eps)
         self.momentum = momentum
@@ -390,6 +468,7 @@ class FusedRowwiseAdagrad:
         self._ws16 = None
 
     workspace_w16 = _workspace_w16
+    workspace_step = _workspace_step
 
     def check(self, weight: torch.Tensor) -> None:
         """refusals that must come before any kernel of the step has run"""
@@ -439,6 +518,11 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     # and hence of the gradient autograd hands back; the weight, the sums and every update stay fp32, the kernels
     # round once on the store and read the 16-bit gradient in place.  out= must then have that dtype.
     _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
+    if fused_sgd is not None and fused_sgd.lr is not None:
+        check_accumulator("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
+                          fused_sgd.accumulator, bool(fused_sgd.deterministic), fused_sgd.rounding)
+        if fused_sgd.accumulator == "step" and mode == "max":
+            raise NotImplementedError("accumulator='step' with mode='max'")
     if weight.dtype in _lib.W16_DTYPES:
         # a 16-bit table (bf16 / fp16 weight): rows up-converted exactly, fp32 sums, the output defaults to the
         # weight's dtype.  What it does not take is refused here, before any kernel has run.

@@ -96,6 +96,11 @@ def parse_args(argv=None):
     p.add_argument("--adagrad_deterministic", action="store_true",
                    help="with --adagrad: fold a row's gradient in lookup order over the step's sorted lookups instead "
                         "of by atomics -- bit-reproducible, and without the [cache rows, D] fp32 accumulator")
+    p.add_argument("--step_accumulator", action="store_true",
+                   help="with --adagrad, or with a 16-bit --table_dtype and --fused_sgd: the fused update's fp32 "
+                        "accumulator has a row per lookup of a step at most instead of one per cache row "
+                        "(accumulator='step'); not with --adagrad_deterministic, and --adagrad on a 16-bit table needs "
+                        "--weight_rounding nearest with it")
     p.add_argument("--fold_hook", action="store_true", help="write [B,F,D] from the gather kernel")
     p.add_argument("--window_keys", action="store_true",
                    help="the window's cache op also groups every batch's slots by row (source-row keys): the forward "
@@ -501,12 +506,25 @@ def _evaluate(model, loader, stage, args, device, rank, world):
     return auroc, acc
 
 
+def check_step_accumulator(args):
+    """--step_accumulator: refused here, before a device is touched, with the library's own refusals"""
+    from cachedembedding_amd.functional import check_accumulator
+    if not (args.adagrad or args.fused_sgd):
+        raise ValueError("--step_accumulator sizes the accumulator of a fused update: pass --adagrad, or --fused_sgd "
+                         "with a 16-bit --table_dtype")
+    table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
+    check_accumulator("rowwise_adagrad" if args.adagrad else "sgd", table, "step", bool(args.adagrad_deterministic),
+                      args.weight_rounding)
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.adagrad_deterministic and not args.adagrad:
         raise ValueError("--adagrad_deterministic chooses how --adagrad folds the gradient: pass --adagrad as well")
     if args.adagrad_deterministic and args.table_dtype != "fp32" and args.weight_rounding == "stochastic":
         raise NotImplementedError("--adagrad_deterministic rounds a 16-bit table to nearest: pass --weight_rounding nearest")
+    if args.step_accumulator:
+        check_step_accumulator(args)
     if not args.use_cache:
         raise NotImplementedError("Other EmbeddingBags are under development")   # recsys/models/dlrm.py:83-84
     rank = int(os.environ.get("RANK", "0"))
@@ -561,9 +579,10 @@ def main(argv=None):
         embed.set_weight_rounding(args.weight_rounding, seed=args.seed)
     groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world}]
     if args.adagrad:
-        embed.set_fused_rowwise_adagrad(args.learning_rate, deterministic=args.adagrad_deterministic)
+        embed.set_fused_rowwise_adagrad(args.learning_rate, deterministic=args.adagrad_deterministic,
+                                        accumulator="step" if args.step_accumulator else "cache")
     elif args.fused_sgd:
-        embed.set_fused_sgd(args.learning_rate)
+        embed.set_fused_sgd(args.learning_rate, accumulator="step" if args.step_accumulator else "cache")
     else:
         groups.insert(0, {"params": list(model.sparse_modules.parameters()), "lr": args.learning_rate})
     optimizer = torch.optim.Adagrad(groups) if args.adagrad else torch.optim.SGD(groups)

@@ -437,6 +437,43 @@ int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype, int64_t nu
                                   int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
                                   size_t workspace_bytes, ce_stream_t stream);
 
+/* Step-sized accumulator for the atomic fused updates (additions to API 6): the update of ce_bag_backward_rowwise_adagrad*
+ * (weight_dtype = CE_ACT_F32, CE_OPT_ROWWISE_ADAGRAD) and of ce_bag_backward_update_w16 / _src_w16 (bf16 / fp16 table,
+ * either optimizer) with an fp32 accumulator of cap = min(nnz, num_rows) rows instead of num_rows: a step cannot touch
+ * more distinct slots than it has lookups.  The argument lists are those of the _w16 entries.  One stream, no host
+ * synchronisation, no allocation, launch shapes fixed by the arguments (capture-safe):
+ *   mark (as above: byte flags, the 16-bit table's step counter) -> an ordered compaction of the flagged slots
+ *   (list[u] = the u-th flagged slot ascending, cidx[slot] = u, their number U; the flags return to zero) -> one
+ *   elementwise pass that rewrites the slots / the row half of the keys as cidx[.] into the workspace (lookups outside
+ *   [0, num_rows) -> -1, ignored rows and padding keys stay) -> the same dense backward into acc[cap, dim] ->
+ *   one apply pass over u < U that updates W[list[u]] and momentum[row_of_slot[list[u]]] and zeroes acc[u].
+ * Given the same folded gradient the apply pass writes the bits of the entries above, stochastic rounding of an SGD step
+ * included (same hash of seed, step counter, row and element).
+ * CE_ERR_UNSUPPORTED before the first launch: CE_OPT_SGD on an fp32 table (it has no accumulator), and row-wise Adagrad
+ * with CE_ROUND_STOCHASTIC on a 16-bit table.  `rounding` and `seed` are ignored for an fp32 table.  Every other refusal
+ * is that of the entries above, from the arguments alone.
+ * Workspace: ce_bag_backward_update_compact_workspace(num_rows, nnz, dim) bytes, 256-byte aligned, at most
+ * 6 * num_rows + cap * (4 * dim + 4) + 8 * ce_bag_presort_len(nnz) + 65536 -- nothing in it is proportional to
+ * num_rows * dim.  In order, each part padded to 256 bytes: the 64-bit step counter, U, byte flags [num_rows], fp32 acc
+ * [cap, dim], then cidx, the scan's counts (one per CE_COMPACT_BLOCK slots), list and the rewritten slots / keys.  Zero-filled
+ * by its owner once; every call leaves the counter counting the calls, the flags and acc zero; the rest needs no
+ * initialising.  The layout depends on (num_rows, nnz, dim): before a workspace serves another triple its owner
+ * zero-fills it again (the counter may be kept). */
+#define CE_COMPACT_BLOCK 4096
+size_t ce_bag_backward_update_compact_workspace(int64_t num_rows, int64_t nnz, int32_t dim);
+int ce_bag_backward_update_compact(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                   const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                   int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                   int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                   const uint64_t* presorted, const int32_t* row_of_slot, float* momentum,
+                                   int64_t momentum_rows, float lr, float eps, int32_t optimizer, int32_t rounding,
+                                   uint64_t seed, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_update_compact_src(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
+                                       const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                       const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                       float eps, int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                       size_t workspace_bytes, ce_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6].  Device state arrays are owned by the caller (so the Python
  * mirror can expose them as tensors: cached_idx_map, inverted_cached_idx, idx_map,
