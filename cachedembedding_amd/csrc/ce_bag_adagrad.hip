@@ -1,214 +1,43 @@
-// Fused exact row-wise Adagrad for the cached table (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0; the
-// reference's baseline maps --adagrad to it: baselines/dlrm_main.py:698-702).  Per step and per UNIQUE row r looked up:
+// Fused optimizer updates of the cached table: exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0;
+// the reference's baseline maps --adagrad to it: baselines/dlrm_main.py:698-702) on fp32, bf16 and fp16 rows, and SGD
+// on bf16 / fp16 rows.  Per step and per UNIQUE row r looked up:
 //   g = sum of the step's gradient rows of r ;  m[r] += sum_d g[d]^2 / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps)
-// "Exact": the non-linear update sees the row's whole gradient of the batch, so duplicate lookups are folded across
-// the whole batch first.  Three launches, no host synchronisation, no allocation, shapes fixed by the inputs (the
-// backward can be captured into a hipGraph):
-//   1. k_adagrad_mark_*: flags[slot] = 1 for every slot the step looks up (plain byte stores; racing writers all store
-//      the same value);
-//   2. the existing dense backward (ce_bag_backward_dense* / the key-streaming k_bag_bwd_stream) scatters the step's
-//      gradient into acc[slot] -- fp32 [num_rows, D], runs folded in registers and one atomic row update per run;
-//   3. k_adagrad_apply: a wave reads 64 flags at once, and a lane group per flagged slot reads acc, reduces sum g^2
-//      across its lanes, updates m[row_of_slot[slot]] and W[slot], and writes acc and the flag back to zero.
-// The workspace (acc + flags) is zero-filled by its owner once and left zero-filled by every call, so no memset runs
-// between steps.  The momentum is indexed by host-table row (row_of_slot = cached_idx_map) and never moves with the
-// cache; a slot maps to one row for the whole step, so folding by slot is folding by row.
+// (SGD: W[r] -= lr * g).  "Exact": the non-linear update sees the row's whole gradient of the batch, so duplicate
+// lookups are folded across the whole batch first.  Three ways to fold:
+//   * cache-sized accumulator (ce_bag_backward_rowwise_adagrad*, ce_bag_backward_update*_w16): k_mark_* flags the
+//     step's slots, the dense backward (ce_bag.hip) scatters into acc[num_rows, D] by atomics, k_rows_apply walks the
+//     flags and updates every flagged slot;
+//   * step-sized accumulator (ce_bag_backward_update_compact*): the flagged slots are numbered first, the
+//     same backward scatters into acc[min(nnz, num_rows), D], k_compact_apply walks the list;
+//   * deterministic, no accumulator (ce_bag_backward_update_sorted): the lookups are sorted by row and
+//     k_sorted_fold / k_sorted_combine fold a row's gradient in registers, in lookup order.
+// The two atomic forms hand a row's folded gradient to update_row(), which holds the whole arithmetic of the update --
+// spelled out, with contraction off -- so they agree bit for bit by construction; tests/test_gpu_fused_update_bits.py
+// pins those bits.  The sorted form keeps its own copy of the update (sorted_apply_row, its own walk, its own checks in
+// the entry): DESIGN.md 3.5 says why.  No host synchronisation, no allocation, launch shapes fixed by the arguments (a
+// backward can be captured into a hipGraph).  The momentum is indexed by host-table row (row_of_slot = cached_idx_map)
+// and never moves with the cache; a slot maps to one row for the whole step, so folding by slot is folding by row.
 #include "ce_common.h"
 
 namespace ce {
 
-struct AdagradArgs {
-  float* weight;             // [num_rows, D]
-  float* acc;                // [num_rows, D], zero outside a call
-  uint8_t* flags;            // [num_rows], zero outside a call
-  const int32_t* row_of_slot;  // NULL: momentum is indexed by slot
-  float* momentum;           // [momentum_rows]
-  int64_t momentum_rows;
-  uint32_t num_rows;
-  int32_t rowlen;            // vector chunks per row
-  int32_t g_log2;            // log2(lanes per row)
-  int32_t dim;
-  float lr;
-  float eps;
-};
-
-__global__ __launch_bounds__(256) void k_adagrad_mark_slots(const int64_t* __restrict__ slots, int64_t n,
-                                                            uint32_t num_rows, uint8_t* __restrict__ flags) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int64_t s = slots[i];
-    if (s >= 0 && s < (int64_t)num_rows) flags[s] = 1;
-  }
-}
-
-// source-row keys (row << 32 | grad_out row); row 0xffffffff = ignored lookup / padding of the last segment
-__global__ __launch_bounds__(256) void k_adagrad_mark_keys(const unsigned long long* __restrict__ keys, int64_t n,
-                                                           uint32_t num_rows, uint8_t* __restrict__ flags) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint32_t s = (uint32_t)(keys[i] >> 32);
-    if (s < num_rows) flags[s] = 1;
-  }
-}
-
-__device__ __forceinline__ float sq_sum(float v) { return v * v; }
-__device__ __forceinline__ float sq_sum(f32x4 v) { return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
-
-// one wave per 64 consecutive slots (grid-stride); the flagged ones are handed to the wave's lane groups in rounds
-template <typename VT, int NCH>
-__global__ __launch_bounds__(256) void k_adagrad_apply(AdagradArgs a) {
-  const int G = 1 << a.g_log2;
-  const int lane = threadIdx.x & 63;
-  const int q = lane >> a.g_log2;            // lane group within the wave
-  const int gl = lane & (G - 1);
-  const int ngw = 64 >> a.g_log2;            // lane groups per wave
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  VT* W = (VT*)a.weight;
-  VT* A = (VT*)a.acc;
-  for (int64_t base = wave * 64; base < (int64_t)a.num_rows; base += nwaves * 64) {
-    const int64_t mine = base + lane;
-    const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
-    unsigned long long m = __ballot(flagged);
-    while (m) {
-      unsigned long long mm = m;
-      for (int k = 0; k < q; ++k) mm &= mm - 1;          // this group's slot: the q-th lowest flagged one
-      for (int k = 0; k < ngw; ++k) m &= m - 1;          // the round's slots leave the wave's mask
-      if (mm == 0) continue;
-      const int64_t s = base + (__ffsll((long long)mm) - 1);
-      VT g[NCH];
-      float ss = 0.f;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int idx = gl + c * G;
-        g[c] = idx < a.rowlen ? A[s * a.rowlen + idx] : vzero<VT>();
-        ss += sq_sum(g[c]);
-      }
-      for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, G);
-      const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
-      if (r >= 0 && r < a.momentum_rows) {
-        const float mr = a.momentum[r] + ss / (float)a.dim;
-        const float mult = a.lr / (sqrtf(mr) + a.eps);
-        if (gl == 0) a.momentum[r] = mr;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int idx = gl + c * G;
-          if (idx < a.rowlen) W[s * a.rowlen + idx] = W[s * a.rowlen + idx] - g[c] * mult;
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int idx = gl + c * G;
-        if (idx < a.rowlen) A[s * a.rowlen + idx] = vzero<VT>();
-      }
-    }
-    if (flagged) a.flags[mine] = 0;
-  }
-}
-
-struct AdagradWs {
-  float* acc;
-  uint8_t* flags;
-  size_t bytes;
-};
-
-static AdagradWs carve_adagrad(void* ws, int64_t num_rows, int32_t dim) {
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  AdagradWs w{};
-  char* p = (char*)ws;
-  size_t o = 0;
-  w.acc = (float*)(p + o);    o = al(o + (size_t)num_rows * dim * 4);
-  w.flags = (uint8_t*)(p + o); o = al(o + (size_t)num_rows);
-  w.bytes = o;
-  return w;
-}
-
-// everything the two entries can refuse, BEFORE their first launch: the workspace stays zero-filled on every error.
-// The row geometry is asked for with the weakest alignment of the three launches' (weight, acc -- 256-byte aligned
-// by carve_adagrad -- and grad_out): a dim that fits the scalar form fits the vector form.
-static int adagrad_check(float* weight, int64_t num_rows, int32_t dim, const void* grad_out, int act, float* momentum,
-                         int64_t momentum_rows, float lr, float eps, void* workspace, size_t workspace_bytes) {
-  CE_REQUIRE(weight && grad_out && momentum && workspace, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  CE_REQUIRE(dim > 0, CE_ERR_INVALID, "dim must be positive");
-  CE_REQUIRE(momentum_rows > 0, CE_ERR_INVALID, "momentum_rows must be positive");
-  CE_REQUIRE(lr >= 0.f && eps > 0.f, CE_ERR_INVALID, "lr must be >= 0 and eps > 0");
-  CE_REQUIRE(workspace_bytes >= carve_adagrad(nullptr, num_rows, dim).bytes, CE_ERR_INVALID, "workspace too small");
-  CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
-  RowGeom r;
-  return row_geometry(dim, al16(weight) && act_aligned(grad_out, act), r);
-}
-
-static int launch_apply(float* weight, int64_t num_rows, int32_t dim, const int32_t* row_of_slot, float* momentum,
-                        int64_t momentum_rows, float lr, float eps, const AdagradWs& ws, hipStream_t s) {
-  RowGeom r;
-  int rc = row_geometry(dim, al16(weight), r);
-  if (rc) return rc;
-  AdagradArgs a{};
-  a.weight = weight;
-  a.acc = ws.acc;
-  a.flags = ws.flags;
-  a.row_of_slot = row_of_slot;
-  a.momentum = momentum;
-  a.momentum_rows = momentum_rows;
-  a.num_rows = (uint32_t)num_rows;
-  a.rowlen = r.rowlen;
-  a.g_log2 = r.g_log2;
-  a.dim = dim;
-  a.lr = lr;
-  a.eps = eps;
-  const dim3 g(grid_for(cdiv(num_rows, 64), 4)), b(256);
-  for_lanes(r.vec, r.nch, [&](auto l) {
-    hipLaunchKernelGGL((k_adagrad_apply<typename decltype(l)::VT, decltype(l)::NCH>), g, b, 0, s, a);
-  });
-  CE_LAUNCH_CHECK();
-  return CE_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// 16-bit table (bf16 / fp16 rows): the same three launches for SGD as well.  fp32 atomics cannot land on 16-bit rows
-// and a 16-bit atomic per partial sum would round once per lookup, so the step's gradient is folded into the fp32
-// accumulator and k_rows_apply_w16 rounds the row ONCE: w = up(W16[s]) (exact), x = the fp32 update, W16[s] = round(x).
-// The workspace is carve_adagrad's plus one 64-bit step counter: one thread of the mark kernel -- the first launch of
-// the sequence -- adds one to it, the apply pass reads it, so a replayed graph draws fresh random bits every step.
+// The update of one row
 
-struct W16Args {
-  void* weight;              // [num_rows, D] of WT
-  float* acc;
-  uint8_t* flags;
-  const unsigned long long* counter;
-  const int32_t* row_of_slot;
-  float* momentum;
+// what update_row reads: the argument structs of the atomic forms' kernels embed it
+struct UpdateArgs {
+  void* weight;                       // [num_rows, D] of WT
+  const int32_t* row_of_slot;         // NULL: momentum is indexed by slot
+  float* momentum;                    // [momentum_rows]
   int64_t momentum_rows;
-  uint64_t seed;
-  uint32_t num_rows;
-  int32_t rowlen;            // f32x4 chunks per row
-  int32_t g_log2;
+  uint64_t seed;                      // stochastic rounding only, as the step counter
+  const unsigned long long* counter;
+  int32_t rowlen;                     // chunks per row
+  int32_t g_log2;                     // log2(lanes per row)
   int32_t dim;
   float lr;
   float eps;
 };
-
-__global__ __launch_bounds__(256) void k_w16_mark_slots(const int64_t* __restrict__ slots, int64_t n, uint32_t num_rows,
-                                                        uint8_t* __restrict__ flags, unsigned long long* counter) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int64_t s = slots[i];
-    if (s >= 0 && s < (int64_t)num_rows) flags[s] = 1;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_w16_mark_keys(const unsigned long long* __restrict__ keys, int64_t n,
-                                                       uint32_t num_rows, uint8_t* __restrict__ flags,
-                                                       unsigned long long* counter) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint32_t s = (uint32_t)(keys[i] >> 32);
-    if (s < num_rows) flags[s] = 1;
-  }
-}
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -236,156 +65,200 @@ __device__ __forceinline__ f16_t round_stochastic(float x, uint32_t rnd, f16_t) 
   return (f16_t)__uint_as_float(t);
 }
 
-// the same walk over the flags as k_adagrad_apply: one wave per 64 slots, a ballot, one lane group per flagged slot
-template <typename WT, int NCH, bool ADAGRAD, bool STOCH>
-__global__ __launch_bounds__(256) void k_rows_apply_w16(W16Args a) {
-  using T = Act<WT, f32x4>;
-  const int G = 1 << a.g_log2;
-  const int lane = threadIdx.x & 63;
-  const int q = lane >> a.g_log2;
-  const int gl = lane & (G - 1);
-  const int ngw = 64 >> a.g_log2;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  typename T::V* W = (typename T::V*)a.weight;
-  f32x4* A = (f32x4*)a.acc;
-  uint64_t step_key = 0;
-  if (STOCH) step_key = mix64(a.seed + 0xD6E8FEB86659FD93ull * *a.counter);
-  for (int64_t base = wave * 64; base < (int64_t)a.num_rows; base += nwaves * 64) {
-    const int64_t mine = base + lane;
-    const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
-    unsigned long long m = __ballot(flagged);
-    while (m) {
-      unsigned long long mm = m;
-      for (int k = 0; k < q; ++k) mm &= mm - 1;
-      for (int k = 0; k < ngw; ++k) m &= m - 1;
-      if (mm == 0) continue;
-      const int64_t s = base + (__ffsll((long long)mm) - 1);
-      f32x4 g[NCH];
-      float ss = 0.f;
+// Sum of a lane's squares, SPELLED OUT: this is the specification, not a reading of what a compiler
+// made of `ss += x^2 + y^2 + z^2 + w^2`.  A chunk's four squares are either rounded one by one and added ("plain":
+// ((x^2 + y^2) + z^2) + w^2) or folded into a chain of fused multiply-adds ("chain": fma(w, w, fma(z, z, fma(x, x,
+// y * y)))).  fp32 table: the lane's LAST chunk plain, the chunks before it chains; 16-bit table: chains only; scalar
+// lanes: one chain over the lane's elements, started by the second one (g1 * g1, then fma g0, g2, g3).  Chunk sums are
+// added in chunk order.
+__device__ __forceinline__ float sq_plain(f32x4 v) {
+#pragma clang fp contract(off)
+  const float xx = v.x * v.x, yy = v.y * v.y, zz = v.z * v.z, ww = v.w * v.w;
+  return ((xx + yy) + zz) + ww;
+}
+__device__ __forceinline__ float sq_chain(f32x4 v) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(v.w, v.w, __builtin_fmaf(v.z, v.z, __builtin_fmaf(v.x, v.x, v.y * v.y)));
+}
+template <typename WT, int NCH>
+__device__ __forceinline__ float lane_sq_sum(const f32x4 (&g)[NCH]) {
+#pragma clang fp contract(off)
+  constexpr bool w32 = std::is_same<WT, float>::value;
+  float ss = (w32 && NCH == 1) ? sq_plain(g[0]) : sq_chain(g[0]);
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int idx = gl + c * G;
-        g[c] = idx < a.rowlen ? A[s * a.rowlen + idx] : vzero<f32x4>();
-        ss += sq_sum(g[c]);
-      }
-      const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
-      float mult = a.lr;
-      bool update = true;
-      if (ADAGRAD) {
-        for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, G);
-        update = r >= 0 && r < a.momentum_rows;
-        if (update) {
-          const float mr = a.momentum[r] + ss / (float)a.dim;
-          mult = a.lr / (sqrtf(mr) + a.eps);
-          if (gl == 0) a.momentum[r] = mr;
-        }
-      }
-      if (update) {
-        uint64_t row_key = 0;
-        if (STOCH) row_key = mix64(step_key ^ (uint64_t)r);
+  for (int c = 1; c < NCH; ++c) ss = ss + ((w32 && c == NCH - 1) ? sq_plain(g[c]) : sq_chain(g[c]));
+  return ss;
+}
+template <typename WT, int NCH>
+__device__ __forceinline__ float lane_sq_sum(const float (&g)[NCH]) {
+#pragma clang fp contract(off)
+  // as in sq_chain, the SECOND square is the one rounded on its own and the first is fused onto it
+  if (NCH == 1) return g[0] * g[0];
+  float ss = __builtin_fmaf(g[0], g[0], g[NCH > 1 ? 1 : 0] * g[NCH > 1 ? 1 : 0]);
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int idx = gl + c * G;
-          if (idx < a.rowlen) {
-            const f32x4 x = T::up(W[s * a.rowlen + idx]) - g[c] * mult;
-            if (STOCH) {
-              const uint64_t h = mix64(row_key + (uint64_t)idx);     // 16 bits for each of the chunk's 4 elements
-              typename T::V o;
-              o.x = round_stochastic(x.x, (uint32_t)h, WT{});
-              o.y = round_stochastic(x.y, (uint32_t)(h >> 16), WT{});
-              o.z = round_stochastic(x.z, (uint32_t)(h >> 32), WT{});
-              o.w = round_stochastic(x.w, (uint32_t)(h >> 48), WT{});
-              W[s * a.rowlen + idx] = o;
-            } else {
-              W[s * a.rowlen + idx] = T::down(x);
-            }
-          }
-        }
-      }
+  for (int c = 2; c < NCH; ++c) ss = __builtin_fmaf(g[c], g[c], ss);
+  return ss;
+}
+
+// w - g * m with ONE rounding per element
+__device__ __forceinline__ float fnma(float g, float m, float w) { return __builtin_fmaf(-g, m, w); }
+__device__ __forceinline__ f32x4 fnma(f32x4 g, float m, f32x4 w) {
+  return __builtin_elementwise_fma(-g, f32x4{m, m, m, m}, w);
+}
+
+// the key of a step's random bits (0 where nothing is rounded stochastically): the step counter lives in the workspace
+// and the first launch of the step adds one to it, so a replayed graph draws fresh bits every step
+template <bool STOCH> __device__ __forceinline__ uint64_t step_key(const UpdateArgs& a) {
+  return STOCH ? mix64(a.seed + 0xD6E8FEB86659FD93ull * *a.counter) : 0;
+}
+
+// The whole update of the row in slot s from g, its folded gradient of the step (zero in chunks past rowlen), by the
+// row's lane group (lane gl of G; every lane of the group must be here: the reduction shuffles across it).
+//   adagrad: ss = sum of the group's lane_sq_sum (xor tree, widest stride first); r outside the momentum: nothing
+//            happens; m[r] = m[r] + ss / D (lane 0 writes); mult = lr / (sqrt(m[r]) + eps).   sgd: mult = lr.
+//   x = fma(-g, mult, up(W[s])) per element; W[s] = x (fp32), nearest(x), or round_stochastic(x, 16 bits of
+//   mix64(mix64(step_key ^ r) + chunk index) per element).
+template <typename VT, typename WT, int NCH, bool STOCH>
+__device__ __forceinline__ void update_row(const UpdateArgs& a, uint64_t step_key, int64_t s, const VT (&g)[NCH],
+                                           int gl, int G, bool adagrad) {
+#pragma clang fp contract(off)
+  using T = Act<WT, VT>;
+  static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
+  typename T::V* W = (typename T::V*)a.weight + s * a.rowlen;
+  const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
+  float mult = a.lr;
+  if (adagrad) {
+    float ss = lane_sq_sum<WT, NCH>(g);
+    for (int off = G >> 1; off > 0; off >>= 1) ss = ss + __shfl_xor(ss, off, G);
+    if (r < 0 || r >= a.momentum_rows) return;
+    const float mr = a.momentum[r] + ss / (float)a.dim;
+    mult = a.lr / (sqrtf(mr) + a.eps);
+    if (gl == 0) a.momentum[r] = mr;
+  }
+  uint64_t row_key = 0;
+  if (STOCH) row_key = mix64(step_key ^ (uint64_t)r);
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int idx = gl + c * G;
-        if (idx < a.rowlen) A[s * a.rowlen + idx] = vzero<f32x4>();
-      }
+  for (int c = 0; c < NCH; ++c) {
+    const int idx = gl + c * G;
+    if (idx >= a.rowlen) continue;
+    const VT x = fnma(g[c], mult, T::up(W[idx]));
+    if constexpr (STOCH) {
+      const uint64_t h = mix64(row_key + (uint64_t)idx);         // 16 bits for each of the chunk's 4 elements
+      typename T::V o;
+      o.x = round_stochastic(x.x, (uint32_t)h, WT{});
+      o.y = round_stochastic(x.y, (uint32_t)(h >> 16), WT{});
+      o.z = round_stochastic(x.z, (uint32_t)(h >> 32), WT{});
+      o.w = round_stochastic(x.w, (uint32_t)(h >> 48), WT{});
+      W[idx] = o;
+    } else {
+      W[idx] = T::down(x);
     }
-    if (flagged) a.flags[mine] = 0;
   }
 }
 
-struct W16Ws {
-  AdagradWs base;
-  unsigned long long* counter;
-  size_t bytes;
+// a lane's chunks of one row of an fp32 buffer: read (zero past rowlen), and written back as zero
+template <typename VT, int NCH>
+__device__ __forceinline__ void load_row(VT (&g)[NCH], const VT* row, int gl, int G, int rowlen) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) g[c] = gl + c * G < rowlen ? row[gl + c * G] : vzero<VT>();
+}
+template <typename VT, int NCH> __device__ __forceinline__ void zero_row(VT* row, int gl, int G, int rowlen) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    if (gl + c * G < rowlen) row[gl + c * G] = vzero<VT>();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The wave walk: one wave per 64 consecutive positions (grid-stride), the positions that hold work handed to the
+// wave's lane groups in rounds.
+
+struct LaneGroup {
+  int G, lane, q, gl, ngw;            // lanes per group; lane in the wave; group in the wave; lane in the group; groups
+  int64_t wave, nwaves;
+};
+__device__ __forceinline__ LaneGroup lane_group(int g_log2) {
+  LaneGroup l;
+  l.G = 1 << g_log2;
+  l.lane = threadIdx.x & 63;
+  l.q = l.lane >> g_log2;
+  l.gl = l.lane & (l.G - 1);
+  l.ngw = 64 >> g_log2;
+  l.wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  l.nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  return l;
+}
+
+// body(i) once for every lane i of the wave whose `pred` is set, run by a whole lane group: group q takes the q-th
+// lowest set bit, the round's ngw bits leave the mask, and the lanes of a group that got no bit skip the body (so a
+// sub-wave shuffle inside it sees whole groups).  Every lane of the wave must call this.  The body captures BY VALUE:
+// by reference the kernel's locals are reached through the closure, which costs registers.
+template <typename F> __device__ __forceinline__ void for_each_flagged(bool pred, const LaneGroup& l, F&& body) {
+  unsigned long long m = __ballot(pred);
+  while (m) {
+    unsigned long long mm = m;
+    for (int k = 0; k < l.q; ++k) mm &= mm - 1;
+    for (int k = 0; k < l.ngw; ++k) m &= m - 1;
+    if (mm == 0) continue;
+    body(__ffsll((long long)mm) - 1);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Cache-sized accumulator.  The workspace (acc + flags, zero-filled by its owner once and left zero-filled by every
+// call, so no memset runs between steps) and, for a 16-bit table, one 64-bit step counter behind it.  fp32 atomics
+// cannot land on 16-bit rows and a 16-bit atomic per partial sum would round once per lookup, so there the step's
+// gradient is folded into the fp32 accumulator as well and the row is rounded ONCE.
+
+// flags[slot] = 1 for every slot the step looks up (plain byte stores; racing writers all store the same value); the
+// first launch of a step also counts it (counter: NULL where nothing reads it, an fp32 table)
+__global__ __launch_bounds__(256) void k_mark_slots(const int64_t* __restrict__ slots, int64_t n, uint32_t num_rows,
+                                                    uint8_t* __restrict__ flags, unsigned long long* counter) {
+  if (counter && blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t s = slots[i];
+    if (s >= 0 && s < (int64_t)num_rows) flags[s] = 1;
+  }
+}
+
+// source-row keys (row << 32 | grad_out row); row 0xffffffff = ignored lookup / padding of the last segment
+__global__ __launch_bounds__(256) void k_mark_keys(const unsigned long long* __restrict__ keys, int64_t n,
+                                                   uint32_t num_rows, uint8_t* __restrict__ flags,
+                                                   unsigned long long* counter) {
+  if (counter && blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint32_t s = (uint32_t)(keys[i] >> 32);
+    if (s < num_rows) flags[s] = 1;
+  }
+}
+
+struct ApplyArgs {
+  UpdateArgs u;
+  float* acc;                // [num_rows, D], zero outside a call
+  uint8_t* flags;            // [num_rows], zero outside a call
+  uint32_t num_rows;
 };
 
-static W16Ws carve_w16(void* ws, int64_t num_rows, int32_t dim) {
-  W16Ws w{};
-  w.base = carve_adagrad(ws, num_rows, dim);
-  w.counter = (unsigned long long*)((char*)ws + w.base.bytes);
-  w.bytes = w.base.bytes + 256;
-  return w;
-}
-
-// everything the two update entries can refuse, before their first launch (arguments alone: no launch, no HIP call)
-static int w16_update_check(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, const void* grad_out,
-                            int act, float* momentum, int64_t momentum_rows, float lr, float eps, int32_t optimizer,
-                            int32_t rounding, void* workspace, size_t workspace_bytes) {
-  CE_REQUIRE_ACT(act);
-  int rc = w16_check(weight_dtype, dim);
-  if (rc) return rc;
-  CE_REQUIRE(optimizer == CE_OPT_SGD || optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_INVALID,
-             "unknown optimizer %d (CE_OPT_SGD / CE_OPT_ROWWISE_ADAGRAD)", (int)optimizer);
-  CE_REQUIRE(rounding == CE_ROUND_NEAREST || rounding == CE_ROUND_STOCHASTIC, CE_ERR_INVALID,
-             "unknown rounding %d (CE_ROUND_NEAREST / CE_ROUND_STOCHASTIC)", (int)rounding);
-  CE_REQUIRE(weight && grad_out && workspace, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  CE_REQUIRE(lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
-  if (optimizer == CE_OPT_ROWWISE_ADAGRAD) {
-    CE_REQUIRE(momentum && momentum_rows > 0, CE_ERR_INVALID, "row-wise Adagrad needs its momentum");
-    CE_REQUIRE(eps > 0.f, CE_ERR_INVALID, "eps must be > 0");
+// a wave reads 64 flags at once, and a lane group per flagged slot reads acc, updates the row and writes acc and the
+// flag back to zero
+template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH>
+__global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
+  const LaneGroup l = lane_group(a.u.g_log2);
+  VT* A = (VT*)a.acc;
+  const uint64_t key = step_key<STOCH>(a.u);
+  for (int64_t base = l.wave * 64; base < (int64_t)a.num_rows; base += l.nwaves * 64) {
+    const int64_t mine = base + l.lane;
+    const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
+    for_each_flagged(flagged, l, [=](int i) {
+      const int64_t s = base + i;
+      VT g[NCH];
+      load_row(g, A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
+      update_row<VT, WT, NCH, STOCH>(a.u, key, s, g, l.gl, l.G, ADAGRAD);
+      zero_row<VT, NCH>(A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
+    });
+    if (flagged) a.flags[mine] = 0;
   }
-  CE_REQUIRE(workspace_bytes >= carve_w16(nullptr, num_rows, dim).bytes, CE_ERR_INVALID, "workspace too small");
-  CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
-  CE_REQUIRE(al16(weight), CE_ERR_INVALID, "a 16-bit table must be 16-byte aligned");
-  // the scatter into acc takes the vector or the scalar form by grad_out's alignment; both must fit the dim
-  RowGeom r;
-  return row_geometry(dim, act_aligned(grad_out, act), r);
-}
-
-static int launch_apply_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
-                            const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr, float eps,
-                            int32_t optimizer, int32_t rounding, uint64_t seed, const W16Ws& ws, hipStream_t s) {
-  RowGeom r;
-  int rc = row_geometry(dim, true, r);
-  if (rc) return rc;
-  W16Args a{};
-  a.weight = weight;
-  a.acc = ws.base.acc;
-  a.flags = ws.base.flags;
-  a.counter = ws.counter;
-  a.row_of_slot = row_of_slot;
-  a.momentum = momentum;
-  a.momentum_rows = momentum_rows;
-  a.seed = seed;
-  a.num_rows = (uint32_t)num_rows;
-  a.rowlen = r.rowlen;
-  a.g_log2 = r.g_log2;
-  a.dim = dim;
-  a.lr = lr;
-  a.eps = eps;
-  const dim3 g(grid_for(cdiv(num_rows, 64), 4)), b(256);
-  const bool ada = optimizer == CE_OPT_ROWWISE_ADAGRAD, st = rounding == CE_ROUND_STOCHASTIC;
-  for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
-    using WT = typename decltype(w)::AT;
-    constexpr int N = decltype(l)::NCH;
-    if (ada && st) hipLaunchKernelGGL((k_rows_apply_w16<WT, N, true, true>), g, b, 0, s, a);
-    else if (ada) hipLaunchKernelGGL((k_rows_apply_w16<WT, N, true, false>), g, b, 0, s, a);
-    else if (st) hipLaunchKernelGGL((k_rows_apply_w16<WT, N, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_rows_apply_w16<WT, N, false, false>), g, b, 0, s, a);
-  });
-  CE_LAUNCH_CHECK();
-  return CE_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -398,9 +271,7 @@ static int launch_apply_w16(void* weight, int32_t weight_dtype, int64_t num_rows
 // Partial rows: the chunk that starts at sorted position p takes row 2 * (p / 64) + (first chunk of its run).  Runs
 // that own partial rows are longer than 64, so an aligned block of 64 positions holds at most one run start of that
 // kind and at most one later chunk start: 2 * ceil(nnz / 64) rows, no compaction, no counter.
-// The update is k_adagrad_apply's / k_rows_apply_w16's: the same lane-group shape, the same reduction tree, the same
-// expressions, so a row looked up once gets the same bits.  A 16-bit row is stored with the nearest cast;
-// CE_ROUND_STOCHASTIC on a 16-bit table is refused by the entry.
+// A 16-bit row is stored with the nearest cast; CE_ROUND_STOCHASTIC on a 16-bit table is refused by the entry.
 static_assert(CE_SORTED_CHUNK == 64, "the partial-row numbering and the wave walk assume 64 positions per chunk");
 
 struct SortedArgs {
@@ -439,50 +310,12 @@ __device__ __forceinline__ int64_t run_start(const int32_t* __restrict__ rows, i
   return hi;
 }
 
-// sum of a lane's squares, SPELLED OUT.  `ss += sq_sum(g[c])` is one expression in k_adagrad_apply and k_rows_apply_w16,
-// but under -ffp-contract=fast the compiler rounds it differently per instantiation: a chunk's four squares are either
-// rounded one by one and added ("plain": ((x^2 + y^2) + z^2) + w^2) or folded into a chain of fused multiply-adds
-// ("chain": fma(w, w, fma(z, z, fma(x, x, y * y)))).  A row looked up once must get the bits of those kernels, so the
-// form each of them compiled to (read off their ISA) is written here with contraction off and explicit
-// fmas, which also keeps the two kernels below from drifting apart.  fp32 table: the lane's LAST chunk plain, the
-// chunks before it chains; 16-bit table: chains only; scalar lanes: one chain over the lane's elements, started by the
-// second one (g1 * g1, then fma g0, g2, g3).  Chunk sums
-// are added in chunk order.
-__device__ __forceinline__ float sq_plain(f32x4 v) {
-#pragma clang fp contract(off)
-  const float xx = v.x * v.x, yy = v.y * v.y, zz = v.z * v.z, ww = v.w * v.w;
-  return ((xx + yy) + zz) + ww;
-}
-__device__ __forceinline__ float sq_chain(f32x4 v) {
-#pragma clang fp contract(off)
-  return __builtin_fmaf(v.w, v.w, __builtin_fmaf(v.z, v.z, __builtin_fmaf(v.x, v.x, v.y * v.y)));
-}
-template <typename WT, int NCH>
-__device__ __forceinline__ float sorted_sq_sum(const f32x4 (&g)[NCH]) {
-#pragma clang fp contract(off)
-  constexpr bool w32 = std::is_same<WT, float>::value;
-  float ss = (w32 && NCH == 1) ? sq_plain(g[0]) : sq_chain(g[0]);
-#pragma unroll
-  for (int c = 1; c < NCH; ++c) ss = ss + ((w32 && c == NCH - 1) ? sq_plain(g[c]) : sq_chain(g[c]));
-  return ss;
-}
-template <typename WT, int NCH>
-__device__ __forceinline__ float sorted_sq_sum(const float (&g)[NCH]) {
-#pragma clang fp contract(off)
-  // as in sq_chain, the SECOND square is the one rounded on its own and the first is fused onto it
-  if (NCH == 1) return g[0] * g[0];
-  float ss = __builtin_fmaf(g[0], g[0], g[NCH > 1 ? 1 : 0] * g[NCH > 1 ? 1 : 0]);
-#pragma unroll
-  for (int c = 2; c < NCH; ++c) ss = __builtin_fmaf(g[c], g[c], ss);
-  return ss;
-}
-
 // the update of one row by its lane group: g = the row's whole gradient of the step (zero in chunks past rowlen)
 template <typename VT, typename WT, int NCH>
 __device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s, const VT (&g)[NCH], int gl, int G) {
   using T = Act<WT, VT>;
   typename T::V* W = (typename T::V*)a.weight;
-  float ss = sorted_sq_sum<WT, NCH>(g);
+  float ss = lane_sq_sum<WT, NCH>(g);
   const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
   float mult = a.lr;
   bool update = true;
@@ -504,7 +337,7 @@ __device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s,
 }
 
 // one wave per 64 consecutive sorted positions (grid-stride): every lane finds out whether its position starts a chunk,
-// the chunk heads are handed to the wave's lane groups in rounds (the walk of k_adagrad_apply)
+// the chunk heads are handed to the wave's lane groups in rounds (the walk for_each_flagged wraps, written out)
 template <typename VT, typename AT, typename WT, int NCH>
 __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
   using TA = Act<AT, VT>;
@@ -630,37 +463,17 @@ __global__ __launch_bounds__(256) void k_sorted_combine(SortedArgs a) {
   }
 }
 
-// workspace: the sort arrays, then the partial rows; nothing in it needs initialising
-struct SortedWs {
-  void* sort;
-  float* partials;
-  size_t bytes;
-};
-
-static SortedWs carve_sorted(void* ws, int64_t nnz, int32_t dim) {
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const int64_t n = nnz < 1 ? 1 : nnz;
-  SortedWs w{};
-  char* p = (char*)ws;
-  size_t o = 0;
-  w.sort = p + o;                           o = al(o + sorted_rows_bytes(n));
-  w.partials = (float*)(p + o);             o = al(o + (size_t)(2 * cdiv(n, CE_SORTED_CHUNK)) * (size_t)dim * 4);
-  w.bytes = o;
-  return w;
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------
-// Step-sized accumulator (ce_bag_backward_update_compact*).  The atomic updates above fold the step's
+// Step-sized accumulator (ce_bag_backward_update_compact*).  The cache-sized form folds the step's
 // gradient into acc[num_rows, D]; a step touches at most cap = min(nnz, num_rows) distinct slots, so here the flagged
 // slots are numbered 0 .. U-1 in ascending order and the SAME dense backward scatters into acc[cap, D] through the
 // renumbered indices / keys.  One stream, no host synchronisation, no allocation, launch shapes fixed by the arguments
 // (U stays on the device and is read by the apply kernel):
-//   1. k_adagrad_mark_* / k_w16_mark_* (unchanged): flags[slot] = 1, the 16-bit path's step counter += 1;
+//   1. k_mark_*: flags[slot] = 1, the step counter += 1 (a 16-bit table);
 //   2. k_compact_count + k_compact_emit: list[u] = the u-th flagged slot, cidx[slot] = u, U; the flags go back to zero;
 //   3. k_compact_remap_slots / _keys: slots -> cidx[slot] (-1 outside [0, num_rows)), row << 32 | x -> cidx[row] << 32 | x;
 //   4. ce_bag_backward_dense_act / _dense_src_act (unchanged) into acc[cap, D] with num_rows = cap;
-//   5. k_compact_apply: a lane group per u < U updates W[list[u]] / momentum[row_of_slot[list[u]]] and zeroes acc[u].
+//   5. k_compact_apply: a lane group per u < U updates the row in slot list[u] and zeroes acc[u].
 // cidx is written for flagged slots only and read for flagged slots only (a lookup the remap reads was marked in this
 // call), so it is never initialised and never cleared; list and the remap buffer likewise.
 constexpr int kCompactRounds = 16;                                   // 64-slot ballots per wave
@@ -775,92 +588,77 @@ __global__ __launch_bounds__(256) void k_compact_remap_keys(const unsigned long 
 }
 
 struct CompactArgs {
-  void* weight;              // [num_rows, D] of WT
+  UpdateArgs u;
   float* acc;                // [cap, D], zero outside a call
   const int32_t* list;       // [cap]: list[u] = the u-th flagged slot
   const int32_t* n_list;     // U, written by k_compact_emit
-  const unsigned long long* counter;
-  const int32_t* row_of_slot;
-  float* momentum;
-  int64_t momentum_rows;
-  uint64_t seed;
-  int32_t rowlen;
-  int32_t g_log2;
-  int32_t dim;
   int32_t adagrad;
-  float lr;
-  float eps;
 };
 
-// one lane group per list entry (grid-stride over u < U; the grid is sized by cap).  The update is k_adagrad_apply's /
-// k_rows_apply_w16's: the same lane-group shape and reduction tree, the sum of squares in the form those kernels
-// compiled to (sorted_sq_sum), the same expressions for the row and the random bits of a stochastically rounded SGD
-// step -- given the same acc row, the same bits.
+// one lane group per list entry (grid-stride over u < U; the grid is sized by cap)
 template <typename VT, typename WT, int NCH, bool STOCH>
 __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
-  using T = Act<WT, VT>;
-  static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
-  const int G = 1 << a.g_log2;
+  const int G = 1 << a.u.g_log2;
   const int gl = threadIdx.x & (G - 1);
-  const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.g_log2;
-  const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) >> a.g_log2;
-  typename T::V* W = (typename T::V*)a.weight;
+  const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.u.g_log2;
+  const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) >> a.u.g_log2;
   VT* A = (VT*)a.acc;
   const int64_t n = *a.n_list;
-  uint64_t step_key = 0;
-  if (STOCH) step_key = mix64(a.seed + 0xD6E8FEB86659FD93ull * *a.counter);
+  const uint64_t key = step_key<STOCH>(a.u);
   for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
-    const int64_t s = a.list[u];
     VT g[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int idx = gl + c * G;
-      g[c] = idx < a.rowlen ? A[u * a.rowlen + idx] : vzero<VT>();
-    }
-    const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
-    float mult = a.lr;
-    bool update = true;
-    if (a.adagrad) {
-      float ss = sorted_sq_sum<WT, NCH>(g);
-      for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, G);
-      update = r >= 0 && r < a.momentum_rows;
-      if (update) {
-        const float mr = a.momentum[r] + ss / (float)a.dim;
-        mult = a.lr / (sqrtf(mr) + a.eps);
-        if (gl == 0) a.momentum[r] = mr;
-      }
-    }
-    if (update) {
-      uint64_t row_key = 0;
-      if (STOCH) row_key = mix64(step_key ^ (uint64_t)r);
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int idx = gl + c * G;
-        if (idx < a.rowlen) {
-          const VT x = T::up(W[s * a.rowlen + idx]) - g[c] * mult;
-          if constexpr (STOCH) {
-            const uint64_t h = mix64(row_key + (uint64_t)idx);       // 16 bits for each of the chunk's 4 elements
-            typename T::V o;
-            o.x = round_stochastic(x.x, (uint32_t)h, WT{});
-            o.y = round_stochastic(x.y, (uint32_t)(h >> 16), WT{});
-            o.z = round_stochastic(x.z, (uint32_t)(h >> 32), WT{});
-            o.w = round_stochastic(x.w, (uint32_t)(h >> 48), WT{});
-            W[s * a.rowlen + idx] = o;
-          } else {
-            W[s * a.rowlen + idx] = T::down(x);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int idx = gl + c * G;
-      if (idx < a.rowlen) A[u * a.rowlen + idx] = vzero<VT>();
-    }
+    load_row(g, A + u * a.u.rowlen, gl, G, a.u.rowlen);
+    update_row<VT, WT, NCH, STOCH>(a.u, key, (int64_t)a.list[u], g, gl, G, a.adagrad);
+    zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
   }
 }
 
-// workspace: what must be zero outside a call (flags, acc) and the step counter, then what needs no initialising.
+// ---------------------------------------------------------------------------------------------------------------
+// Host side: the workspaces, the one check, the launches
+
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// cache-sized: acc, flags, and the step counter of a 16-bit table
+struct ApplyWs {
+  float* acc;
+  uint8_t* flags;
+  unsigned long long* counter;        // NULL for an fp32 table
+  size_t bytes;
+};
+
+static ApplyWs carve_apply(void* ws, int64_t num_rows, int32_t dim, bool w16) {
+  ApplyWs w{};
+  char* p = (char*)ws;
+  size_t o = 0;
+  w.acc = (float*)(p + o);     o = al256(o + (size_t)num_rows * dim * 4);
+  w.flags = (uint8_t*)(p + o); o = al256(o + (size_t)num_rows);
+  if (w16) {
+    w.counter = (unsigned long long*)(p + o);
+    o += 256;
+  }
+  w.bytes = o;
+  return w;
+}
+
+// sorted: the sort arrays, then the partial rows; nothing in it needs initialising
+struct SortedWs {
+  void* sort;
+  float* partials;
+  size_t bytes;
+};
+
+static SortedWs carve_sorted(void* ws, int64_t nnz, int32_t dim) {
+  const int64_t n = nnz < 1 ? 1 : nnz;
+  SortedWs w{};
+  char* p = (char*)ws;
+  size_t o = 0;
+  w.sort = p + o;                           o = al256(o + sorted_rows_bytes(n));
+  w.partials = (float*)(p + o);             o = al256(o + (size_t)(2 * cdiv(n, CE_SORTED_CHUNK)) * (size_t)dim * 4);
+  w.bytes = o;
+  return w;
+}
+
+// step-sized: what must be zero outside a call (flags, acc) and the step counter, then what needs no initialising.
 // The layout depends on num_rows, nnz and dim: a workspace serves ONE such triple (its owner zero-fills it again,
 // counter apart, before it serves another).
 struct CompactWs {
@@ -877,77 +675,152 @@ struct CompactWs {
 };
 
 static CompactWs carve_compact(void* ws, int64_t num_rows, int64_t nnz, int32_t dim) {
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   CompactWs w{};
   w.cap = nnz < num_rows ? nnz : num_rows;
   char* p = (char*)ws;
   size_t o = 0;
   w.counter = (unsigned long long*)(p + o);  o += 256;
   w.n_list = (int32_t*)(p + o);              o += 256;
-  w.flags = (uint8_t*)(p + o);               o = al(o + (size_t)num_rows);
-  w.acc = (float*)(p + o);                   o = al(o + (size_t)w.cap * dim * 4);
-  w.cidx = (int32_t*)(p + o);                o = al(o + (size_t)num_rows * 4);
-  w.blk_count = (int32_t*)(p + o);           o = al(o + (size_t)cdiv(num_rows, CE_COMPACT_BLOCK) * 4);
-  w.list = (int32_t*)(p + o);                o = al(o + (size_t)w.cap * 4);
-  w.remap = p + o;                           o = al(o + (size_t)ce_bag_presort_len(nnz) * 8);
+  w.flags = (uint8_t*)(p + o);               o = al256(o + (size_t)num_rows);
+  w.acc = (float*)(p + o);                   o = al256(o + (size_t)w.cap * dim * 4);
+  w.cidx = (int32_t*)(p + o);                o = al256(o + (size_t)num_rows * 4);
+  w.blk_count = (int32_t*)(p + o);           o = al256(o + (size_t)cdiv(num_rows, CE_COMPACT_BLOCK) * 4);
+  w.list = (int32_t*)(p + o);                o = al256(o + (size_t)w.cap * 4);
+  w.remap = p + o;                           o = al256(o + (size_t)ce_bag_presort_len(nnz) * 8);
   w.bytes = o;
   return w;
 }
 
-// everything the two entries can refuse, from the arguments alone: no launch and no HIP call before the last check
-static int compact_check(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
-                         const void* grad_out, int act, float* momentum, int64_t momentum_rows, float lr, float eps,
-                         int32_t optimizer, int32_t rounding, void* workspace, size_t workspace_bytes, RowGeom& r) {
-  CE_REQUIRE_ACT(act);
-  CE_REQUIRE(weight_dtype == CE_ACT_F32 || weight_dtype == CE_ACT_BF16 || weight_dtype == CE_ACT_F16, CE_ERR_INVALID,
-             "unknown weight_dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)weight_dtype);
-  const bool w16 = weight_dtype != CE_ACT_F32;
-  if (w16) {
-    int rc = w16_check(weight_dtype, dim);
-    if (rc) return rc;
-  }
-  CE_REQUIRE(optimizer == CE_OPT_SGD || optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_INVALID,
-             "unknown optimizer %d (CE_OPT_SGD / CE_OPT_ROWWISE_ADAGRAD)", (int)optimizer);
-  CE_REQUIRE(rounding == CE_ROUND_NEAREST || rounding == CE_ROUND_STOCHASTIC, CE_ERR_INVALID,
-             "unknown rounding %d (CE_ROUND_NEAREST / CE_ROUND_STOCHASTIC)", (int)rounding);
-  CE_REQUIRE(w16 || optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_UNSUPPORTED,
-             "CE_OPT_SGD on an fp32 table folds straight into the rows: it has no accumulator to compact");
-  CE_REQUIRE(!(w16 && optimizer == CE_OPT_ROWWISE_ADAGRAD && rounding == CE_ROUND_STOCHASTIC), CE_ERR_UNSUPPORTED,
-             "row-wise Adagrad with CE_ROUND_STOCHASTIC on a 16-bit table is not taken with the step-sized accumulator");
-  CE_REQUIRE(weight && grad_out && workspace, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(dim > 0, CE_ERR_INVALID, "dim must be positive");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  CE_REQUIRE(nnz >= 0 && nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "nnz out of range");
-  CE_REQUIRE(lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
-  if (optimizer == CE_OPT_ROWWISE_ADAGRAD) {
-    CE_REQUIRE(momentum && momentum_rows > 0, CE_ERR_INVALID, "row-wise Adagrad needs its momentum");
-    CE_REQUIRE(eps > 0.f, CE_ERR_INVALID, "eps must be > 0");
-  }
-  CE_REQUIRE(workspace_bytes >= carve_compact(nullptr, num_rows, nnz, dim).bytes, CE_ERR_INVALID,
-             "workspace too small");
-  CE_REQUIRE((((uintptr_t)workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
-  CE_REQUIRE(!w16 || al16(weight), CE_ERR_INVALID, "a 16-bit table must be 16-byte aligned");
-  // the scatter into acc takes the vector or the scalar form by grad_out's alignment, the apply pass by the table's
-  // (a 16-bit table: vector lanes only); a dim that fits the scalar form fits the vector form
-  RowGeom weakest;
-  int rc = row_geometry(dim, (w16 || al16(weight)) && act_aligned(grad_out, act), weakest);
-  if (rc) return rc;
-  return row_geometry(dim, w16 || al16(weight), r);
+// the arguments every update entry has (the fp32 Adagrad entries: CE_ACT_F32, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST)
+struct UpdateCall {
+  void* weight;
+  int32_t weight_dtype;
+  int64_t num_rows;
+  int32_t dim;
+  int64_t nnz;
+  const void* grad_out;
+  int32_t act;
+  const int32_t* row_of_slot;
+  float* momentum;
+  int64_t momentum_rows;
+  float lr, eps;
+  int32_t optimizer, rounding;
+  uint64_t seed;
+  void* workspace;
+  size_t workspace_bytes;
+  bool w16() const { return weight_dtype != CE_ACT_F32; }
+  bool adagrad() const { return optimizer == CE_OPT_ROWWISE_ADAGRAD; }
+  bool stochastic() const { return rounding == CE_ROUND_STOCHASTIC; }
+};
+
+static UpdateArgs update_args(const UpdateCall& c, const RowGeom& r, const unsigned long long* counter) {
+  UpdateArgs u{};
+  u.weight = c.weight;
+  u.row_of_slot = c.row_of_slot;
+  u.momentum = c.momentum;
+  u.momentum_rows = c.momentum_rows;
+  u.seed = c.seed;
+  u.counter = counter;
+  u.rowlen = r.rowlen;
+  u.g_log2 = r.g_log2;
+  u.dim = c.dim;
+  u.lr = c.lr;
+  u.eps = c.eps;
+  return u;
 }
 
-static void launch_compact_mark(bool w16, const void* src, bool keys, int64_t n, int64_t num_rows, const CompactWs& ws,
-                                hipStream_t s) {
-  const dim3 g(grid_for(n, 256)), b(256);
-  const uint32_t R = (uint32_t)num_rows;
-  if (keys) {
-    const unsigned long long* k = (const unsigned long long*)src;
-    if (w16) hipLaunchKernelGGL(k_w16_mark_keys, g, b, 0, s, k, n, R, ws.flags, ws.counter);
-    else hipLaunchKernelGGL(k_adagrad_mark_keys, g, b, 0, s, k, n, R, ws.flags);
-  } else {
-    const int64_t* i = (const int64_t*)src;
-    if (w16) hipLaunchKernelGGL(k_w16_mark_slots, g, b, 0, s, i, n, R, ws.flags, ws.counter);
-    else hipLaunchKernelGGL(k_adagrad_mark_slots, g, b, 0, s, i, n, R, ws.flags);
+// How the entries' checks differ -- everything else is the same conditions in the same order.
+struct EntryRules {
+  bool w16_only;             // ce_*_w16: CE_ACT_F32 is no table of theirs
+  const char* not_taken;     // non-NULL: a (table, optimizer, rounding) the entry does not take: CE_ERR_UNSUPPORTED
+  bool nnz_in_range;         // nnz sizes the workspace: it must lie in [0, 2^31) here (the others look at it later)
+  size_t (*workspace)(int64_t num_rows, int64_t nnz, int32_t dim);
+};
+
+// Everything an atomic update entry (cache-sized or step-sized accumulator) can refuse, from the arguments alone and BEFORE its first launch (no HIP call either): the
+// workspace stays as it was on every error.  r: the lane shape of the launch that updates the rows.  The row geometry
+// is first asked for with the weakest alignment of all the call's launches (weight, grad_out; the accumulators are
+// 256-byte aligned by their carve): a dim that fits the scalar form fits the vector form.
+static int update_check(const UpdateCall& c, const EntryRules& e, RowGeom& r) {
+  CE_REQUIRE_ACT(c.act);
+  if (!e.w16_only)
+    CE_REQUIRE(c.weight_dtype == CE_ACT_F32 || c.weight_dtype == CE_ACT_BF16 || c.weight_dtype == CE_ACT_F16,
+               CE_ERR_INVALID, "unknown weight_dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)c.weight_dtype);
+  const bool w16 = e.w16_only || c.w16();
+  if (w16) {
+    int rc = w16_check(c.weight_dtype, c.dim);
+    if (rc) return rc;
   }
+  CE_REQUIRE(c.optimizer == CE_OPT_SGD || c.optimizer == CE_OPT_ROWWISE_ADAGRAD, CE_ERR_INVALID,
+             "unknown optimizer %d (CE_OPT_SGD / CE_OPT_ROWWISE_ADAGRAD)", (int)c.optimizer);
+  CE_REQUIRE(c.rounding == CE_ROUND_NEAREST || c.rounding == CE_ROUND_STOCHASTIC, CE_ERR_INVALID,
+             "unknown rounding %d (CE_ROUND_NEAREST / CE_ROUND_STOCHASTIC)", (int)c.rounding);
+  CE_REQUIRE(!e.not_taken, CE_ERR_UNSUPPORTED, "%s", e.not_taken);
+  CE_REQUIRE(c.weight && c.grad_out && c.workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(c.dim > 0, CE_ERR_INVALID, "dim must be positive");
+  CE_REQUIRE(c.num_rows > 0 && c.num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE(!e.nnz_in_range || (c.nnz >= 0 && c.nnz < (int64_t)INT32_MAX), CE_ERR_INVALID, "nnz out of range");
+  CE_REQUIRE(c.lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
+  if (c.adagrad()) {
+    CE_REQUIRE(c.momentum && c.momentum_rows > 0, CE_ERR_INVALID, "row-wise Adagrad needs its momentum");
+    CE_REQUIRE(c.eps > 0.f, CE_ERR_INVALID, "eps must be > 0");
+  }
+  CE_REQUIRE(c.workspace_bytes >= e.workspace(c.num_rows, c.nnz, c.dim), CE_ERR_INVALID, "workspace too small");
+  CE_REQUIRE((((uintptr_t)c.workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
+  CE_REQUIRE(!w16 || al16(c.weight), CE_ERR_INVALID, "a 16-bit table must be 16-byte aligned");
+  int rc = row_geometry(c.dim, al16(c.weight) && act_aligned(c.grad_out, c.act), r);
+  if (rc) return rc;
+  // the scatter into acc takes the vector or the scalar form by grad_out's alignment, the apply pass by the table's
+  return row_geometry(c.dim, al16(c.weight), r);
+}
+
+// the one place that turns (weight_dtype, RowGeom) into the table's row type and the lane shape of a launch:
+// f(Lanes<VT, N>, ActTag<WT>) -- an fp32 table in either lane form, a 16-bit table in vector lanes
+template <typename F> static inline void for_table(int weight_dtype, const RowGeom& r, F&& f) {
+  if (weight_dtype == CE_ACT_F32) for_lanes(r.vec, r.nch, [&](auto l) { f(l, ActTag<float>{}); });
+  else for_w16(r.nch, weight_dtype, f);
+}
+
+static void launch_mark(const void* src, bool keys, int64_t n, int64_t num_rows, uint8_t* flags,
+                        unsigned long long* counter, hipStream_t s) {
+  const dim3 g(grid_for(n, 256)), b(256);
+  if (keys)
+    hipLaunchKernelGGL(k_mark_keys, g, b, 0, s, (const unsigned long long*)src, n, (uint32_t)num_rows, flags, counter);
+  else
+    hipLaunchKernelGGL(k_mark_slots, g, b, 0, s, (const int64_t*)src, n, (uint32_t)num_rows, flags, counter);
+}
+
+// The cache-sized update after its check: mark `n` slots / keys of `src`, scatter(acc) = the caller's dense backward,
+// apply.  An fp32 table is row-wise Adagrad with its rows stored as they are; a 16-bit table takes either optimizer and
+// either rounding.
+template <typename Scatter>
+static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const void* src, bool keys, int64_t n,
+                              hipStream_t s, Scatter&& scatter) {
+  const ApplyWs ws = carve_apply(c.workspace, c.num_rows, c.dim, c.w16());
+  launch_mark(src, keys, n, c.num_rows, ws.flags, ws.counter, s);
+  CE_LAUNCH_CHECK();
+  int rc = scatter(ws.acc);
+  if (rc) return rc;
+  ApplyArgs a{};
+  a.u = update_args(c, r, ws.counter);
+  a.acc = ws.acc;
+  a.flags = ws.flags;
+  a.num_rows = (uint32_t)c.num_rows;
+  const dim3 g(grid_for(cdiv(c.num_rows, 64), 4)), b(256);
+  const bool ada = c.adagrad(), st = c.stochastic();
+  for_table(c.weight_dtype, r, [&](auto l, auto w) {
+    using VT = typename decltype(l)::VT;
+    using WT = typename decltype(w)::AT;
+    constexpr int N = decltype(l)::NCH;
+    if constexpr (std::is_same<WT, float>::value)
+      hipLaunchKernelGGL((k_rows_apply<VT, float, N, true, false>), g, b, 0, s, a);
+    else if (ada && st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, true>), g, b, 0, s, a);
+    else if (ada) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, false>), g, b, 0, s, a);
+    else if (st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, false>), g, b, 0, s, a);
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
 }
 
 static int launch_compact_scan(int64_t num_rows, const CompactWs& ws, hipStream_t s) {
@@ -959,53 +832,59 @@ static int launch_compact_scan(int64_t num_rows, const CompactWs& ws, hipStream_
   return CE_OK;
 }
 
-static int launch_compact_apply(void* weight, int32_t weight_dtype, int32_t dim, const RowGeom& r,
-                                const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr, float eps,
-                                int32_t optimizer, int32_t rounding, uint64_t seed, const CompactWs& ws, hipStream_t s) {
+static int launch_compact_apply(const UpdateCall& c, const RowGeom& r, const CompactWs& ws, hipStream_t s) {
   CompactArgs a{};
-  a.weight = weight;
+  a.u = update_args(c, r, ws.counter);
   a.acc = ws.acc;
   a.list = ws.list;
   a.n_list = ws.n_list;
-  a.counter = ws.counter;
-  a.row_of_slot = row_of_slot;
-  a.momentum = momentum;
-  a.momentum_rows = momentum_rows;
-  a.seed = seed;
-  a.rowlen = r.rowlen;
-  a.g_log2 = r.g_log2;
-  a.dim = dim;
-  a.adagrad = optimizer == CE_OPT_ROWWISE_ADAGRAD;
-  a.lr = lr;
-  a.eps = eps;
+  a.adagrad = c.adagrad();
   const dim3 g(grid_for(ws.cap, 256 >> r.g_log2)), b(256);
-  if (weight_dtype == CE_ACT_F32) {
-    for_lanes(r.vec, r.nch, [&](auto l) {
-      hipLaunchKernelGGL((k_compact_apply<typename decltype(l)::VT, float, decltype(l)::NCH, false>), g, b, 0, s, a);
-    });
-  } else {
-    const bool st = rounding == CE_ROUND_STOCHASTIC;
-    for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
-      using WT = typename decltype(w)::AT;
-      constexpr int N = decltype(l)::NCH;
-      if (st) hipLaunchKernelGGL((k_compact_apply<f32x4, WT, N, true>), g, b, 0, s, a);
-      else hipLaunchKernelGGL((k_compact_apply<f32x4, WT, N, false>), g, b, 0, s, a);
-    });
-  }
+  for_table(c.weight_dtype, r, [&](auto l, auto w) {
+    using VT = typename decltype(l)::VT;
+    using WT = typename decltype(w)::AT;
+    constexpr int N = decltype(l)::NCH;
+    if constexpr (std::is_same<WT, float>::value)
+      hipLaunchKernelGGL((k_compact_apply<VT, float, N, false>), g, b, 0, s, a);
+    else if (c.stochastic())
+      hipLaunchKernelGGL((k_compact_apply<VT, WT, N, true>), g, b, 0, s, a);
+    else
+      hipLaunchKernelGGL((k_compact_apply<VT, WT, N, false>), g, b, 0, s, a);
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
+}
+
+// what the step-sized entries do not take
+static const char* compact_not_taken(const UpdateCall& c) {
+  if (!c.w16() && !c.adagrad())
+    return "CE_OPT_SGD on an fp32 table folds straight into the rows: it has no accumulator to compact";
+  if (c.w16() && c.adagrad() && c.stochastic())
+    return "row-wise Adagrad with CE_ROUND_STOCHASTIC on a 16-bit table is not taken with the step-sized accumulator";
+  return nullptr;
+}
+
+static const EntryRules kFp32Rules{
+    false, nullptr, false, [](int64_t R, int64_t, int32_t D) { return carve_apply(nullptr, R, D, false).bytes; }};
+static const EntryRules kW16Rules{
+    true, nullptr, false, [](int64_t R, int64_t, int32_t D) { return carve_apply(nullptr, R, D, true).bytes; }};
+static EntryRules compact_rules(const UpdateCall& c) {
+  return {false, compact_not_taken(c), true,
+          [](int64_t R, int64_t n, int32_t D) { return carve_compact(nullptr, R, n, D).bytes; }};
 }
 
 }  // namespace ce
 
 using namespace ce;
 
+// ---- fp32 table, row-wise Adagrad, cache-sized accumulator.  nnz == 0 returns before the arguments are looked at.
+
 extern "C" size_t ce_bag_backward_rowwise_adagrad_workspace(int64_t num_rows, int32_t dim) {
   if (num_rows < 0 || dim < 0) return 0;
-  return carve_adagrad(nullptr, num_rows, dim).bytes;
+  return carve_apply(nullptr, num_rows, dim, false).bytes;
 }
 
-// grad_out of the activation type act_dtype: step 2 reads it natively, acc and everything after it are fp32
+// grad_out of the activation type act_dtype: the scatter reads it natively, acc and everything after it are fp32
 extern "C" int ce_bag_backward_rowwise_adagrad_act(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
                                                    int64_t nnz, const void* offsets, int32_t offsets_are_i64,
                                                    int64_t num_bags, int32_t include_last_offset,
@@ -1016,20 +895,17 @@ extern "C" int ce_bag_backward_rowwise_adagrad_act(float* weight, int64_t num_ro
                                                    void* workspace, size_t workspace_bytes, ce_stream_t stream) {
   CE_REQUIRE_ACT(act_dtype);
   if (num_bags == 0 || nnz == 0) return CE_OK;
-  int rc = adagrad_check(weight, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps, workspace,
-                         workspace_bytes);
+  const UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum, momentum_rows,
+                     lr, eps, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST, 0, workspace, workspace_bytes};
+  RowGeom r;
+  int rc = update_check(c, kFp32Rules, r);
   if (rc) return rc;
   CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const AdagradWs ws = carve_adagrad(workspace, num_rows, dim);
-  hipLaunchKernelGGL(k_adagrad_mark_slots, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz,
-                     (uint32_t)num_rows, ws.flags);
-  CE_LAUNCH_CHECK();
-  rc = ce_bag_backward_dense_act(ws.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                                 include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
-                                 presorted, stream);
-  if (rc) return rc;
-  return launch_apply(weight, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps, ws, s);
+  return update_cache_sized(c, r, indices, false, nnz, (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_act(acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                                     include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                                     presorted, stream);
+  });
 }
 
 extern "C" int ce_bag_backward_rowwise_adagrad(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1053,19 +929,15 @@ extern "C" int ce_bag_backward_rowwise_adagrad_src_act(float* weight, int64_t nu
                                                        void* workspace, size_t workspace_bytes, ce_stream_t stream) {
   CE_REQUIRE_ACT(act_dtype);
   if (nnz == 0) return CE_OK;
-  int rc = adagrad_check(weight, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps, workspace,
-                         workspace_bytes);
+  const UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum, momentum_rows,
+                     lr, eps, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST, 0, workspace, workspace_bytes};
+  RowGeom r;
+  int rc = update_check(c, kFp32Rules, r);
   if (rc) return rc;
   CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const AdagradWs ws = carve_adagrad(workspace, num_rows, dim);
-  const int64_t total = ce_bag_presort_len(nnz);
-  hipLaunchKernelGGL(k_adagrad_mark_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
-                     (const unsigned long long*)src_keys, total, (uint32_t)num_rows, ws.flags);
-  CE_LAUNCH_CHECK();
-  rc = ce_bag_backward_dense_src_act(ws.acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
-  if (rc) return rc;
-  return launch_apply(weight, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps, ws, s);
+  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(nnz), (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_src_act(acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
+  });
 }
 
 extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
@@ -1078,11 +950,11 @@ extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_ro
                                                  workspace_bytes, stream);
 }
 
-// ---- 16-bit table: mark (+ step counter), the dense backward into acc, k_rows_apply_w16
+// ---- 16-bit table, either optimizer, cache-sized accumulator.  Here and below nnz == 0 returns AFTER the check.
 
 extern "C" size_t ce_bag_backward_w16_workspace(int64_t num_rows, int32_t dim) {
   if (num_rows < 0 || dim < 0) return 0;
-  return carve_w16(nullptr, num_rows, dim).bytes;
+  return carve_apply(nullptr, num_rows, dim, true).bytes;
 }
 
 extern "C" int ce_bag_backward_update_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -1093,8 +965,10 @@ extern "C" int ce_bag_backward_update_w16(void* weight, int32_t weight_dtype, in
                                           const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
                                           float eps, int32_t optimizer, int32_t rounding, uint64_t seed,
                                           void* workspace, size_t workspace_bytes, ce_stream_t stream) {
-  int rc = w16_update_check(weight, weight_dtype, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps,
-                            optimizer, rounding, workspace, workspace_bytes);
+  const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+                     momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
+  RowGeom r;
+  int rc = update_check(c, kW16Rules, r);
   if (rc) return rc;
   if (num_bags == 0 || nnz == 0) return CE_OK;
   CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
@@ -1104,17 +978,11 @@ extern "C" int ce_bag_backward_update_w16(void* weight, int32_t weight_dtype, in
              "mode must be sum, or mean without per_sample_weights");
   CE_REQUIRE(hook_features >= 0 && (hook_features == 0 || num_bags % hook_features == 0), CE_ERR_INVALID,
              "hook_features must divide num_bags");
-  hipStream_t s = (hipStream_t)stream;
-  const W16Ws ws = carve_w16(workspace, num_rows, dim);
-  hipLaunchKernelGGL(k_w16_mark_slots, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz, (uint32_t)num_rows,
-                     ws.base.flags, ws.counter);
-  CE_LAUNCH_CHECK();
-  rc = ce_bag_backward_dense_act(ws.base.acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                                 include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
-                                 presorted, stream);
-  if (rc) return rc;
-  return launch_apply_w16(weight, weight_dtype, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps,
-                          optimizer, rounding, seed, ws, s);
+  return update_cache_sized(c, r, indices, false, nnz, (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_act(acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                                     include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                                     presorted, stream);
+  });
 }
 
 extern "C" int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -1123,21 +991,16 @@ extern "C" int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype
                                               int64_t momentum_rows, float lr, float eps, int32_t optimizer,
                                               int32_t rounding, uint64_t seed, void* workspace,
                                               size_t workspace_bytes, ce_stream_t stream) {
-  int rc = w16_update_check(weight, weight_dtype, num_rows, dim, grad_out, act_dtype, momentum, momentum_rows, lr, eps,
-                            optimizer, rounding, workspace, workspace_bytes);
+  const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+                     momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
+  RowGeom r;
+  int rc = update_check(c, kW16Rules, r);
   if (rc) return rc;
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(src_keys && nnz > 0 && nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "null keys or nnz out of range");
-  hipStream_t s = (hipStream_t)stream;
-  const W16Ws ws = carve_w16(workspace, num_rows, dim);
-  const int64_t total = ce_bag_presort_len(nnz);
-  hipLaunchKernelGGL(k_w16_mark_keys, dim3(grid_for(total, 256)), dim3(256), 0, s, (const unsigned long long*)src_keys,
-                     total, (uint32_t)num_rows, ws.base.flags, ws.counter);
-  CE_LAUNCH_CHECK();
-  rc = ce_bag_backward_dense_src_act(ws.base.acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
-  if (rc) return rc;
-  return launch_apply_w16(weight, weight_dtype, num_rows, dim, row_of_slot, momentum, momentum_rows, lr, eps,
-                          optimizer, rounding, seed, ws, s);
+  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(nnz), (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_src_act(acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
+  });
 }
 
 // ---- step-sized accumulator: mark, compact, remap, the dense backward into acc[cap, D], apply over the list
@@ -1155,9 +1018,10 @@ extern "C" int ce_bag_backward_update_compact(void* weight, int32_t weight_dtype
                                               const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
                                               float lr, float eps, int32_t optimizer, int32_t rounding, uint64_t seed,
                                               void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+                     momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
   RowGeom r;
-  int rc = compact_check(weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, momentum, momentum_rows, lr,
-                         eps, optimizer, rounding, workspace, workspace_bytes, r);
+  int rc = update_check(c, compact_rules(c), r);
   if (rc) return rc;
   if (num_bags == 0 || nnz == 0) return CE_OK;
   CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
@@ -1168,7 +1032,7 @@ extern "C" int ce_bag_backward_update_compact(void* weight, int32_t weight_dtype
              "hook_features must divide num_bags");
   hipStream_t s = (hipStream_t)stream;
   const CompactWs ws = carve_compact(workspace, num_rows, nnz, dim);
-  launch_compact_mark(weight_dtype != CE_ACT_F32, indices, false, nnz, num_rows, ws, s);
+  launch_mark(indices, false, nnz, num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
   rc = launch_compact_scan(num_rows, ws, s);
   if (rc) return rc;
   // segment-sorted keys hold the rows themselves: with them the scatter never reads `indices`, so only they are remapped
@@ -1190,8 +1054,7 @@ extern "C" int ce_bag_backward_update_compact(void* weight, int32_t weight_dtype
                                  include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
                                  keys, stream);
   if (rc) return rc;
-  return launch_compact_apply(weight, weight_dtype, dim, r, row_of_slot, momentum, momentum_rows, lr, eps, optimizer,
-                              rounding, seed, ws, s);
+  return launch_compact_apply(c, r, ws, s);
 }
 
 extern "C" int ce_bag_backward_update_compact_src(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -1200,16 +1063,17 @@ extern "C" int ce_bag_backward_update_compact_src(void* weight, int32_t weight_d
                                                   float* momentum, int64_t momentum_rows, float lr, float eps,
                                                   int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
                                                   size_t workspace_bytes, ce_stream_t stream) {
+  const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+                     momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
   RowGeom r;
-  int rc = compact_check(weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, momentum, momentum_rows, lr,
-                         eps, optimizer, rounding, workspace, workspace_bytes, r);
+  int rc = update_check(c, compact_rules(c), r);
   if (rc) return rc;
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
   hipStream_t s = (hipStream_t)stream;
   const CompactWs ws = carve_compact(workspace, num_rows, nnz, dim);
   const int64_t total = ce_bag_presort_len(nnz);
-  launch_compact_mark(weight_dtype != CE_ACT_F32, src_keys, true, total, num_rows, ws, s);
+  launch_mark(src_keys, true, total, num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
   rc = launch_compact_scan(num_rows, ws, s);
   if (rc) return rc;
   hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
@@ -1218,8 +1082,7 @@ extern "C" int ce_bag_backward_update_compact_src(void* weight, int32_t weight_d
   CE_LAUNCH_CHECK();
   rc = ce_bag_backward_dense_src_act(ws.acc, ws.cap, dim, nnz, grad_out, act_dtype, (const uint64_t*)ws.remap, stream);
   if (rc) return rc;
-  return launch_compact_apply(weight, weight_dtype, dim, r, row_of_slot, momentum, momentum_rows, lr, eps, optimizer,
-                              rounding, seed, ws, s);
+  return launch_compact_apply(c, r, ws, s);
 }
 
 // ---- deterministic, accumulator-free: sort, fold + apply, combine + apply

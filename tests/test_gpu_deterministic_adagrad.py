@@ -315,7 +315,7 @@ def test_rows_looked_up_once_equal_the_atomic_path(D, kind):
 @pytest.mark.parametrize("D,kind", [(512, "fp32"), (512, "bf16-nearest"), (768, "fp32"), (1024, "fp32"),
                                     (1024, "fp16-nearest"), (6, "fp32"), (70, "fp32"), (130, "fp32"), (250, "fp32")])
 def test_rows_looked_up_once_every_lane_shape(D, kind):
-    """the same on the other lane shapes -- the sum of squares is spelled out per shape (sorted_sq_sum): the vector form
+    """the same on the other lane shapes -- the sum of squares is spelled out per shape (lane_sq_sum): the vector form
     with 2 chunks per lane (D = 512), 3 rounded up to 4 (768) and 4 (1024), and the scalar form (dim % 4 != 0) with 1, 2,
     3-of-4 and 4 chunks per lane (D = 6, 70, 130, 250); 2500 distinct rows + 37 ignored slots of a table of 3000"""
     _once(D, kind, 3000, 2500, 37)

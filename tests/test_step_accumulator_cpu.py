@@ -110,7 +110,7 @@ def test_refusals_come_from_the_arguments_alone():
             assert "CE_ROUND_STOCHASTIC" in L.last_error()
         assert call(**sgd) == L.CE_ERR_UNSUPPORTED and "no accumulator" in L.last_error()
         assert call(rnd=L.CE_ROUND_STOCHASTIC, **sgd) == L.CE_ERR_UNSUPPORTED
-        # those of adagrad_check / w16_update_check
+        # those of the cache-sized entries (the same update_check)
         for bad in (dict(weight=None), dict(go=None), dict(ws=None), dict(mom=None)):
             assert call(**bad) == L.CE_ERR_INVALID, bad
         for bad in (dict(act=7), dict(wd=7), dict(opt=2), dict(rnd=2), dict(D=0), dict(lr=-1.0), dict(eps=0.0),
