@@ -22,22 +22,11 @@
 // The sums and the updates are fp32; the forward's output and the backward's grad_out have the activation
 // type AT (fp32, bf16, fp16: Act<AT, VT> in ce_common.h) the four bag kernels are templated on.  The table is fp32, or
 // -- the two forwards only (WT; ce_bag_forward_w16 / _src_keys_w16) -- bf16 / fp16; its update is ce_bag_adagrad.hip's.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "ce_common.h"
 
 namespace ce {
-
-// Ablation switches of the backward kernels (CE_BWD_DEBUG: 1 = racy read-modify-write instead of atomics, 2 = no
-// update traffic, 3 / 4 = tile prologue only, 5 = untransposed atomics, 6 = plain stores; DESIGN.md section 4 quotes
-// them).  They produce WRONG results by design, so a product build compiles them out: -DCE_ABLATIONS brings them back.
-#ifdef CE_ABLATIONS
-#define CE_DBG(x) (x)
-#else
-#define CE_DBG(x) 0
-#endif
 
 struct BagParams {
   const float* weight;      // fwd: rows to gather from
@@ -56,11 +45,12 @@ struct BagParams {
   int32_t hookF;            // 0 = plain [num_bags, D]
   int32_t hookB;            // num_bags / hookF
   float alpha;              // bwd scale (1 or -lr)
-  int32_t debug;            // ablation switch (CE_BWD_DEBUG): 0 = normal
+  int32_t pad0;             // pad0, pad1: unused; dropping them re-schedules every k_bag_bwd_tile / k_bag_bwd_stream, so
+                            // they go with the next change that re-times the backward
   uint32_t num_rows;        // rows of the gathered / updated table: out-of-range indices are ignored
   int32_t tile_len;         // lookups per workgroup tile of the sorted scatter
   const unsigned long long* presorted;   // optional: segment-grouped keys from ce_bag_presort* (no sort in the kernel)
-  int32_t policy;           // bit 0: fwd output stores non-temporal; bit 1: bwd gradient-row loads non-temporal
+  int32_t pad1;
   int32_t interleave;       // key-walking kernels: lane group j of workgroup b takes share j * gridDim + b (see share_of)
 };
 
@@ -78,10 +68,6 @@ struct BagParams {
 __device__ __forceinline__ int64_t share_of(const BagParams& p, int grp, int ngroups) {
   return p.interleave ? (int64_t)grp * gridDim.x + blockIdx.x : (int64_t)blockIdx.x * ngroups + grp;
 }
-
-// cache policies of the two big streams: both non-temporal (the sweeps of rounds 3-5 that said so
-// are in profiles/ and docs/history.md, their switches are gone)
-constexpr int kBagPolicy = 3;
 
 // offsets == nullptr: the caller states one id per bag, in order (offsets = arange; ce_bag_forward, the presorts)
 __device__ __forceinline__ int ld_off(const BagParams& p, int i) {
@@ -112,13 +98,13 @@ __device__ __forceinline__ u32x2 swap_with_pair(u32x2 v) {
 
 constexpr int kIdxStage = 2048;   // indices of one 64-bag tile staged in LDS (8 KB per wave)
 
-// Output store of the forward: non-temporal (SP = 1).  The output is written once and read by another kernel; what
-// matters is how much of the L2 / Infinity Cache it takes from the cache rows the gather wants to find there (the
-// sc1 / sc0 sc1 / sc1 nt forms measured the same or slower: profiles/r03_probe_fwd_xcd.txt, docs/history.md).
-template <int SP, typename T>
+// Output store of the forward: non-temporal, like the backward's gradient-row loads (the sweeps of rounds 3-5 that
+// said so are in profiles/ and docs/history.md; their switches are gone).  The output is written once and read by
+// another kernel; what matters is how much of the L2 / Infinity Cache it takes from the cache rows the gather wants to
+// find there (the sc1 / sc0 sc1 / sc1 nt forms measured the same or slower: profiles/r03_probe_fwd_xcd.txt).
+template <typename T>
 __device__ __forceinline__ void store_out(T* p, T v) {
-  if (SP == 0) *p = v;
-  else __builtin_nontemporal_store(v, p);
+  __builtin_nontemporal_store(v, p);
 }
 
 // STAGE: tiles with multi-id bags stage their indices in LDS (32 KB per workgroup); the launcher picks the
@@ -126,7 +112,7 @@ __device__ __forceinline__ void store_out(T* p, T v) {
 // AT: the output's element type (Act<AT, VT>, ce_common.h): sums stay fp32, the store rounds.
 // WT: the table's element type (float, or bf16 / fp16 with f32x4 lanes: a lane's chunk is then 8 bytes of the row,
 // up-converted exactly on load).
-template <typename VT, int NCH, bool STAGE, int U, int NTS, typename AT, typename WT = float>
+template <typename VT, int NCH, bool STAGE, int U, typename AT, typename WT = float>
 __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   using A = Act<AT, VT>;
   using T = Act<WT, VT>;
@@ -187,7 +173,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
               const int ch = gl + c * G;
               if (ch < rowlen) {
                 VT val = p.psw ? v[u][c] * wi : v[u][c];
-                store_out<NTS>(&O[orow * rowlen + ch], A::down(val));
+                store_out(&O[orow * rowlen + ch], A::down(val));
               }
             }
           }
@@ -255,7 +241,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
           for (int c = 0; c < NCH; ++c) {
             const int ch = gl + c * G;
             if (ch < rowlen) {
-              store_out<NTS>(&O[orow * rowlen + ch], A::down(acc[c]));
+              store_out(&O[orow * rowlen + ch], A::down(acc[c]));
             }
           }
         }
@@ -280,13 +266,8 @@ __device__ __forceinline__ void atomic_add_vec(f32x4* dst, f32x4 v) {
 // atomic path is paid per line request.  A 4x4 butterfly transpose across the lane blocks of the group
 // (2 x 2 xor-shuffles) regroups the data so that atomic instruction c covers one contiguous block of G
 // floats: 4x fewer line requests per row (255 -> ~150 us/step measured).
-__device__ __forceinline__ void flush_chunk(float* row_base, f32x4 v, int gl, int G, int c, int rowlen, int debug) {
-  if (debug == 6) {                                          // ablation: plain store instead of the atomics (wrong result)
-    const int ch6 = gl + c * G;
-    if (ch6 < rowlen) ((f32x4*)row_base)[ch6] = v;
-    return;
-  }
-  if (G >= 4 && debug == 0 && (c + 1) * G <= rowlen) {      // group-uniform: whole chunk present
+__device__ __forceinline__ void flush_chunk(float* row_base, f32x4 v, int gl, int G, int c, int rowlen) {
+  if (G >= 4 && (c + 1) * G <= rowlen) {      // group-uniform: whole chunk present
     const int q = G >> 2;                     // lanes per lane block
     const int kb = gl / q;                    // my lane block 0..3
     const int m = gl - kb * q;
@@ -308,26 +289,22 @@ __device__ __forceinline__ void flush_chunk(float* row_base, f32x4 v, int gl, in
     return;
   }
   const int ch = gl + c * G;
-  if (ch >= rowlen) return;
-  f32x4* dst = (f32x4*)row_base + ch;
-  if (debug == 0 || debug == 5) atomic_add_vec(dst, v);
-  else if (debug == 1) *dst = *dst + v;                      // ablation: plain read-modify-write (racy)
-  else if (debug == 2) { if (v.x == 12345.678f) *dst = v; }  // ablation: no update traffic
+  if (ch < rowlen) atomic_add_vec((f32x4*)row_base + ch, v);
 }
-__device__ __forceinline__ void flush_chunk(float* row_base, float v, int gl, int G, int c, int rowlen, int debug) {
+__device__ __forceinline__ void flush_chunk(float* row_base, float v, int gl, int G, int c, int rowlen) {
   const int ch = gl + c * G;
-  if (ch >= rowlen) return;
-  float* dst = row_base + ch;
-  if (debug == 0 || debug == 5) atomic_add_vec(dst, v);
-  else if (debug == 1) *dst = *dst + v;
-  else if (debug == 2) { if (v == 12345.678f) *dst = v; }
+  if (ch < rowlen) atomic_add_vec(row_base + ch, v);
 }
+
+// rows in flight per lane group of k_bag_bwd_rows and of k_rows_axpy (whose launcher sizes its grid by it)
+constexpr int rows_unroll(int nch) { return nch == 1 ? 4 : (nch == 2 ? 2 : 1); }
+constexpr int axpy_unroll(int nch) { return nch == 1 ? 8 : (nch == 2 ? 4 : 2); }
 
 // Per-lookup gradient rows (COO values of the sparse=True backward; dest_index redirects row j):
 // dst[indices ? indices[j] : j] = alpha*scale*psw[j]*grad_out[bag(j)].
 template <typename VT, int NCH>
 __global__ __launch_bounds__(256) void k_bag_bwd_rows(BagParams p) {
-  constexpr int U = (NCH == 1) ? 4 : (NCH == 2 ? 2 : 1);
+  constexpr int U = rows_unroll(NCH);
   const int lane = threadIdx.x & 63;
   const int G = 1 << p.g_log2;
   const int gpw = 64 >> p.g_log2;
@@ -581,7 +558,7 @@ __global__ __launch_bounds__(1024) void k_bag_presort_seg(const int64_t* __restr
           unsigned low = (unsigned)e;
           // lay.offsets == nullptr: one id per bag, in order (bag of lookup j = j) -- what every Criteo / Avazu
           // batch is; saves the two offset loads per lookup that find_bag needs to establish it (-12 us per window)
-          if (SRC && !(CE_DBG(lay.debug) & 2))
+          if (SRC)
             low = (unsigned)out_row(q, lay.offsets ? find_bag(q, sib * kSegLen + e) : sib * kSegLen + e);
           // SRC: an ignored lookup (slot -1 / out of range) keeps its output row under the row 0xffffffff -- the
           // backward skips it like padding (row >= num_rows), the key-driven forward writes its zero row; it goes to
@@ -589,10 +566,6 @@ __global__ __launch_bounds__(1024) void k_bag_presort_seg(const int64_t* __restr
           key[r] = ((unsigned long long)(valid ? (uint32_t)row : 0xffffffffu) << 32) | low;
           if (valid) bkt[r] = (int)(row & (kSegBuckets - 1));
         }
-      }
-      if (CE_DBG(lay.debug) & 8) {       // ablation: no LDS atomic
-        place[r] = 0;
-        continue;
       }
       // Places inside the bucket: one returning LDS atomic per lane.  (Round 2 matched the lanes of a wave that hold
       // the same bucket with 13 ballots and let a leader reserve for all of them: on the bench's slots the ballots
@@ -780,7 +753,6 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
         if (row != 0xffffffffu) kr[r] = K::make(row, i);
       }
     }
-    if (CE_DBG(p.debug) == 3) { __syncthreads(); continue; }
     // ---- b. sort (row major, lookup minor) -> runs are in lookup order, invalid keys last
     //         (skipped when the cache op already sorted this tile: ce_bag_presort)
     if (presorted) {
@@ -793,7 +765,6 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
     // ---- c. reduce: every lane group walks ONE contiguous, equal share of the tile's sorted positions (13 chunks
     // of 64 over 8 groups cost two rounds -- the same as 16; 104 positions each cost 6.5/8 of that), R gradient
     // rows in flight, folding equal rows in lookup order; one atomic row update per (row, share).
-    if (CE_DBG(p.debug) == 4) continue;
     const int kChunk = (nv + ngroups - 1) / ngroups;
     const int nchunks = (nv + kChunk - 1) / kChunk;
     for (int ck = grp; ck < nchunks; ck += ngroups) {
@@ -830,7 +801,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
 #pragma unroll
               for (int c = 0; c < NCH; ++c) {
                 if (cur != K::row_invalid())
-                  flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen, CE_DBG(p.debug));
+                  flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen);
                 acc[c] = vzero<VT>();
               }
               cur = rw[t];
@@ -842,7 +813,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
       }
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        if (cur != K::row_invalid()) flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen, CE_DBG(p.debug));
+        if (cur != K::row_invalid()) flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen);
       }
     }
     __syncthreads();
@@ -871,7 +842,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
 // clock and channel -- 6.3 M lane-ops per launch = 24 us that do not overlap with the gather (profiles/r03_probe_*).
 // AT: grad_out's element type -- only the gather changes; fold, old rows and update are fp32 whatever it is.
 // PAIR (16-bit AT, f32x4 lanes): the gather of two keys' gradient rows is ONE 16-byte load per lane (see u32x4 above).
-template <typename VT, int NCH, int R, bool NTG, bool EXCL, typename AT, bool PAIR = false>
+template <typename VT, int NCH, int R, bool EXCL, typename AT, bool PAIR = false>
 __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t total, const long long* __restrict__ seg_ranges) {
   using A = Act<AT, VT>;
   static_assert(!PAIR || (sizeof(typename A::V) == 8 && R % 2 == 0), "PAIR: 4 x 16 bit per lane, keys two at a time");
@@ -953,7 +924,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
           const int ch = gl + c * G;
           v[t][c] = vzero<VT>();
           if (!PAIR && on && ch < rowlen)
-            v[t][c] = A::up(NTG ? __builtin_nontemporal_load(&GO[src * rowlen + ch]) : GO[src * rowlen + ch]);
+            v[t][c] = A::up(__builtin_nontemporal_load(&GO[src * rowlen + ch]));
           if (EXCL) {
             w2[t][c] = vzero<VT>();
             if (head && ch < rowlen) w2[t][c] = WV[(int64_t)rw[t] * rowlen + ch];
@@ -990,7 +961,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
                   const int ch = gl + c * G;
                   if (ch < rowlen) ((VT*)(p.dst + (int64_t)cur * dim))[ch] = acc[c];
                 } else {
-                  flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen, CE_DBG(p.debug));
+                  flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen);
                 }
               }
               acc[c] = EXCL ? w2[EXCL ? t : 0][c] : vzero<VT>();
@@ -1011,7 +982,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
         const int ch = gl + c * G;
         if (ch < rowlen) ((VT*)(p.dst + (int64_t)cur * dim))[ch] = acc[c];
       } else {
-        flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen, CE_DBG(p.debug));
+        flush_chunk(p.dst + (int64_t)cur * dim, acc[c], gl, G, c, rowlen);
       }
     }
   }
@@ -1029,7 +1000,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
 // AT: the output's element type; the row is rounded once per store, so `prev` stays the fp32 row.
 // PAIR (16-bit AT, f32x4 lanes): the stores of two keys are ONE 16-byte store per lane (see u32x4 above).
 // WT: the table's element type (a 16-bit table whose type differs from AT: the row is up-converted on load).
-template <typename VT, int NCH, int R, int NTS, typename AT, bool PAIR = false, typename WT = float>
+template <typename VT, int NCH, int R, typename AT, bool PAIR = false, typename WT = float>
 __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t total) {      // 4 waves per SIMD: <= 128 VGPRs
   using A = Act<AT, VT>;
   using T = Act<WT, VT>;
@@ -1107,7 +1078,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
             const int ch = gl + c * G;
             const u32x2 got = swap_with_pair(odd ? r0[c] : r1[c]);
             const u32x4 o = odd ? u32x4{got.x, got.y, r1[c].x, r1[c].y} : u32x4{r0[c].x, r0[c].y, got.x, got.y};
-            if (km != ~0ull && ch < rowlen) store_out<NTS>((u32x4*)p.dst + ((orow * rowlen + ch) >> 1), o);
+            if (km != ~0ull && ch < rowlen) store_out((u32x4*)p.dst + ((orow * rowlen + ch) >> 1), o);
           }
         }
         prev_row = last;
@@ -1128,7 +1099,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const int ch = gl + c * G;
-          if (ch < rowlen) store_out<NTS>(&O[orow * rowlen + ch], A::down(prev[c]));
+          if (ch < rowlen) store_out(&O[orow * rowlen + ch], A::down(prev[c]));
         }
       }
       prev_row = last;
@@ -1144,7 +1115,7 @@ __global__ __launch_bounds__(256) void k_rows_axpy(float* __restrict__ dst, uint
                                                    const int64_t* __restrict__ index, int64_t n,
                                                    const VT* __restrict__ src, int rowlen, int g_log2, int dim,
                                                    float alpha) {
-  constexpr int U = (NCH == 1) ? 8 : (NCH == 2 ? 4 : 2);
+  constexpr int U = axpy_unroll(NCH);
   const int lane = threadIdx.x & 63;
   const int G = 1 << g_log2;
   const int gpw = 64 >> g_log2;
@@ -1176,7 +1147,7 @@ __global__ __launch_bounds__(256) void k_rows_axpy(float* __restrict__ dst, uint
     for (int u = 0; u < U; ++u) {
       if (row[u] < 0) continue;
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) flush_chunk(dst + row[u] * dim, v[u][c] * alpha, gl, G, c, rowlen, 0);
+      for (int c = 0; c < NCH; ++c) flush_chunk(dst + row[u] * dim, v[u][c] * alpha, gl, G, c, rowlen);
     }
   }
 }
@@ -1208,7 +1179,6 @@ static int fill_params(BagParams& p, RowGeom& r, int32_t dim, bool aligned, cons
   p.hookB = hookF ? (int32_t)(num_bags / hookF) : 0;
   p.alpha = 1.f;
   p.num_rows = 0xffffffffu;
-  p.policy = kBagPolicy;
   return CE_OK;
 }
 
@@ -1219,6 +1189,10 @@ static int fill_params_keys(BagParams& p, RowGeom& r, int32_t dim, bool aligned,
 
 template <typename F> static void for_lanes_act(const RowGeom& r, int act, F&& f) {
   for_lanes(r.vec, r.nch, [&](auto l) { for_act(act, [&](auto a) { f(l, a); }); });
+}
+// ... and with the table's type (the two forwards): f(Lanes<VT, N>, ActTag<WT>, ActTag<AT>)
+template <typename F> static void for_table_act(int weight_dtype, const RowGeom& r, int act, F&& f) {
+  for_table(weight_dtype, r, [&](auto l, auto w) { for_act(act, [&](auto a) { f(l, w, a); }); });
 }
 
 // rows in flight per lane group, by lane shape: k_bag_fwd's U and k_bag_bwd_tile's R ...
@@ -1250,29 +1224,88 @@ static dim3 keys_grid(int64_t total, int g_log2, int per_cu) {
 
 // grad accumulation / fused SGD by target row: grouped segments (ce_bag_presort*) are walked as they are, otherwise
 // the kernel sorts 1024-lookup tiles itself
-static int launch_bwd_scatter(const BagParams& p, const RowGeom& r, int act, hipStream_t s) {
-  BagParams q = p;
-#ifdef CE_ABLATIONS
-  { const char* dbg = getenv("CE_BWD_DEBUG"); q.debug = dbg ? atoi(dbg) : 0; }
-#endif
+static int launch_bwd_scatter(BagParams& p, const RowGeom& r, int act, hipStream_t s) {
   // sorted keys: a tile count that is a multiple of the CU count (425,984 keys -> 512 tiles of 832, two per CU,
   // instead of 416 tiles = one or two per CU): 80 -> 72.5 us.  More, smaller tiles lose to the per-tile prologue
   // (3/CU 77 us, 4/CU 85 us, 8/CU 94 us), and the self-sorting path does not gain (92 us either way).
-  q.tile_len = kBwdTile;
+  p.tile_len = kBwdTile;
   const int64_t total = p.presorted ? padded_keys(p.nnz) : p.nnz;
   if (p.presorted) {
     constexpr int per_cu = 2;
     if (total > (int64_t)kNumCU * 256)
-      q.tile_len = (int)std::min<int64_t>(kBwdTile, (cdiv(total, (int64_t)kNumCU * per_cu) + 15) & ~15ll);
+      p.tile_len = (int)std::min<int64_t>(kBwdTile, (cdiv(total, (int64_t)kNumCU * per_cu) + 15) & ~15ll);
   }
-  dim3 grid(std::min((int)cdiv(total, q.tile_len), kMaxBlocks)), block(256);
-  const bool k32 = q.num_rows <= (1u << 22) - 2;
+  dim3 grid(std::min((int)cdiv(total, p.tile_len), kMaxBlocks)), block(256);
+  const bool k32 = p.num_rows <= (1u << 22) - 2;
   for_lanes_act(r, act, [&](auto l, auto a) {
     using VT = typename decltype(l)::VT;
     using AT = typename decltype(a)::AT;
     constexpr int N = decltype(l)::NCH, R = tile_unroll<VT, N>();
-    if (k32) hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, uint32_t, R, AT>), grid, block, 0, s, q);
-    else hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, unsigned long long, R, AT>), grid, block, 0, s, q);
+    if (k32) hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, uint32_t, R, AT>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, unsigned long long, R, AT>), grid, block, 0, s, p);
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
+// The gather-shaped forward over filled BagParams.  weight_dtype: CE_ACT_F32, or a 16-bit table's type -- the same
+// kernel with the row type WT; only the vector lane shape exists there, a lane's chunk is 8 bytes of the row.
+static int launch_fwd(BagParams& p, const RowGeom& r, const void* weight, int weight_dtype, int64_t num_rows, void* out,
+                      int act, hipStream_t s) {
+  p.weight = (const float*)weight;
+  p.dst = (float*)out;
+  CE_REQUIRE_ROWS(num_rows);
+  p.num_rows = (uint32_t)num_rows;
+  dim3 grid(bag_grid(p.num_bags)), block(256);
+  const bool stage = p.nnz != p.num_bags;      // multi-id bags possible
+  for_table_act(weight_dtype, r, act, [&](auto l, auto w, auto a) {
+    using VT = typename decltype(l)::VT;
+    using WT = typename decltype(w)::AT;
+    using AT = typename decltype(a)::AT;
+    constexpr int N = decltype(l)::NCH, U = tile_unroll<VT, N>();
+    if (stage) hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, AT, WT>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, AT, WT>), grid, block, 0, s, p);
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
+// The key-driven forward.  An fp32 table has the PAIR form for a 16-bit output; a 16-bit table only the converting
+// instantiation (WT != AT: exact up-conversion, one rounding on the store) -- equal types never get here, see
+// ce_bag_forward_src_keys_w16.
+static int launch_fwd_keys(const void* weight, int weight_dtype, int64_t num_rows, int32_t dim, bool aligned, int64_t nnz,
+                           const uint64_t* src_keys, void* out, int act, hipStream_t s) {
+  BagParams p{};
+  RowGeom r;
+  int rc = fill_params_keys(p, r, dim, aligned, nnz);
+  if (rc) return rc;
+  p.weight = (const float*)weight;
+  p.dst = (float*)out;
+  p.num_rows = (uint32_t)num_rows;
+  p.presorted = (const unsigned long long*)src_keys;
+  p.interleave = 0;
+  const int64_t total = padded_keys(nnz);
+  // 16 workgroups per CU: more than fit at once (97 VGPRs: 5), so the dispatcher hands the shares out as CUs free up
+  // (measured at the bench shape beside the cache op: 4/CU 72-74 us per launch, 8/CU 66-70, 16/CU 63-64, 32/CU 62-65;
+  // alone: 8/CU 48, 16/CU 46.7, 5/CU -- exactly resident -- 43 but 66 beside the cache op)
+  const dim3 g = keys_grid(total, p.g_log2, 16), b(256);
+  const bool pair = pair16(r, act, dim, out);       // 16 bytes of a 16-bit output per lane: two keys at a time
+  for_table_act(weight_dtype, r, act, [&](auto l, auto w, auto a) {
+    using VT = typename decltype(l)::VT;
+    using WT = typename decltype(w)::AT;
+    using AT = typename decltype(a)::AT;
+    constexpr int N = decltype(l)::NCH, R = keys_unroll<VT, N>();
+    if constexpr (std::is_same<WT, float>::value) {
+      if constexpr (kHasPair<VT, AT>) {
+        if (pair) {
+          hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, AT, true>), g, b, 0, s, p, total);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, AT>), g, b, 0, s, p, total);
+    } else if constexpr (!std::is_same<AT, WT>::value) {
+      hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, AT, false, WT>), g, b, 0, s, p, total);
+    }
   });
   CE_LAUNCH_CHECK();
   return CE_OK;
@@ -1296,22 +1329,7 @@ extern "C" int ce_bag_forward_act(const float* weight, int64_t num_rows, int32_t
   int rc = fill_params(p, r, dim, al16(weight) && act_aligned(out, act_dtype), indices, nnz, offsets, offsets_are_i64,
                        num_bags, include_last_offset, per_sample_weights, mode, hook_features);
   if (rc) return rc;
-  p.weight = weight;
-  p.dst = (float*)out;
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  p.num_rows = (uint32_t)num_rows;
-  dim3 grid(bag_grid(num_bags)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const bool stage = nnz != num_bags;      // multi-id bags possible
-  for_lanes_act(r, act_dtype, [&](auto l, auto a) {
-    using VT = typename decltype(l)::VT;
-    using AT = typename decltype(a)::AT;
-    constexpr int N = decltype(l)::NCH, U = tile_unroll<VT, N>();
-    if (stage) hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, 1, AT>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, 1, AT>), grid, block, 0, s, p);
-  });
-  CE_LAUNCH_CHECK();
-  return CE_OK;
+  return launch_fwd(p, r, weight, CE_ACT_F32, num_rows, out, act_dtype, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1340,7 +1358,7 @@ static int backward_scatter_impl(float* dst, float alpha, int64_t num_rows, int3
   p.dst = dst;
   p.grad_out = grad_out;
   p.alpha = alpha;
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE_ROWS(num_rows);
   p.num_rows = (uint32_t)num_rows;
   p.presorted = (const unsigned long long*)presorted;
   return launch_bwd_scatter(p, r, act, (hipStream_t)stream);
@@ -1418,7 +1436,7 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
   CE_REQUIRE_ACT(act);
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(dst && grad_out && keys, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE_ROWS(num_rows);
   BagParams p{};
   RowGeom r;
   int rc = fill_params_keys(p, r, dim, al16(dst) && act_aligned(grad_out, act), nnz);
@@ -1428,9 +1446,6 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
   p.alpha = alpha;
   p.num_rows = (uint32_t)num_rows;
   p.presorted = (const unsigned long long*)keys;
-#ifdef CE_ABLATIONS
-  { const char* dbg = getenv("CE_BWD_DEBUG"); p.debug = dbg ? atoi(dbg) : 0; }
-#endif
   p.interleave = 1;
   const int64_t total = padded_keys(nnz);
   // 6 workgroups per CU, i.e. 12288 shares of ~35 keys at the bench shape.  Alone on the GPU the share size matters
@@ -1451,7 +1466,7 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
     constexpr bool has_excl = sizeof(VT) == 16 && N == 1, has_pair = kHasPair<VT, AT>;
     auto launch = [&](auto ex, auto pr) {
       constexpr bool EX = decltype(ex)::value, PR = decltype(pr)::value;
-      hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, true, EX, AT, PR>), g, b, 0, s, p, total, rg);
+      hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, EX, AT, PR>), g, b, 0, s, p, total, rg);
     };
     if constexpr (has_excl && has_pair) { if (excl && pair) return launch(std::true_type{}, std::true_type{}); }
     if constexpr (has_excl) { if (excl) return launch(std::true_type{}, std::false_type{}); }
@@ -1497,37 +1512,9 @@ extern "C" int ce_bag_forward_src_keys_act(const float* weight, int64_t num_rows
   CE_REQUIRE_ACT(act_dtype);
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  BagParams p{};
-  RowGeom r;
-  int rc = fill_params_keys(p, r, dim, al16(weight) && act_aligned(out, act_dtype), nnz);
-  if (rc) return rc;
-  p.weight = weight;
-  p.dst = (float*)out;
-  p.num_rows = (uint32_t)num_rows;
-  p.presorted = (const unsigned long long*)src_keys;
-  p.interleave = 0;
-  const int64_t total = padded_keys(nnz);
-  // 16 workgroups per CU: more than fit at once (97 VGPRs: 5), so the dispatcher hands the shares out as CUs free up
-  // (measured at the bench shape beside the cache op: 4/CU 72-74 us per launch, 8/CU 66-70, 16/CU 63-64, 32/CU 62-65;
-  // alone: 8/CU 48, 16/CU 46.7, 5/CU -- exactly resident -- 43 but 66 beside the cache op)
-  const dim3 g = keys_grid(total, p.g_log2, 16), b(256);
-  hipStream_t s = (hipStream_t)stream;
-  const bool pair = pair16(r, act_dtype, dim, out);       // 16 bytes of a 16-bit output per lane: two keys at a time
-  for_lanes_act(r, act_dtype, [&](auto l, auto a) {
-    using VT = typename decltype(l)::VT;
-    using AT = typename decltype(a)::AT;
-    constexpr int N = decltype(l)::NCH, R = keys_unroll<VT, N>();
-    if constexpr (kHasPair<VT, AT>) {
-      if (pair) {
-        hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT, true>), g, b, 0, s, p, total);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT>), g, b, 0, s, p, total);
-  });
-  CE_LAUNCH_CHECK();
-  return CE_OK;
+  CE_REQUIRE_ROWS(num_rows);
+  return launch_fwd_keys(weight, CE_ACT_F32, num_rows, dim, al16(weight) && act_aligned(out, act_dtype), nnz, src_keys, out,
+                         act_dtype, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_forward_src_keys(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
@@ -1535,8 +1522,7 @@ extern "C" int ce_bag_forward_src_keys(const float* weight, int64_t num_rows, in
   return ce_bag_forward_src_keys_act(weight, num_rows, dim, nnz, src_keys, out, CE_ACT_F32, stream);
 }
 
-// ---- forward from a 16-bit table: the same kernels with the row type WT; only the vector lane shape exists
-// (dim % 8 == 0), a lane's chunk is 8 bytes of the row
+// ---- forward from a 16-bit table (dim % 8 == 0, everything aligned: refused here, not fallen back from)
 extern "C" int ce_bag_forward_w16(const void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
                                   const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
                                   int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
@@ -1556,30 +1542,11 @@ extern "C" int ce_bag_forward_w16(const void* weight, int32_t weight_dtype, int6
   rc = fill_params(p, r, dim, true, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
                    per_sample_weights, mode, hook_features);
   if (rc) return rc;
-  p.weight = (const float*)weight;
-  p.dst = (float*)out;
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  p.num_rows = (uint32_t)num_rows;
-  dim3 grid(bag_grid(num_bags)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const bool stage = nnz != num_bags;      // multi-id bags possible
-  for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
-    for_act(act_dtype, [&](auto a) {
-      using VT = typename decltype(l)::VT;
-      using AT = typename decltype(a)::AT;
-      using WT = typename decltype(w)::AT;
-      constexpr int N = decltype(l)::NCH, U = tile_unroll<VT, N>();
-      if (stage) hipLaunchKernelGGL((k_bag_fwd<VT, N, true, U, 1, AT, WT>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((k_bag_fwd<VT, N, false, U, 1, AT, WT>), grid, block, 0, s, p);
-    });
-  });
-  CE_LAUNCH_CHECK();
-  return CE_OK;
+  return launch_fwd(p, r, weight, weight_dtype, num_rows, out, act_dtype, (hipStream_t)stream);
 }
 
 // Output type == table type: the forward moves bits, so it IS the fp32 key-driven forward over the same bytes seen as
-// an fp32 [num_rows, dim / 2] table (nothing converts, an ignored lookup's row is zero).  Other pairs: the converting
-// instantiation (exact up-conversion, one rounding on the store).
+// an fp32 [num_rows, dim / 2] table (nothing converts, an ignored lookup's row is zero).  Other pairs convert.
 extern "C" int ce_bag_forward_src_keys_w16(const void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
                                            int64_t nnz, const uint64_t* src_keys, void* out, int32_t act_dtype,
                                            ce_stream_t stream) {
@@ -1588,138 +1555,100 @@ extern "C" int ce_bag_forward_src_keys_w16(const void* weight, int32_t weight_dt
   if (rc) return rc;
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE_ROWS(num_rows);
   CE_REQUIRE(al16(weight) && act_aligned(out, act_dtype), CE_ERR_INVALID,
              "a 16-bit table must be 16-byte aligned and its output on the vector boundary");
   if (act_dtype == weight_dtype) {
     CE_REQUIRE(al16(out), CE_ERR_INVALID, "the bit-copying forward needs a 16-byte aligned output");
     return ce_bag_forward_src_keys_act((const float*)weight, num_rows, dim / 2, nnz, src_keys, out, CE_ACT_F32, stream);
   }
-  BagParams p{};
-  RowGeom r;
-  rc = fill_params_keys(p, r, dim, true, nnz);
-  if (rc) return rc;
-  p.weight = (const float*)weight;
-  p.dst = (float*)out;
-  p.num_rows = (uint32_t)num_rows;
-  p.presorted = (const unsigned long long*)src_keys;
-  p.interleave = 0;
-  const int64_t total = padded_keys(nnz);
-  const dim3 g = keys_grid(total, p.g_log2, 16), b(256);
-  hipStream_t s = (hipStream_t)stream;
-  for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
-    for_act(act_dtype, [&](auto a) {
-      using VT = typename decltype(l)::VT;
-      using AT = typename decltype(a)::AT;
-      using WT = typename decltype(w)::AT;
-      constexpr int N = decltype(l)::NCH, R = keys_unroll<VT, N>();
-      if constexpr (!std::is_same<AT, WT>::value)       // (equal types left above)
-        hipLaunchKernelGGL((k_bag_fwd_keys<VT, N, R, 1, AT, false, WT>), g, b, 0, s, p, total);
-    });
-  });
-  CE_LAUNCH_CHECK();
-  return CE_OK;
+  return launch_fwd_keys(weight, weight_dtype, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
 }
 
-extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : cdiv(nnz, kSegLen) * kSegLen; }
+extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : padded_keys(nnz); }
 
-static int presort_window_impl(const int64_t* indices, int64_t nnz_per_batch, int64_t n_batches, int64_t num_rows,
-                               uint64_t* keys_out, const BagParams* lay, int64_t off_stride, const int64_t* ids,
-                               int64_t* ids_minmax, ce_stream_t stream) {
+// the refusals of a window's bag layout, and the BagParams the presort kernel reads it from
+static int window_layout(BagParams& lay, const BagLayout& L, const int64_t* indices, int64_t nnz_per_batch) {
+  CE_REQUIRE(L.num_bags > 0 && L.offsets_batch_stride >= 0, CE_ERR_INVALID, "bad offsets");
+  CE_REQUIRE(L.offsets || L.num_bags == nnz_per_batch, CE_ERR_INVALID,
+             "offsets may only be NULL for the one-id-per-bag layout (num_bags == nnz_per_batch)");
+  RowGeom unused;
+  return fill_params(lay, unused, 4, true, indices, nnz_per_batch, L.offsets, L.offsets_are_i64, L.num_bags,
+                     L.include_last_offset, nullptr, CE_MODE_SUM, L.hook_features);
+}
+
+// The one launch site of k_bag_presort_seg.  The window's slots come as `indices`, or (ROWS) as slots_io + inverted +
+// status: rows that the kernel turns into slots in place.  L: source-row keys for that layout (SRC), else keys =
+// row << 32 | lookup in segment; ids_minmax with it: owner-exclusive runs and the segments' id ranges (EXCL).
+static int launch_presort(const int64_t* indices, int64_t* slots_io, const int32_t* inverted, const int* status,
+                          int64_t nnz_per_batch, int64_t n_batches, int64_t num_rows, const BagLayout* L,
+                          const int64_t* ids, int64_t* ids_minmax, uint64_t* keys_out, hipStream_t s) {
   if (nnz_per_batch == 0 || n_batches == 0) return CE_OK;
-  CE_REQUIRE(indices && keys_out && nnz_per_batch > 0 && n_batches > 0, CE_ERR_INVALID, "bad arguments");
+  CE_REQUIRE((slots_io ? inverted && status : indices != nullptr) && keys_out && nnz_per_batch > 0 && n_batches > 0,
+             CE_ERR_INVALID, "bad arguments");
   CE_REQUIRE(nnz_per_batch < (int64_t)INT32_MAX - kSegLen, CE_ERR_INVALID, "batch too large");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE_ROWS(num_rows);
   const int64_t spb = cdiv(nnz_per_batch, kSegLen);
   const int64_t nseg = spb * n_batches;
   CE_REQUIRE(spb < (int64_t)INT32_MAX && nseg < (int64_t)INT32_MAX, CE_ERR_INVALID, "too many segments");
+  BagParams lay{};
+  if (L) {
+    int rc = window_layout(lay, *L, indices, nnz_per_batch);
+    if (rc) return rc;
+  }
   const dim3 grid((unsigned)std::min<int64_t>(nseg, kMaxBlocks)), block(1024);
-  int64_t* const no_io = nullptr;
-  const int32_t* const no_inv = nullptr;
-  const int* const no_st = nullptr;
-  if (lay && ids_minmax)
-    hipLaunchKernelGGL((k_bag_presort_seg<true, true, false>), grid, block, 0, (hipStream_t)stream, indices, nnz_per_batch,
-                       (int32_t)spb, nseg, (uint32_t)num_rows, (unsigned long long*)keys_out, *lay, off_stride, ids,
-                       ids_minmax, no_io, no_inv, no_st);
-  else if (lay)
-    hipLaunchKernelGGL((k_bag_presort_seg<true, false, false>), grid, block, 0, (hipStream_t)stream, indices, nnz_per_batch,
-                       (int32_t)spb, nseg, (uint32_t)num_rows, (unsigned long long*)keys_out, *lay, off_stride,
-                       (const int64_t*)nullptr, (int64_t*)nullptr, no_io, no_inv, no_st);
-  else
-    hipLaunchKernelGGL((k_bag_presort_seg<false, false, false>), grid, block, 0, (hipStream_t)stream, indices, nnz_per_batch,
-                       (int32_t)spb, nseg, (uint32_t)num_rows, (unsigned long long*)keys_out, BagParams{}, 0ll,
-                       (const int64_t*)nullptr, (int64_t*)nullptr, no_io, no_inv, no_st);
+  const int64_t off_stride = L ? L->offsets_batch_stride : 0;
+  auto launch = [&](auto src, auto excl, auto rows) {
+    hipLaunchKernelGGL((k_bag_presort_seg<decltype(src)::value, decltype(excl)::value, decltype(rows)::value>), grid, block,
+                       0, s, indices, nnz_per_batch, (int32_t)spb, nseg, (uint32_t)num_rows,
+                       (unsigned long long*)keys_out, lay, off_stride, ids, ids_minmax, slots_io, inverted, status);
+  };
+  const std::true_type yes{};
+  const std::false_type no{};
+  if (slots_io && L) launch(yes, no, yes);
+  else if (slots_io) launch(no, no, yes);
+  else if (L && ids_minmax) launch(yes, yes, no);
+  else if (L) launch(yes, no, no);
+  else launch(no, no, no);
   CE_LAUNCH_CHECK();
   return CE_OK;
 }
 
 namespace ce {
 int presort_window_from_rows(int64_t* slots_io, int64_t nnz_per_batch, int64_t n_batches, int64_t num_rows,
-                             const int32_t* inverted, const int* status, int32_t src_keys, const void* offsets,
-                             int32_t offsets_are_i64, int64_t offsets_batch_stride, int64_t num_bags,
-                             int32_t include_last_offset, int64_t hook_features, uint64_t* keys_out, hipStream_t stream) {
-  if (nnz_per_batch == 0 || n_batches == 0) return CE_OK;
-  CE_REQUIRE(slots_io && keys_out && inverted && status && nnz_per_batch > 0 && n_batches > 0, CE_ERR_INVALID, "bad arguments");
-  CE_REQUIRE(nnz_per_batch < (int64_t)INT32_MAX - kSegLen, CE_ERR_INVALID, "batch too large");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
-  const int64_t spb = cdiv(nnz_per_batch, kSegLen);
-  const int64_t nseg = spb * n_batches;
-  CE_REQUIRE(spb < (int64_t)INT32_MAX && nseg < (int64_t)INT32_MAX, CE_ERR_INVALID, "too many segments");
-  const dim3 grid((unsigned)std::min<int64_t>(nseg, kMaxBlocks)), block(1024);
-  if (src_keys) {
-    CE_REQUIRE(num_bags > 0 && offsets_batch_stride >= 0, CE_ERR_INVALID, "bad offsets");
-    CE_REQUIRE(offsets || num_bags == nnz_per_batch, CE_ERR_INVALID,
-               "offsets may only be NULL for the one-id-per-bag layout (num_bags == nnz_per_batch)");
-    BagParams lay{};
-    RowGeom unused;
-    int rc = fill_params(lay, unused, 4, true, nullptr, nnz_per_batch, offsets, offsets_are_i64, num_bags,
-                         include_last_offset, nullptr, CE_MODE_SUM, hook_features);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_bag_presort_seg<true, false, true>), grid, block, 0, stream, (const int64_t*)nullptr,
-                       nnz_per_batch, (int32_t)spb, nseg, (uint32_t)num_rows, (unsigned long long*)keys_out, lay,
-                       offsets_batch_stride, (const int64_t*)nullptr, (int64_t*)nullptr, slots_io, inverted, status);
-  } else {
-    hipLaunchKernelGGL((k_bag_presort_seg<false, false, true>), grid, block, 0, stream, (const int64_t*)nullptr,
-                       nnz_per_batch, (int32_t)spb, nseg, (uint32_t)num_rows, (unsigned long long*)keys_out, BagParams{},
-                       0ll, (const int64_t*)nullptr, (int64_t*)nullptr, slots_io, inverted, status);
-  }
-  CE_LAUNCH_CHECK();
-  return CE_OK;
+                             const int32_t* inverted, const int* status, int32_t src_keys, const BagLayout& lay,
+                             uint64_t* keys_out, hipStream_t stream) {
+  // (a null slots_io is refused like every other null here: with it gone the launcher looks for `indices`)
+  return launch_presort(nullptr, slots_io, inverted, status, nnz_per_batch, n_batches, num_rows, src_keys ? &lay : nullptr,
+                        nullptr, nullptr, keys_out, stream);
 }
 }  // namespace ce
 
 extern "C" int ce_bag_presort_window(const int64_t* indices, int64_t nnz_per_batch, int64_t n_batches,
                                      int64_t num_rows, uint64_t* keys_out, ce_stream_t stream) {
-  return presort_window_impl(indices, nnz_per_batch, n_batches, num_rows, keys_out, nullptr, 0, nullptr, nullptr, stream);
+  return launch_presort(indices, nullptr, nullptr, nullptr, nnz_per_batch, n_batches, num_rows, nullptr, nullptr, nullptr,
+                        keys_out, (hipStream_t)stream);
 }
 
 static int presort_window_src_impl(const int64_t* indices, int64_t nnz_per_batch, int64_t n_batches, int64_t num_rows,
-                                   const void* offsets, int32_t offsets_are_i64, int64_t offsets_batch_stride,
-                                   int64_t num_bags, int32_t include_last_offset, int64_t hook_features,
-                                   const int64_t* ids, uint64_t* keys_out, int64_t* seg_id_ranges, ce_stream_t stream) {
+                                   const BagLayout& L, const int64_t* ids, uint64_t* keys_out, int64_t* seg_id_ranges,
+                                   ce_stream_t stream) {
   if (nnz_per_batch == 0 || n_batches == 0) return CE_OK;
-  CE_REQUIRE(num_bags > 0 && offsets_batch_stride >= 0, CE_ERR_INVALID, "bad offsets");
-  CE_REQUIRE(offsets || num_bags == nnz_per_batch, CE_ERR_INVALID,
-             "offsets may only be NULL for the one-id-per-bag layout (num_bags == nnz_per_batch)");
+  // these entries refuse a bad layout before a bad size (the launcher, like the cache op's form, after): asked twice
   BagParams lay{};
-  RowGeom unused;
-  int rc = fill_params(lay, unused, 4, true, indices, nnz_per_batch, offsets, offsets_are_i64, num_bags,
-                       include_last_offset, nullptr, CE_MODE_SUM, hook_features);
+  int rc = window_layout(lay, L, indices, nnz_per_batch);
   if (rc) return rc;
-#ifdef CE_ABLATIONS
-  { const char* dbg = getenv("CE_PRESORT_DEBUG"); lay.debug = dbg ? atoi(dbg) : 0; }
-#endif
-  return presort_window_impl(indices, nnz_per_batch, n_batches, num_rows, keys_out, &lay, offsets_batch_stride, ids,
-                             seg_id_ranges, stream);
+  return launch_presort(indices, nullptr, nullptr, nullptr, nnz_per_batch, n_batches, num_rows, &L, ids, seg_id_ranges,
+                        keys_out, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_presort_window_src(const int64_t* indices, int64_t nnz_per_batch, int64_t n_batches,
                                          int64_t num_rows, const void* offsets, int32_t offsets_are_i64,
                                          int64_t offsets_batch_stride, int64_t num_bags, int32_t include_last_offset,
                                          int64_t hook_features, uint64_t* keys_out, ce_stream_t stream) {
-  return presort_window_src_impl(indices, nnz_per_batch, n_batches, num_rows, offsets, offsets_are_i64,
-                                 offsets_batch_stride, num_bags, include_last_offset, hook_features, nullptr, keys_out,
-                                 nullptr, stream);
+  return presort_window_src_impl(indices, nnz_per_batch, n_batches, num_rows,
+                                 {offsets, offsets_are_i64, offsets_batch_stride, num_bags, include_last_offset, hook_features},
+                                 nullptr, keys_out, nullptr, stream);
 }
 
 extern "C" int ce_bag_presort_window_src_excl(const int64_t* indices, int64_t nnz_per_batch, int64_t n_batches,
@@ -1728,9 +1657,9 @@ extern "C" int ce_bag_presort_window_src_excl(const int64_t* indices, int64_t nn
                                               int32_t include_last_offset, int64_t hook_features, const int64_t* ids,
                                               uint64_t* keys_out, int64_t* seg_id_ranges, ce_stream_t stream) {
   CE_REQUIRE(seg_id_ranges, CE_ERR_INVALID, "null seg_id_ranges");
-  return presort_window_src_impl(indices, nnz_per_batch, n_batches, num_rows, offsets, offsets_are_i64,
-                                 offsets_batch_stride, num_bags, include_last_offset, hook_features, ids, keys_out,
-                                 seg_id_ranges, stream);
+  return presort_window_src_impl(indices, nnz_per_batch, n_batches, num_rows,
+                                 {offsets, offsets_are_i64, offsets_batch_stride, num_bags, include_last_offset, hook_features},
+                                 ids, keys_out, seg_id_ranges, stream);
 }
 
 extern "C" int ce_bag_presort(const int64_t* indices, int64_t nnz, int64_t num_rows, uint64_t* keys_out,
@@ -1743,12 +1672,11 @@ extern "C" int ce_rows_axpy(float* weight, int64_t num_rows, int32_t dim, const 
   if (n == 0) return CE_OK;
   CE_REQUIRE(weight && index && src_rows, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(dim > 0 && n > 0 && n < (int64_t)INT32_MAX, CE_ERR_INVALID, "bad sizes");
-  CE_REQUIRE(num_rows > 0 && num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE_ROWS(num_rows);
   RowGeom r;
   int rc = row_geometry(dim, al16(weight) && al16(src_rows), r);
   if (rc) return rc;
-  const int u = r.nch == 1 ? 8 : (r.nch == 2 ? 4 : 2);       // k_rows_axpy's U
-  const int64_t per_block = (int64_t)(64 >> r.g_log2) * u * 4;
+  const int64_t per_block = (int64_t)(64 >> r.g_log2) * axpy_unroll(r.nch) * 4;
   dim3 grid(grid_for(n, (int)per_block)), block(256);
   hipStream_t s = (hipStream_t)stream;
   for_lanes(r.vec, r.nch, [&](auto l) {

@@ -774,13 +774,6 @@ static int update_check(const UpdateCall& c, const EntryRules& e, RowGeom& r) {
   return row_geometry(c.dim, al16(c.weight), r);
 }
 
-// the one place that turns (weight_dtype, RowGeom) into the table's row type and the lane shape of a launch:
-// f(Lanes<VT, N>, ActTag<WT>) -- an fp32 table in either lane form, a 16-bit table in vector lanes
-template <typename F> static inline void for_table(int weight_dtype, const RowGeom& r, F&& f) {
-  if (weight_dtype == CE_ACT_F32) for_lanes(r.vec, r.nch, [&](auto l) { f(l, ActTag<float>{}); });
-  else for_w16(r.nch, weight_dtype, f);
-}
-
 static void launch_mark(const void* src, bool keys, int64_t n, int64_t num_rows, uint8_t* flags,
                         unsigned long long* counter, hipStream_t s) {
   const dim3 g(grid_for(n, 256)), b(256);

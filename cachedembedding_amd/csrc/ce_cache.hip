@@ -50,6 +50,14 @@
 #include "ce_cache_worker.h"
 
 
+// the window's keys, written by the call's last kernel (ce_cache_prepare_ids_keys)
+struct KeysTail {
+  int64_t n_batches, nnz_per_batch;
+  int32_t src_keys;
+  ce::BagLayout lay;
+  uint64_t* keys_out;
+};
+
 struct ce_cache {
   ce_cache_config_t cfg;
   ce::Layout L;
@@ -129,16 +137,7 @@ struct ce_cache {
     long long sel_out_job = 0;
     int sel_wbuf = 0, sel_n_vblocks = 0;
     const void* prof = nullptr;      // the phase timers the first half recorded into (they may be switched off / on in between)
-    struct {
-      int64_t n_batches, nnz_per_batch;
-      int32_t src_keys;
-      const void* offsets;
-      int32_t offsets_are_i64;
-      int64_t offsets_batch_stride, num_bags;
-      int32_t include_last_offset;
-      int64_t hook_features;
-      uint64_t* keys_out;
-    } tail;
+    KeysTail tail{};
   } pend;
 };
 
@@ -861,18 +860,6 @@ static int select_and_stage(ce_cache* h, const SelArgs& a, int* pmark_io) {
   return CE_OK;
 }
 
-// the window's keys, written by the call's last kernel (ce_cache_prepare_ids_keys)
-struct KeysTail {
-  int64_t n_batches, nnz_per_batch;
-  int32_t src_keys;
-  const void* offsets;
-  int32_t offsets_are_i64;
-  int64_t offsets_batch_stride, num_bags;
-  int32_t include_last_offset;
-  int64_t hook_features;
-  uint64_t* keys_out;
-};
-
 // how the ids are marked: rows in frequency order (idx_map present) -- the hot rows sit in the lowest bitmap words, an
 // LDS window absorbs them, cold lookups issue their atomicOr directly; rows in id order -- hot rows are scattered,
 // every wave would hammer their words (421 us per 3.4 M ids), so equal words of a wave are merged first.  (rocprofv3,
@@ -1026,9 +1013,7 @@ static int chained_first_half(ce_cache* h, const int64_t* ids, int64_t n, int64_
   x.sel_pending = true;
   x.sel_s = s; x.sel_n = n; x.sel_steady = steady; x.sel_out_job = out_job; x.sel_wbuf = wbuf;
   x.sel_n_vblocks = (int)cdiv(h->cfg.cuda_row_num, 4096);
-  if (tail)
-    x.tail = {tail->n_batches, tail->nnz_per_batch, tail->src_keys, tail->offsets, tail->offsets_are_i64,
-              tail->offsets_batch_stride, tail->num_bags, tail->include_last_offset, tail->hook_features, tail->keys_out};
+  if (tail) x.tail = *tail;
   (void)L;
   if (split) {
     x.active = true;
@@ -1285,9 +1270,7 @@ static int prepare_ids_impl(ce_cache_t* h, const int64_t* ids, int64_t n, int64_
   x.chained = false;
   x.sel_pending = defer_sel;
   x.sel_s = s; x.sel_n = n; x.sel_steady = steady; x.sel_out_job = out_job; x.sel_wbuf = wbuf; x.sel_n_vblocks = n_vblocks;
-  if (tail)
-    x.tail = {tail->n_batches, tail->nnz_per_batch, tail->src_keys, tail->offsets, tail->offsets_are_i64,
-              tail->offsets_batch_stride, tail->num_bags, tail->include_last_offset, tail->hook_features, tail->keys_out};
+  if (tail) x.tail = *tail;
   if (split) {
     x.active = true;
     CE_LAUNCH_CHECK();
@@ -1306,7 +1289,7 @@ static int launch_slots_keys(ce_cache* h) {
   const ce_stream_t stream = (ce_stream_t)s;
   const int lfu = c.evict_strategy == CE_EVICT_LFU;
   PhaseProf* const prof = (h->prof && (const void*)h->prof == x.prof) ? h->prof : nullptr;
-  const decltype(x.tail)* const tail = x.has_tail ? &x.tail : nullptr;
+  const KeysTail* const tail = x.has_tail ? &x.tail : nullptr;
   int rc = CE_OK;
   if (n > 0 && lfu) {
     // ~8 k lookups per workgroup keep the LDS hash table (8192 entries) below half full
@@ -1314,18 +1297,16 @@ static int launch_slots_keys(ce_cache* h) {
                        c.inverted_cached_idx, c.freq_cnter, (const Ctl*)h->ctl);
     if (tail) {
       rc = tail->src_keys
-               ? ce_bag_presort_window_src(slots_out, tail->nnz_per_batch, tail->n_batches, C, tail->offsets,
-                                           tail->offsets_are_i64, tail->offsets_batch_stride, tail->num_bags,
-                                           tail->include_last_offset, tail->hook_features, tail->keys_out, stream)
+               ? ce_bag_presort_window_src(slots_out, tail->nnz_per_batch, tail->n_batches, C, tail->lay.offsets,
+                                           tail->lay.offsets_are_i64, tail->lay.offsets_batch_stride, tail->lay.num_bags,
+                                           tail->lay.include_last_offset, tail->lay.hook_features, tail->keys_out, stream)
                : ce_bag_presort_window(slots_out, tail->nnz_per_batch, tail->n_batches, C, tail->keys_out, stream);
       if (rc) return rc;
     }
   } else if (n > 0 && tail) {
     // rows -> slots AND the window's keys in one pass (k_slots would write 8 bytes per id for the presort to read back)
     rc = presort_window_from_rows(slots_out, tail->nnz_per_batch, tail->n_batches, C, c.inverted_cached_idx,
-                                  &h->ctl->status, tail->src_keys, tail->offsets, tail->offsets_are_i64,
-                                  tail->offsets_batch_stride, tail->num_bags, tail->include_last_offset,
-                                  tail->hook_features, tail->keys_out, s);
+                                  &h->ctl->status, tail->src_keys, tail->lay, tail->keys_out, s);
     if (rc) return rc;
   } else if (n > 0) {
     hipLaunchKernelGGL(k_slots, dim3(grid_for(n, 256 * 4)), dim3(256), 0, s, slots_out, n, c.inverted_cached_idx,
@@ -1458,8 +1439,8 @@ extern "C" int ce_cache_prepare_ids_keys(ce_cache_t* h, const int64_t* ids, int6
                                          int32_t include_last_offset, int64_t hook_features, uint64_t* keys_out,
                                          ce_stream_t stream) {
   CE_REQUIRE(n_batches > 0 && nnz_per_batch > 0 && keys_out, CE_ERR_INVALID, "bad window shape / null keys_out");
-  KeysTail t{n_batches, nnz_per_batch, src_keys, offsets, offsets_are_i64, offsets_batch_stride, num_bags,
-             include_last_offset, hook_features, keys_out};
+  KeysTail t{n_batches, nnz_per_batch, src_keys,
+             {offsets, offsets_are_i64, offsets_batch_stride, num_bags, include_last_offset, hook_features}, keys_out};
   return prepare_ids_impl(h, ids, n_batches * nnz_per_batch, slots_out, stream, 0, &t);
 }
 
@@ -1470,8 +1451,8 @@ extern "C" int ce_cache_prepare_ids_begin(ce_cache_t* h, const int64_t* ids, int
                                           ce_stream_t stream) {
   CE_REQUIRE(n_batches > 0 && nnz_per_batch > 0, CE_ERR_INVALID, "bad window shape");
   if (!keys_out) return prepare_ids_impl(h, ids, n_batches * nnz_per_batch, slots_out, stream, 0, nullptr, 1);
-  KeysTail t{n_batches, nnz_per_batch, src_keys, offsets, offsets_are_i64, offsets_batch_stride, num_bags,
-             include_last_offset, hook_features, keys_out};
+  KeysTail t{n_batches, nnz_per_batch, src_keys,
+             {offsets, offsets_are_i64, offsets_batch_stride, num_bags, include_last_offset, hook_features}, keys_out};
   return prepare_ids_impl(h, ids, n_batches * nnz_per_batch, slots_out, stream, 0, &t, 1);
 }
 

@@ -83,15 +83,24 @@ static inline int grid_for(int64_t work_items, int per_block) {
   return (int)b;
 }
 
+// The bag layout of a window's batches, as ce_bag_presort_window_src takes it: batch b's offsets start
+// offsets_batch_stride elements after batch b - 1's (offsets == nullptr: one id per bag, in order).
+struct BagLayout {
+  const void* offsets;
+  int32_t offsets_are_i64;
+  int64_t offsets_batch_stride, num_bags;
+  int32_t include_last_offset;
+  int64_t hook_features;
+};
+
 // ce_bag.hip, for the cache manager (ce_cache.hip): the window presort with the cache op's last step folded in.
 // slots_io holds the ROW of every id (what k_mark left there; -1 = no lookup); the kernel turns it into the slot in
 // place (inverted[row]; -1 everywhere when *status != CE_OK) and writes the window's keys in the same pass -- instead
-// of k_slots writing 8 bytes per id that the presort reads straight back.  lay_* as ce_bag_presort_window_src;
+// of k_slots writing 8 bytes per id that the presort reads straight back.  lay as ce_bag_presort_window_src;
 // src_keys == 0: keys = row << 32 | lookup in segment (ce_bag_presort_window).
 int presort_window_from_rows(int64_t* slots_io, int64_t nnz_per_batch, int64_t n_batches, int64_t num_rows,
-                             const int32_t* inverted, const int* status, int32_t src_keys, const void* offsets,
-                             int32_t offsets_are_i64, int64_t offsets_batch_stride, int64_t num_bags,
-                             int32_t include_last_offset, int64_t hook_features, uint64_t* keys_out, hipStream_t stream);
+                             const int32_t* inverted, const int* status, int32_t src_keys, const BagLayout& lay,
+                             uint64_t* keys_out, hipStream_t stream);
 
 // ce_host.hip: pins the CALLING thread to the CPUs of the current GPU's NUMA node (sysfs local_cpulist of its PCI
 // function, intersected with the CPUs the process may use); no-op when that cannot be read or CE_NUMA_BIND=0.  For
@@ -145,6 +154,9 @@ static inline bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 // (the alignment that rows of dim % 4 == 0 elements keep there: dim = 20, 100 included)
 static inline bool act_aligned(const void* q, int act) { return (((uintptr_t)q) & (act == CE_ACT_F32 ? 15 : 7)) == 0; }
 
+#define CE_REQUIRE_ROWS(num_rows) \
+  CE_REQUIRE((num_rows) > 0 && (num_rows) < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range")
+
 #define CE_REQUIRE_ACT(act)                                                                            \
   CE_REQUIRE((act) == CE_ACT_F32 || (act) == CE_ACT_BF16 || (act) == CE_ACT_F16, CE_ERR_INVALID,       \
              "unknown activation dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)(act))
@@ -185,6 +197,13 @@ template <typename F> static inline void for_w16(int nch, int weight_dtype, F&& 
     if (nch == 1) f(Lanes<f32x4, 1>{}, w); else if (nch == 2) f(Lanes<f32x4, 2>{}, w); else f(Lanes<f32x4, 4>{}, w);
   };
   if (weight_dtype == CE_ACT_BF16) lanes(ActTag<bf16_t>{}); else lanes(ActTag<f16_t>{});
+}
+
+// the one place that turns (weight_dtype, RowGeom) into the table's row type and the lane shape of a launch:
+// f(Lanes<VT, N>, ActTag<WT>) -- an fp32 table in either lane form, a 16-bit table in vector lanes
+template <typename F> static inline void for_table(int weight_dtype, const RowGeom& r, F&& f) {
+  if (weight_dtype == CE_ACT_F32) for_lanes(r.vec, r.nch, [&](auto l) { f(l, ActTag<float>{}); });
+  else for_w16(r.nch, weight_dtype, f);
 }
 
 }  // namespace ce

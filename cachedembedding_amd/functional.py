@@ -94,25 +94,20 @@ class _BagFn(torch.autograd.Function):
             and mode == _lib.CE_MODE_SUM and num_bags == indices.numel()
         # the ce_*_act entries for every dtype: the kernels store the output as `act` (CE_ACT_F32: the fp32 form)
         act = _lib.ACT_DTYPES[out_dtype]
+        if from_keys:
+            # one id per bag: out[bag] = W[slot], and the window's keys hold (slot, output row) grouped by slot
+            args = (indices.numel(), ptr(presorted.keys), ptr(out), act, stream_ptr())
+        else:
+            args = (ptr(indices), indices.numel(), ptr(offsets), int(offsets.dtype == torch.int64), num_bags,
+                    int(include_last), ptr(psw), mode, hook_features, ptr(out), act, stream_ptr())
         if w16:
             # a 16-bit table: the same two kernels with the row type as a further argument (rows up-converted exactly,
             # fp32 sums, one rounding on the store; from keys with out_dtype == the table's dtype: a bit copy)
-            wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], weight.shape[0], dim)
-            if from_keys:
-                check(lib.ce_bag_forward_src_keys_w16(*wd, indices.numel(), ptr(presorted.keys), ptr(out), act,
-                                                      stream_ptr()))
-            else:
-                check(lib.ce_bag_forward_w16(*wd, ptr(indices), indices.numel(), ptr(offsets),
-                                             int(offsets.dtype == torch.int64), num_bags, int(include_last), ptr(psw),
-                                             mode, hook_features, ptr(out), act, stream_ptr()))
-        elif from_keys:
-            # one id per bag: out[bag] = W[slot], and the window's keys hold (slot, output row) grouped by slot
-            check(lib.ce_bag_forward_src_keys_act(ptr(weight), weight.shape[0], dim, indices.numel(),
-                                                  ptr(presorted.keys), ptr(out), act, stream_ptr()))
+            fn = lib.ce_bag_forward_src_keys_w16 if from_keys else lib.ce_bag_forward_w16
+            check(fn(ptr(weight), _lib.ACT_DTYPES[weight.dtype], weight.shape[0], dim, *args))
         else:
-            check(lib.ce_bag_forward_act(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(),
-                                         ptr(offsets), int(offsets.dtype == torch.int64), num_bags, int(include_last),
-                                         ptr(psw), mode, hook_features, ptr(out), act, stream_ptr()))
+            fn = lib.ce_bag_forward_src_keys_act if from_keys else lib.ce_bag_forward_act
+            check(fn(ptr(weight), weight.shape[0], dim, *args))
         # bwd_scale (scale_grad_by_freq): per-lookup factor of the backward only; it takes the place of psw there
         ctx.save_for_backward(indices, offsets, psw if bwd_scale is None else bwd_scale.contiguous())
         ctx.weight = weight
@@ -155,14 +150,10 @@ class _BagFn(torch.autograd.Function):
             # presorted keys and from source-row keys; what it does not take was refused before the forward.
             with torch.no_grad():
                 ws = fused.workspace_step(R, nnz, dim, weight.device)
-                mom = fused.momentum if rowwise else None
-                stoch = fused.rounding == "stochastic" and weight.dtype in _lib.W16_DTYPES
                 wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
-                tail = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), float(fused.lr),
-                        float(fused.eps) if rowwise else 0.0,
-                        _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
-                        _lib.CE_ROUND_STOCHASTIC if stoch else _lib.CE_ROUND_NEAREST,
-                        int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr())
+                # (an fp32 table is never rounded, whatever fused.rounding says)
+                w16 = weight.dtype in _lib.W16_DTYPES
+                tail = _update_tail(fused, rowwise, fused.rounding if w16 else "nearest", ws)
                 if src:
                     check(lib.ce_bag_backward_update_compact_src(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                 else:
@@ -174,12 +165,8 @@ class _BagFn(torch.autograd.Function):
             # slots + offsets -- presorted keys of either kind are not needed and ignored
             with torch.no_grad():
                 ws = fused.workspace_sorted(R, nnz, dim, weight.device)
-                mom = fused.momentum
-                check(lib.ce_bag_backward_update_sorted(
-                    ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim, *slots_args, act, ptr(fused.row_of_slot),
-                    ptr(mom), mom.numel(), float(fused.lr), float(fused.eps), _lib.CE_OPT_ROWWISE_ADAGRAD,
-                    _lib.CE_ROUND_STOCHASTIC if fused.rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
-                    int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr()))
+                check(lib.ce_bag_backward_update_sorted(ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim, *slots_args,
+                                                        act, *_update_tail(fused, True, fused.rounding, ws)))
             return (None,) * 14
         if weight.dtype in _lib.W16_DTYPES:
             # 16-bit table (the combinations it does not take were refused in embedding_bag, before the forward)
@@ -188,12 +175,7 @@ class _BagFn(torch.autograd.Function):
                 # mark + the dense backward into an fp32 accumulator + one apply pass that rounds every row once
                 with torch.no_grad():
                     ws = fused.workspace_w16(R, dim, weight.device)
-                    mom = fused.momentum if rowwise else None
-                    tail = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), float(fused.lr),
-                            float(fused.eps) if rowwise else 0.0,
-                            _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
-                            _lib.CE_ROUND_STOCHASTIC if fused.rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
-                            int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr())
+                    tail = _update_tail(fused, rowwise, fused.rounding, ws)
                     if src:
                         check(lib.ce_bag_backward_update_src_w16(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                     else:
@@ -290,6 +272,17 @@ class _BagFn(torch.autograd.Function):
         return gw, None, None, gpsw, None, None, None, None, None, None, None, None, None, None
 
 
+def _update_tail(fused, rowwise: bool, rounding: str, ws: torch.Tensor) -> tuple:
+    """what the ce_bag_backward_update_* entries take behind the lookups: row_of_slot, momentum and its length, lr, eps,
+    optimizer, rounding, seed, workspace, stream.  `rounding` is the caller's: the entries do not agree on when
+    fused.rounding counts."""
+    mom = fused.momentum if rowwise else None
+    return (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), float(fused.lr),
+            float(fused.eps) if rowwise else 0.0, _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
+            _lib.CE_ROUND_STOCHASTIC if rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
+            int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr())
+
+
 _DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
 
 
@@ -348,14 +341,22 @@ def renorm_rows_(weight: torch.Tensor, indices: torch.Tensor, max_norm: float, n
                                  float(norm_type), ptr(ws), ws.numel(), stream_ptr()))
 
 
+def _cached_bytes(self, attr: str, need: int, device, zero: bool) -> torch.Tensor:
+    """the byte buffer kept in self.<attr>: reused while it holds `need` bytes on `device`, else dropped BEFORE its
+    successor is allocated -- zero-filled (for kernels that leave it zero-filled again) or uninitialised"""
+    ws = getattr(self, attr)
+    if ws is not None and ws.numel() >= need and ws.device == device:
+        return ws
+    del ws
+    setattr(self, attr, None)
+    setattr(self, attr, (torch.zeros if zero else torch.empty)(need, dtype=torch.uint8, device=device))
+    return getattr(self, attr)
+
+
 def _workspace_w16(self, num_rows: int, dim: int, device) -> torch.Tensor:
     """workspace of the 16-bit table's update (fp32 accumulator [num_rows, dim] -- twice the 16-bit rows it serves --,
     byte flags, the step counter): zero-filled once; every call leaves it zero-filled except the counter"""
-    need = lib.ce_bag_backward_w16_workspace(num_rows, dim)
-    if self._ws16 is None or self._ws16.numel() < need or self._ws16.device != device:
-        self._ws16 = None
-        self._ws16 = torch.zeros(need, dtype=torch.uint8, device=device)
-    return self._ws16
+    return _cached_bytes(self, "_ws16", lib.ce_bag_backward_w16_workspace(num_rows, dim), device, zero=True)
 
 
 ACCUMULATORS = ("cache", "step")
@@ -426,10 +427,7 @@ class FusedSGD:
     workspace_step = _workspace_step
 
     def workspace(self, num_rows: int, nnz: int, device) -> torch.Tensor:
-        need = lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return _cached_bytes(self, "_ws", lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz), device, zero=False)
 
 
 class FusedRowwiseAdagrad:
@@ -490,18 +488,12 @@ class FusedRowwiseAdagrad:
     def workspace_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
         """workspace of the deterministic path (sort arrays, partial rows): nothing in it needs initialising"""
         need = lib.ce_bag_backward_update_sorted_workspace(num_rows, nnz, dim)
-        if self._ws_sorted is None or self._ws_sorted.numel() < need or self._ws_sorted.device != device:
-            self._ws_sorted = None
-            self._ws_sorted = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws_sorted
+        return _cached_bytes(self, "_ws_sorted", need, device, zero=False)
 
     def workspace(self, num_rows: int, dim: int, device) -> torch.Tensor:
         # zero-filled once; every call of the kernels leaves it zero-filled again
         need = lib.ce_bag_backward_rowwise_adagrad_workspace(num_rows, dim)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = None
-            self._ws = torch.zeros(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return _cached_bytes(self, "_ws", need, device, zero=True)
 
 
 def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional[torch.Tensor] = None,
