@@ -38,6 +38,8 @@ CE_ROUND_NEAREST = 0
 CE_ROUND_STOCHASTIC = 1
 CE_SORTED_CHUNK = 64
 CE_COMPACT_BLOCK = 4096
+CE_ACC_CACHE = 0
+CE_ACC_STEP = 1
 CE_TRANSPORT_ZEROCOPY = 0
 CE_TRANSPORT_STAGED = 1
 CE_TRANSPORT_WORKER = 2
@@ -97,6 +99,10 @@ _STREAM = [c_void_p]
 _ADAGRAD_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t] + _STREAM
 _W16 = [c_void_p, c_int32]      # the 16-bit table and its CE_ACT_* code
 _W16_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
+# keys, row_of_slot, momentum, momentum_rows, lr (device pointer), eps, optimizer, rounding, seed, accumulator, workspace,
+# workspace_bytes, stream
+_LRDEV_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int32, c_int32, c_uint64, c_int32, c_void_p,
+                       c_size_t] + _STREAM
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -162,6 +168,13 @@ SIGNATURES = {
     "ce_bag_backward_update_compact_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
     "ce_bag_backward_update_compact": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL),
     "ce_bag_backward_update_compact_src": (c_int, _W16 + _SRC[1:] + _ACT + _W16_TAIL),
+    # the learning rate as ONE fp32 in device memory, read by the kernels when they run: the _act / _w16 lists with lr a
+    # pointer; the update pair also takes the accumulator (CE_ACC_*) behind the seed and covers the cache-sized fp32
+    # Adagrad, the cache-sized 16-bit and the step-sized entries
+    "ce_bag_backward_sgd_lrdev": (c_int, _BAG + _ACT + [c_void_p] + _KEYS + _STREAM),
+    "ce_bag_backward_sgd_src_lrdev": (c_int, _SRC + _ACT + [c_void_p] + _KEYS + [c_void_p] + _STREAM),
+    "ce_bag_backward_update_lrdev": (c_int, _W16 + _BAG[1:] + _ACT + _LRDEV_TAIL),
+    "ce_bag_backward_update_src_lrdev": (c_int, _W16 + _SRC[1:] + _ACT + _LRDEV_TAIL),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),

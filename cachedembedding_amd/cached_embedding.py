@@ -7,14 +7,14 @@ constructor order and forward signature per SURVEY.md 8(b) / Appendix A.7.
 """
 from __future__ import annotations
 
-from typing import Callable, Iterator, List, Optional, Tuple
+from typing import Callable, Iterator, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
-from .functional import FusedRowwiseAdagrad, FusedSGD, check_accumulator, embedding_bag
+from .functional import FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_lr, check_lr_path, embedding_bag
 
 
 class CachedEmbeddingBag(nn.Module):
@@ -107,10 +107,16 @@ class CachedEmbeddingBag(nn.Module):
     def set_cache_mgr_async_copy(self, flag: bool):
         self.cache_weight_mgr.set_async_copy(flag)
 
-    def set_fused_sgd(self, lr: Optional[float], deterministic: bool = False, accumulator: str = "cache"):
+    def set_fused_sgd(self, lr: Union[float, torch.Tensor, None], deterministic: bool = False,
+                      accumulator: str = "cache"):
         """Apply SGD(lr) to the cache rows inside backward (K13+K14 fused).  lr=None restores
         the plain autograd behaviour (grad handed to torch.optim).  accumulator="step" (a 16-bit table only): the
-        update's fp32 accumulator has a row per lookup of the step at most instead of one per cache row."""
+        update's fp32 accumulator has a row per lookup of the step at most instead of one per cache row.
+        lr may be a tensor (functional.check_lr: one fp32 element on the cache's device): it is kept by reference and
+        read by the kernels when they run, so fill_ / copy_ into it changes the rate of the next step -- also of a
+        step replayed from a hipGraph.  Not with deterministic=True."""
+        if isinstance(lr, torch.Tensor):                        # (a float or None: nothing new is looked at)
+            check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
             check_accumulator("sgd", self.table_dtype, accumulator, bool(deterministic), self.weight_rounding)
         if lr is not None and self.fused_adagrad.lr is not None:
@@ -121,8 +127,8 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_sgd.deterministic = deterministic
         self.fused_sgd.accumulator = accumulator
 
-    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8, deterministic: bool = False,
-                                  accumulator: str = "cache"):
+    def set_fused_rowwise_adagrad(self, lr: Union[float, torch.Tensor, None], eps: float = 1e-8,
+                                  deterministic: bool = False, accumulator: str = "cache"):
         """Apply exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0; the reference's baseline
         --adagrad) to the cache rows inside backward.  The state is one fp32 accumulator per row of the host table,
         `cache_weight_mgr.momentum1` (device, zeroed when first enabled, indexed like `weight`); it stays in HBM and
@@ -132,7 +138,10 @@ class CachedEmbeddingBag(nn.Module):
         A 16-bit table needs set_weight_rounding("nearest") with it: the sorted fold does not round stochastically.
         accumulator="step": the atomic update with an fp32 accumulator of min(lookups of a step, cache rows) rows
         instead of one as large as the cache (FusedRowwiseAdagrad); not with deterministic=True, and a 16-bit table
-        needs set_weight_rounding("nearest") first."""
+        needs set_weight_rounding("nearest") first.
+        lr may be a tensor, as in set_fused_sgd; not with deterministic=True."""
+        if isinstance(lr, torch.Tensor):                        # (a float or None: nothing new is looked at)
+            check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
             check_accumulator("rowwise_adagrad", self.table_dtype, accumulator, bool(deterministic),
                               self.weight_rounding)

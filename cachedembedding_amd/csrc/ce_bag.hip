@@ -691,8 +691,11 @@ __global__ __launch_bounds__(1024) void k_bag_presort_seg(const int64_t* __restr
   }
 }
 
-template <typename VT, int NCH, typename KT, int R, typename AT>
-__global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
+// LRDEV: the scale is -(*lr_dev), one fp32 in device memory read when the kernel runs (the fused SGD step of the
+// ce_*_lrdev entries: a replayed graph follows a learning-rate schedule), instead of p.alpha.  A separate instantiation,
+// so the by-value one keeps its instructions; a negation, so the bits are those of alpha = -lr.
+template <typename VT, int NCH, typename KT, int R, typename AT, bool LRDEV = false>
+__global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p, const float* __restrict__ lr_dev) {
   using K = KeyOps<KT>;
   using A = Act<AT, VT>;
   __shared__ KT keys[kBwdTile];
@@ -707,6 +710,8 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
   const int rowlen = p.rowlen;
   const int dim = rowlen * (int)(sizeof(VT) / 4);
   const typename A::V* __restrict__ GO = (const typename A::V*)p.grad_out;
+  float alpha = p.alpha;
+  if constexpr (LRDEV) alpha = -*lr_dev;        // uniform over the launch: once per thread, not per lookup
   // tile_len <= kBwdTile is chosen by the launcher so that the tile count is a multiple of the CU count
   // (425,984 lookups -> 512 tiles of 832: two per CU, instead of 416 tiles = 1 or 2 per CU).
   // presorted: the tiles are tile_len consecutive positions of the segment-padded key array (any alignment)
@@ -742,7 +747,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
       }
       if (j >= 0) {
         const int bag = find_bag(p, j);
-        float sc = p.alpha;
+        float sc = alpha;
         if (p.psw) sc *= p.psw[j];
         if (p.mode == CE_MODE_MEAN) {
           const int len = bag_end(p, bag) - ld_off(p, bag);
@@ -842,8 +847,10 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p) {
 // clock and channel -- 6.3 M lane-ops per launch = 24 us that do not overlap with the gather (profiles/r03_probe_*).
 // AT: grad_out's element type -- only the gather changes; fold, old rows and update are fp32 whatever it is.
 // PAIR (16-bit AT, f32x4 lanes): the gather of two keys' gradient rows is ONE 16-byte load per lane (see u32x4 above).
-template <typename VT, int NCH, int R, bool EXCL, typename AT, bool PAIR = false>
-__global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t total, const long long* __restrict__ seg_ranges) {
+// LRDEV: alpha = -(*lr_dev), read from device memory when the kernel runs (see k_bag_bwd_tile).
+template <typename VT, int NCH, int R, bool EXCL, typename AT, bool PAIR = false, bool LRDEV = false>
+__global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t total, const long long* __restrict__ seg_ranges,
+                                                        const float* __restrict__ lr_dev) {
   using A = Act<AT, VT>;
   static_assert(!PAIR || (sizeof(typename A::V) == 8 && R % 2 == 0), "PAIR: 4 x 16 bit per lane, keys two at a time");
   __shared__ unsigned long long lk[256 * (R > 4 ? R : 4)];     // ngroups * kc, worst case G = 1
@@ -879,7 +886,8 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
   const int64_t s0 = share_of(p, grp, ngroups) * share;
   const int64_t s1 = min(total, s0 + share);
   if (s0 >= s1) return;
-  const float alpha = p.alpha;
+  float alpha = p.alpha;
+  if constexpr (LRDEV) alpha = -*lr_dev;        // uniform over the launch: once per thread, not per key
   const int kc = 4 * G > R ? 4 * G : R;         // keys staged per refill (G is a power of two: a multiple of R)
   unsigned long long* mylk = lk + grp * kc;
   VT acc[NCH];
@@ -1224,7 +1232,8 @@ static dim3 keys_grid(int64_t total, int g_log2, int per_cu) {
 
 // grad accumulation / fused SGD by target row: grouped segments (ce_bag_presort*) are walked as they are, otherwise
 // the kernel sorts 1024-lookup tiles itself
-static int launch_bwd_scatter(BagParams& p, const RowGeom& r, int act, hipStream_t s) {
+// lr_dev (the fused SGD step only): non-NULL = the scale is -(*lr_dev) read by the kernel, p.alpha is not looked at
+static int launch_bwd_scatter(BagParams& p, const RowGeom& r, int act, const float* lr_dev, hipStream_t s) {
   // sorted keys: a tile count that is a multiple of the CU count (425,984 keys -> 512 tiles of 832, two per CU,
   // instead of 416 tiles = one or two per CU): 80 -> 72.5 us.  More, smaller tiles lose to the per-tile prologue
   // (3/CU 77 us, 4/CU 85 us, 8/CU 94 us), and the self-sorting path does not gain (92 us either way).
@@ -1241,8 +1250,11 @@ static int launch_bwd_scatter(BagParams& p, const RowGeom& r, int act, hipStream
     using VT = typename decltype(l)::VT;
     using AT = typename decltype(a)::AT;
     constexpr int N = decltype(l)::NCH, R = tile_unroll<VT, N>();
-    if (k32) hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, uint32_t, R, AT>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, unsigned long long, R, AT>), grid, block, 0, s, p);
+    auto launch = [&](auto key, auto dev) {
+      hipLaunchKernelGGL((k_bag_bwd_tile<VT, N, decltype(key), R, AT, decltype(dev)::value>), grid, block, 0, s, p, lr_dev);
+    };
+    if (lr_dev) k32 ? launch(uint32_t{}, std::true_type{}) : launch(0ull, std::true_type{});
+    else k32 ? launch(uint32_t{}, std::false_type{}) : launch(0ull, std::false_type{});
   });
   CE_LAUNCH_CHECK();
   return CE_OK;
@@ -1341,8 +1353,8 @@ extern "C" int ce_bag_forward(const float* weight, int64_t num_rows, int32_t dim
 }
 
 // dst += alpha * (the lookups' gradient rows), by slots + offsets: the dense gradient (dst = grad_weight, alpha = 1)
-// and the fused SGD step (dst = the table, alpha = -lr)
-static int backward_scatter_impl(float* dst, float alpha, int64_t num_rows, int32_t dim, const int64_t* indices,
+// and the fused SGD step (dst = the table, alpha = -lr; or lr_dev non-NULL: alpha = -(*lr_dev), read by the kernel)
+static int backward_scatter_impl(float* dst, float alpha, const float* lr_dev, int64_t num_rows, int32_t dim, const int64_t* indices,
                                  int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
                                  int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
                                  int64_t hook_features, const void* grad_out, int act, const uint64_t* presorted,
@@ -1361,7 +1373,7 @@ static int backward_scatter_impl(float* dst, float alpha, int64_t num_rows, int3
   CE_REQUIRE_ROWS(num_rows);
   p.num_rows = (uint32_t)num_rows;
   p.presorted = (const unsigned long long*)presorted;
-  return launch_bwd_scatter(p, r, act, (hipStream_t)stream);
+  return launch_bwd_scatter(p, r, act, lr_dev, (hipStream_t)stream);
 }
 
 extern "C" int ce_bag_backward_dense(float* grad_weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -1369,7 +1381,7 @@ extern "C" int ce_bag_backward_dense(float* grad_weight, int64_t num_rows, int32
                                      int64_t num_bags, int32_t include_last_offset,
                                      const float* per_sample_weights, int32_t mode, int64_t hook_features,
                                      const float* grad_out, ce_stream_t stream) {
-  return backward_scatter_impl(grad_weight, 1.f, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+  return backward_scatter_impl(grad_weight, 1.f, nullptr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                                include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
                                nullptr, stream);
 }
@@ -1380,7 +1392,7 @@ extern "C" int ce_bag_backward_dense_act(float* grad_weight, int64_t num_rows, i
                                          const float* per_sample_weights, int32_t mode, int64_t hook_features,
                                          const void* grad_out, int32_t act_dtype, const uint64_t* presorted_keys,
                                          ce_stream_t stream) {
-  return backward_scatter_impl(grad_weight, 1.f, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+  return backward_scatter_impl(grad_weight, 1.f, nullptr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                                include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
                                presorted_keys, stream);
 }
@@ -1392,7 +1404,7 @@ extern "C" int ce_bag_backward_dense_presorted(float* grad_weight, int64_t num_r
                                                int32_t mode, int64_t hook_features, const float* grad_out,
                                                const uint64_t* presorted_keys, ce_stream_t stream) {
   CE_REQUIRE(presorted_keys, CE_ERR_INVALID, "null presorted_keys");
-  return backward_scatter_impl(grad_weight, 1.f, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+  return backward_scatter_impl(grad_weight, 1.f, nullptr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                                include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
                                presorted_keys, stream);
 }
@@ -1401,7 +1413,7 @@ extern "C" int ce_bag_backward_sgd(float* weight, int64_t num_rows, int32_t dim,
                                    int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
                                    int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
                                    int64_t hook_features, const float* grad_out, float lr, ce_stream_t stream) {
-  return backward_scatter_impl(weight, -lr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+  return backward_scatter_impl(weight, -lr, nullptr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                                include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
                                nullptr, stream);
 }
@@ -1411,7 +1423,19 @@ extern "C" int ce_bag_backward_sgd_act(float* weight, int64_t num_rows, int32_t 
                                        int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
                                        int64_t hook_features, const void* grad_out, int32_t act_dtype, float lr,
                                        const uint64_t* presorted_keys, ce_stream_t stream) {
-  return backward_scatter_impl(weight, -lr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+  return backward_scatter_impl(weight, -lr, nullptr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
+                               presorted_keys, stream);
+}
+
+// lr in device memory: the same call with the pointer handed to the kernel (alpha is not looked at)
+extern "C" int ce_bag_backward_sgd_lrdev(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                         int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                         int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                         int64_t hook_features, const void* grad_out, int32_t act_dtype, const float* lr,
+                                         const uint64_t* presorted_keys, ce_stream_t stream) {
+  CE_REQUIRE(lr, CE_ERR_INVALID, "lr: null device pointer");
+  return backward_scatter_impl(weight, 0.f, lr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                                include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
                                presorted_keys, stream);
 }
@@ -1423,7 +1447,7 @@ extern "C" int ce_bag_backward_sgd_presorted(float* weight, int64_t num_rows, in
                                              const float* grad_out, float lr, const uint64_t* presorted_keys,
                                              ce_stream_t stream) {
   CE_REQUIRE(presorted_keys, CE_ERR_INVALID, "null presorted_keys");
-  return backward_scatter_impl(weight, -lr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+  return backward_scatter_impl(weight, -lr, nullptr, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                                include_last_offset, per_sample_weights, mode, hook_features, grad_out, CE_ACT_F32,
                                presorted_keys, stream);
 }
@@ -1431,8 +1455,10 @@ extern "C" int ce_bag_backward_sgd_presorted(float* weight, int64_t num_rows, in
 // keys = row << 32 | grad_out row (ce_bag_presort_window_src); alpha * grad_out rows are folded into dst.
 // seg_ranges (fused SGD only): the batch's segment id ranges from ce_bag_presort_window_src_excl -> owner-exclusive
 // rows are updated with plain read-modify-writes (k_bag_bwd_stream<EXCL>)
+// lr_dev: as in backward_scatter_impl
 static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int act,
-                             float alpha, const uint64_t* keys, const int64_t* seg_ranges, ce_stream_t stream) {
+                             float alpha, const float* lr_dev, const uint64_t* keys, const int64_t* seg_ranges,
+                             ce_stream_t stream) {
   CE_REQUIRE_ACT(act);
   if (nnz == 0) return CE_OK;
   CE_REQUIRE(dst && grad_out && keys, CE_ERR_INVALID, "null pointer");
@@ -1466,7 +1492,8 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
     constexpr bool has_excl = sizeof(VT) == 16 && N == 1, has_pair = kHasPair<VT, AT>;
     auto launch = [&](auto ex, auto pr) {
       constexpr bool EX = decltype(ex)::value, PR = decltype(pr)::value;
-      hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, EX, AT, PR>), g, b, 0, s, p, total, rg);
+      if (lr_dev) hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, EX, AT, PR, true>), g, b, 0, s, p, total, rg, lr_dev);
+      else hipLaunchKernelGGL((k_bag_bwd_stream<VT, N, R, EX, AT, PR>), g, b, 0, s, p, total, rg, lr_dev);
     };
     if constexpr (has_excl && has_pair) { if (excl && pair) return launch(std::true_type{}, std::true_type{}); }
     if constexpr (has_excl) { if (excl) return launch(std::true_type{}, std::false_type{}); }
@@ -1480,31 +1507,39 @@ static int launch_bwd_stream(float* dst, int64_t num_rows, int32_t dim, int64_t 
 extern "C" int ce_bag_backward_sgd_presorted_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                  const float* grad_out, float lr, const uint64_t* src_keys,
                                                  ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, src_keys, nullptr, stream);
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, nullptr, src_keys, nullptr, stream);
 }
 
 extern "C" int ce_bag_backward_sgd_presorted_src_excl(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                       const float* grad_out, float lr, const uint64_t* src_keys,
                                                       const int64_t* seg_id_ranges, ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, src_keys, seg_id_ranges, stream);
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, -lr, nullptr, src_keys, seg_id_ranges, stream);
 }
 
 extern "C" int ce_bag_backward_sgd_src_act(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                            const void* grad_out, int32_t act_dtype, float lr, const uint64_t* src_keys,
                                            const int64_t* seg_id_ranges, ce_stream_t stream) {
-  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, act_dtype, -lr, src_keys, seg_id_ranges, stream);
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, act_dtype, -lr, nullptr, src_keys, seg_id_ranges, stream);
+}
+
+extern "C" int ce_bag_backward_sgd_src_lrdev(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                             const void* grad_out, int32_t act_dtype, const float* lr,
+                                             const uint64_t* src_keys, const int64_t* seg_id_ranges,
+                                             ce_stream_t stream) {
+  CE_REQUIRE(lr, CE_ERR_INVALID, "lr: null device pointer");
+  return launch_bwd_stream(weight, num_rows, dim, nnz, grad_out, act_dtype, 0.f, lr, src_keys, seg_id_ranges, stream);
 }
 
 extern "C" int ce_bag_backward_dense_src_act(float* grad_weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                              const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
                                              ce_stream_t stream) {
-  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, act_dtype, 1.f, src_keys, nullptr, stream);
+  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, act_dtype, 1.f, nullptr, src_keys, nullptr, stream);
 }
 
 extern "C" int ce_bag_backward_dense_presorted_src(float* grad_weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                                    const float* grad_out, const uint64_t* src_keys,
                                                    ce_stream_t stream) {
-  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, 1.f, src_keys, nullptr, stream);
+  return launch_bwd_stream(grad_weight, num_rows, dim, nnz, grad_out, CE_ACT_F32, 1.f, nullptr, src_keys, nullptr, stream);
 }
 
 extern "C" int ce_bag_forward_src_keys_act(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,

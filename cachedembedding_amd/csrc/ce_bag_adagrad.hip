@@ -37,7 +37,11 @@ struct UpdateArgs {
   int32_t dim;
   float lr;
   float eps;
+  const float* lr_dev;                // non-NULL (the ce_*_lrdev entries): the learning rate is *lr_dev, `lr` is not read
 };
+
+// the launch's learning rate: uniform, so a kernel reads it once per thread, at its top, and hands it to update_row
+__device__ __forceinline__ float learning_rate(const UpdateArgs& a) { return a.lr_dev ? *a.lr_dev : a.lr; }
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -112,27 +116,27 @@ template <bool STOCH> __device__ __forceinline__ uint64_t step_key(const UpdateA
   return STOCH ? mix64(a.seed + 0xD6E8FEB86659FD93ull * *a.counter) : 0;
 }
 
-// The whole update of the row in slot s from g, its folded gradient of the step (zero in chunks past rowlen), by the
+// The whole update of the row in slot s from g, its folded gradient of the step, with the learning rate lr (zero in chunks past rowlen), by the
 // row's lane group (lane gl of G; every lane of the group must be here: the reduction shuffles across it).
 //   adagrad: ss = sum of the group's lane_sq_sum (xor tree, widest stride first); r outside the momentum: nothing
 //            happens; m[r] = m[r] + ss / D (lane 0 writes); mult = lr / (sqrt(m[r]) + eps).   sgd: mult = lr.
 //   x = fma(-g, mult, up(W[s])) per element; W[s] = x (fp32), nearest(x), or round_stochastic(x, 16 bits of
 //   mix64(mix64(step_key ^ r) + chunk index) per element).
 template <typename VT, typename WT, int NCH, bool STOCH>
-__device__ __forceinline__ void update_row(const UpdateArgs& a, uint64_t step_key, int64_t s, const VT (&g)[NCH],
-                                           int gl, int G, bool adagrad) {
+__device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64_t step_key, int64_t s,
+                                           const VT (&g)[NCH], int gl, int G, bool adagrad) {
 #pragma clang fp contract(off)
   using T = Act<WT, VT>;
   static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
   typename T::V* W = (typename T::V*)a.weight + s * a.rowlen;
   const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
-  float mult = a.lr;
+  float mult = lr;
   if (adagrad) {
     float ss = lane_sq_sum<WT, NCH>(g);
     for (int off = G >> 1; off > 0; off >>= 1) ss = ss + __shfl_xor(ss, off, G);
     if (r < 0 || r >= a.momentum_rows) return;
     const float mr = a.momentum[r] + ss / (float)a.dim;
-    mult = a.lr / (sqrtf(mr) + a.eps);
+    mult = lr / (sqrtf(mr) + a.eps);
     if (gl == 0) a.momentum[r] = mr;
   }
   uint64_t row_key = 0;
@@ -247,6 +251,7 @@ __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
   const LaneGroup l = lane_group(a.u.g_log2);
   VT* A = (VT*)a.acc;
   const uint64_t key = step_key<STOCH>(a.u);
+  const float lr = learning_rate(a.u);
   for (int64_t base = l.wave * 64; base < (int64_t)a.num_rows; base += l.nwaves * 64) {
     const int64_t mine = base + l.lane;
     const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
@@ -254,7 +259,7 @@ __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
       const int64_t s = base + i;
       VT g[NCH];
       load_row(g, A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
-      update_row<VT, WT, NCH, STOCH>(a.u, key, s, g, l.gl, l.G, ADAGRAD);
+      update_row<VT, WT, NCH, STOCH>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD);
       zero_row<VT, NCH>(A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
     });
     if (flagged) a.flags[mine] = 0;
@@ -605,10 +610,11 @@ __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   VT* A = (VT*)a.acc;
   const int64_t n = *a.n_list;
   const uint64_t key = step_key<STOCH>(a.u);
+  const float lr = learning_rate(a.u);
   for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
     VT g[NCH];
     load_row(g, A + u * a.u.rowlen, gl, G, a.u.rowlen);
-    update_row<VT, WT, NCH, STOCH>(a.u, key, (int64_t)a.list[u], g, gl, G, a.adagrad);
+    update_row<VT, WT, NCH, STOCH>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad);
     zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
   }
 }
@@ -708,6 +714,7 @@ struct UpdateCall {
   uint64_t seed;
   void* workspace;
   size_t workspace_bytes;
+  const float* lr_dev = nullptr;      // the ce_*_lrdev entries: the learning rate in device memory (`lr` is then 0)
   bool w16() const { return weight_dtype != CE_ACT_F32; }
   bool adagrad() const { return optimizer == CE_OPT_ROWWISE_ADAGRAD; }
   bool stochastic() const { return rounding == CE_ROUND_STOCHASTIC; }
@@ -726,6 +733,7 @@ static UpdateArgs update_args(const UpdateCall& c, const RowGeom& r, const unsig
   u.dim = c.dim;
   u.lr = c.lr;
   u.eps = c.eps;
+  u.lr_dev = c.lr_dev;
   return u;
 }
 
@@ -857,8 +865,14 @@ static const char* compact_not_taken(const UpdateCall& c) {
   return nullptr;
 }
 
-static const EntryRules kFp32Rules{
-    false, nullptr, false, [](int64_t R, int64_t, int32_t D) { return carve_apply(nullptr, R, D, false).bytes; }};
+// the fp32 table's cache-sized update is row-wise Adagrad only (the by-value entries have no optimizer argument)
+static EntryRules fp32_rules(const UpdateCall& c) {
+  return {false,
+          c.adagrad() ? nullptr
+                      : "CE_OPT_SGD on an fp32 table folds straight into the rows: it has no accumulator "
+                        "(ce_bag_backward_sgd_lrdev / _sgd_src_lrdev)",
+          false, [](int64_t R, int64_t, int32_t D) { return carve_apply(nullptr, R, D, false).bytes; }};
+}
 static const EntryRules kW16Rules{
     true, nullptr, false, [](int64_t R, int64_t, int32_t D) { return carve_apply(nullptr, R, D, true).bytes; }};
 static EntryRules compact_rules(const UpdateCall& c) {
@@ -866,11 +880,161 @@ static EntryRules compact_rules(const UpdateCall& c) {
           [](int64_t R, int64_t n, int32_t D) { return carve_compact(nullptr, R, n, D).bytes; }};
 }
 
+// the lookups of the slots + offsets entries
+struct SlotLookups {
+  const int64_t* indices;
+  const void* offsets;
+  int32_t off64;
+  int64_t num_bags;
+  int32_t include_last;
+  const float* psw;
+  int32_t mode;
+  int64_t hookF;
+  const uint64_t* presorted;
+};
+
+// the dense backward of the call's lookups into acc[rows, dim], reading `idx` / `keys` in place of the caller's
+static int scatter_slots(float* acc, int64_t rows, const UpdateCall& c, const SlotLookups& L, const int64_t* idx,
+                         const uint64_t* keys, ce_stream_t stream) {
+  return ce_bag_backward_dense_act(acc, rows, c.dim, idx, c.nnz, L.offsets, L.off64, L.num_bags, L.include_last, L.psw,
+                                   L.mode, L.hookF, c.grad_out, c.act, keys, stream);
+}
+
+// ---- The entries' bodies.  A by-value entry and the ce_*_lrdev entry that covers it are ONE function each: c.lr_dev is
+// NULL (the learning rate is c.lr) or the device pointer (c.lr is 0 and passes the host's range check; the kernels of
+// the apply pass read *c.lr_dev).  Checks, their order and the launch sequence are written once.
+
+// fp32 table, row-wise Adagrad, cache-sized accumulator.  nnz == 0 returns before the arguments are looked at.
+static int adagrad_fp32_slots(const UpdateCall& c, const SlotLookups& L, ce_stream_t stream) {
+  CE_REQUIRE_ACT(c.act);
+  if (L.num_bags == 0 || c.nnz == 0) return CE_OK;
+  RowGeom r;
+  int rc = update_check(c, fp32_rules(c), r);
+  if (rc) return rc;
+  CE_REQUIRE(L.indices && L.offsets, CE_ERR_INVALID, "null pointer");
+  return update_cache_sized(c, r, L.indices, false, c.nnz, (hipStream_t)stream, [&](float* acc) {
+    return scatter_slots(acc, c.num_rows, c, L, L.indices, L.presorted, stream);
+  });
+}
+
+static int adagrad_fp32_src(const UpdateCall& c, const uint64_t* src_keys, ce_stream_t stream) {
+  CE_REQUIRE_ACT(c.act);
+  if (c.nnz == 0) return CE_OK;
+  RowGeom r;
+  int rc = update_check(c, fp32_rules(c), r);
+  if (rc) return rc;
+  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
+  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(c.nnz), (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_src_act(acc, c.num_rows, c.dim, c.nnz, c.grad_out, c.act, src_keys, stream);
+  });
+}
+
+// 16-bit table, either optimizer, cache-sized accumulator.  Here and below nnz == 0 returns AFTER the check.
+static int update_w16_slots(const UpdateCall& c, const SlotLookups& L, ce_stream_t stream) {
+  RowGeom r;
+  int rc = update_check(c, kW16Rules, r);
+  if (rc) return rc;
+  if (L.num_bags == 0 || c.nnz == 0) return CE_OK;
+  CE_REQUIRE(L.indices && L.offsets, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(L.num_bags > 0 && c.nnz > 0 && L.num_bags < (int64_t)INT32_MAX - 64 && c.nnz < (int64_t)INT32_MAX,
+             CE_ERR_INVALID, "sizes out of range");
+  CE_REQUIRE(L.mode == CE_MODE_SUM || (L.mode == CE_MODE_MEAN && !L.psw), CE_ERR_INVALID,
+             "mode must be sum, or mean without per_sample_weights");
+  CE_REQUIRE(L.hookF >= 0 && (L.hookF == 0 || L.num_bags % L.hookF == 0), CE_ERR_INVALID,
+             "hook_features must divide num_bags");
+  return update_cache_sized(c, r, L.indices, false, c.nnz, (hipStream_t)stream, [&](float* acc) {
+    return scatter_slots(acc, c.num_rows, c, L, L.indices, L.presorted, stream);
+  });
+}
+
+static int update_w16_src(const UpdateCall& c, const uint64_t* src_keys, ce_stream_t stream) {
+  RowGeom r;
+  int rc = update_check(c, kW16Rules, r);
+  if (rc) return rc;
+  if (c.nnz == 0) return CE_OK;
+  CE_REQUIRE(src_keys && c.nnz > 0 && c.nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "null keys or nnz out of range");
+  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(c.nnz), (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_src_act(acc, c.num_rows, c.dim, c.nnz, c.grad_out, c.act, src_keys, stream);
+  });
+}
+
+// step-sized accumulator: mark, compact, remap, the dense backward into acc[cap, D], apply over the list
+static int update_compact_slots(const UpdateCall& c, const SlotLookups& L, ce_stream_t stream) {
+  RowGeom r;
+  int rc = update_check(c, compact_rules(c), r);
+  if (rc) return rc;
+  if (L.num_bags == 0 || c.nnz == 0) return CE_OK;
+  CE_REQUIRE(L.indices && L.offsets, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(L.num_bags > 0 && L.num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "sizes out of range");
+  CE_REQUIRE(L.mode == CE_MODE_SUM || (L.mode == CE_MODE_MEAN && !L.psw), CE_ERR_INVALID,
+             "mode must be sum, or mean without per_sample_weights");
+  CE_REQUIRE(L.hookF >= 0 && (L.hookF == 0 || L.num_bags % L.hookF == 0), CE_ERR_INVALID,
+             "hook_features must divide num_bags");
+  hipStream_t s = (hipStream_t)stream;
+  const CompactWs ws = carve_compact(c.workspace, c.num_rows, c.nnz, c.dim);
+  launch_mark(L.indices, false, c.nnz, c.num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
+  rc = launch_compact_scan(c.num_rows, ws, s);
+  if (rc) return rc;
+  // segment-sorted keys hold the rows themselves: with them the scatter never reads `indices`, so only they are remapped
+  const int64_t* idx = L.indices;
+  const uint64_t* keys = nullptr;
+  if (L.presorted) {
+    const int64_t total = ce_bag_presort_len(c.nnz);
+    hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
+                       (const unsigned long long*)L.presorted, total, (uint32_t)c.num_rows, ws.cidx, (uint32_t)ws.cap, 1,
+                       (unsigned long long*)ws.remap);
+    keys = (const uint64_t*)ws.remap;
+  } else {
+    hipLaunchKernelGGL(k_compact_remap_slots, dim3(grid_for(c.nnz, 256)), dim3(256), 0, s, L.indices, c.nnz,
+                       (uint32_t)c.num_rows, ws.cidx, (uint32_t)ws.cap, (int64_t*)ws.remap);
+    idx = (const int64_t*)ws.remap;
+  }
+  CE_LAUNCH_CHECK();
+  rc = scatter_slots(ws.acc, ws.cap, c, L, idx, keys, stream);
+  if (rc) return rc;
+  return launch_compact_apply(c, r, ws, s);
+}
+
+static int update_compact_src(const UpdateCall& c, const uint64_t* src_keys, ce_stream_t stream) {
+  RowGeom r;
+  int rc = update_check(c, compact_rules(c), r);
+  if (rc) return rc;
+  if (c.nnz == 0) return CE_OK;
+  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const CompactWs ws = carve_compact(c.workspace, c.num_rows, c.nnz, c.dim);
+  const int64_t total = ce_bag_presort_len(c.nnz);
+  launch_mark(src_keys, true, total, c.num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
+  rc = launch_compact_scan(c.num_rows, ws, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
+                     (const unsigned long long*)src_keys, total, (uint32_t)c.num_rows, ws.cidx, (uint32_t)ws.cap, 0,
+                     (unsigned long long*)ws.remap);
+  CE_LAUNCH_CHECK();
+  rc = ce_bag_backward_dense_src_act(ws.acc, ws.cap, c.dim, c.nnz, c.grad_out, c.act, (const uint64_t*)ws.remap, stream);
+  if (rc) return rc;
+  return launch_compact_apply(c, r, ws, s);
+}
+
+// Which covered entry a ce_*_lrdev call is, from its accumulator and its table; `run` gets the call as that entry
+// takes it.  lr == NULL and an unknown accumulator are refused first: before anything the covered entry looks at.
+template <typename Fp32, typename W16, typename Compact>
+static int lrdev_dispatch(UpdateCall c, int32_t accumulator, Fp32&& fp32, W16&& w16, Compact&& compact) {
+  CE_REQUIRE(c.lr_dev, CE_ERR_INVALID, "lr: null device pointer");
+  CE_REQUIRE(accumulator == CE_ACC_CACHE || accumulator == CE_ACC_STEP, CE_ERR_INVALID,
+             "unknown accumulator %d (CE_ACC_CACHE / CE_ACC_STEP)", (int)accumulator);
+  if (accumulator == CE_ACC_STEP) return compact(c);
+  if (c.weight_dtype != CE_ACT_F32) return w16(c);
+  c.rounding = CE_ROUND_NEAREST;      // an fp32 row is stored as it is: the covered entry has neither argument
+  c.seed = 0;
+  return fp32(c);
+}
+
 }  // namespace ce
 
 using namespace ce;
 
-// ---- fp32 table, row-wise Adagrad, cache-sized accumulator.  nnz == 0 returns before the arguments are looked at.
+// ---- fp32 table, row-wise Adagrad, cache-sized accumulator
 
 extern "C" size_t ce_bag_backward_rowwise_adagrad_workspace(int64_t num_rows, int32_t dim) {
   if (num_rows < 0 || dim < 0) return 0;
@@ -886,19 +1050,10 @@ extern "C" int ce_bag_backward_rowwise_adagrad_act(float* weight, int64_t num_ro
                                                    const uint64_t* presorted, const int32_t* row_of_slot,
                                                    float* momentum, int64_t momentum_rows, float lr, float eps,
                                                    void* workspace, size_t workspace_bytes, ce_stream_t stream) {
-  CE_REQUIRE_ACT(act_dtype);
-  if (num_bags == 0 || nnz == 0) return CE_OK;
   const UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum, momentum_rows,
                      lr, eps, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST, 0, workspace, workspace_bytes};
-  RowGeom r;
-  int rc = update_check(c, kFp32Rules, r);
-  if (rc) return rc;
-  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
-  return update_cache_sized(c, r, indices, false, nnz, (hipStream_t)stream, [&](float* acc) {
-    return ce_bag_backward_dense_act(acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                                     include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
-                                     presorted, stream);
-  });
+  return adagrad_fp32_slots(c, {indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights,
+                                mode, hook_features, presorted}, stream);
 }
 
 extern "C" int ce_bag_backward_rowwise_adagrad(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
@@ -920,17 +1075,9 @@ extern "C" int ce_bag_backward_rowwise_adagrad_src_act(float* weight, int64_t nu
                                                        const uint64_t* src_keys, const int32_t* row_of_slot,
                                                        float* momentum, int64_t momentum_rows, float lr, float eps,
                                                        void* workspace, size_t workspace_bytes, ce_stream_t stream) {
-  CE_REQUIRE_ACT(act_dtype);
-  if (nnz == 0) return CE_OK;
   const UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum, momentum_rows,
                      lr, eps, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST, 0, workspace, workspace_bytes};
-  RowGeom r;
-  int rc = update_check(c, kFp32Rules, r);
-  if (rc) return rc;
-  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
-  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(nnz), (hipStream_t)stream, [&](float* acc) {
-    return ce_bag_backward_dense_src_act(acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
-  });
+  return adagrad_fp32_src(c, src_keys, stream);
 }
 
 extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
@@ -943,7 +1090,7 @@ extern "C" int ce_bag_backward_rowwise_adagrad_src(float* weight, int64_t num_ro
                                                  workspace_bytes, stream);
 }
 
-// ---- 16-bit table, either optimizer, cache-sized accumulator.  Here and below nnz == 0 returns AFTER the check.
+// ---- 16-bit table, either optimizer, cache-sized accumulator
 
 extern "C" size_t ce_bag_backward_w16_workspace(int64_t num_rows, int32_t dim) {
   if (num_rows < 0 || dim < 0) return 0;
@@ -960,22 +1107,8 @@ extern "C" int ce_bag_backward_update_w16(void* weight, int32_t weight_dtype, in
                                           void* workspace, size_t workspace_bytes, ce_stream_t stream) {
   const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
                      momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
-  RowGeom r;
-  int rc = update_check(c, kW16Rules, r);
-  if (rc) return rc;
-  if (num_bags == 0 || nnz == 0) return CE_OK;
-  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_bags > 0 && nnz > 0 && num_bags < (int64_t)INT32_MAX - 64 && nnz < (int64_t)INT32_MAX, CE_ERR_INVALID,
-             "sizes out of range");
-  CE_REQUIRE(mode == CE_MODE_SUM || (mode == CE_MODE_MEAN && !per_sample_weights), CE_ERR_INVALID,
-             "mode must be sum, or mean without per_sample_weights");
-  CE_REQUIRE(hook_features >= 0 && (hook_features == 0 || num_bags % hook_features == 0), CE_ERR_INVALID,
-             "hook_features must divide num_bags");
-  return update_cache_sized(c, r, indices, false, nnz, (hipStream_t)stream, [&](float* acc) {
-    return ce_bag_backward_dense_act(acc, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
-                                     include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
-                                     presorted, stream);
-  });
+  return update_w16_slots(c, {indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                              hook_features, presorted}, stream);
 }
 
 extern "C" int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -986,17 +1119,10 @@ extern "C" int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype
                                               size_t workspace_bytes, ce_stream_t stream) {
   const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
                      momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
-  RowGeom r;
-  int rc = update_check(c, kW16Rules, r);
-  if (rc) return rc;
-  if (nnz == 0) return CE_OK;
-  CE_REQUIRE(src_keys && nnz > 0 && nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "null keys or nnz out of range");
-  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(nnz), (hipStream_t)stream, [&](float* acc) {
-    return ce_bag_backward_dense_src_act(acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
-  });
+  return update_w16_src(c, src_keys, stream);
 }
 
-// ---- step-sized accumulator: mark, compact, remap, the dense backward into acc[cap, D], apply over the list
+// ---- step-sized accumulator
 
 extern "C" size_t ce_bag_backward_update_compact_workspace(int64_t num_rows, int64_t nnz, int32_t dim) {
   if (num_rows < 0 || num_rows >= (int64_t)INT32_MAX || nnz < 0 || nnz >= (int64_t)INT32_MAX || dim < 0) return 0;
@@ -1013,41 +1139,8 @@ extern "C" int ce_bag_backward_update_compact(void* weight, int32_t weight_dtype
                                               void* workspace, size_t workspace_bytes, ce_stream_t stream) {
   const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
                      momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
-  RowGeom r;
-  int rc = update_check(c, compact_rules(c), r);
-  if (rc) return rc;
-  if (num_bags == 0 || nnz == 0) return CE_OK;
-  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_bags > 0 && num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "sizes out of range");
-  CE_REQUIRE(mode == CE_MODE_SUM || (mode == CE_MODE_MEAN && !per_sample_weights), CE_ERR_INVALID,
-             "mode must be sum, or mean without per_sample_weights");
-  CE_REQUIRE(hook_features >= 0 && (hook_features == 0 || num_bags % hook_features == 0), CE_ERR_INVALID,
-             "hook_features must divide num_bags");
-  hipStream_t s = (hipStream_t)stream;
-  const CompactWs ws = carve_compact(workspace, num_rows, nnz, dim);
-  launch_mark(indices, false, nnz, num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
-  rc = launch_compact_scan(num_rows, ws, s);
-  if (rc) return rc;
-  // segment-sorted keys hold the rows themselves: with them the scatter never reads `indices`, so only they are remapped
-  const int64_t* idx = indices;
-  const uint64_t* keys = nullptr;
-  if (presorted) {
-    const int64_t total = ce_bag_presort_len(nnz);
-    hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
-                       (const unsigned long long*)presorted, total, (uint32_t)num_rows, ws.cidx, (uint32_t)ws.cap, 1,
-                       (unsigned long long*)ws.remap);
-    keys = (const uint64_t*)ws.remap;
-  } else {
-    hipLaunchKernelGGL(k_compact_remap_slots, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz,
-                       (uint32_t)num_rows, ws.cidx, (uint32_t)ws.cap, (int64_t*)ws.remap);
-    idx = (const int64_t*)ws.remap;
-  }
-  CE_LAUNCH_CHECK();
-  rc = ce_bag_backward_dense_act(ws.acc, ws.cap, dim, idx, nnz, offsets, offsets_are_i64, num_bags,
-                                 include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype,
-                                 keys, stream);
-  if (rc) return rc;
-  return launch_compact_apply(c, r, ws, s);
+  return update_compact_slots(c, {indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights,
+                                  mode, hook_features, presorted}, stream);
 }
 
 extern "C" int ce_bag_backward_update_compact_src(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -1058,24 +1151,40 @@ extern "C" int ce_bag_backward_update_compact_src(void* weight, int32_t weight_d
                                                   size_t workspace_bytes, ce_stream_t stream) {
   const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
                      momentum_rows, lr, eps, optimizer, rounding, seed, workspace, workspace_bytes};
-  RowGeom r;
-  int rc = update_check(c, compact_rules(c), r);
-  if (rc) return rc;
-  if (nnz == 0) return CE_OK;
-  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const CompactWs ws = carve_compact(workspace, num_rows, nnz, dim);
-  const int64_t total = ce_bag_presort_len(nnz);
-  launch_mark(src_keys, true, total, num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
-  rc = launch_compact_scan(num_rows, ws, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
-                     (const unsigned long long*)src_keys, total, (uint32_t)num_rows, ws.cidx, (uint32_t)ws.cap, 0,
-                     (unsigned long long*)ws.remap);
-  CE_LAUNCH_CHECK();
-  rc = ce_bag_backward_dense_src_act(ws.acc, ws.cap, dim, nnz, grad_out, act_dtype, (const uint64_t*)ws.remap, stream);
-  if (rc) return rc;
-  return launch_compact_apply(c, r, ws, s);
+  return update_compact_src(c, src_keys, stream);
+}
+
+// ---- the learning rate in device memory: the three pairs above behind one pair of entries
+
+extern "C" int ce_bag_backward_update_lrdev(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                            const int64_t* indices, int64_t nnz, const void* offsets,
+                                            int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                            const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                            const void* grad_out, int32_t act_dtype, const uint64_t* presorted,
+                                            const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
+                                            const float* lr, float eps, int32_t optimizer, int32_t rounding,
+                                            uint64_t seed, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                            ce_stream_t stream) {
+  const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+                     momentum_rows, 0.f, eps, optimizer, rounding, seed, workspace, workspace_bytes, lr};
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, presorted};
+  return lrdev_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_slots(u, L, stream); },
+                        [&](const UpdateCall& u) { return update_w16_slots(u, L, stream); },
+                        [&](const UpdateCall& u) { return update_compact_slots(u, L, stream); });
+}
+
+extern "C" int ce_bag_backward_update_src_lrdev(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                                int64_t nnz, const void* grad_out, int32_t act_dtype,
+                                                const uint64_t* src_keys, const int32_t* row_of_slot, float* momentum,
+                                                int64_t momentum_rows, const float* lr, float eps, int32_t optimizer,
+                                                int32_t rounding, uint64_t seed, int32_t accumulator, void* workspace,
+                                                size_t workspace_bytes, ce_stream_t stream) {
+  const UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+                     momentum_rows, 0.f, eps, optimizer, rounding, seed, workspace, workspace_bytes, lr};
+  return lrdev_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_src(u, src_keys, stream); },
+                        [&](const UpdateCall& u) { return update_w16_src(u, src_keys, stream); },
+                        [&](const UpdateCall& u) { return update_compact_src(u, src_keys, stream); });
 }
 
 // ---- deterministic, accumulator-free: sort, fold + apply, combine + apply

@@ -143,6 +143,9 @@ class _BagFn(torch.autograd.Function):
             grad_out = grad_out.float()
         slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
                       hook_features, ptr(grad_out))
+        # a tensor learning rate goes to the ce_*_lrdev entries, whose kernels read it when they run (nothing here
+        # does); a float to the by-value entries.  What the tensor form does not take was refused before the forward.
+        lr_dev = (rowwise or sgd) and isinstance(fused.lr, torch.Tensor)
         if (rowwise or sgd) and fused.accumulator == "step":
             # the atomic update with an accumulator of min(nnz, rows) rows (ce_bag_backward_update_compact*): mark, an
             # ordered compaction of the flagged slots, the slots / keys renumbered, the same dense backward, one apply
@@ -153,11 +156,13 @@ class _BagFn(torch.autograd.Function):
                 wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
                 # (an fp32 table is never rounded, whatever fused.rounding says)
                 w16 = weight.dtype in _lib.W16_DTYPES
-                tail = _update_tail(fused, rowwise, fused.rounding if w16 else "nearest", ws)
+                tail = _update_tail(fused, rowwise, fused.rounding if w16 else "nearest", ws, _lib.CE_ACC_STEP)
                 if src:
-                    check(lib.ce_bag_backward_update_compact_src(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                    fn = lib.ce_bag_backward_update_src_lrdev if lr_dev else lib.ce_bag_backward_update_compact_src
+                    check(fn(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                 else:
-                    check(lib.ce_bag_backward_update_compact(*wd, *slots_args, act, ptr(pre), *tail))
+                    fn = lib.ce_bag_backward_update_lrdev if lr_dev else lib.ce_bag_backward_update_compact
+                    check(fn(*wd, *slots_args, act, ptr(pre), *tail))
             return (None,) * 14
         if rowwise and fused.deterministic:
             # bit-reproducible row-wise Adagrad without the [rows, D] accumulator (ce_bag_backward_update_sorted): fp32
@@ -175,11 +180,13 @@ class _BagFn(torch.autograd.Function):
                 # mark + the dense backward into an fp32 accumulator + one apply pass that rounds every row once
                 with torch.no_grad():
                     ws = fused.workspace_w16(R, dim, weight.device)
-                    tail = _update_tail(fused, rowwise, fused.rounding, ws)
+                    tail = _update_tail(fused, rowwise, fused.rounding, ws, _lib.CE_ACC_CACHE)
                     if src:
-                        check(lib.ce_bag_backward_update_src_w16(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                        fn = lib.ce_bag_backward_update_src_lrdev if lr_dev else lib.ce_bag_backward_update_src_w16
+                        check(fn(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                     else:
-                        check(lib.ce_bag_backward_update_w16(*wd, *slots_args, act, ptr(pre), *tail))
+                        fn = lib.ce_bag_backward_update_lrdev if lr_dev else lib.ce_bag_backward_update_w16
+                        check(fn(*wd, *slots_args, act, ptr(pre), *tail))
                 return (None,) * 14
             # no fused optimizer: the dense gradient is accumulated in fp32 and cast once to the parameter's dtype
             g32 = torch.zeros(R, dim, device=weight.device, dtype=torch.float32)
@@ -194,6 +201,15 @@ class _BagFn(torch.autograd.Function):
             with torch.no_grad():
                 ws = fused.workspace(R, dim, weight.device)
                 mom = fused.momentum
+                if lr_dev:
+                    # the cache-sized fp32 update behind the entry that covers it (CE_ACT_F32, CE_ACC_CACHE)
+                    wd = (ptr(weight), _lib.CE_ACT_F32, R, dim)
+                    tail = _update_tail(fused, True, "nearest", ws, _lib.CE_ACC_CACHE)
+                    if src:
+                        check(lib.ce_bag_backward_update_src_lrdev(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                    else:
+                        check(lib.ce_bag_backward_update_lrdev(*wd, *slots_args, act, ptr(pre), *tail))
+                    return (None,) * 14
                 tail = (ptr(fused.row_of_slot), ptr(mom), mom.numel(), float(fused.lr), float(fused.eps), ptr(ws),
                         ws.numel(), stream_ptr())
                 if src:
@@ -210,12 +226,12 @@ class _BagFn(torch.autograd.Function):
                     check(lib.ce_bag_backward_sgd_sorted(ptr(weight), R, dim, *slots_args, float(fused.lr), ptr(ws),
                                                          ws.numel(), stream_ptr()))
                 elif src:
-                    check(lib.ce_bag_backward_sgd_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act,
-                                                          float(fused.lr), ptr(pre.keys), ptr(pre.ranges),
-                                                          stream_ptr()))
+                    fn = lib.ce_bag_backward_sgd_src_lrdev if lr_dev else lib.ce_bag_backward_sgd_src_act
+                    check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, _lr_arg(fused), ptr(pre.keys),
+                             ptr(pre.ranges), stream_ptr()))
                 else:
-                    check(lib.ce_bag_backward_sgd_act(ptr(weight), R, dim, *slots_args, act, float(fused.lr),
-                                                      ptr(pre), stream_ptr()))
+                    fn = lib.ce_bag_backward_sgd_lrdev if lr_dev else lib.ce_bag_backward_sgd_act
+                    check(fn(ptr(weight), R, dim, *slots_args, act, _lr_arg(fused), ptr(pre), stream_ptr()))
         elif sparse and COALESCED_SPARSE_GRAD and nnz > 0 and not torch.cuda.is_current_stream_capturing():
             # sparse=True (scripts/kaggle.sh:71 --use_sparse_embed_grad): the COO gradient is handed over COALESCED --
             # unique rows (ce_dedupe_bucket_rows), ascending, each with the sum of its lookups' gradient rows (the dense
@@ -272,15 +288,52 @@ class _BagFn(torch.autograd.Function):
         return gw, None, None, gpsw, None, None, None, None, None, None, None, None, None, None
 
 
-def _update_tail(fused, rowwise: bool, rounding: str, ws: torch.Tensor) -> tuple:
+def check_lr(lr):
+    """What a fused update's learning rate may be: None (the update is off), a number, or a tensor of ONE fp32 element,
+    contiguous, that does not require grad.  The tensor is kept by reference and never read on the host: the kernels
+    read it when they run (the ce_*_lrdev entries), so a fill_ / copy_ before a step -- or before the replay of a
+    hipGraph that captured the step -- is the learning rate of that step.  Its device is checked against the weight in
+    embedding_bag, before the forward.  Host logic only; nothing here looks at the value."""
+    if isinstance(lr, torch.Tensor):
+        if lr.dtype != torch.float32:
+            raise TypeError(f"a tensor learning rate must be torch.float32 (got {lr.dtype})")
+        if lr.numel() != 1:
+            raise ValueError(f"a tensor learning rate must have one element (got {lr.numel()})")
+        if lr.requires_grad:
+            raise ValueError("a tensor learning rate must not require grad")
+        if not lr.is_contiguous():
+            raise ValueError("a tensor learning rate must be contiguous")
+    return lr
+
+
+def _lr_arg(fused):
+    """the learning-rate argument of a C entry: the device address of a tensor (ce_*_lrdev), else the float"""
+    return ptr(fused.lr) if isinstance(fused.lr, torch.Tensor) else float(fused.lr)
+
+
+class _CheckedLr:
+    """`lr` of FusedSGD / FusedRowwiseAdagrad: check_lr runs on every assignment, a direct one included"""
+
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        self._lr = check_lr(value)
+
+
+def _update_tail(fused, rowwise: bool, rounding: str, ws: torch.Tensor, accumulator: Optional[int] = None) -> tuple:
     """what the ce_bag_backward_update_* entries take behind the lookups: row_of_slot, momentum and its length, lr, eps,
     optimizer, rounding, seed, workspace, stream.  `rounding` is the caller's: the entries do not agree on when
-    fused.rounding counts."""
+    fused.rounding counts.  A tensor learning rate: the tail of the ce_*_lrdev pair instead -- lr as a device address
+    and `accumulator` (CE_ACC_*: which of the entries it covers the call is) behind the seed."""
     mom = fused.momentum if rowwise else None
-    return (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), float(fused.lr),
+    lr_dev = isinstance(fused.lr, torch.Tensor)
+    return (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), _lr_arg(fused),
             float(fused.eps) if rowwise else 0.0, _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
             _lib.CE_ROUND_STOCHASTIC if rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
-            int(fused.seed) & (2 ** 64 - 1), ptr(ws), ws.numel(), stream_ptr())
+            int(fused.seed) & (2 ** 64 - 1)) + ((accumulator,) if lr_dev else ()) + (ptr(ws), ws.numel(), stream_ptr())
 
 
 _DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
@@ -403,16 +456,32 @@ def _workspace_step(self, num_rows: int, nnz: int, dim: int, device) -> torch.Te
     return ws
 
 
-class FusedSGD:
+def check_lr_path(lr, deterministic: bool, mode: Optional[str] = None) -> None:
+    """Refusals of a tensor learning rate that do not depend on the weight: the sorted, deterministic updates and
+    mode='max' take a float only.  Host logic only, asked before the forward."""
+    if not isinstance(lr, torch.Tensor):
+        return
+    if deterministic:
+        raise NotImplementedError("a tensor learning rate with deterministic=True: the sorted updates take a float")
+    if mode == "max":
+        raise NotImplementedError("a tensor learning rate with mode='max'")
+
+
+class FusedSGD(_CheckedLr):
     """Switch for the fused backward+SGD path of one embedding module.
 
     lr=None disables fusion (the module behaves exactly like nn.EmbeddingBag under
     torch.optim.SGD); deterministic=True uses the sorted segmented update instead of atomics.
     accumulator="step" (a 16-bit table only; an fp32 table's SGD has no accumulator): the update's fp32 accumulator has
-    min(lookups of the step, rows) rows instead of one per row of the weight."""
+    min(lookups of the step, rows) rows instead of one per row of the weight.
+    lr may be a tensor (check_lr): one fp32 element on the weight's device, kept by reference and read by the kernels
+    when they run -- rewrite it in place (fill_ / copy_) between steps or between replays of a captured step.  Not
+    with deterministic=True and not with mode='max'."""
 
-    def __init__(self, lr: Optional[float] = None, deterministic: bool = False, accumulator: str = "cache"):
+    def __init__(self, lr: Union[float, torch.Tensor, None] = None, deterministic: bool = False,
+                 accumulator: str = "cache"):
         check_accumulator("sgd", None, accumulator, bool(deterministic))
+        check_lr_path(check_lr(lr), bool(deterministic))
         self.lr = lr
         self.deterministic = deterministic
         self.accumulator = accumulator
@@ -430,7 +499,7 @@ class FusedSGD:
         return _cached_bytes(self, "_ws", lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz), device, zero=False)
 
 
-class FusedRowwiseAdagrad:
+class FusedRowwiseAdagrad(_CheckedLr):
     """Switch for the fused backward + exact row-wise Adagrad update of one embedding module (FBGEMM's
     EXACT_ROWWISE_ADAGRAD, weight_decay = 0).  Per step and per UNIQUE row r the step looks up, with g the sum of the
     row's gradient rows in the batch:  m[r] += sum(g * g) / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps).
@@ -448,11 +517,15 @@ class FusedRowwiseAdagrad:
     accumulator="step": the atomic update keeps its speed but folds into an fp32 accumulator of min(lookups of the
     step, rows) rows -- the flagged slots are compacted and the lookups renumbered first -- instead of one as large as
     the weight ("cache", the default).  Not with deterministic=True, and on a 16-bit table with rounding="nearest"
-    only: both are refused before any kernel runs."""
+    only: both are refused before any kernel runs.
 
-    def __init__(self, lr: Optional[float] = None, eps: float = 1e-8, momentum: Optional[torch.Tensor] = None,
-                 row_of_slot: Optional[torch.Tensor] = None, deterministic: bool = False, accumulator: str = "cache"):
+    lr may be a tensor, as for FusedSGD (check_lr); not with deterministic=True."""
+
+    def __init__(self, lr: Union[float, torch.Tensor, None] = None, eps: float = 1e-8,
+                 momentum: Optional[torch.Tensor] = None, row_of_slot: Optional[torch.Tensor] = None,
+                 deterministic: bool = False, accumulator: str = "cache"):
         check_accumulator("rowwise_adagrad", None, accumulator, bool(deterministic))
+        check_lr_path(check_lr(lr), bool(deterministic))
         self.lr = lr
         self.deterministic = bool(deterministic)
         self.accumulator = accumulator
@@ -515,6 +588,12 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                           fused_sgd.accumulator, bool(fused_sgd.deterministic), fused_sgd.rounding)
         if fused_sgd.accumulator == "step" and mode == "max":
             raise NotImplementedError("accumulator='step' with mode='max'")
+        if isinstance(fused_sgd.lr, torch.Tensor):
+            # asked again here: .lr, .deterministic and the weight can all change after the switch was built
+            check_lr_path(check_lr(fused_sgd.lr), bool(fused_sgd.deterministic), mode)
+            if fused_sgd.lr.device != weight.device:
+                raise ValueError(f"the learning-rate tensor is on {fused_sgd.lr.device}, the weight on "
+                                 f"{weight.device}: the kernels read it from device memory")
     if weight.dtype in _lib.W16_DTYPES:
         # a 16-bit table (bf16 / fp16 weight): rows up-converted exactly, fp32 sums, the output defaults to the
         # weight's dtype.  What it does not take is refused here, before any kernel has run.

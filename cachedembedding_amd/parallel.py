@@ -577,6 +577,10 @@ class RowwiseShardedEmbeddingBag(nn.Module):
         return self.cache_weight_mgr.weight
 
     def set_fused_sgd(self, lr: Optional[float]):
+        if isinstance(lr, torch.Tensor):
+            raise NotImplementedError("a tensor learning rate is not implemented for the row-wise sharded embedding "
+                                      "(RowwiseShardedEmbeddingBag / GraphedShardedWindow): its owner-side update "
+                                      "takes a float")
         self._lr[0] = lr
 
     def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8):

@@ -432,6 +432,8 @@ class GraphedWindow:
 
     step_fn(slots_i, i) runs one training step on batch i of the window; it is recorded once per buffer.
     All tensors it reads besides `slots_i` must be static (offsets, upstream gradient / dense inputs).
+    The learning rate a captured step_fn uses can be a tensor (embed.set_fused_sgd(tensor) / set_fused_rowwise_adagrad):
+    the kernels read it when the graph replays, so it is rewritten in place (fill_ / copy_) between `run` calls.
 
     graph_cache_op (overlap=True, zero-copy transport): the cache op + presort of a window are captured too, as a
     graph of their own that run_and_submit replays on the side stream -- a window then costs the host one copy of the

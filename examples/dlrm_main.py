@@ -60,6 +60,14 @@ def parse_args(argv=None):
     p.add_argument("--dense_arch_layer_sizes", type=str, default="512,256,128")
     p.add_argument("--over_arch_layer_sizes", type=str, default="1024,1024,512,256,1")
     p.add_argument("--learning_rate", type=float, default=1.0)
+    # baselines/dlrm_main.py:223-242, with the progress counted over the run's total iterations
+    p.add_argument("--change_lr", action="store_true",
+                   help="change the learning rate part way through training.  With --graph_step the captured step is "
+                        "not captured again: the fused update and the dense step read the rate from one device tensor "
+                        "that is rewritten at the change point")
+    p.add_argument("--lr_change_point", type=float, default=0.80,
+                   help="the point through the run's total iterations (all epochs) after which the rate changes")
+    p.add_argument("--lr_after_change_point", type=float, default=0.20, help="learning rate after the change point")
     p.add_argument("--seed", type=int, default=1024)
     # hot-path flags, same names as recsys/dlrm_main.py:120-166
     p.add_argument("--use_cache", action="store_true")
@@ -294,6 +302,87 @@ def _eager_step(model, optimizer, criterion, dense, sparse, labels, keys):
     return loss
 
 
+def lr_changes_after(it: int, total: int, point: float) -> bool:
+    """baselines/dlrm_main.py:453-455: checked after iteration `it` (0-based, counted over the whole run) has trained;
+    true = the iterations from `it + 1` on train with --lr_after_change_point"""
+    return it / total > point
+
+
+class DenseStep:
+    """The dense optimizer step with the learning rate in a device tensor, for --graph_step --change_lr: stock
+    torch.optim.SGD / Adagrad turn a tensor lr into a Python scalar (alpha=-lr), which a capture cannot record.  SGD:
+    p -= lr * g.  Adagrad with torch's defaults (lr_decay 0, eps 1e-10, initial_accumulator_value 0): s += g * g ;
+    p -= lr * g / (sqrt(s) + eps).  _foreach ops that read the tensor on the device; the embedding's fused update reads
+    the same one."""
+
+    def __init__(self, params, lr: torch.Tensor, adagrad: bool = False):
+        self.params, self.lr = list(params), lr.view(())
+        self.sums = [torch.zeros_like(p) for p in self.params] if adagrad else None
+
+    def zero_grad(self, set_to_none: bool = True):
+        for p in self.params:
+            p.grad = None
+
+    @torch.no_grad()
+    def step(self):
+        grads = [p.grad for p in self.params]
+        if self.sums is not None:
+            torch._foreach_addcmul_(self.sums, grads, grads)
+            std = torch._foreach_sqrt(self.sums)
+            torch._foreach_add_(std, 1e-10)
+            grads = torch._foreach_div(grads, std)
+        torch._foreach_sub_(self.params, torch._foreach_mul(grads, self.lr))
+
+
+def make_optimizer(model, args, device, world: int):
+    """(optimizer, lr tensor or None): the embedding's fused update is switched on and the optimizer of everything else
+    built.  --graph_step --change_lr: both read the rate from one device tensor (DenseStep, set_fused_*(tensor))."""
+    embed = model.sparse_modules.embed
+    acc = "step" if args.step_accumulator else "cache"
+    lr_t = None
+    if args.change_lr and args.graph_step:
+        lr_t = torch.full((1,), args.learning_rate, dtype=torch.float32, device=device)
+    lr = args.learning_rate if lr_t is None else lr_t
+    groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world, "lr_scale": world}]
+    if args.adagrad:
+        embed.set_fused_rowwise_adagrad(lr, deterministic=args.adagrad_deterministic, accumulator=acc)
+    elif args.fused_sgd:
+        embed.set_fused_sgd(lr, accumulator=acc)
+    else:
+        groups.insert(0, {"params": list(model.sparse_modules.parameters()), "lr": args.learning_rate, "lr_scale": 1})
+    if lr_t is not None:
+        return DenseStep(groups[0]["params"], lr_t, adagrad=args.adagrad), lr_t
+    return (torch.optim.Adagrad(groups) if args.adagrad else torch.optim.SGD(groups)), None
+
+
+class LrChange:
+    """--change_lr: after the iteration at which lr_changes_after turns true, once -- the device tensor is rewritten
+    (--graph_step: the captured step reads it, nothing is captured again), or the dense groups' lr is set in
+    param_groups and the fused update set again by value."""
+
+    def __init__(self, args, total: int, optimizer, embed, lr_tensor=None):
+        self.args, self.total, self.optimizer, self.embed, self.lr_tensor = args, total, optimizer, embed, lr_tensor
+        self.it, self.pending = 0, bool(args.change_lr)
+
+    def after_iteration(self):
+        it, self.it = self.it, self.it + 1
+        if not self.pending or not lr_changes_after(it, self.total, self.args.lr_change_point):
+            return
+        self.pending = False
+        new, args = self.args.lr_after_change_point, self.args
+        print(f"Changing learning rate to: {new}")
+        if self.lr_tensor is not None:
+            self.lr_tensor.fill_(new)
+            return
+        for g in self.optimizer.param_groups:
+            g["lr"] = new * g.get("lr_scale", 1)
+        acc = "step" if args.step_accumulator else "cache"
+        if args.adagrad:
+            self.embed.set_fused_rowwise_adagrad(new, deterministic=args.adagrad_deterministic, accumulator=acc)
+        elif args.fused_sgd:
+            self.embed.set_fused_sgd(new, accumulator=acc)
+
+
 class _GraphedStep:
     """One training iteration captured in a hipGraph on static inputs (--graph_step): torch.cuda.graph around exactly the
     calls of _eager_step.  The embedding's kernels are launched through the C ABI on the current stream, so they are
@@ -335,20 +424,20 @@ class _GraphedStep:
         return self.loss
 
 
-def train(model, optimizer, loader, args, device, rank, world, record=None):
-    """recsys/dlrm_main.py:206-297 (see _train); --graph_step: on a stream of its own"""
+def train(model, optimizer, loader, args, device, rank, world, record=None, lr_change=None):
+    """recsys/dlrm_main.py:206-297 (see _train); --graph_step: on a stream of its own.  lr_change: the run's LrChange"""
     if args.graph_step and torch.cuda.current_stream(device) == torch.cuda.default_stream(device):
         # a step can only be captured on a stream of its own: the whole loop runs there
         main = torch.cuda.Stream(device=device)
         main.wait_stream(torch.cuda.default_stream(device))
         with torch.cuda.stream(main):
-            out = train(model, optimizer, loader, args, device, rank, world, record)
+            out = train(model, optimizer, loader, args, device, rank, world, record, lr_change)
         torch.cuda.default_stream(device).wait_stream(main)
         return out
-    return _train(model, optimizer, loader, args, device, rank, world, record)
+    return _train(model, optimizer, loader, args, device, rank, world, record, lr_change)
 
 
-def _train(model, optimizer, loader, args, device, rank, world, record=None):
+def _train(model, optimizer, loader, args, device, rank, world, record=None, lr_change=None):
     """recsys/dlrm_main.py:206-297.  record: a list that receives every step's loss (as device scalars: no sync).  Default: the reference's window block (one synchronous prepare_ids per
     prefetch_num batches).  --overlap_cache_op: the cache op of window k+1 runs on a side stream while window k trains
     (pipeline.PrefetchWindow, protect_depth 1, swap traffic through the worker transport when the window is large)."""
@@ -369,6 +458,7 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None):
                          if (args.overlap_cache_op and args.arrangement == "auto") else None)
     train.window = win
     graphed = None
+    train.graph_captures = 0
     if args.graph_step and (world > 1 or not ((args.fused_sgd or args.adagrad) and args.fold_hook)):
         raise ValueError("--graph_step needs --fused_sgd (or --adagrad) --fold_hook and one process (DDP's bucket hooks "
                          "and the sparse "
@@ -401,9 +491,12 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None):
                 if args.graph_step and graphed is None and done + 1 >= args.graph_after \
                         and dense_l[k].shape[0] == args.batch_size:
                     graphed = _GraphedStep(model, optimizer, criterion, dense_l[k], sparse_l[k], labels_l[k], keys_k)
+                    train.graph_captures += 1
             if record is not None:
                 record.append(loss.detach().clone() if graphed is not None else loss.detach())
             done += 1
+            if lr_change is not None:
+                lr_change.after_iteration()
         elapsed += time.time() - start
         start = time.time()
         if steady["t0"] is None and done >= args.warmup_batches:
@@ -525,6 +618,9 @@ def main(argv=None):
         raise NotImplementedError("--adagrad_deterministic rounds a 16-bit table to nearest: pass --weight_rounding nearest")
     if args.step_accumulator:
         check_step_accumulator(args)
+    if args.change_lr and args.graph_step and args.adagrad_deterministic:
+        raise NotImplementedError("--graph_step --change_lr keeps the learning rate in a device tensor, which the "
+                                  "sorted update (--adagrad_deterministic) does not read")
     if not args.use_cache:
         raise NotImplementedError("Other EmbeddingBags are under development")   # recsys/models/dlrm.py:83-84
     rank = int(os.environ.get("RANK", "0"))
@@ -577,15 +673,7 @@ def main(argv=None):
     embed.set_cache_mgr_async_copy(args.use_cache_mgr_async_copy)
     if args.table_dtype != "fp32":
         embed.set_weight_rounding(args.weight_rounding, seed=args.seed)
-    groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world}]
-    if args.adagrad:
-        embed.set_fused_rowwise_adagrad(args.learning_rate, deterministic=args.adagrad_deterministic,
-                                        accumulator="step" if args.step_accumulator else "cache")
-    elif args.fused_sgd:
-        embed.set_fused_sgd(args.learning_rate, accumulator="step" if args.step_accumulator else "cache")
-    else:
-        groups.insert(0, {"params": list(model.sparse_modules.parameters()), "lr": args.learning_rate})
-    optimizer = torch.optim.Adagrad(groups) if args.adagrad else torch.optim.SGD(groups)
+    optimizer, lr_tensor = make_optimizer(model, args, device, world)
     if loader is None:
         loader = SyntheticLoader(sizes, args.batch_size, args.num_dense_features, args.limit_train_batches,
                                  args.seed + 17)
@@ -610,9 +698,11 @@ def main(argv=None):
             test_loader = _Limit(test_loader, args.limit_test_batches)
     results = {"val_aurocs": [], "val_accuracies": [], "test_auroc": None, "test_accuracy": None}   # TrainValTestResults
     main.results, main.model, main.val_loader, main.test_loader = results, model, val_loader, test_loader
+    lr_change = LrChange(args, len(loader) * args.epochs, optimizer, embed, lr_tensor) if args.change_lr else None
     for epoch in range(args.epochs):
         rec = []
-        done, elapsed, loss = train(model, optimizer, loader, args, device, rank, world, record=rec)
+        done, elapsed, loss = train(model, optimizer, loader, args, device, rank, world, record=rec,
+                                    lr_change=lr_change)
         if args.eval_acc:                                        # recsys/dlrm_main.py:358-363
             auroc, acc = _evaluate(model, val_loader, "val", args, device, rank, world)
             results["val_aurocs"].append(auroc)

@@ -477,8 +477,66 @@ int ce_bag_backward_update_compact_src(void* weight, int32_t weight_dtype, int64
                                        float eps, int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
                                        size_t workspace_bytes, ce_stream_t stream);
 
+/* Learning rate from device memory for the atomic fused updates (additions to API 6).  Every fused update above takes
+ * `float lr`; a hipGraph capture freezes that float, so a replayed step cannot follow a learning-rate schedule.  The
+ * four entries below are existing argument lists with `float lr` replaced by `const float* lr`:
+ *   ce_bag_backward_sgd_lrdev        the list of ce_bag_backward_sgd_act     (fp32 table, slots + offsets, optional keys)
+ *   ce_bag_backward_sgd_src_lrdev    the list of ce_bag_backward_sgd_src_act (source-row keys, optional seg_id_ranges)
+ *   ce_bag_backward_update_lrdev     the list of ce_bag_backward_update_w16 plus `accumulator` behind `seed`; it covers
+ *                                      CE_ACC_CACHE, CE_ACT_F32 table : ce_bag_backward_rowwise_adagrad_act
+ *                                      CE_ACC_CACHE, 16-bit table     : ce_bag_backward_update_w16
+ *                                      CE_ACC_STEP                    : ce_bag_backward_update_compact
+ *   ce_bag_backward_update_src_lrdev the same from source-row keys: ce_bag_backward_rowwise_adagrad_src_act,
+ *                                    ce_bag_backward_update_src_w16, ce_bag_backward_update_compact_src
+ * The workspace is the one the covered entry takes for that accumulator and table type (ce_bag_backward_rowwise_adagrad_
+ * workspace, ce_bag_backward_w16_workspace, ce_bag_backward_update_compact_workspace).
+ *   - `lr` points to ONE fp32 in device memory, 4-byte aligned.
+ *   - The kernels of the call read it when they RUN (once per thread, at the top of the kernel): a stream-ordered write
+ *     before the call counts, and a replayed graph reads the value of the moment of the replay.
+ *   - Nothing on the host reads the value: no synchronisation, no allocation.  The launch shapes are those of the
+ *     by-value sibling, so the entry is capture-safe as that one is.
+ *   - With *lr == v the entry writes the bits the by-value sibling writes for lr = v: weights, momentum and the
+ *     stochastic rounding bits (the SGD scatter scales by -(*lr), a negation; the apply pass is the same update_row).
+ *   - The host cannot check the value.  The by-value update entries refuse lr < 0; here a negative or NaN value takes
+ *     part in the arithmetic as it is.
+ *   - lr == NULL is CE_ERR_INVALID ("lr: null device pointer") before the first launch, and it is the FIRST check of
+ *     the entry: it comes before every refusal of the sibling, also for a call the sibling returns from at once
+ *     (nnz == 0).  In the two update entries an unknown accumulator code is the second check (CE_ERR_INVALID).
+ *   - Every other refusal has the sibling's code, message and position in the order of checks; the by-value entry and
+ *     this one are the same function, called with and without the pointer.
+ *   - The update entries refuse what the covered entry refuses: CE_OPT_SGD on an fp32 table (CE_ERR_UNSUPPORTED with
+ *     either accumulator, where the sibling's not-taken check stands: the two sgd entries above are that update),
+ *     row-wise Adagrad with CE_ROUND_STOCHASTIC on a 16-bit table with CE_ACC_STEP, and everything else.  With
+ *     CE_ACC_CACHE on an fp32 table `rounding` and `seed` are not looked at (the covered entry has neither).
+ * Not covered: the sorted, deterministic updates (ce_bag_backward_sgd_sorted, ce_bag_backward_update_sorted),
+ * ce_bag_backward_max and ce_rows_axpy keep `float lr` / `float alpha` only. */
+#define CE_ACC_CACHE 0
+#define CE_ACC_STEP 1
+int ce_bag_backward_sgd_lrdev(float* weight, int64_t num_rows, int32_t dim,
+                              const int64_t* indices, int64_t nnz,
+                              const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                              int32_t include_last_offset, const float* per_sample_weights,
+                              int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                              const float* lr, const uint64_t* presorted_keys, ce_stream_t stream);
+int ce_bag_backward_sgd_src_lrdev(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                  const void* grad_out, int32_t act_dtype, const float* lr, const uint64_t* src_keys,
+                                  const int64_t* seg_id_ranges, ce_stream_t stream);
+int ce_bag_backward_update_lrdev(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                 const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                 int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                 int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                 const uint64_t* presorted, const int32_t* row_of_slot, float* momentum,
+                                 int64_t momentum_rows, const float* lr, float eps, int32_t optimizer, int32_t rounding,
+                                 uint64_t seed, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                 ce_stream_t stream);
+int ce_bag_backward_update_src_lrdev(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
+                                     const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                     const int32_t* row_of_slot, float* momentum, int64_t momentum_rows,
+                                     const float* lr, float eps, int32_t optimizer, int32_t rounding, uint64_t seed,
+                                     int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
- * CachedParamMgr [A.1-A.6].  Device state arrays are owned by the caller (so the Python
+ * CachedParamMgr [A.1-A.6]. Device state arrays are owned by the caller (so the Python
  * mirror can expose them as tensors: cached_idx_map, inverted_cached_idx, idx_map,
  * freq_cnter, cuda_cached_weight); the library owns only the opaque scratch it is handed.
  * Row ids are int32 on the device (num_embeddings < 2^31), counters int64.
