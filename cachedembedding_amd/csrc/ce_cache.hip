@@ -7,21 +7,30 @@
 // every count the host would need (unique rows, misses, victims) stays in a device-side
 // control block, and the per-call statistics are stored straight into a pinned host ring.
 //
-//   mark      ids -> rows (idx_map) -> bits in a row bitmap (N/8 bytes); the row of every id is left in
-//             slots_out for the last kernel                                                 [unique, K2/K3]
-//   count     unique / missing rows per 32768-row chunk, and per 64 chunks; miss = inverted[row] < 0   [K4]
-//   emit      every workgroup adds up the counts before its own (that IS the scan), workgroup 0 also does the
-//             plan (capacity check, k = miss - free); miss rows in ascending order; hit slots stamped with the
-//             call epoch; bitmap cleared
-//   keys/hist x<=8/victims      exact k-smallest selection over all slots          [K5]
-//   evict     victims' rows written back to the host table, maps cleared           [K6]
-//   free      first n_miss free slots ascending (ordered compaction)              [K7]
-//   admit     miss rows host -> cache rows, maps + counters updated               [K8/K9]
-//   slots     inverted[idx_map[id]] for every id, LFU counters += multiplicity    [K10/K11]
+// The front of a call (unique rows, misses, plan) comes in two forms, launch_front_kernels picks one:
 //
-// A bitmap replaces torch.unique's sort: it yields the unique rows already in ascending
-// order (the order A.4 pairs missing rows with free slots in) for N/8 bytes of streaming
-// traffic instead of a multi-pass radix sort of every id.  Victim selection is a radix
+//   per-lookup front   k_touch (one thread per id: a resident row's slot stamped, a missing row test-and-set in the row
+//                      bitmap and appended to an unordered list, the id's row left in slots_out) + k_miss_rank (every
+//                      missing row at its rank = the ascending miss list, + the plan).  Every launched call of the zero-copy,
+//                      staged and chained-admission worker arrangements; its bits and counters are cleared by the
+//                      call's k_keys (take_front_tail).
+//   bitmap front       k_begin / k_mark / k_count / k_emit: ids -> bits in a row bitmap (N/8 bytes), unique / missing
+//                      rows counted per 32768-row chunk, every workgroup of k_emit adds up the counts before its own
+//                      (that IS the scan) and workgroup 0 does the plan.  Captured zero-copy calls (no call number to
+//                      stamp with), the worker arrangement with host-gather admission (it reads k_emit's mailbox) and
+//                      tables beyond 2^29 rows.
+//
+// Behind either front (DESIGN.md 3.1 has the table: arrangement -> functions -> stream of every launch):
+//
+//   keys/hist x<=8/victims      exact k-smallest selection over all slots          [K5]   launch_keys_hist
+//   evict     victims' rows written back to the host table, maps cleared           [K6]   select_and_stage
+//   free      first n_miss free slots ascending (ordered compaction)              [K7]
+//   admit     miss rows host -> cache rows, maps + counters updated               [K8/K9] admit_parked / admit_zero_copy /
+//                                                                                         admit_staged / chained_*_half
+//   slots     inverted[idx_map[id]] for every id, LFU counters += multiplicity    [K10/K11] launch_slots_keys
+//
+// Either front replaces torch.unique's sort: the bitmap yields the unique rows already in ascending
+// order (the order A.4 pairs missing rows with free slots in) instead of a multi-pass radix sort of every id.  Victim selection is a radix
 // select on 64-bit keys that encode the canonical order of SURVEY.md Appendix B#1
 // (LFU: (freq asc, slot asc); DATASET: cpu_row_idx desc), so evict sets are id-exact
 // against oracle/cache_oracle.py.  Row payloads move either by zero-copy kernels that
@@ -59,89 +68,110 @@ struct KeysTail {
 };
 
 struct ce_cache {
-  ce_cache_config_t cfg;
-  ce::Layout L;
-  char* ws;
-  ce::Ctl* ctl;
-  uint32_t* bitmap;
-  int32_t *blk_unique, *blk_miss, *coarse, *miss_list, *slot_epoch, *victims, *blk_free, *free_list;
-  int32_t* miss_list_b[2];     // [0] = miss_list, [1] = the second pair (chained admission: by call parity)
-  int32_t* free_list_b[2];
-  ce::ChainWords* chain;       // row counts for the admission stream
-  unsigned long long *lb_emit, *lb_remap;      // look-back words (ce_cache_fused.h)
-  unsigned lb_tag;             // calls that used them (every such call rewrites every word under its own tag)
-  ce::FrontWords* front;       // [2]: counters of the per-lookup front (k_touch / k_miss_rank), by parity of front_calls
-  int32_t *fine_cnt, *coarse_cnt;
-  long long front_calls;       // calls that took the per-lookup front
-  bool front_cleanup_pending;  // ... and whose k_keys has not been launched yet (it clears the front's bits and counters)
-  unsigned long long* keys;
-  uint32_t* hist;
-  ce_call_stats_t* ring;       // pinned host
-  ce_call_stats_t* ring_dev;   // device-visible alias
-  hipEvent_t ev;
-  float* stage;                // device staging for evicted rows (inside the workspace)
-  int32_t* stage_idx;          // host row of every staged victim
-  long long seq;               // calls issued
-  long long drained;           // calls whose stats were folded into history
+  ce_cache_config_t cfg{};
+  ce::Layout L{};
+  char* ws = nullptr;
+  template <typename T> T* at(size_t offset) const { return (T*)(ws + offset); }      // a workspace array (ce::Layout)
+  ce::Ctl* ctl = nullptr;
+  uint32_t* bitmap = nullptr;
+  int32_t *blk_unique = nullptr, *blk_miss = nullptr, *coarse = nullptr, *miss_list = nullptr, *slot_epoch = nullptr,
+          *victims = nullptr, *blk_free = nullptr, *free_list = nullptr;
+  int32_t* miss_list_b[2] = {};     // [0] = miss_list, [1] = the second pair (chained admission: by call parity)
+  int32_t* free_list_b[2] = {};
+  ce::ChainWords* chain = nullptr;       // row counts for the admission stream
+  unsigned long long *lb_emit = nullptr, *lb_remap = nullptr;      // look-back words (ce_cache_fused.h)
+  unsigned lb_tag = 0;         // calls that used them (every such call rewrites every word under its own tag)
+  ce::FrontWords* front = nullptr;       // [2]: counters of the per-lookup front (k_touch / k_miss_rank), by parity of front_calls
+  int32_t *fine_cnt = nullptr, *coarse_cnt = nullptr;
+  long long front_calls = 0;   // calls that took the per-lookup front
+  bool front_cleanup_pending = false;  // ... and whose k_keys has not been launched yet (it clears the front's bits and counters)
+  unsigned long long* keys = nullptr;
+  uint32_t* hist = nullptr;
+  ce_call_stats_t* ring = nullptr;       // pinned host
+  ce_call_stats_t* ring_dev = nullptr;   // device-visible alias
+  hipEvent_t ev = nullptr;
+  float* stage = nullptr;      // device staging for evicted rows (inside the workspace)
+  int32_t* stage_idx = nullptr;          // host row of every staged victim
+  long long seq = 0;           // calls issued
+  long long drained = 0;       // calls whose stats were folded into history
   std::vector<ce_call_stats_t> history;
-  int64_t cpu_to_cuda_numel, cuda_to_cpu_numel, cache_miss, total_cache;
-  int vec;                     // rows moved as 16-B vectors
-  int rowlen, g_log2, slot_bits, word_bits;
+  int64_t cpu_to_cuda_numel = 0, cuda_to_cpu_numel = 0, cache_miss = 0, total_cache = 0;
+  int vec = 0;                 // rows moved as 16-B vectors
+  int rowlen = 0, g_log2 = 0, slot_bits = 0, word_bits = 0;
   // staged transport
-  int host_threads;
-  float* stage_dev;            // device staging [stage_rows, D]
-  float* stage_host;           // pinned host staging
-  int32_t* list_host;          // pinned host copy of row/slot lists
-  ce::Ctl* ctl_host;           // pinned host copy of the control block
-  int64_t stage_rows;
-  int64_t list_rows;           // capacity of list_host
-  int64_t buffer_rows;         // > 0: staged transfers go through at most this many staging rows at a time
-  ce::RowPool* pool;           // host threads of the staged transport (created on first use)
-  ce::SwapEngine* wb;          // CE_TRANSPORT_WORKER state (created on first use)
-  unsigned long long* evt_keys[2];   // rows staged by the write-back job of either parity (ce::EvTable; worker transport)
-  int32_t* evt_pos[2];
-  uint32_t evt_mask;
-  float* stage2;               // second eviction staging buffer + row list, admission staging (workspace)
-  int32_t* stage_idx2;
-  float* in_stage;
-  long long hist_base;         // seq of history[0]
-  ce::PhaseProf* prof;         // optional per-phase hipEvent timers (ce_cache_set_profiling)
-  uint64_t freq_bound;         // LFU: upper bound of any freq_cnter value (shortens the radix select)
-  uint64_t graph_freq_limit;   // LFU: freq_bound the most recently captured call's pass count allows for
-  bool freq_bound_known;       // false after a preload with caller-supplied counters until the caller states their max
-  long long n_failed;          // finished prepare_ids calls whose status was not CE_OK
-  int last_fail_status;
-  long long last_fail_seq;
+  int host_threads = 1;
+  float* stage_dev = nullptr;  // device staging [stage_rows, D]
+  float* stage_host = nullptr; // pinned host staging
+  int32_t* list_host = nullptr;          // pinned host copy of row/slot lists
+  ce::Ctl* ctl_host = nullptr; // pinned host copy of the control block
+  int64_t stage_rows = 0;
+  int64_t list_rows = 0;       // capacity of list_host
+  int64_t buffer_rows = 0;     // > 0: staged transfers go through at most this many staging rows at a time
+  ce::RowPool* pool = nullptr; // host threads of the staged transport (created on first use)
+  ce::SwapEngine* wb = nullptr;          // CE_TRANSPORT_WORKER state (created on first use)
+  unsigned long long* evt_keys[2] = {};  // rows staged by the write-back job of either parity (ce::EvTable; worker transport)
+  int32_t* evt_pos[2] = {};
+  uint32_t evt_mask = 0;
+  float* stage2 = nullptr;     // second eviction staging buffer + row list, admission staging (workspace)
+  int32_t* stage_idx2 = nullptr;
+  float* in_stage = nullptr;
+  long long hist_base = 1;     // seq of history[0]
+  ce::PhaseProf* prof = nullptr;         // optional per-phase hipEvent timers (ce_cache_set_profiling)
+  uint64_t freq_bound = 0;     // LFU: upper bound of any freq_cnter value (shortens the radix select)
+  uint64_t graph_freq_limit = ~0ull;     // LFU: freq_bound the most recently captured call's pass count allows for
+  bool freq_bound_known = true;          // false after a preload with caller-supplied counters until the caller states their max
+  long long n_failed = 0;      // finished prepare_ids calls whose status was not CE_OK
+  int last_fail_status = CE_OK;
+  long long last_fail_seq = 0;
   // "the cache has no free slot left": true once a finished prepare_ids record issued after the last flush says so,
   // until the next flush or failed call.  Calls launched while it holds take the steady-state form (free slots = this
   // call's victims: no free-list scan, see free_list_from_victims); the device re-checks the premise (k_emit).
-  bool free_zero;
-  long long free_reset_seq;    // records up to this call number say nothing about the present
-  bool deferred_rows;          // chained admission: calls do not make their stream wait for the rows (ce_cache_wait_rows)
-  // a prepare_ids call issued in two halves (ce_cache_prepare_ids_begin / _finish): what the second half needs
+  bool free_zero = false;
+  long long free_reset_seq = 0;          // records up to this call number say nothing about the present
+  bool deferred_rows = false;  // chained admission: calls do not make their stream wait for the rows (ce_cache_wait_rows)
+  // The one description of a prepare_ids call in flight, filled by record_call before the call's first launch and read
+  // by everything behind it (select_and_stage, the second halves).  A call issued in two halves
+  // (ce_cache_prepare_ids_begin / _finish) stays `active` in between.
   struct Pending {
     bool active = false;
     int64_t n = 0;
     int64_t* slots_out = nullptr;
-    hipStream_t s = nullptr;
+    hipStream_t s = nullptr;     // the call's stream: every launch and phase mark that is not on the admission stream
     bool worker = false, capturing = false, has_tail = false;
-    long long in_job = 0, seq_arg = 0;
-    int cap_groups = 1, swap_threads = 256, pslot = 0, pmark = 0;
     bool chained = false;        // chained admission: the second half is chained_second_half
     long long call = 0;          // its ticket (SwapEngine::chain_calls)
     int parity = 0;
-    bool sel_pending = false;    // the selection / staging part has not been launched yet (select_and_stage)
-    hipStream_t sel_s = nullptr;
-    int64_t sel_n = 0;
-    bool sel_steady = false;
-    long long sel_out_job = 0;
-    int sel_wbuf = 0, sel_n_vblocks = 0;
-    const void* prof = nullptr;      // the phase timers the first half recorded into (they may be switched off / on in between)
+    long long in_job = 0, seq_arg = 0;     // (seq_arg 0: a captured call, the device's own count)
+    int cap_groups = 1, swap_threads = 256;
+    bool sel_pending = false;    // host-gather admission in two halves: select_and_stage opens the second half
+    bool sel_steady = false;     // steady-state form (see free_zero): the slots to fill are this call's victims
+    long long sel_out_job = 0;   // worker transport: the call's write-back job and its staging buffer
+    int sel_wbuf = 0;
+    int pslot = 0, pmark = 0;    // phase timers: the call's slot, its next mark (phase_mark)
+    const void* prof = nullptr;  // the timers the first half recorded into (they may be switched off / on in between)
     KeysTail tail{};
   } pend;
 };
 
 using namespace ce;
+
+// The one place that turns h->vec into the row type of a row-moving kernel: f is a generic lambda and gets a tag to read
+// the type from (typename decltype(r)::VT), like for_lanes / for_table of ce_common.h.  (Not row_geometry(): it refuses
+// rows of more than 4 chunks per lane, and the cache's kernels walk rows of any length.)
+template <typename VT_> struct RowTag { typedef VT_ VT; };
+template <typename F> static inline void for_rows(const ce_cache* h, F&& f) {
+  if (h->vec) f(RowTag<f32x4>{}); else f(RowTag<float>{});
+}
+
+// the phase timers of the call in flight: those its first half recorded into, if they are still the handle's
+static PhaseProf* live_prof(const ce_cache* h) {
+  return (h->prof && (const void*)h->prof == h->pend.prof) ? h->prof : nullptr;
+}
+// ... and the call's next mark, on the call's stream
+static void phase_mark(ce_cache* h) {
+  ce_cache::Pending& x = h->pend;
+  if (PhaseProf* const prof = live_prof(h)) (void)hipEventRecord(prof->ev[x.pslot][x.pmark++], x.s);
+}
 
 static int ensure_writeback(ce_cache* h);
 
@@ -231,70 +261,40 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
   h->cfg = *cfg;
   h->L = L;
   h->ws = (char*)cfg->workspace;
-  h->ctl = (Ctl*)(h->ws + L.ctl);
-  h->bitmap = (uint32_t*)(h->ws + L.bitmap);
-  h->blk_unique = (int32_t*)(h->ws + L.blk_unique);
-  h->blk_miss = (int32_t*)(h->ws + L.blk_miss);
-  h->coarse = (int32_t*)(h->ws + L.coarse);
-  h->miss_list = (int32_t*)(h->ws + L.miss_list);
-  h->slot_epoch = (int32_t*)(h->ws + L.slot_epoch);
-  h->keys = (unsigned long long*)(h->ws + L.keys);
-  h->hist = (uint32_t*)(h->ws + L.hist);
-  h->victims = (int32_t*)(h->ws + L.victims);
-  h->blk_free = (int32_t*)(h->ws + L.blk_free);
-  h->free_list = (int32_t*)(h->ws + L.free_list);
+  h->ctl = h->at<Ctl>(L.ctl);
+  h->bitmap = h->at<uint32_t>(L.bitmap);
+  h->blk_unique = h->at<int32_t>(L.blk_unique);
+  h->blk_miss = h->at<int32_t>(L.blk_miss);
+  h->coarse = h->at<int32_t>(L.coarse);
+  h->miss_list = h->at<int32_t>(L.miss_list);
+  h->slot_epoch = h->at<int32_t>(L.slot_epoch);
+  h->keys = h->at<unsigned long long>(L.keys);
+  h->hist = h->at<uint32_t>(L.hist);
+  h->victims = h->at<int32_t>(L.victims);
+  h->blk_free = h->at<int32_t>(L.blk_free);
+  h->free_list = h->at<int32_t>(L.free_list);
   h->miss_list_b[0] = h->miss_list;
-  h->miss_list_b[1] = (int32_t*)(h->ws + L.miss_list2);
+  h->miss_list_b[1] = h->at<int32_t>(L.miss_list2);
   h->free_list_b[0] = h->free_list;
-  h->free_list_b[1] = (int32_t*)(h->ws + L.free_list2);
-  h->chain = (ChainWords*)(h->ws + L.chain);
-  h->lb_emit = (unsigned long long*)(h->ws + L.lb_emit);
-  h->lb_remap = (unsigned long long*)(h->ws + L.lb_remap);
-  h->lb_tag = 0;
-  h->front = (FrontWords*)(h->ws + L.front);
-  h->fine_cnt = (int32_t*)(h->ws + L.fine_cnt);
-  h->coarse_cnt = (int32_t*)(h->ws + L.coarse_cnt);
-  h->front_calls = 0;
-  h->front_cleanup_pending = false;
-  h->seq = h->drained = 0;
-  h->cpu_to_cuda_numel = h->cuda_to_cpu_numel = h->cache_miss = h->total_cache = 0;
+  h->free_list_b[1] = h->at<int32_t>(L.free_list2);
+  h->chain = h->at<ChainWords>(L.chain);
+  h->lb_emit = h->at<unsigned long long>(L.lb_emit);
+  h->lb_remap = h->at<unsigned long long>(L.lb_remap);
+  h->front = h->at<FrontWords>(L.front);
+  h->fine_cnt = h->at<int32_t>(L.fine_cnt);
+  h->coarse_cnt = h->at<int32_t>(L.coarse_cnt);
+  h->stage = h->at<float>(L.stage);
+  h->stage_idx = h->at<int32_t>(L.stage_idx);
+  h->stage2 = h->at<float>(L.stage2);
+  h->stage_idx2 = h->at<int32_t>(L.stage_idx2);
+  h->in_stage = h->at<float>(L.in_stage);
   const int D = cfg->embedding_dim;
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   h->vec = (D % 4 == 0) && al16(cfg->cache_weight) && al16(cfg->host_weight_dev);
   h->rowlen = h->vec ? D / 4 : D;
-  int g = 1, gl2 = 0;
-  while (g < h->rowlen && g < 64) { g <<= 1; ++gl2; }
-  h->g_log2 = gl2;
-  int sb = 1;
-  while ((1ll << sb) < cfg->cuda_row_num) ++sb;
-  h->slot_bits = sb;
-  int wb = 1;
-  while ((1ll << wb) < cdiv(cfg->num_embeddings, 32)) ++wb;
-  h->word_bits = wb;
+  for (int g = 1; g < h->rowlen && g < 64; g <<= 1) ++h->g_log2;
+  for (h->slot_bits = 1; (1ll << h->slot_bits) < cfg->cuda_row_num;) ++h->slot_bits;
+  for (h->word_bits = 1; (1ll << h->word_bits) < cdiv(cfg->num_embeddings, 32);) ++h->word_bits;
   h->host_threads = (int)std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-  h->stage_dev = nullptr;
-  h->stage_host = nullptr;
-  h->list_host = nullptr;
-  h->ctl_host = nullptr;
-  h->stage_rows = 0;
-  h->list_rows = 0;
-  h->buffer_rows = 0;
-  h->pool = nullptr;
-  h->wb = nullptr;
-  h->hist_base = 1;
-  h->prof = nullptr;
-  h->freq_bound = 0;
-  h->graph_freq_limit = ~0ull;
-  h->freq_bound_known = true;
-  h->n_failed = 0;
-  h->last_fail_status = CE_OK;
-  h->last_fail_seq = 0;
-  h->free_zero = false;
-  h->free_reset_seq = 0;
-  h->deferred_rows = false;
-  h->stage2 = (float*)(h->ws + L.stage2);
-  h->stage_idx2 = (int32_t*)(h->ws + L.stage_idx2);
-  h->in_stage = (float*)(h->ws + L.in_stage);
 
   hipStream_t s = (hipStream_t)stream;
   void* ring_host = nullptr;
@@ -308,8 +308,6 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
   void* ring_dev = nullptr;
   if (hipHostGetDevicePointer(&ring_dev, ring_host, 0) != hipSuccess) ring_dev = ring_host;
   h->ring_dev = (ce_call_stats_t*)ring_dev;
-  h->stage = (float*)(h->ws + L.stage);
-  h->stage_idx = (int32_t*)(h->ws + L.stage_idx);
   if (hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess) {
     (void)hipHostFree(ring_host);
     delete h;
@@ -569,15 +567,8 @@ static int ensure_writeback(ce_cache* h) {
     set_error("swap worker setup failed (pinned buffers / streams / events)");
     return rc;
   }
-  w->deferred_rows = h->deferred_rows;
   h->wb = w;
   return CE_OK;
-}
-
-// rows moved per staged transfer: everything at once, or `buffer_rows` at a time (upstream's buffer_size /
-// LimitBuffIndexCopyer: a bounded staging buffer walked in chunks)
-static int64_t staged_chunk(const ce_cache* h, int64_t rows) {
-  return (h->buffer_rows > 0 && h->buffer_rows < rows) ? h->buffer_rows : rows;
 }
 
 extern "C" int ce_cache_set_freq_bound(ce_cache_t* h, int64_t bound) {
@@ -606,74 +597,22 @@ extern "C" int ce_cache_preload(ce_cache_t* h, const int32_t* rows, const int64_
   rc = join_rows(h, s);
   if (rc) return rc;
   h->seq += 1;
-  const int32_t epoch = (int32_t)(h->seq & 0x3fffffff);
   const int64_t groups_per_block = 256 >> h->g_log2;
-  if (h->vec)
-    hipLaunchKernelGGL((k_admit<f32x4>), dim3(grid_for(n, (int)groups_per_block * kSwapRows)), dim3(256), 0, s, rows,
-                       (const int32_t*)nullptr, (const long long*)nullptr, (long long)n,
-                       (const f32x4*)c.host_weight_dev, (f32x4*)c.cache_weight, h->rowlen, h->g_log2,
-                       (const Ctl*)nullptr, 0ll);
-  else
-    hipLaunchKernelGGL((k_admit<float>), dim3(grid_for(n, (int)groups_per_block * kSwapRows)), dim3(256), 0, s, rows,
-                       (const int32_t*)nullptr, (const long long*)nullptr, (long long)n,
-                       (const float*)c.host_weight_dev, (float*)c.cache_weight, h->rowlen, h->g_log2,
-                       (const Ctl*)nullptr, 0ll);
+  for_rows(h, [&](auto r) {
+    using VT = typename decltype(r)::VT;
+    hipLaunchKernelGGL((k_admit<VT>), dim3(grid_for(n, (int)groups_per_block * kSwapRows)), dim3(256), 0, s, rows,
+                       (const int32_t*)nullptr, (const long long*)nullptr, (long long)n, (const VT*)c.host_weight_dev,
+                       (VT*)c.cache_weight, h->rowlen, h->g_log2, (const Ctl*)nullptr, 0ll);
+  });
   // preloaded rows must not look "protected" to the first prepare_ids: stamp them as never used
   hipLaunchKernelGGL(k_admit_maps, dim3(grid_for(n, 256)), dim3(256), 0, s, rows, (const int32_t*)nullptr,
                      (const long long*)nullptr, (long long)n, c.cached_idx_map, c.inverted_cached_idx,
                      c.freq_cnter, freq_vals, h->slot_epoch, kEpochNever, (Ctl*)nullptr,
                      (ce_call_stats_t*)nullptr, 0ll, (const unsigned long long*)nullptr, 0ll);
-  (void)epoch;
   hipLaunchKernelGGL(k_preload_end, dim3(1), dim3(1), 0, s, (long long)n, h->ctl, h->ring_dev + (h->seq % kRing),
                      h->seq);
   CE_LAUNCH_CHECK();
   CE_HIP_CHECK(hipEventRecord(h->ev, s));
-  return CE_OK;
-}
-
-// staged transport: rows move through pinned staging with host worker threads touching the table
-static int staged_swap(ce_cache* h, hipStream_t s) {
-  const ce_cache_config_t& c = h->cfg;
-  const int D = c.embedding_dim;
-  const size_t rowbytes = (size_t)D * sizeof(float);
-  // the host needs the counts and the lists: one sync point per call (the reference has one per phase)
-  if (!h->ctl_host) CE_HIP_CHECK(hipHostMalloc((void**)&h->ctl_host, sizeof(Ctl), hipHostMallocDefault));
-  CE_HIP_CHECK(hipMemcpyAsync(h->ctl_host, h->ctl, sizeof(Ctl), hipMemcpyDeviceToHost, s));
-  CE_HIP_CHECK(hipStreamSynchronize(s));
-  const Ctl ctl = *h->ctl_host;
-  if (ctl.status != CE_OK) return CE_OK;
-  const int64_t k = ctl.k_evict, m = ctl.n_miss;
-  const int64_t big = std::max<int64_t>(std::max(k, m), 1);
-  int rc = ensure_staging(h, staged_chunk(h, big), big);
-  if (rc) return rc;
-  const int gpb = 256 >> h->g_log2;
-  if (k > 0) {
-    // D2H: evicted rows packed on the device, copied, scattered into the table by worker threads
-    int32_t* evicted_rows_dev = h->free_list;   // free_list is not live yet: reuse as the row list
-    hipLaunchKernelGGL(k_evict_maps, dim3(grid_for(k, 256)), dim3(256), 0, s, h->victims, c.cached_idx_map,
-                       c.inverted_cached_idx, evicted_rows_dev, h->ctl);
-    CE_HIP_CHECK(hipMemcpyAsync(h->list_host, evicted_rows_dev, (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    const int64_t chunk = staged_chunk(h, k);
-    for (int64_t off = 0; off < k; off += chunk) {
-      const int64_t cnt = std::min(chunk, k - off);
-      if (h->vec)
-        hipLaunchKernelGGL((k_pack_rows<f32x4>), dim3(grid_for(cnt, gpb)), dim3(256), 0, s,
-                           (const int32_t*)h->victims + off, (long long)cnt, (const f32x4*)c.cache_weight,
-                           (f32x4*)h->stage_dev, h->rowlen, h->g_log2);
-      else
-        hipLaunchKernelGGL((k_pack_rows<float>), dim3(grid_for(cnt, gpb)), dim3(256), 0, s,
-                           (const int32_t*)h->victims + off, (long long)cnt, (const float*)c.cache_weight,
-                           (float*)h->stage_dev, h->rowlen, h->g_log2);
-      CE_HIP_CHECK(hipMemcpyAsync(h->stage_host, h->stage_dev, (size_t)cnt * rowbytes, hipMemcpyDeviceToHost, s));
-      CE_HIP_CHECK(hipStreamSynchronize(s));
-      float* table = c.host_weight;
-      const float* st = h->stage_host;
-      const int32_t* rows = h->list_host + off;
-      host_pool(h)->parallel(cnt, [=](int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i) memcpy(table + (size_t)rows[i] * D, st + (size_t)i * D, rowbytes);
-      });
-    }
-  }
   return CE_OK;
 }
 
@@ -730,22 +669,6 @@ static FrontTail take_front_tail(ce_cache* h) {
   return FrontTail{h->victims, h->front + (h->front_calls & 1), h->bitmap, h->fine_cnt, h->coarse_cnt};
 }
 
-// Second part of a cache op's front: victim selection, staging of the victims (and the write-back job), free-slot list.
-// Runs inline behind the front, or -- a call in two halves on the worker transport -- at the start of the SECOND half:
-// the admission kernel behind the front reads the host table over PCIe for ~0.7 ms, and these kernels run 2-3x slower
-// beside it (find_evict_ids 0.042 -> 0.072 ms, evict_stage 0.030 -> 0.065 ms in the bench's phase timers); behind the
-// window's training steps the admission has long finished and they run alone, while the admission itself starts as
-// early as before.
-struct SelArgs {
-  hipStream_t s;
-  int64_t n;
-  bool worker, capturing, steady;
-  long long out_job, seq_arg;
-  int wbuf, n_vblocks, pslot;
-  const void* prof_id;
-  int32_t* free_list;
-};
-
 // radix passes the victim select needs (the top one is taken by the key kernel itself)
 static int select_top_pass(ce_cache* h, int64_t n, bool capturing) {
   const ce_cache_config_t& c = h->cfg;
@@ -777,86 +700,174 @@ static int select_top_pass(ce_cache* h, int64_t n, bool capturing) {
   return top_pass;
 }
 
-static int select_and_stage(ce_cache* h, const SelArgs& a, int* pmark_io) {
+// victim selection, first part: the keys (k_keys' prologue also clears what the per-lookup front left behind) and the
+// histogram passes below the top one.  Returns the top pass.  (All kernels return at once when k == 0.)
+static int launch_keys_hist(ce_cache* h) {
+  const ce_cache::Pending& x = h->pend;
   const ce_cache_config_t& c = h->cfg;
-  const Layout& L = h->L;
-  const int64_t N = c.num_embeddings, C = c.cuda_row_num, n = a.n;
-  hipStream_t s = a.s;
-  const bool worker = a.worker, capturing = a.capturing, steady = a.steady;
-  const long long out_job = a.out_job, seq_arg = a.seq_arg;
-  const int wbuf = a.wbuf, n_vblocks = a.n_vblocks, pslot = a.pslot;
+  const int64_t N = c.num_embeddings, C = c.cuda_row_num;
   const int lfu = c.evict_strategy == CE_EVICT_LFU;
-  const int gpb = 256 >> h->g_log2;
-  ce_call_stats_t* const ring = h->ring_dev;
-  PhaseProf* const prof = (h->prof && (const void*)h->prof == a.prof_id) ? h->prof : nullptr;
-  int pmark = *pmark_io;
-  int rc = CE_OK;
-#define CE_PHASE() do { if (prof) (void)hipEventRecord(prof->ev[pslot][pmark++], s); } while (0)
-  // ---- victim selection (all kernels return at once when k == 0)
-  const int cgrid = grid_for(C, 256 * 4);
-  const int top_pass = select_top_pass(h, n, capturing);
+  const int top_pass = select_top_pass(h, x.n, x.capturing);
   const FrontTail ft = take_front_tail(h);
-  hipLaunchKernelGGL(k_keys, dim3(std::min(cgrid, 512)), dim3(256), 0, s, c.cached_idx_map, c.freq_cnter, h->slot_epoch, C, N,
-                     seq_arg, c.protect_depth, h->slot_bits, lfu, top_pass, h->keys, h->hist, h->ctl, ft.miss_tmp, ft.fw,
-                     ft.bitmap, ft.fine, ft.coarse, (int)L.n_chunks);
+  hipLaunchKernelGGL(k_keys, dim3(std::min(grid_for(C, 256 * 4), 512)), dim3(256), 0, x.s, c.cached_idx_map, c.freq_cnter,
+                     h->slot_epoch, C, N, x.seq_arg, c.protect_depth, h->slot_bits, lfu, top_pass, h->keys, h->hist, h->ctl,
+                     ft.miss_tmp, ft.fw, ft.bitmap, ft.fine, ft.coarse, (int)h->L.n_chunks);
   const int hgrid = (int)std::min<int64_t>(kNumCU, std::max<int64_t>(1, cdiv(C, 1024 * 4)));
   // (all passes in ONE workgroup for small caches was tried for the B = 2048 shapes: a single CU keeps too few key
   // loads in flight -- 0.38 ms per call against 0.05 ms for the 5 launch pairs.  What works per launch: every
   // workgroup of pass p recomputes the digits of the level above it from that level's histogram in its prologue --
   // select_level -- so there is no pick kernel at all)
   for (int pass = top_pass - 1; pass >= 0; --pass)
-    hipLaunchKernelGGL(k_hist, dim3(hgrid), dim3(1024), 0, s, h->keys, C, pass, top_pass, h->hist, h->ctl);
+    hipLaunchKernelGGL(k_hist, dim3(hgrid), dim3(1024), 0, x.s, h->keys, C, pass, top_pass, h->hist, h->ctl);
+  return top_pass;
+}
+
+// ---- staged transport (CE_TRANSPORT_STAGED): rows move through pinned staging + hipMemcpyAsync, host worker threads
+// touch the table.  staged_swap is the D2H half (the call's victims, from select_and_stage), admit_staged the H2D half
+// (its missed rows, from the second half).
+
+// rows moved per staged transfer: everything at once, or `buffer_rows` at a time (upstream's buffer_size /
+// LimitBuffIndexCopyer: a bounded staging buffer walked in chunks)
+static int64_t staged_chunk(const ce_cache* h, int64_t rows) {
+  return (h->buffer_rows > 0 && h->buffer_rows < rows) ? h->buffer_rows : rows;
+}
+static size_t rowbytes(const ce_cache* h) { return (size_t)h->cfg.embedding_dim * sizeof(float); }
+
+static int staged_swap(ce_cache* h, hipStream_t s) {
+  const ce_cache_config_t& c = h->cfg;
+  const int D = c.embedding_dim;
+  // the host needs the counts and the lists: one sync point per call (the reference has one per phase)
+  if (!h->ctl_host) CE_HIP_CHECK(hipHostMalloc((void**)&h->ctl_host, sizeof(Ctl), hipHostMallocDefault));
+  CE_HIP_CHECK(hipMemcpyAsync(h->ctl_host, h->ctl, sizeof(Ctl), hipMemcpyDeviceToHost, s));
+  CE_HIP_CHECK(hipStreamSynchronize(s));
+  const Ctl ctl = *h->ctl_host;
+  if (ctl.status != CE_OK) return CE_OK;
+  const int64_t k = ctl.k_evict, m = ctl.n_miss;
+  const int64_t big = std::max<int64_t>(std::max(k, m), 1);
+  int rc = ensure_staging(h, staged_chunk(h, big), big);
+  if (rc) return rc;
+  const int gpb = 256 >> h->g_log2;
+  if (k > 0) {
+    // D2H: evicted rows packed on the device, copied, scattered into the table by worker threads
+    int32_t* evicted_rows_dev = h->free_list;   // free_list is not live yet: reuse as the row list
+    hipLaunchKernelGGL(k_evict_maps, dim3(grid_for(k, 256)), dim3(256), 0, s, h->victims, c.cached_idx_map,
+                       c.inverted_cached_idx, evicted_rows_dev, h->ctl);
+    CE_HIP_CHECK(hipMemcpyAsync(h->list_host, evicted_rows_dev, (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    const int64_t chunk = staged_chunk(h, k);
+    for (int64_t off = 0; off < k; off += chunk) {
+      const int64_t cnt = std::min(chunk, k - off);
+      for_rows(h, [&](auto r) {
+        using VT = typename decltype(r)::VT;
+        hipLaunchKernelGGL((k_pack_rows<VT>), dim3(grid_for(cnt, gpb)), dim3(256), 0, s, (const int32_t*)h->victims + off,
+                           (long long)cnt, (const VT*)c.cache_weight, (VT*)h->stage_dev, h->rowlen, h->g_log2);
+      });
+      CE_HIP_CHECK(hipMemcpyAsync(h->stage_host, h->stage_dev, (size_t)cnt * rowbytes(h), hipMemcpyDeviceToHost, s));
+      CE_HIP_CHECK(hipStreamSynchronize(s));
+      float* table = c.host_weight;
+      const float* st = h->stage_host;
+      const int32_t* rows = h->list_host + off;
+      const size_t rb = rowbytes(h);
+      host_pool(h)->parallel(cnt, [=](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) memcpy(table + (size_t)rows[i] * D, st + (size_t)i * D, rb);
+      });
+    }
+  }
+  return CE_OK;
+}
+
+// ... H2D: worker threads gather the missed rows out of the table into pinned staging, k_unpack_rows puts them in
+// their slots
+static int admit_staged(ce_cache* h) {
+  const ce_cache_config_t& c = h->cfg;
+  hipStream_t s = h->pend.s;
+  const Ctl ctl = *h->ctl_host;   // filled by staged_swap
+  const int64_t m = (ctl.status == CE_OK) ? ctl.n_miss : 0;
+  if (m <= 0) return CE_OK;
+  const int D = c.embedding_dim, gpb = 256 >> h->g_log2;
+  const size_t rb = rowbytes(h);
+  CE_HIP_CHECK(hipMemcpyAsync(h->list_host, h->miss_list, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+  CE_HIP_CHECK(hipStreamSynchronize(s));
+  const float* table = c.host_weight;
+  float* st = h->stage_host;
+  const int64_t chunk = staged_chunk(h, m);
+  for (int64_t off = 0; off < m; off += chunk) {
+    const int64_t cnt = std::min(chunk, m - off);
+    if (off > 0) CE_HIP_CHECK(hipStreamSynchronize(s));      // the staging buffer is reused
+    const int32_t* rows = h->list_host + off;
+    host_pool(h)->parallel(cnt, [=](int64_t lo, int64_t hi) {
+      for (int64_t i = lo; i < hi; ++i) memcpy(st + (size_t)i * D, table + (size_t)rows[i] * D, rb);
+    });
+    CE_HIP_CHECK(hipMemcpyAsync(h->stage_dev, h->stage_host, (size_t)cnt * rb, hipMemcpyHostToDevice, s));
+    for_rows(h, [&](auto r) {
+      using VT = typename decltype(r)::VT;
+      hipLaunchKernelGGL((k_unpack_rows<VT>), dim3(grid_for(cnt, gpb)), dim3(256), 0, s, (const int32_t*)h->free_list + off,
+                         (long long)cnt, (const VT*)h->stage_dev, (VT*)c.cache_weight, h->rowlen, h->g_log2);
+    });
+  }
+  return CE_OK;
+}
+
+// Second part of a cache op's front: victim selection, staging of the victims (and the write-back job), free-slot list.
+// Runs inline behind the front, or -- a call in two halves on the worker transport -- at the start of the SECOND half:
+// the admission kernel behind the front reads the host table over PCIe for ~0.7 ms, and these kernels run 2-3x slower
+// beside it (find_evict_ids 0.042 -> 0.072 ms, evict_stage 0.030 -> 0.065 ms in the bench's phase timers); behind the
+// window's training steps the admission has long finished and they run alone, while the admission itself starts as
+// early as before.
+static int select_and_stage(ce_cache* h) {
+  const ce_cache::Pending& x = h->pend;
+  const ce_cache_config_t& c = h->cfg;
+  const Layout& L = h->L;
+  const int64_t C = c.cuda_row_num;
+  hipStream_t s = x.s;
+  const bool worker = x.worker, steady = x.sel_steady;
+  const int wbuf = x.sel_wbuf, n_vblocks = (int)cdiv(C, 4096), gpb = 256 >> h->g_log2;
+  int32_t* const free_list = h->free_list_b[x.chained ? x.parity : 0];
+  // ---- victim selection
+  const int top_pass = launch_keys_hist(h);
   hipLaunchKernelGGL(k_victims, dim3((unsigned)n_vblocks), dim3(256), 0, s, h->keys, C, h->victims, L.list_cap, h->ctl,
-                     (const uint32_t*)h->hist, top_pass, ring, seq_arg, steady ? h->blk_free : (int32_t*)nullptr);
-  CE_PHASE();
-  float* const stage_cur = (worker && wbuf) ? h->stage2 : h->stage;
-  int32_t* const stage_idx_cur = (worker && wbuf) ? h->stage_idx2 : h->stage_idx;
+                     (const uint32_t*)h->hist, top_pass, h->ring_dev, x.seq_arg, steady ? h->blk_free : (int32_t*)nullptr);
+  phase_mark(h);
   if (c.transport == CE_TRANSPORT_ZEROCOPY || worker) {
     // ---- victims -> HBM staging (fast); rows beyond the staging capacity (rare) are written back directly;
     // map clear, free-slot list, admit stay on the caller's stream
+    float* const stage_cur = (worker && wbuf) ? h->stage2 : h->stage;
+    int32_t* const stage_idx_cur = (worker && wbuf) ? h->stage_idx2 : h->stage_idx;
     const long long scap = (long long)L.stage_rows;
     const int sgrid = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(L.stage_rows, gpb)));
     WbMail* const mail = worker ? h->wb->mail_dev + wbuf : nullptr;
     const dim3 sg(sgrid + (steady ? n_vblocks : 0));        // + the free-list workgroups of the steady-state form
     const EvTable evt = (worker && h->wb->chained) ? EvTable{h->evt_keys[wbuf], h->evt_pos[wbuf], h->evt_mask}
                                                      : EvTable{nullptr, nullptr, 0u};
-    if (h->vec) {
-      hipLaunchKernelGGL((k_evict_stage<f32x4>), sg, dim3(256), 0, s, h->victims, c.cached_idx_map,
-                         c.inverted_cached_idx, (const f32x4*)c.cache_weight, (f32x4*)stage_cur, stage_idx_cur, scap, h->rowlen, h->g_log2,
-                         h->ctl, mail, out_job, sgrid, (const unsigned long long*)h->keys, C, (const int32_t*)h->blk_free,
-                         a.free_list, evt, L.list_cap > L.stage_rows ? (f32x4*)c.host_weight_dev : (f32x4*)nullptr);
-    } else {
-      hipLaunchKernelGGL((k_evict_stage<float>), sg, dim3(256), 0, s, h->victims, c.cached_idx_map,
-                         c.inverted_cached_idx, (const float*)c.cache_weight, (float*)stage_cur, stage_idx_cur, scap, h->rowlen, h->g_log2,
-                         h->ctl, mail, out_job, sgrid, (const unsigned long long*)h->keys, C, (const int32_t*)h->blk_free,
-                         a.free_list, evt, L.list_cap > L.stage_rows ? (float*)c.host_weight_dev : (float*)nullptr);
-    }
+    for_rows(h, [&](auto r) {
+      using VT = typename decltype(r)::VT;
+      hipLaunchKernelGGL((k_evict_stage<VT>), sg, dim3(256), 0, s, h->victims, c.cached_idx_map, c.inverted_cached_idx,
+                         (const VT*)c.cache_weight, (VT*)stage_cur, stage_idx_cur, scap, h->rowlen, h->g_log2, h->ctl, mail,
+                         x.sel_out_job, sgrid, (const unsigned long long*)h->keys, C, (const int32_t*)h->blk_free, free_list,
+                         evt, L.list_cap > L.stage_rows ? (VT*)c.host_weight_dev : (VT*)nullptr);
+    });
     if (worker) {
       // the write-back worker takes it from here: D2H of the packed block + scatter into the table
       CE_HIP_CHECK(hipEventRecord(h->wb->out_ev[wbuf], s));
       h->wb->push_out();
     }
   } else {
-    rc = staged_swap(h, s);
+    const int rc = staged_swap(h, s);
     if (rc) return rc;
   }
-  CE_PHASE();
+  phase_mark(h);
   // (one workgroup walks 4096 slots per round: beyond a few rounds the pair of wide kernels is faster --
   // C = 94 k, Avazu at 1 %: 18.3 us against 13.6 us for the pair)
   if (steady) {
     // (the list was written by k_evict_stage's free-list workgroups)
   } else if (C <= 16384) {
-    hipLaunchKernelGGL(k_free_single, dim3(1), dim3(1024), 0, s, c.cached_idx_map, C, a.free_list, h->ctl);
+    hipLaunchKernelGGL(k_free_single, dim3(1), dim3(1024), 0, s, c.cached_idx_map, C, free_list, h->ctl);
   } else {
     hipLaunchKernelGGL(k_free_count, dim3((unsigned)L.n_slot_blocks), dim3(256), 0, s, c.cached_idx_map, C,
                        h->blk_free, h->ctl);
     hipLaunchKernelGGL(k_free_emit, dim3((unsigned)L.n_slot_blocks), dim3(256), 0, s, c.cached_idx_map, C,
-                       h->blk_free, a.free_list, h->ctl);
+                       h->blk_free, free_list, h->ctl);
   }
-  CE_PHASE();
-#undef CE_PHASE
-  *pmark_io = pmark;
-  (void)rc;
+  phase_mark(h);
   return CE_OK;
 }
 
@@ -946,32 +957,63 @@ static int prepare_ids_second_half(ce_cache* h);
 static int chained_second_half(ce_cache* h);
 static int launch_slots_keys(ce_cache* h);
 
+// Fills the call record (ce_cache::Pending) from what the first half knows, after the call has its number (h->seq) and
+// before its first launch.  out_job / in_job: the worker transport's job numbers of the call, chain_call: its ticket
+// on the chained admission -- 0 where the call has none.
+static ce_cache::Pending& record_call(ce_cache* h, int64_t n, int64_t* slots_out, hipStream_t s, const KeysTail* tail,
+                                      bool worker, bool capturing, int split, long long out_job, long long in_job,
+                                      long long chain_call) {
+  const ce_cache_config_t& c = h->cfg;
+  ce_cache::Pending x;
+  x.n = n;
+  x.slots_out = slots_out;
+  x.s = s;
+  x.worker = worker;
+  x.capturing = capturing;
+  x.has_tail = tail != nullptr;
+  if (tail) x.tail = *tail;
+  x.chained = chain_call > 0;
+  x.call = chain_call;
+  x.parity = (int)(chain_call & 1);
+  x.in_job = in_job;
+  x.seq_arg = capturing ? 0ll : (long long)h->seq;
+  // swap kernels: small grid (default 2 workgroups per CU's worth of slots is left to training kernels)
+  // protect_depth > 0 means the call overlaps with training kernels on another stream: stay small (32
+  // workgroups measured best: 1.43 -> 1.82 G lookups/s); alone on the GPU a wider grid finishes sooner
+  const int swap_blocks = c.protect_depth > 0 ? 32 : 512;
+  x.swap_threads = 256;
+  x.cap_groups = (int)std::min<int64_t>(swap_blocks, std::max<int64_t>(1, cdiv(h->L.list_cap, (x.swap_threads >> h->g_log2) * kSwapRows)));
+  // the selection / staging part moves into the second half: always on the chained admission, and for a call in two
+  // halves on the host-gather one
+  x.sel_pending = x.chained || (split && worker);
+  x.sel_steady = h->free_zero && !capturing && (c.transport == CE_TRANSPORT_ZEROCOPY || worker);
+  x.sel_out_job = out_job;
+  x.sel_wbuf = (int)(out_job & 1);
+  x.pslot = (int)(h->seq % kProfDepth);
+  x.prof = h->prof;
+  return h->pend = x;
+}
+
 // Chained admission, first half: the fused front on the call's stream, the admission kernel behind its event on the
 // admission stream.  (SwapEngine: why no thread and no parked stream.)
 static int chained_first_half(ce_cache* h, const int64_t* ids, int64_t n, int64_t* slots_out, hipStream_t s,
                               int allow_pad, const KeysTail* tail, int split) {
   SwapEngine* const w = h->wb;
-  const Layout& L = h->L;
   const long long out_job = w->out_issued + 1;
-  const int wbuf = (int)(out_job & 1);
   // write-back out_job - 2 has landed: its staging buffer is this call's, and everything older is in the host table
   // the admission kernel is about to read (what job out_job - 1 still carries it takes from that job's staging buffer)
   int rc = w->wait_out(out_job - 2);
   if (rc) return rc;
-  const long long call = ++w->chain_calls;
-  const int parity = (int)(call & 1);
-  const bool steady = h->free_zero;
-  const long long seq_arg = (long long)h->seq;
-  PhaseProf* const prof = h->prof;
-  const int pslot = (int)(h->seq % kProfDepth);
-  int pmark = 0;
+  ce_cache::Pending& x = record_call(h, n, slots_out, s, tail, true, false, split, out_job, 0ll, ++w->chain_calls);
+  const int parity = x.parity, pslot = x.pslot;
+  PhaseProf* const prof = live_prof(h);
   if (prof) {
     prof->collect(pslot);
     prof->chained[pslot] = true;
-    (void)hipEventRecord(prof->ev[pslot][pmark++], s);
   }
-  launch_front_kernels(h, ids, n, slots_out, s, allow_pad, steady, seq_arg, h->miss_list_b[parity], (WbMail*)nullptr, 0ll,
-                       (int32_t*)nullptr, &h->chain->n_admit[parity], true);
+  phase_mark(h);
+  launch_front_kernels(h, ids, n, slots_out, s, allow_pad, x.sel_steady, x.seq_arg, h->miss_list_b[parity], (WbMail*)nullptr,
+                       0ll, (int32_t*)nullptr, &h->chain->n_admit[parity], true);
   CE_HIP_CHECK(hipEventRecord(w->ev_miss[parity], s));
   CE_HIP_CHECK(hipStreamWaitEvent(w->in_stream, w->ev_miss[parity], 0));
   if (prof) (void)hipEventRecord(prof->adm0[pslot], w->in_stream);
@@ -994,27 +1036,14 @@ static int chained_first_half(ce_cache* h, const int64_t* ids, int64_t n, int64_
     const bool has_prev = prev >= w->probe_floor && !landed;
     const unsigned long long* ek = has_prev ? h->evt_keys[pb] : nullptr;
     const long long* n_ptr = &h->chain->n_admit[parity];
-    if (h->vec)
-      hipLaunchKernelGGL((k_admit_probe<f32x4>), dim3(blocks), dim3(1024), 0, w->in_stream, h->miss_list_b[parity], n_ptr,
-                         (const f32x4*)h->cfg.host_weight_dev, (f32x4*)h->in_stage, h->rowlen, h->g_log2, ek,
-                         (const int32_t*)h->evt_pos[pb], h->evt_mask, (uint32_t)prev,
-                         (const f32x4*)(pb ? h->stage2 : h->stage));
-    else
-      hipLaunchKernelGGL((k_admit_probe<float>), dim3(blocks), dim3(1024), 0, w->in_stream, h->miss_list_b[parity], n_ptr,
-                         (const float*)h->cfg.host_weight_dev, (float*)h->in_stage, h->rowlen, h->g_log2, ek,
-                         (const int32_t*)h->evt_pos[pb], h->evt_mask, (uint32_t)prev,
-                         (const float*)(pb ? h->stage2 : h->stage));
+    for_rows(h, [&](auto r) {
+      using VT = typename decltype(r)::VT;
+      hipLaunchKernelGGL((k_admit_probe<VT>), dim3(blocks), dim3(1024), 0, w->in_stream, h->miss_list_b[parity], n_ptr,
+                         (const VT*)h->cfg.host_weight_dev, (VT*)h->in_stage, h->rowlen, h->g_log2, ek,
+                         (const int32_t*)h->evt_pos[pb], h->evt_mask, (uint32_t)prev, (const VT*)(pb ? h->stage2 : h->stage));
+    });
   }
-  if (prof) (void)hipEventRecord(prof->ev[pslot][pmark++], s);
-  ce_cache::Pending& x = h->pend;
-  x.n = n; x.slots_out = slots_out; x.s = s; x.worker = true; x.capturing = false; x.has_tail = tail != nullptr;
-  x.in_job = 0; x.seq_arg = seq_arg; x.pslot = pslot; x.pmark = pmark; x.prof = prof;
-  x.chained = true; x.call = call; x.parity = parity;
-  x.sel_pending = true;
-  x.sel_s = s; x.sel_n = n; x.sel_steady = steady; x.sel_out_job = out_job; x.sel_wbuf = wbuf;
-  x.sel_n_vblocks = (int)cdiv(h->cfg.cuda_row_num, 4096);
-  if (tail) x.tail = *tail;
-  (void)L;
+  phase_mark(h);
   if (split) {
     x.active = true;
     CE_LAUNCH_CHECK();
@@ -1035,7 +1064,7 @@ static int chained_second_half(ce_cache* h) {
   hipStream_t s = x.s;
   const int parity = x.parity, wbuf = x.sel_wbuf, pslot = x.pslot;
   const long long call = x.call, out_job = x.sel_out_job;
-  PhaseProf* const prof = (h->prof && (const void*)h->prof == x.prof) ? h->prof : nullptr;
+  PhaseProf* const prof = live_prof(h);
   if (prof) {
     (void)hipEventRecord(prof->resume[pslot], s);
     prof->resumed[pslot] = true;
@@ -1045,20 +1074,12 @@ static int chained_second_half(ce_cache* h) {
   // lists come up for reuse with the next front: this call's selection goes behind the previous call's rows.
   if (call > 1) CE_HIP_CHECK(hipStreamWaitEvent(s, w->ev_rows[(call - 1) % SwapEngine::kRowsRing], 0));
   hipEvent_t sel_done = w->out_ev[wbuf];
-  if (x.sel_steady && x.sel_n <= kScanMaxIds) {
+  if (x.sel_steady && x.n <= kScanMaxIds) {
     // a full cache: keys, the histogram passes, the victims ranked into the ascending free-slot list, then ONE kernel
     // for staging + both maps
-    const int64_t N = c.num_embeddings, C = c.cuda_row_num;
-    const int lfu = c.evict_strategy == CE_EVICT_LFU;
-    const int top_pass = select_top_pass(h, x.sel_n, false);
-    const FrontTail ft = take_front_tail(h);
-    hipLaunchKernelGGL(k_keys, dim3(std::min(grid_for(C, 256 * 4), 512)), dim3(256), 0, s, c.cached_idx_map, c.freq_cnter,
-                       h->slot_epoch, C, N, x.seq_arg, c.protect_depth, h->slot_bits, lfu, top_pass, h->keys, h->hist, h->ctl,
-                       ft.miss_tmp, ft.fw, ft.bitmap, ft.fine, ft.coarse, (int)L.n_chunks);
-    const int hgrid = (int)std::min<int64_t>(kNumCU, std::max<int64_t>(1, cdiv(C, 1024 * 4)));
-    for (int pass = top_pass - 1; pass >= 0; --pass)
-      hipLaunchKernelGGL(k_hist, dim3(hgrid), dim3(1024), 0, s, h->keys, C, pass, top_pass, h->hist, h->ctl);
-    if (prof) (void)hipEventRecord(prof->ev[pslot][x.pmark++], s);
+    const int64_t C = c.cuda_row_num;
+    const int top_pass = launch_keys_hist(h);
+    phase_mark(h);
     StageArgs a;
     a.cached_idx_map = c.cached_idx_map;
     a.inverted = c.inverted_cached_idx;
@@ -1091,20 +1112,17 @@ static int chained_second_half(ce_cache* h) {
     hipLaunchKernelGGL(k_rank_victims, dim3((unsigned)cdiv(C, kRemapSlots)), dim3(256), 0, s, a);
     {
       const int gpb = 256 >> h->g_log2;
-      const int sgrid = (int)std::min<int64_t>(x.sel_n <= 600000 ? 256 : 512,
+      const int sgrid = (int)std::min<int64_t>(x.n <= 600000 ? 256 : 512,
                                                std::max<int64_t>(1, cdiv(L.stage_rows, gpb * kStageRowsInFlight)));
       hipLaunchKernelGGL(k_stage_maps, dim3(sgrid), dim3(256), 0, s, a);
     }
     CE_HIP_CHECK(hipEventRecord(w->out_ev[wbuf], s));
     w->push_out();
-    if (prof)
-      for (int j = 0; j < 2; ++j) (void)hipEventRecord(prof->ev[pslot][x.pmark++], s);      // (free list: inside)
+    for (int j = 0; j < 2; ++j) phase_mark(h);      // (free list: inside)
   } else {
     // the cache still has free slots (warm-up): the per-phase kernels, then the maps -- before the rows, which they
     // do not need -- with the count the unpack kernel moves
-    SelArgs sel{s, x.sel_n, true, false, x.sel_steady, out_job, x.seq_arg, wbuf, x.sel_n_vblocks, pslot, x.prof,
-                h->free_list_b[parity]};
-    int rc0 = select_and_stage(h, sel, &x.pmark);
+    int rc0 = select_and_stage(h);
     if (rc0) return rc0;
     hipLaunchKernelGGL(k_admit_maps, dim3(grid_for(L.list_cap, 256)), dim3(256), 0, s, h->miss_list_b[parity],
                        h->free_list_b[parity], (const long long*)&h->ctl->n_miss, 0ll, c.cached_idx_map,
@@ -1116,38 +1134,30 @@ static int chained_second_half(ce_cache* h) {
   CE_HIP_CHECK(hipStreamWaitEvent(w->in_stream, sel_done, 0));
   {
     const int gpb = 256 >> h->g_log2;
-    const int ugrid = (int)std::min<int64_t>(x.sel_n <= 600000 ? 128 : 512, std::max<int64_t>(1, cdiv(L.stage_rows, gpb)));
+    const int ugrid = (int)std::min<int64_t>(x.n <= 600000 ? 128 : 512, std::max<int64_t>(1, cdiv(L.stage_rows, gpb)));
     const long long prev = out_job - 1;
     const int pb = (int)(prev & 1);
     const unsigned long long* ek = prev >= w->probe_floor ? h->evt_keys[pb] : nullptr;
     const bool tail_possible = L.list_cap > L.stage_rows;
-    if (h->vec)
-      hipLaunchKernelGGL((k_unpack_chained<f32x4>), dim3(ugrid), dim3(256), 0, w->in_stream, h->free_list_b[parity],
-                         (const long long*)&h->chain->n_unpack[parity], (long long)L.stage_rows,
-                         (const f32x4*)h->in_stage, (f32x4*)c.cache_weight, h->rowlen, h->g_log2,
-                         (const int32_t*)h->miss_list_b[parity],
-                         tail_possible ? (const f32x4*)c.host_weight_dev : (const f32x4*)nullptr, ek,
-                         (const int32_t*)h->evt_pos[pb], h->evt_mask, (uint32_t)prev,
-                         (const f32x4*)(pb ? h->stage2 : h->stage));
-    else
-      hipLaunchKernelGGL((k_unpack_chained<float>), dim3(ugrid), dim3(256), 0, w->in_stream, h->free_list_b[parity],
-                         (const long long*)&h->chain->n_unpack[parity], (long long)L.stage_rows,
-                         (const float*)h->in_stage, (float*)c.cache_weight, h->rowlen, h->g_log2,
-                         (const int32_t*)h->miss_list_b[parity],
-                         tail_possible ? (const float*)c.host_weight_dev : (const float*)nullptr, ek,
-                         (const int32_t*)h->evt_pos[pb], h->evt_mask, (uint32_t)prev,
-                         (const float*)(pb ? h->stage2 : h->stage));
+    for_rows(h, [&](auto r) {
+      using VT = typename decltype(r)::VT;
+      hipLaunchKernelGGL((k_unpack_chained<VT>), dim3(ugrid), dim3(256), 0, w->in_stream, h->free_list_b[parity],
+                         (const long long*)&h->chain->n_unpack[parity], (long long)L.stage_rows, (const VT*)h->in_stage,
+                         (VT*)c.cache_weight, h->rowlen, h->g_log2, (const int32_t*)h->miss_list_b[parity],
+                         tail_possible ? (const VT*)c.host_weight_dev : (const VT*)nullptr, ek,
+                         (const int32_t*)h->evt_pos[pb], h->evt_mask, (uint32_t)prev, (const VT*)(pb ? h->stage2 : h->stage));
+    });
   }
   if (prof) (void)hipEventRecord(prof->adm1[pslot], w->in_stream);
   hipEvent_t rows = w->ev_rows[call % SwapEngine::kRowsRing];
   CE_HIP_CHECK(hipEventRecord(rows, w->in_stream));
-  if (prof) (void)hipEventRecord(prof->ev[pslot][x.pmark++], s);      // ("admit_swap" is timed on the admission stream)
+  phase_mark(h);      // ("admit_swap" is timed on the admission stream)
   int rc = launch_slots_keys(h);
   if (rc) return rc;
   if (prof) prof->pending[pslot] = true;
   CE_LAUNCH_CHECK();
   // the caller's stream order covers the rows unless it asked to wait for them itself (ce_cache_wait_rows)
-  if (!w->deferred_rows) CE_HIP_CHECK(hipStreamWaitEvent(s, rows, 0));
+  if (!h->deferred_rows) CE_HIP_CHECK(hipStreamWaitEvent(s, rows, 0));
   CE_HIP_CHECK(hipEventRecord(h->ev, s));
   return CE_OK;
 }
@@ -1175,10 +1185,7 @@ static int prepare_ids_impl(ce_cache_t* h, const int64_t* ids, int64_t n, int64_
   }
   int rc = capturing ? CE_OK : before_call(h);
   if (rc) return rc;
-  const ce_cache_config_t& c = h->cfg;
-  const Layout& L = h->L;
-  const int64_t N = c.num_embeddings, C = c.cuda_row_num;
-  bool worker = c.transport == CE_TRANSPORT_WORKER;
+  bool worker = h->cfg.transport == CE_TRANSPORT_WORKER;
   if (worker) {
     rc = ensure_writeback(h);
     if (rc) return rc;
@@ -1190,19 +1197,10 @@ static int prepare_ids_impl(ce_cache_t* h, const int64_t* ids, int64_t n, int64_
     }
   }
   if (!capturing) h->seq += 1;
-  const long long seq_arg = capturing ? 0ll : (long long)h->seq;     // 0: the device's own count
-  ce_call_stats_t* const ring = h->ring_dev;
-  // swap kernels: small grid (default 2 workgroups per CU's worth of slots is left to training kernels)
-  // protect_depth > 0 means the call overlaps with training kernels on another stream: stay small (32
-  // workgroups measured best: 1.43 -> 1.82 G lookups/s); alone on the GPU a wider grid finishes sooner
-  const int swap_blocks = c.protect_depth > 0 ? 32 : 512;
-  const int swap_threads = 256;
-  const int cap_groups = (int)std::min<int64_t>(swap_blocks, std::max<int64_t>(1, cdiv(L.list_cap, (swap_threads >> h->g_log2) * kSwapRows)));
 
   // worker transport with the host-gather admission: job numbers / staging buffer of this call; the launch thread only
   // waits here when a worker is two calls behind (its buffers and events are about to be reused)
   long long out_job = 0, in_job = 0;
-  int wbuf = 0;
   if (worker) {
     rc = worker_selftest(h, s);
     if (rc == CE_ERR_UNSUPPORTED) {
@@ -1228,22 +1226,15 @@ static int prepare_ids_impl(ce_cache_t* h, const int64_t* ids, int64_t n, int64_
     }
     out_job = h->wb->out_issued + 1;
     in_job = h->wb->in_issued + 1;
-    wbuf = (int)(out_job & 1);
     rc = h->wb->wait_out(out_job - 2);
     if (rc == CE_OK) rc = h->wb->wait_in(in_job - 2);
     if (rc) return rc;
   }
-  // steady-state form (see ce_cache::free_zero): the slots to fill are this call's victims
-  const bool steady = h->free_zero && !capturing && (c.transport == CE_TRANSPORT_ZEROCOPY || worker);
-  const int n_vblocks = (int)cdiv(C, 4096);
-  PhaseProf* const prof = h->prof;
-  const int pslot = (int)(h->seq % kProfDepth);
-  int pmark = 0;
-  if (prof) prof->collect(pslot);
-#define CE_PHASE() do { if (prof) (void)hipEventRecord(prof->ev[pslot][pmark++], s); } while (0)
-  CE_PHASE();
+  ce_cache::Pending& x = record_call(h, n, slots_out, s, tail, worker, capturing, split, out_job, in_job, 0ll);
+  if (PhaseProf* const prof = live_prof(h)) prof->collect(x.pslot);
+  phase_mark(h);
   // (a captured call keeps the two-pass front: its look-back tag would be frozen into the graph)
-  launch_front_kernels(h, ids, n, slots_out, s, allow_pad, steady, seq_arg, h->miss_list,
+  launch_front_kernels(h, ids, n, slots_out, s, allow_pad, x.sel_steady, x.seq_arg, h->miss_list,
                        worker ? h->wb->mail_dev + 2 : (WbMail*)nullptr, in_job,
                        worker ? h->wb->miss_host_dev : (int32_t*)nullptr, (long long*)nullptr, !capturing);
   // the admission worker starts gathering the missed rows (host table -> pinned staging -> in_stage) right behind
@@ -1252,25 +1243,12 @@ static int prepare_ids_impl(ce_cache_t* h, const int64_t* ids, int64_t n, int64_
     CE_HIP_CHECK(hipEventRecord(h->wb->in_ev[in_job & 1], s));
     h->wb->push_in(out_job - 1);
   }
-  CE_PHASE();
-  SelArgs sel{s, n, worker, capturing, steady, out_job, seq_arg, wbuf, n_vblocks, pslot, (const void*)prof, h->free_list};
-  // a call in two halves on the worker transport: the selection / staging part moves into the second half
-  const bool defer_sel = split && worker;
-  if (!defer_sel) {
-    rc = select_and_stage(h, sel, &pmark);
+  phase_mark(h);
+  if (!x.sel_pending) {
+    rc = select_and_stage(h);
     if (rc) return rc;
   }
-#undef CE_PHASE
   // ---- second half: from here on the call needs the missed rows
-  ce_cache::Pending& x = h->pend;
-  x.n = n; x.slots_out = slots_out; x.s = s; x.worker = worker; x.capturing = capturing; x.has_tail = tail != nullptr;
-  x.in_job = in_job; x.seq_arg = seq_arg; x.cap_groups = cap_groups; x.swap_threads = swap_threads; x.pslot = pslot;
-  x.pmark = pmark;
-  x.prof = prof;
-  x.chained = false;
-  x.sel_pending = defer_sel;
-  x.sel_s = s; x.sel_n = n; x.sel_steady = steady; x.sel_out_job = out_job; x.sel_wbuf = wbuf; x.sel_n_vblocks = n_vblocks;
-  if (tail) x.tail = *tail;
   if (split) {
     x.active = true;
     CE_LAUNCH_CHECK();
@@ -1281,14 +1259,13 @@ static int prepare_ids_impl(ce_cache_t* h, const int64_t* ids, int64_t n, int64_
 
 // the slots (and the window's keys) of the call's ids: the call's last launch
 static int launch_slots_keys(ce_cache* h) {
-  ce_cache::Pending& x = h->pend;
+  const ce_cache::Pending& x = h->pend;
   const ce_cache_config_t& c = h->cfg;
   const int64_t C = c.cuda_row_num, n = x.n;
   int64_t* const slots_out = x.slots_out;
   hipStream_t s = x.s;
   const ce_stream_t stream = (ce_stream_t)s;
   const int lfu = c.evict_strategy == CE_EVICT_LFU;
-  PhaseProf* const prof = (h->prof && (const void*)h->prof == x.prof) ? h->prof : nullptr;
   const KeysTail* const tail = x.has_tail ? &x.tail : nullptr;
   int rc = CE_OK;
   if (n > 0 && lfu) {
@@ -1312,7 +1289,55 @@ static int launch_slots_keys(ce_cache* h) {
     hipLaunchKernelGGL(k_slots, dim3(grid_for(n, 256 * 4)), dim3(256), 0, s, slots_out, n, c.inverted_cached_idx,
                        (const Ctl*)h->ctl);
   }
-  if (prof) (void)hipEventRecord(prof->ev[x.pslot][x.pmark++], s);                   // end of "ids_to_slots"
+  phase_mark(h);                   // end of "ids_to_slots"
+  return CE_OK;
+}
+
+// ---- the three admission forms of a call that is not chained: the missed rows into their slots, on the call's stream
+
+// worker transport, host-gather admission: the missed rows arrive in in_stage through the admission worker; the stream
+// parks in the command processor until the worker's store to the pinned word it polls
+static int admit_parked(ce_cache* h) {
+  const ce_cache::Pending& x = h->pend;
+  const ce_cache_config_t& c = h->cfg;
+  const Layout& L = h->L;
+  const long long scap = (long long)L.stage_rows;
+  CE_HIP_CHECK(hipStreamWaitValue64(x.s, h->wb->sig, (uint64_t)x.in_job, hipStreamWaitValueGte, ~0ull));
+  const int ugrid = (int)std::min<int64_t>(1024, std::max<int64_t>(1, cdiv(L.stage_rows, 256 >> h->g_log2)));
+  for_rows(h, [&](auto r) {
+    using VT = typename decltype(r)::VT;
+    hipLaunchKernelGGL((k_unpack_admitted<VT>), dim3(ugrid), dim3(256), 0, x.s, h->free_list,
+                       (const long long*)&h->ctl->n_miss, scap, (const VT*)h->in_stage, (VT*)c.cache_weight, h->rowlen,
+                       h->g_log2, h->ctl, (const unsigned long long*)(h->wb->sig_dev + 1), x.in_job,
+                       (const int32_t*)h->miss_list,
+                       L.list_cap > L.stage_rows ? (const VT*)c.host_weight_dev : (const VT*)nullptr);
+  });
+  return CE_OK;
+}
+
+// zero-copy transport: write-back of the staged victims + admission of the missed rows, one launch, both PCIe
+// directions busy
+static int admit_zero_copy(ce_cache* h) {
+  const ce_cache::Pending& x = h->pend;
+  const ce_cache_config_t& c = h->cfg;
+  const long long scap = (long long)h->L.stage_rows;
+  const int cap_groups = x.cap_groups;
+  // workgroups of the write-back part: as many as admit when the call has the GPU to itself; half as many when it
+  // overlaps with training (protect_depth > 0) -- PCIe writes are what slows the kernels next to them, and fewer
+  // rows leave than enter (32 + 16 workgroups: 2.11 -> 2.22 G lookups/s; 32 + 8 makes the write-back the bottleneck)
+  const int wb_groups = c.protect_depth > 0 ? std::max(1, cap_groups / 2) : cap_groups;
+  auto swap = [&](auto r, auto rows) {
+    using VT = typename decltype(r)::VT;
+    hipLaunchKernelGGL((k_swap<VT, decltype(rows)::value>), dim3(wb_groups + cap_groups), dim3(x.swap_threads), 0, x.s,
+                       h->stage_idx, (const VT*)h->stage, scap, wb_groups, h->miss_list, h->free_list,
+                       (const long long*)&h->ctl->n_miss, (VT*)c.host_weight_dev, (VT*)c.cache_weight, h->rowlen,
+                       h->g_log2, (const Ctl*)h->ctl);
+  };
+  // rows in flight per lane group: 16 keeps a window-sized swap (50 k rows) on a small grid; a call of a few thousand
+  // rows (B = 2048 shapes) would then fill only a handful of groups -- 4 spreads it (38 -> 21 us per call).  (Vector
+  // rows only: there is no k_swap<float, 4>.)
+  if (h->vec && x.n <= 131072) swap(RowTag<f32x4>{}, std::integral_constant<int, 4>{});
+  else for_rows(h, [&](auto r) { swap(r, std::integral_constant<int, 16>{}); });
   return CE_OK;
 }
 
@@ -1320,111 +1345,33 @@ static int prepare_ids_second_half(ce_cache* h) {
   ce_cache::Pending& x = h->pend;
   if (x.chained) return chained_second_half(h);
   x.active = false;
+  PhaseProf* const prof = live_prof(h);
+  int rc = CE_OK;
   if (x.sel_pending) {
     x.sel_pending = false;
-    SelArgs sel{x.sel_s, x.sel_n, x.worker, x.capturing, x.sel_steady, x.sel_out_job, x.seq_arg, x.sel_wbuf, x.sel_n_vblocks,
-                x.pslot, x.prof, h->free_list};
-    if (h->prof && (const void*)h->prof == x.prof) {
-      (void)hipEventRecord(h->prof->resume[x.pslot], x.sel_s);
-      h->prof->resumed[x.pslot] = true;
+    if (prof) {
+      (void)hipEventRecord(prof->resume[x.pslot], x.s);
+      prof->resumed[x.pslot] = true;
     }
-    int rc0 = select_and_stage(h, sel, &x.pmark);
-    if (rc0) return rc0;
+    rc = select_and_stage(h);
+    if (rc) return rc;
   }
   const ce_cache_config_t& c = h->cfg;
-  const Layout& L = h->L;
-  const int64_t n = x.n;
   hipStream_t s = x.s;
-  const bool worker = x.worker, capturing = x.capturing;
-  const long long in_job = x.in_job;
-  const int cap_groups = x.cap_groups, gpb = 256 >> h->g_log2;
-  const dim3 swap_block(x.swap_threads);
-  PhaseProf* const prof = (h->prof && (const void*)h->prof == x.prof) ? h->prof : nullptr;
-  const int pslot = x.pslot;
-  int rc = CE_OK;
-  if (worker) {
-    // host-gather admission: the missed rows arrive in in_stage through the admission worker; this stream parks in
-    // the command processor until the worker's store to the pinned word it polls
-    const long long scap = (long long)L.stage_rows;
-    CE_HIP_CHECK(hipStreamWaitValue64(s, h->wb->sig, (uint64_t)in_job, hipStreamWaitValueGte, ~0ull));
-    const int ugrid = (int)std::min<int64_t>(1024, std::max<int64_t>(1, cdiv(L.stage_rows, gpb)));
-    if (h->vec) {
-      hipLaunchKernelGGL((k_unpack_admitted<f32x4>), dim3(ugrid), dim3(256), 0, s, h->free_list,
-                         (const long long*)&h->ctl->n_miss, scap, (const f32x4*)h->in_stage, (f32x4*)c.cache_weight,
-                         h->rowlen, h->g_log2, h->ctl, (const unsigned long long*)(h->wb->sig_dev + 1),
-                         in_job, (const int32_t*)h->miss_list,
-                         L.list_cap > L.stage_rows ? (const f32x4*)c.host_weight_dev : (const f32x4*)nullptr);
-    } else {
-      hipLaunchKernelGGL((k_unpack_admitted<float>), dim3(ugrid), dim3(256), 0, s, h->free_list,
-                         (const long long*)&h->ctl->n_miss, scap, (const float*)h->in_stage, (float*)c.cache_weight,
-                         h->rowlen, h->g_log2, h->ctl, (const unsigned long long*)(h->wb->sig_dev + 1),
-                         in_job, (const int32_t*)h->miss_list,
-                         L.list_cap > L.stage_rows ? (const float*)c.host_weight_dev : (const float*)nullptr);
-    }
-  } else if (c.transport == CE_TRANSPORT_ZEROCOPY) {
-    // write-back of the staged victims + admission of the missed rows, one launch, both PCIe directions busy
-    const long long scap = (long long)L.stage_rows;
-    // rows in flight per lane group: 16 keeps a window-sized swap (50 k rows) on a small grid; a call of a few thousand
-    // rows (B = 2048 shapes) would then fill only a handful of groups -- 4 spreads it (38 -> 21 us per call)
-    const int swap_rows = n <= 131072 ? 4 : kSwapRows;
-    // workgroups of the write-back part: as many as admit when the call has the GPU to itself; half as many when it
-    // overlaps with training (protect_depth > 0) -- PCIe writes are what slows the kernels next to them, and fewer
-    // rows leave than enter (32 + 16 workgroups: 2.11 -> 2.22 G lookups/s; 32 + 8 makes the write-back the bottleneck)
-    const int wb_groups = c.protect_depth > 0 ? std::max(1, cap_groups / 2) : cap_groups;
-#define CE_SWAP(VT, R)                                                                                          \
-  hipLaunchKernelGGL((k_swap<VT, R>), dim3(wb_groups + cap_groups), swap_block, 0, s, h->stage_idx,             \
-                     (const VT*)h->stage, scap, wb_groups, h->miss_list, h->free_list,                           \
-                     (const long long*)&h->ctl->n_miss,                                                          \
-                     (VT*)c.host_weight_dev, (VT*)c.cache_weight, h->rowlen, h->g_log2, (const Ctl*)h->ctl)
-    if (h->vec) {
-      if (swap_rows == 4) CE_SWAP(f32x4, 4); else CE_SWAP(f32x4, 16);
-    } else {
-      CE_SWAP(float, 16);
-    }
-#undef CE_SWAP
-  } else {
-    // H2D: worker threads gather the missed rows out of the table into pinned staging
-    const Ctl ctl = *h->ctl_host;   // filled by staged_swap
-    const int64_t m = (ctl.status == CE_OK) ? ctl.n_miss : 0;
-    if (m > 0) {
-      const int D = c.embedding_dim;
-      const size_t rowbytes = (size_t)D * sizeof(float);
-      CE_HIP_CHECK(hipMemcpyAsync(h->list_host, h->miss_list, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-      CE_HIP_CHECK(hipStreamSynchronize(s));
-      const float* table = c.host_weight;
-      float* st = h->stage_host;
-      const int64_t chunk = staged_chunk(h, m);
-      for (int64_t off = 0; off < m; off += chunk) {
-        const int64_t cnt = std::min(chunk, m - off);
-        if (off > 0) CE_HIP_CHECK(hipStreamSynchronize(s));      // the staging buffer is reused
-        const int32_t* rows = h->list_host + off;
-        host_pool(h)->parallel(cnt, [=](int64_t lo, int64_t hi) {
-          for (int64_t i = lo; i < hi; ++i) memcpy(st + (size_t)i * D, table + (size_t)rows[i] * D, rowbytes);
-        });
-        CE_HIP_CHECK(hipMemcpyAsync(h->stage_dev, h->stage_host, (size_t)cnt * rowbytes, hipMemcpyHostToDevice, s));
-        if (h->vec)
-          hipLaunchKernelGGL((k_unpack_rows<f32x4>), dim3(grid_for(cnt, gpb)), dim3(256), 0, s,
-                             (const int32_t*)h->free_list + off, (long long)cnt, (const f32x4*)h->stage_dev,
-                             (f32x4*)c.cache_weight, h->rowlen, h->g_log2);
-        else
-          hipLaunchKernelGGL((k_unpack_rows<float>), dim3(grid_for(cnt, gpb)), dim3(256), 0, s,
-                             (const int32_t*)h->free_list + off, (long long)cnt, (const float*)h->stage_dev,
-                             (float*)c.cache_weight, h->rowlen, h->g_log2);
-      }
-    }
-  }
+  rc = x.worker ? admit_parked(h) : c.transport == CE_TRANSPORT_ZEROCOPY ? admit_zero_copy(h) : admit_staged(h);
+  if (rc) return rc;
   // map updates + publication of the call's record (the last kernel that can amend it; it also turns a LOST admission
   // job of the host-gather worker into a failed call with nothing marked resident)
-  hipLaunchKernelGGL(k_admit_maps, dim3(grid_for(L.list_cap, 256)), dim3(256), 0, s, h->miss_list, h->free_list,
+  hipLaunchKernelGGL(k_admit_maps, dim3(grid_for(h->L.list_cap, 256)), dim3(256), 0, s, h->miss_list, h->free_list,
                      (const long long*)&h->ctl->n_miss, 0ll, c.cached_idx_map, c.inverted_cached_idx,
                      c.freq_cnter, (const int64_t*)nullptr, h->slot_epoch, 0, h->ctl, h->ring_dev,
                      x.seq_arg, x.worker ? (const unsigned long long*)(h->wb->sig_dev + 1) : nullptr, x.in_job);
-  if (prof) (void)hipEventRecord(prof->ev[pslot][x.pmark++], s);      // end of "admit_swap"
+  phase_mark(h);      // end of "admit_swap"
   rc = launch_slots_keys(h);
   if (rc) return rc;
-  if (prof) prof->pending[pslot] = true;
+  if (prof) prof->pending[x.pslot] = true;
   CE_LAUNCH_CHECK();
-  if (!capturing) CE_HIP_CHECK(hipEventRecord(h->ev, s));
+  if (!x.capturing) CE_HIP_CHECK(hipEventRecord(h->ev, s));
   return CE_OK;
 }
 
@@ -1477,7 +1424,6 @@ extern "C" int ce_cache_set_deferred_rows(ce_cache_t* h, int32_t on) {
   CE_REQUIRE(h, CE_ERR_INVALID, "null handle");
   CE_REQUIRE(!h->pend.active, CE_ERR_INVALID, "a cache op begun with ce_cache_prepare_ids_begin has not been finished");
   h->deferred_rows = on != 0;
-  if (h->wb) h->wb->deferred_rows = h->deferred_rows;
   return CE_OK;
 }
 
@@ -1604,12 +1550,11 @@ extern "C" int ce_cache_flush(ce_cache_t* h, ce_stream_t stream) {
   const int gpb = 256 >> h->g_log2;
   hipLaunchKernelGGL(k_begin, dim3(1), dim3(256), 0, s, h->ctl, (int32_t*)nullptr, 0, (uint32_t*)nullptr,
                      (long long)h->seq);
-  if (h->vec)
-    hipLaunchKernelGGL((k_flush_rows<f32x4>), dim3(grid_for(C, gpb)), dim3(256), 0, s, c.cached_idx_map, C,
-                       (const f32x4*)c.cache_weight, (f32x4*)c.host_weight_dev, h->rowlen, h->g_log2);
-  else
-    hipLaunchKernelGGL((k_flush_rows<float>), dim3(grid_for(C, gpb)), dim3(256), 0, s, c.cached_idx_map, C,
-                       (const float*)c.cache_weight, (float*)c.host_weight_dev, h->rowlen, h->g_log2);
+  for_rows(h, [&](auto r) {
+    using VT = typename decltype(r)::VT;
+    hipLaunchKernelGGL((k_flush_rows<VT>), dim3(grid_for(C, gpb)), dim3(256), 0, s, c.cached_idx_map, C,
+                       (const VT*)c.cache_weight, (VT*)c.host_weight_dev, h->rowlen, h->g_log2);
+  });
   hipLaunchKernelGGL(k_flush_maps, dim3(grid_for(C, 256)), dim3(256), 0, s, c.cached_idx_map, C,
                      c.inverted_cached_idx, c.freq_cnter, h->slot_epoch, h->ctl);
   hipLaunchKernelGGL(k_flush_end, dim3(1), dim3(1), 0, s, C, h->ctl, h->ring_dev + (h->seq % kRing),
@@ -1697,13 +1642,12 @@ extern "C" int ce_cache_writeback_wait(ce_cache_t* h) {
 
 extern "C" int ce_cache_swap_stats(ce_cache_t* h, double* seconds6, int64_t* counts4) {
   CE_REQUIRE(h && seconds6 && counts4, CE_ERR_INVALID, "null argument");
-  double* seconds4 = seconds6;
   for (int i = 0; i < 4; ++i) counts4[i] = 0;
   for (int i = 0; i < 6; ++i) seconds6[i] = 0;
   if (h->wb) {
     std::lock_guard<std::mutex> g(h->wb->m);
-    seconds4[0] = h->wb->out_wait_s; seconds4[1] = h->wb->out_busy_s;
-    seconds4[2] = h->wb->in_wait_s;  seconds4[3] = h->wb->in_busy_s;
+    seconds6[0] = h->wb->out_wait_s; seconds6[1] = h->wb->out_busy_s;
+    seconds6[2] = h->wb->in_wait_s;  seconds6[3] = h->wb->in_busy_s;
     seconds6[4] = h->wb->in_gather_s;
     seconds6[5] = (double)h->wb->in_probed;
     counts4[0] = h->wb->out_rows; counts4[1] = h->wb->out_jobs;

@@ -268,7 +268,6 @@ struct SwapEngine {
   // since (ce_cache_set_transport), which may have re-admitted and evicted the same rows past that buffer -- the host
   // table, where every one of those jobs has landed by then, is the up-to-date copy
   long long probe_floor = 1;
-  bool deferred_rows = false;                      // prepare_ids does not make its stream wait for the rows
   const unsigned long long* evt_keys[2] = {nullptr, nullptr};
   const int32_t* evt_pos[2] = {nullptr, nullptr};
   uint32_t evt_mask = 0;

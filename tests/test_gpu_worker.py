@@ -127,6 +127,69 @@ def test_readmission_of_rows_still_in_flight(strategy, depth, N, C, D, per_call,
         assert st["in_jobs_before_writeback_landed"] >= 10, st
 
 
+@pytest.mark.parametrize("strategy", ["dataset", "lfu"])
+@pytest.mark.parametrize("N,C,D,per_call", [(3001, 257, 20, 100), (6000, 700, 128, 300)])       # scalar rows, vector rows
+@pytest.mark.parametrize("arrangement", ["zerocopy", "staged", "worker_kernel", "worker_sdma"])
+def test_every_arrangement_in_two_halves_and_with_the_keys_tail(arrangement, N, C, D, per_call, strategy, monkeypatch):
+    """The forms of a cache op that the streams above do not reach on every arrangement: the call in two halves
+    (ce_cache_prepare_ids_begin_padded / _begin without and with keys, then _finish) and the whole call with the keys
+    tail (ce_cache_prepare_ids_keys), taking turns call by call, on the zero-copy, staged and worker transports (chained
+    and host-gather admission).  13 calls fill the cache (3) and go round it twice more, so both the warm-up and the
+    steady form of every arrangement run.  Slots, maps, counters and cache payloads against the oracle after every
+    call, the window's keys against a presort of the slots, the host table row for row after the flush."""
+    ce = _ce()
+    from cachedembedding_amd.functional import presort_len, presort_window
+    from oracle.cache_oracle import DATASET, LFU, OracleCachedParamMgr
+    if arrangement.startswith("worker"):
+        monkeypatch.setenv("CE_WORKER_ADMIT", "sdma" if arrangement == "worker_sdma" else "kernel")
+    lfu = strategy == "lfu"
+    rng = np.random.default_rng(N + 31 * C)
+    w = rng.standard_normal((N, D)).astype(np.float32)
+    ora = OracleCachedParamMgr(w.copy(), C, LFU if lfu else DATASET)
+    ora.reorder(None, 0.0)
+    mgr = ce.CachedParamMgr(torch.from_numpy(w.copy()), C, evict_strategy=_strat(ce, strategy),
+                            async_copy=arrangement == "staged")
+    mgr.reorder(None, 0.0)
+    if arrangement.startswith("worker"):
+        mgr.set_transport("worker")
+    klen = presort_len(per_call)
+    evicted = 0
+    for c in range(13):
+        ids = rng.integers(0, N, size=per_call)
+        want = ora.prepare_ids(ids)
+        dev = torch.from_numpy(ids).cuda()
+        slots = torch.empty(1, per_call, dtype=torch.int64, device="cuda")
+        keys = torch.empty(1, klen, dtype=torch.int64, device="cuda")
+        form = (c + 3) % 4
+        if form == 0:
+            mgr.prepare_ids_begin_padded(dev, slots.view(-1))
+            mgr.prepare_ids_finish()
+        elif form == 1:
+            mgr.prepare_ids_begin(dev.view(1, -1), slots)
+            mgr.prepare_ids_finish()
+        elif form == 2:
+            mgr.prepare_ids_begin(dev.view(1, -1), slots, keys)
+            mgr.prepare_ids_finish()
+        else:
+            mgr.prepare_ids_keys(dev.view(1, -1), slots, keys)
+        assert np.array_equal(slots.view(-1).cpu().numpy(), want)
+        if form >= 2:       # (the order inside a 16384-lookup segment depends on an atomic race in either form)
+            ref = presort_window(slots.contiguous(), C)
+            assert torch.equal(keys.view(1, -1, 16384).sort(dim=2).values, ref.view(1, -1, 16384).sort(dim=2).values)
+        evicted += len(ora.traces[-1].evicted_rows)
+        # a training step on the touched rows: every write-back carries a payload the host table has never seen
+        ora.cuda_cached_weight[np.unique(want)] += np.float32(0.25 * (c + 1))
+        with torch.no_grad():
+            mgr.cuda_cached_weight[torch.unique(slots)] += 0.25 * (c + 1)
+        _state_equal(mgr, ora, lfu)
+    assert evicted > 2 * C, "the stream did not go round the cache twice"
+    assert mgr.transport_name == arrangement.split("_")[0]          # (no fall-back to the zero-copy kernels)
+    assert mgr.num_write_back_history == ora.num_write_back_history
+    mgr.flush()
+    ora.flush()
+    np.testing.assert_array_equal(mgr.weight.numpy(), ora.weight)
+
+
 def test_transport_switches_keep_the_table_consistent():
     """zerocopy -> worker -> staged -> worker -> zerocopy in the middle of a stream"""
     ce = _ce()
