@@ -21,16 +21,19 @@ from cachedembedding_amd import synthetic  # noqa: E402
 
 
 def benchmark_cache_embedding(batch_size, embedding_dim, cache_ratio, id_freq_map=None, warmup_ratio=0.0,
-                              use_lfu=False, tables="criteo_kaggle", iters=200, skew=0.25, fused_lr=None, seed=1024):
+                              use_lfu=False, tables="criteo_kaggle", iters=200, skew=0.25, fused_lr=None, seed=1024,
+                              use_lru=False):
     sizes = synthetic.TABLES[tables]
     gen = synthetic.SyntheticKJT(sizes, batch_size, 1, "power_law", skew, seed=seed, device="cuda")
     num_embed = gen.num_embeddings
     cuda_row_num = int(cache_ratio * num_embed)
+    strategy = ce.EvictionStrategy.LRU if use_lru else (
+        ce.EvictionStrategy.LFU if use_lfu else ce.EvictionStrategy.DATASET)
     print(f"batch size: {batch_size}, cached rows: {cuda_row_num},  cached_ratio {cuda_row_num / num_embed}")
     t0 = time.time()
     model = ce.CachedEmbeddingBag(num_embed, embedding_dim, sparse=True, include_last_offset=True, mode="sum",
                                   cache_ratio=cache_ratio, ids_freq_mapping=id_freq_map, warmup_ratio=warmup_ratio,
-                                  evict_strategy=ce.EvictionStrategy.LFU if use_lfu else ce.EvictionStrategy.DATASET)
+                                  evict_strategy=strategy)
     print(f"model init: {time.time() - t0:.2f}s")
     if fused_lr is not None:
         model.set_fused_sgd(fused_lr)
@@ -60,7 +63,9 @@ if __name__ == "__main__":
     ap.add_argument("--cache_ratio", type=float, default=0.02)
     ap.add_argument("--warmup_ratio", type=float, default=0.7)
     ap.add_argument("--tables", default="criteo_kaggle", choices=list(synthetic.TABLES))
-    ap.add_argument("--use_lfu", action="store_true")
+    strat = ap.add_mutually_exclusive_group()
+    strat.add_argument("--use_lfu", action="store_true")
+    strat.add_argument("--use_lru", action="store_true", help="least recently used eviction (EvictionStrategy.LRU)")
     ap.add_argument("--fused_lr", type=float, default=None)
     ap.add_argument("--iters", type=int, default=200)
     a = ap.parse_args()
@@ -68,6 +73,6 @@ if __name__ == "__main__":
     freq = g.id_freq_map(64)
     try:
         benchmark_cache_embedding(a.batch_size, a.embedding_dim, a.cache_ratio, freq, a.warmup_ratio, a.use_lfu,
-                                  a.tables, a.iters, fused_lr=a.fused_lr)
+                                  a.tables, a.iters, fused_lr=a.fused_lr, use_lru=a.use_lru)
     except AssertionError as ae:     # the overflow the reference catches at benchmark_cache.py:106-108
         print(f"batch size: {a.batch_size}, cache ratio: {a.cache_ratio}, raise error: {ae}")

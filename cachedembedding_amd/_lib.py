@@ -27,6 +27,7 @@ CE_ERR_UNSUPPORTED = 5
 CE_ERR_RANGE = 6
 CE_EVICT_DATASET = 0
 CE_EVICT_LFU = 1
+CE_EVICT_LRU = 2
 CE_MODE_SUM = 0
 CE_MODE_MEAN = 1
 CE_ACT_F32 = 0

@@ -22,9 +22,16 @@ from ._lib import CeCacheConfig, CeCallStats, check, lib, ptr, stream_ptr
 
 
 class EvictionStrategy(Enum):
-    """recsys/models/dlrm.py:66,80 choose between these two."""
+    """recsys/models/dlrm.py:66,80 choose between the first two, whose values are upstream's.  LRU (least recently
+    used, at the grain of a prepare_ids call: CE_EVICT_LRU in include/ce_api.h) is this project's own; the values are
+    not the library's codes (upstream's DATASET is 2, the library's 0): EVICT_CODES maps them."""
     LFU = 1
     DATASET = 2
+    LRU = 3
+
+
+EVICT_CODES = {EvictionStrategy.DATASET: _lib.CE_EVICT_DATASET, EvictionStrategy.LFU: _lib.CE_EVICT_LFU,
+               EvictionStrategy.LRU: _lib.CE_EVICT_LRU}
 
 
 class _PinnedBlock:
@@ -174,7 +181,7 @@ class CachedParamMgr(torch.nn.Module):
         cfg.num_embeddings = N
         cfg.cuda_row_num = C
         cfg.embedding_dim = self._lib_dim
-        cfg.evict_strategy = _lib.CE_EVICT_LFU if self._evict_strategy == EvictionStrategy.LFU else _lib.CE_EVICT_DATASET
+        cfg.evict_strategy = EVICT_CODES[self._evict_strategy]
         tr = getattr(self, "_transport", None)        # None = never set (CE_TRANSPORT_ZEROCOPY is 0: test identity)
         cfg.transport = tr if tr is not None else (
             _lib.CE_TRANSPORT_STAGED if self._async_copy else _lib.CE_TRANSPORT_ZEROCOPY)
@@ -246,9 +253,12 @@ class CachedParamMgr(torch.nn.Module):
         if n > 0:
             rows = None
             fvals = None
-            if self._evict_strategy == EvictionStrategy.LFU and freq is not None:
+            if self._evict_strategy in (EvictionStrategy.LFU, EvictionStrategy.LRU) and freq is not None:
+                # the i-th most frequent row into slot i; LRU keeps no counters (its preloaded rows are "never used",
+                # and among those the higher slot leaves first: the least frequent ones)
                 rows = order[:n].to(torch.int32).contiguous()
-                fvals = freq[order[:n]].contiguous()
+                if self._evict_strategy == EvictionStrategy.LFU:
+                    fvals = freq[order[:n]].contiguous()
             with torch.cuda.device(self.device):
                 check(lib.ce_cache_preload(self._handle, ptr(rows), ptr(fvals), n, stream_ptr()))
                 if fvals is not None:

@@ -245,8 +245,9 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
   CE_REQUIRE(cfg->cuda_row_num > 0 && cfg->cuda_row_num <= cfg->num_embeddings, CE_ERR_INVALID,
              "cuda_row_num must be in (0, num_embeddings]");
   CE_REQUIRE(cfg->embedding_dim > 0, CE_ERR_INVALID, "embedding_dim must be positive");
-  CE_REQUIRE(cfg->evict_strategy == CE_EVICT_DATASET || cfg->evict_strategy == CE_EVICT_LFU, CE_ERR_INVALID,
-             "unknown eviction strategy");
+  CE_REQUIRE(cfg->evict_strategy == CE_EVICT_DATASET || cfg->evict_strategy == CE_EVICT_LFU ||
+                 cfg->evict_strategy == CE_EVICT_LRU,
+             CE_ERR_INVALID, "unknown eviction strategy");
   CE_REQUIRE(cfg->cache_weight && cfg->inverted_cached_idx && cfg->cached_idx_map && cfg->workspace,
              CE_ERR_INVALID, "null device array");
   CE_REQUIRE((((uintptr_t)cfg->inverted_cached_idx) & 15) == 0, CE_ERR_INVALID,
@@ -259,6 +260,7 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
 
   ce_cache* h = new ce_cache();
   h->cfg = *cfg;
+  if (cfg->evict_strategy == CE_EVICT_LRU) h->cfg.freq_cnter = nullptr;      // LRU keeps no counters: never touched
   h->L = L;
   h->ws = (char*)cfg->workspace;
   h->ctl = h->at<Ctl>(L.ctl);
@@ -320,8 +322,8 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
   hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(N, 256)), dim3(256), 0, s, cfg->inverted_cached_idx, N, -1);
   hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(C, 256)), dim3(256), 0, s, cfg->cached_idx_map, C, -1);
   hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(C, 256)), dim3(256), 0, s, h->slot_epoch, C, kEpochNever);
-  if (cfg->freq_cnter)
-    hipLaunchKernelGGL(k_fill_i64, dim3(grid_for(C, 256)), dim3(256), 0, s, cfg->freq_cnter, C, (int64_t)INT64_MAX);
+  if (h->cfg.freq_cnter)
+    hipLaunchKernelGGL(k_fill_i64, dim3(grid_for(C, 256)), dim3(256), 0, s, h->cfg.freq_cnter, C, (int64_t)INT64_MAX);
   Ctl init{};
   init.n_free = C;
   (void)hipMemcpyAsync(h->ctl, &init, sizeof(Ctl), hipMemcpyHostToDevice, s);
@@ -573,6 +575,7 @@ static int ensure_writeback(ce_cache* h) {
 
 extern "C" int ce_cache_set_freq_bound(ce_cache_t* h, int64_t bound) {
   CE_REQUIRE(h && bound >= 0, CE_ERR_INVALID, "bad bound");
+  if (h->cfg.evict_strategy == CE_EVICT_LRU) return CE_OK;      // no counters, nothing to bound
   h->freq_bound = std::max<uint64_t>(h->freq_bound, (uint64_t)bound);
   h->freq_bound_known = true;
   return CE_OK;
@@ -584,7 +587,7 @@ extern "C" int ce_cache_preload(ce_cache_t* h, const int32_t* rows, const int64_
   CE_REQUIRE(n >= 0 && n <= h->cfg.cuda_row_num, CE_ERR_INVALID, "preload count out of range");
   CE_REQUIRE(!h->pend.active, CE_ERR_INVALID, "a cache op begun with ce_cache_prepare_ids_begin has not been finished");
   if (n == 0) return CE_OK;
-  if (freq_vals) h->freq_bound_known = false;      // until ce_cache_set_freq_bound states their maximum
+  if (freq_vals && h->cfg.evict_strategy != CE_EVICT_LRU) h->freq_bound_known = false;      // until ce_cache_set_freq_bound states their maximum
   int rc = before_call(h);
   if (rc) return rc;
   if (h->wb) {
@@ -676,7 +679,18 @@ static int select_top_pass(ce_cache* h, int64_t n, bool capturing) {
   // DATASET keys are < N: the digits above the highest digit of N-1 are zero for every eligible slot, so the
   // radix select starts there (3 passes of 11 bits at N = 178 M).
   int top_pass = kLevels - 1;
-  if (c.evict_strategy != CE_EVICT_LFU) {
+  if (c.evict_strategy == CE_EVICT_LRU) {
+    // LRU keys are last use << slot_bits | (2^slot_bits - 1 - slot), the last use being the stamp of the most recent
+    // call that named the slot's row (0 = never).  No stamp exceeds the number of the call that selects, which the
+    // host knows, so the key has bits(call number) + slot_bits significant bits: one pass for the first calls of a
+    // small cache, one more every time the sum crosses a multiple of 11.  Nothing is clamped in the key kernel.
+    // (a captured call is replayed an unknown number of times and reads the call number on the device: it is sized
+    // for the whole 30-bit stamp, 30 + slot_bits <= 61 bits, and never goes stale)
+    const uint64_t last = capturing ? (uint64_t)kEpochMask
+                                    : std::min<uint64_t>((uint64_t)h->pend.seq_arg, (uint64_t)kEpochMask);
+    const int bits = 64 - __builtin_clzll(last | 1ull) + h->slot_bits;
+    top_pass = std::min(kLevels - 1, std::max(0, (bits + kDigitBits - 1) / kDigitBits - 1));
+  } else if (c.evict_strategy != CE_EVICT_LFU) {
     top_pass = 0;
     while (top_pass < kLevels - 1 && ((uint64_t)(N - 1) >> (kDigitBits * (top_pass + 1))) != 0) ++top_pass;
   } else {
@@ -706,11 +720,13 @@ static int launch_keys_hist(ce_cache* h) {
   const ce_cache::Pending& x = h->pend;
   const ce_cache_config_t& c = h->cfg;
   const int64_t N = c.num_embeddings, C = c.cuda_row_num;
-  const int lfu = c.evict_strategy == CE_EVICT_LFU;
   const int top_pass = select_top_pass(h, x.n, x.capturing);
   const FrontTail ft = take_front_tail(h);
-  hipLaunchKernelGGL(k_keys, dim3(std::min(grid_for(C, 256 * 4), 512)), dim3(256), 0, x.s, c.cached_idx_map, c.freq_cnter,
-                     h->slot_epoch, C, N, x.seq_arg, c.protect_depth, h->slot_bits, lfu, top_pass, h->keys, h->hist, h->ctl,
+  const auto keys_kernel = c.evict_strategy == CE_EVICT_LRU   ? k_keys<CE_EVICT_LRU>
+                           : c.evict_strategy == CE_EVICT_LFU ? k_keys<CE_EVICT_LFU>
+                                                              : k_keys<CE_EVICT_DATASET>;
+  hipLaunchKernelGGL(keys_kernel, dim3(std::min(grid_for(C, 256 * 4), 512)), dim3(256), 0, x.s, c.cached_idx_map, c.freq_cnter,
+                     h->slot_epoch, C, N, x.seq_arg, c.protect_depth, h->slot_bits, top_pass, h->keys, h->hist, h->ctl,
                      ft.miss_tmp, ft.fw, ft.bitmap, ft.fine, ft.coarse, (int)h->L.n_chunks);
   const int hgrid = (int)std::min<int64_t>(kNumCU, std::max<int64_t>(1, cdiv(C, 1024 * 4)));
   // (all passes in ONE workgroup for small caches was tried for the B = 2048 shapes: a single CU keeps too few key

@@ -19,6 +19,7 @@ constexpr int kBins = 1 << kDigitBits;
 constexpr int kLevels = 6;             // 6 x 11 >= 64 bits
 constexpr int kHistWords = kLevels * kBins;   // one histogram per radix pass
 constexpr int32_t kEpochNever = -(1 << 30);
+constexpr long long kEpochMask = (1ll << 30) - 1;    // a slot's stamp is the call number modulo 2^30 (call_epoch)
 constexpr int64_t kHistoryKeep = 1 << 16;   // per-call records kept on the host side
 
 struct Ctl {                 // device control block (one per manager)
@@ -47,7 +48,7 @@ struct Ctl {                 // device control block (one per manager)
 
 // call number -> what the kernels need from it (seq_arg != 0: launched with its number; 0: replayed, see Ctl::seq)
 __device__ __forceinline__ long long call_seq(const Ctl* ctl, long long seq_arg) { return seq_arg ? seq_arg : ctl->seq; }
-__device__ __forceinline__ int32_t call_epoch(long long seq) { return (int32_t)(seq & 0x3fffffff); }
+__device__ __forceinline__ int32_t call_epoch(long long seq) { return (int32_t)(seq & kEpochMask); }
 
 struct WbMail {              // pinned host mailbox: how many rows a worker job moves (written by the device)
   long long job;

@@ -6,11 +6,13 @@
 namespace ce {
 
 // selection keys: smaller = evicted first.  Ineligible (empty / protected) = all ones.  The histogram of the TOP digit
-// is taken here too (the keys are in registers): one pass over the keys less.
+// is taken here too (the keys are in registers): one pass over the keys less.  One instance per strategy (CE_EVICT_*):
+// each holds its own key alone, so a strategy pays neither registers nor branches for the others.
+template <int STRATEGY>
 __global__ __launch_bounds__(256) void k_keys(const int32_t* __restrict__ cached_idx_map,
                                               const int64_t* __restrict__ freq,
                                               const int32_t* __restrict__ slot_epoch, int64_t C, int64_t N,
-                                              long long seq_arg, int32_t depth, int slot_bits, int lfu, int top_pass,
+                                              long long seq_arg, int32_t depth, int slot_bits, int top_pass,
                                               unsigned long long* keys, uint32_t* hist, Ctl* ctl,
                                               const int32_t* __restrict__ miss_tmp, const FrontWords* fw,
                                               uint32_t* bitmap, int32_t* fine, int32_t* coarse_cnt, int n_chunks) {
@@ -27,6 +29,14 @@ __global__ __launch_bounds__(256) void k_keys(const int32_t* __restrict__ cached
   // top_pass from an upper bound of the counters; freq_cnter is the caller's tensor, so nothing else guarantees it)
   const int key_bits = (top_pass + 1) * kDigitBits;
   const unsigned long long fmax = (1ull << ((key_bits < 63 ? key_bits : 63) - slot_bits)) - 1;
+  constexpr bool lfu = STRATEGY == CE_EVICT_LFU, lru = STRATEGY == CE_EVICT_LRU;
+  // LRU: last use << slot_bits | (2^slot_bits - 1 - slot), the last use being the slot's stamp (the number of the
+  // most recent call that named its row; kEpochNever, the only negative stamp, counts as 0: never used is older than
+  // any use).  The low field is the slot COUNTED DOWN, so that among slots with the same last use the higher slot
+  // goes first -- not LFU's "slot ascending": a preload by frequency puts the i-th most frequent row into slot i
+  // and never-used rows all tie, so the least frequent preloaded rows must leave first.  Keys are unique, and
+  // nothing is clamped: no stamp exceeds the call number the host sized top_pass for (select_top_pass).
+  const unsigned long long slot_top = (1ull << slot_bits) - 1;
   int elig = 0;
   // four slots per thread in flight (one after the other, a thread of the 512-workgroup grid walked 13 slots of a
   // 1.7 M-slot cache in 13 dependent round trips)
@@ -48,7 +58,9 @@ __global__ __launch_bounds__(256) void k_keys(const int32_t* __restrict__ cached
       const bool prot = (epoch - ep[u]) <= depth;
       unsigned long long key = ~0ull;
       if (row[u] >= 0 && !prot) {
-        if (lfu) {
+        if (lru) {
+          key = ((unsigned long long)(ep[u] < 0 ? 0 : ep[u]) << slot_bits) | (slot_top - (unsigned long long)s);
+        } else if (lfu) {
           unsigned long long uf = fr[u] < 0 ? 0ull : (unsigned long long)fr[u];
           if (uf > fmax) uf = fmax;
           key = (uf << slot_bits) | (unsigned long long)s;

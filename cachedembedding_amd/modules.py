@@ -127,8 +127,12 @@ class FusedSparseModules(nn.Module):
                  cache_ratio: float = 0.01, id_freq_map=None, warmup_ratio: float = 0.7, buffer_size: int = 50_000,
                  is_dist_dataloader: bool = True, use_lfu_eviction: bool = False, use_tablewise_parallel: bool = False,
                  dataset: Optional[str] = None, fold_hook: bool = False, group=None,
-                 output_dtype: Optional[torch.dtype] = None, table_dtype: Optional[torch.dtype] = None):
+                 output_dtype: Optional[torch.dtype] = None, table_dtype: Optional[torch.dtype] = None,
+                 evict_strategy: Optional[EvictionStrategy] = None):
         super().__init__()
+        # evict_strategy (addition): any EvictionStrategy, LRU included; None keeps use_lfu_eviction's meaning
+        if evict_strategy is not None and use_lfu_eviction:
+            raise ValueError("FusedSparseModules: give evict_strategy or use_lfu_eviction, not both")
         # table_dtype (addition): torch.bfloat16 / torch.float16 rows in the host table and in the cache
         # (CachedEmbeddingBag(table_dtype=...)); single-rank column-wise operator only
         if use_tablewise_parallel and _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
@@ -143,7 +147,8 @@ class FusedSparseModules(nn.Module):
         self.fold_hook = fold_hook
         if not use_cache:
             raise NotImplementedError("Other EmbeddingBags are under development")       # dlrm.py:83-84
-        strategy = EvictionStrategy.LFU if use_lfu_eviction else EvictionStrategy.DATASET
+        strategy = evict_strategy if evict_strategy is not None else (
+            EvictionStrategy.LFU if use_lfu_eviction else EvictionStrategy.DATASET)
         if use_tablewise_parallel:
             from .tablewise import ParallelCachedEmbeddingBagTablewise, prepare_tablewise_config
             world = torch.distributed.get_world_size(group) if torch.distributed.is_initialized() else 1

@@ -564,7 +564,7 @@ class RowwiseShardedEmbeddingBag(nn.Module):
             table = HostTable.wrap(_weight_shard.detach().to("cpu", torch.float32).contiguous())
         self.cache_weight_mgr = CachedParamMgr(table, c_local, evict_strategy=evict_strategy, device=dev)
         local_freq = None
-        if ids_freq_mapping is not None and evict_strategy == EvictionStrategy.LFU:
+        if ids_freq_mapping is not None and evict_strategy in (EvictionStrategy.LFU, EvictionStrategy.LRU):
             local_freq = torch.as_tensor(ids_freq_mapping).view(-1)[r::W]
         self.cache_weight_mgr.reorder(local_freq, warmup_ratio)
         self.ops = HipShardOps(self.cache_weight_mgr, self.idx_map, W, r, num_global_rows=num_embeddings)

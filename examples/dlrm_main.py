@@ -33,6 +33,7 @@ import torch.nn as nn
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from cachedembedding_amd import synthetic  # noqa: E402
+from cachedembedding_amd.cache_mgr import EvictionStrategy  # noqa: E402
 from cachedembedding_amd.modules import FiniteDataIter, FusedSparseModules  # noqa: E402
 from cachedembedding_amd.pipeline import PrefetchWindow  # noqa: E402
 from cachedembedding_amd.tracing import phase  # noqa: E402
@@ -74,6 +75,9 @@ def parse_args(argv=None):
     p.add_argument("--cache_ratio", type=float, default=0.01)
     p.add_argument("--use_freq", action="store_true")
     p.add_argument("--use_lfu", action="store_true")
+    p.add_argument("--use_lru", action="store_true",
+                   help="evict the least recently used rows (EvictionStrategy.LRU; not in the reference's cached "
+                        "trainer, its baseline offers it as uvm_lru).  Exclusive with --use_lfu")
     p.add_argument("--warmup_ratio", type=float, default=0.7)
     p.add_argument("--buffer_size", type=int, default=0)
     p.add_argument("--prefetch_num", type=int, default=1)
@@ -143,7 +147,10 @@ def parse_args(argv=None):
     p.add_argument("--weight_rounding", default="stochastic", choices=["nearest", "stochastic"],
                    help="--table_dtype bf16 / fp16: how the fused update rounds a row (set_weight_rounding)")
     p.add_argument("--json_out", type=str, default=None, help="write the run's numbers as one JSON object")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.use_lfu and args.use_lru:
+        p.error("--use_lfu and --use_lru exclude each other")
+    return args
 
 
 _OUTPUT_DTYPES = {"fp32": None, "bf16": torch.bfloat16}
@@ -199,6 +206,7 @@ class HybridParallelDLRM(nn.Module):
             use_cache=args.use_cache, cache_ratio=args.cache_ratio, id_freq_map=id_freq_map,
             warmup_ratio=args.warmup_ratio, buffer_size=args.buffer_size,
             is_dist_dataloader=args.use_distributed_dataloader, use_lfu_eviction=args.use_lfu,
+            evict_strategy=EvictionStrategy.LRU if args.use_lru else None,
             use_tablewise_parallel=args.use_tablewise, dataset=args.dataset, fold_hook=args.fold_hook,
             # (a 16-bit table's output would default to the table's dtype: the flag's fp32 stays fp32)
             output_dtype=_OUTPUT_DTYPES[args.embedding_output_dtype] or
@@ -732,7 +740,7 @@ def main(argv=None):
                     "data": "synthetic",
                     "surface": {k: bool(getattr(args, k)) for k in ("use_overlap", "overlap_cache_op", "fused_sgd",
                                                                     "adagrad", "fold_hook", "window_keys", "tunable_gemm", "graph_step",
-                                                                    "use_sparse_embed_grad", "use_lfu", "use_freq")},
+                                                                    "use_sparse_embed_grad", "use_lfu", "use_lru", "use_freq")},
                     "transport": mgr.transport_name, "iterations": done, "warmup_iterations": args.warmup_batches,
                     "it_per_s": train.steady_it_per_s, "it_per_s_scope": "whole model: data iterator + cache op + "
                     "embedding forward + dense forward + loss + backward + optimizer step",

@@ -41,6 +41,22 @@ extern "C" {
 /* EvictionStrategy (recsys/models/dlrm.py:66,80) */
 #define CE_EVICT_DATASET 0
 #define CE_EVICT_LFU 1
+/* Least recently used, at the grain of a call (an addition to API 6).
+ *  - The last use of a resident row is the most recent ce_cache_prepare_ids-family call (plain, _keys, _begin /
+ *    _finish, padded, captured) that named it; being admitted counts as being named.  A window call is one call:
+ *    all its batches share one recency.  Only the order of calls matters.  ce_cache_lookup_slots is not a use, and a
+ *    padding id (-1 on the padded entries) names nothing.
+ *  - Rows placed by ce_cache_preload have never been used and are older than every used row.
+ *  - The k victims of a call are the k resident, unprotected slots with the oldest last use (protection as for the
+ *    other strategies: the call's own rows plus those used within protect_depth calls).  Among slots with the same
+ *    last use the HIGHER slot leaves first: a preload by frequency puts the i-th most frequent row into slot i and
+ *    never-used rows all tie, so the least frequent preloaded rows leave first.
+ *  - A failed call (bad id, capacity) on the per-lookup front keeps the stamps it wrote, so it counts as a use of the
+ *    resident rows it named; on the bitmap front a failed call stamps nothing and is no use.
+ *  - freq_cnter is neither needed nor touched (NULL is accepted) and ce_cache_set_freq_bound does nothing.
+ *  - The recency is the call number modulo 2^30, as protect_depth's stamp is: the order is defined for fewer than
+ *    2^30 calls (prepare_ids, preload and flush together) on one handle. */
+#define CE_EVICT_LRU 2
 
 /* nn.EmbeddingBag mode (recsys/models/dlrm.py:74 passes 'sum') */
 #define CE_MODE_SUM 0
@@ -556,7 +572,7 @@ typedef struct ce_cache_config {
   int32_t* idx_map;              /* device int32[N] id -> cpu_row_idx, NULL = identity     */
   int32_t* inverted_cached_idx;  /* device int32[N] cpu_row_idx -> slot, -1 = absent (16-B aligned) */
   int32_t* cached_idx_map;       /* device int32[C] slot -> cpu_row_idx, -1 = empty        */
-  int64_t* freq_cnter;           /* device int64[C] (LFU) or NULL                          */
+  int64_t* freq_cnter;           /* device int64[C] (LFU) or NULL; ignored under LRU       */
   void* workspace;               /* device scratch, ce_cache_workspace_bytes() bytes       */
   size_t workspace_bytes;
 } ce_cache_config_t;
@@ -594,7 +610,8 @@ int ce_cache_preload(ce_cache_t* h, const int32_t* rows, const int64_t* freq_val
 
 /* LFU only: tells the manager that no freq_cnter value exceeds `bound` (the largest value handed to
  * ce_cache_preload); together with the ids seen since, this bounds every counter and lets the victim select skip the
- * radix passes above it.  Optional: without it the select runs all 8 byte passes until the bound is known. */
+ * radix passes above it.  Optional: without it the select runs all 8 byte passes until the bound is known.
+ * Under the other strategies it does nothing and returns CE_OK. */
 int ce_cache_set_freq_bound(ce_cache_t* h, int64_t bound);
 
 /* prepare_ids [A.3] -- recsys/dlrm_main.py:259: unique rows of `ids` (device int64[n]; any id outside
