@@ -64,7 +64,9 @@ def _fused(case, path):
     from cachedembedding_amd.functional import FusedRowwiseAdagrad, FusedSGD
     acc = path
     stoch = case.kind.endswith("stoch")
-    # row-wise Adagrad with stochastic rounding on a 16-bit table is deliberately not a case
+    # row-wise Adagrad with stochastic rounding on a 16-bit table is not a case HERE: the fixture records a past
+    # library's bits and that combination's would be the code under test's own.  tests/test_gpu_stochastic_adagrad.py
+    # holds it to tests/stochastic_update_ref.py instead
     assert not (case.adagrad and stoch)
     if case.adagrad:
         f = FusedRowwiseAdagrad(LR, momentum=torch.zeros(R, device="cuda"), accumulator=acc)

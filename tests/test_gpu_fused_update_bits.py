@@ -36,7 +36,7 @@ def test_the_cases_cover_what_they_are_meant_to():
         assert f"{kind}/src/128" in names
     for D in fc.SCALAR_D:
         assert f"fp32-adagrad/slots/{D}" in names
-    # Adagrad with stochastic rounding on a 16-bit table is not run anywhere
+    # Adagrad with stochastic rounding on a 16-bit table is not pinned here but run by tests/test_gpu_stochastic_adagrad.py
     assert not any(c.adagrad and c.kind.endswith("stoch") for c in CASES)
     by = {c.name: c for c in CASES}
     assert by["fp32-adagrad/slots/6"].paths == by["bf16-sgd-stoch/src/128"].paths == ("cache", "step")

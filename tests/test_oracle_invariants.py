@@ -91,7 +91,8 @@ def test_manager_contract_on_random_streams(kind, strategy, depth, use_freq, war
     for call in range(12):
         n = int(rng.integers(1, 4 * u_max + 1))
         pool = rng.choice(N, size=min(N, int(rng.integers(1, u_max + 1))), replace=False)
-        ids = pool[np.minimum((rng.pareto(skew, size=n)).astype(np.int64), len(pool) - 1)].astype(np.int64)
+        # clip BEFORE the cast: at skew 0.3 a draw can exceed 2^63, and such a float casts to INT64_MIN
+        ids = pool[np.minimum(rng.pareto(skew, size=n), len(pool) - 1).astype(np.int64)].astype(np.int64)
         rows_all = v.idx_map[ids]
         rows, cnt = np.unique(rows_all, return_counts=True)
         # ---- the state before the call
