@@ -47,6 +47,7 @@ CE_TRANSPORT_WORKER = 2
 CE_CALL_PREPARE = 0
 CE_CALL_PRELOAD = 1
 CE_CALL_FLUSH = 2
+CE_Q8_HEADER_BYTES = 16
 
 
 class CeCacheConfig(Structure):
@@ -176,6 +177,12 @@ SIGNATURES = {
     "ce_bag_backward_sgd_src_lrdev": (c_int, _SRC + _ACT + [c_void_p] + _KEYS + [c_void_p] + _STREAM),
     "ce_bag_backward_update_lrdev": (c_int, _W16 + _BAG[1:] + _ACT + _LRDEV_TAIL),
     "ce_bag_backward_update_src_lrdev": (c_int, _W16 + _SRC[1:] + _ACT + _LRDEV_TAIL),
+    # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
+    "ce_q8_row_bytes": (c_size_t, [c_int32]),
+    "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),
+    "ce_host_dequantize_q8": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int]),
+    "ce_bag_forward_q8": (c_int, _BAG + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_q8": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),
@@ -324,6 +331,29 @@ def check_w16_dim(dim: int) -> None:
     """a 16-bit table's rows are whole 16-byte units, one lane group per row: refused before the GPU is asked for"""
     if dim % 8 != 0 or dim > 1024 or dim <= 0:
         raise NotImplementedError(f"a 16-bit table needs embedding_dim % 8 == 0 and embedding_dim <= 1024 (got {dim})")
+
+
+# the 8-bit row-wise quantized table (q8) is spelled torch.uint8: a [N, 16 + D] tensor of whole rows
+Q8 = torch.uint8
+
+
+def check_q8_dim(dim: int) -> None:
+    """a q8 row is 16 + dim bytes, whole 16-byte units with 16-byte aligned codes: refused before the GPU is asked for"""
+    if dim % 16 != 0 or dim < 16 or dim > 1024:
+        raise NotImplementedError(f"a q8 (torch.uint8) table needs embedding_dim % 16 == 0 and 16 <= embedding_dim <= 1024 "
+                                  f"(got {dim})")
+
+
+def refuse_q8(what: str, table_dtype) -> None:
+    """the classes a q8 table is not wired into refuse it by name, before the GPU is asked for"""
+    if table_dtype == Q8:
+        raise NotImplementedError(f"{what} with a q8 (torch.uint8) table: a quantized table is served by a single-process "
+                                  "CachedEmbeddingBag (from_pretrained(..., table_dtype=torch.uint8) or quantized())")
+
+
+def q8_row_bytes(dim: int) -> int:
+    check_q8_dim(dim)
+    return CE_Q8_HEADER_BYTES + dim
 
 
 def ptr(t) -> int:

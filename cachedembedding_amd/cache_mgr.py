@@ -70,6 +70,17 @@ class HostTable:
     def allocate(cls, num_embeddings: int, dim: int, threads=0, dtype: torch.dtype = torch.float32) -> "HostTable":
         if not isinstance(threads, int):              # allocate(N, D, dtype)
             threads, dtype = 0, threads
+        if dtype == _lib.Q8:
+            # an 8-bit row-wise quantized table: [N, 16 + D] uint8, whole rows (filled by quantize_from)
+            width = _lib.q8_row_bytes(dim)
+            _lib.require_gpu()
+            hp, dp = ctypes.c_void_p(), ctypes.c_void_p()
+            check(lib.ce_host_alloc(num_embeddings * width, threads or _default_threads(), ctypes.byref(hp),
+                                    ctypes.byref(dp)))
+            carr = (ctypes.c_uint8 * (num_embeddings * width)).from_address(hp.value)
+            carr._ce_block = _PinnedBlock(hp.value)
+            t = torch.from_numpy(np.ctypeslib.as_array(carr))
+            return cls(t.view(num_embeddings, width), hp.value, dp.value, registered=False)
         w16 = _lib.table_code(dtype) != _lib.CE_ACT_F32
         if w16:
             _lib.check_w16_dim(dim)
@@ -89,7 +100,9 @@ class HostTable:
     @classmethod
     def wrap(cls, weight: torch.Tensor) -> "HostTable":
         """Pin + map a tensor the caller owns (the `_weight` / from_pretrained path)."""
-        if _lib.table_code(weight.dtype) != _lib.CE_ACT_F32:
+        if weight.dtype == _lib.Q8:
+            _lib.check_q8_dim(weight.shape[-1] - _lib.CE_Q8_HEADER_BYTES)      # [N, 16 + D] uint8: whole q8 rows
+        elif _lib.table_code(weight.dtype) != _lib.CE_ACT_F32:
             _lib.check_w16_dim(weight.shape[-1])
         _lib.require_gpu()
         assert weight.device.type == "cpu" and weight.is_contiguous()
@@ -98,7 +111,26 @@ class HostTable:
                                    ctypes.byref(dp)))
         return cls(weight, weight.data_ptr(), dp.value, registered=True)
 
+    def quantize_from(self, src, threads: int = 0) -> "HostTable":
+        """Fill this q8 table ([N, 16 + D] uint8) with the quantized rows of `src`: a HostTable or a CPU tensor, [N, D]
+        fp32 / bf16 / fp16 (ce_host_quantize_q8; a row holding a NaN or an infinity raises).  Host work only."""
+        if self.tensor.dtype != _lib.Q8:
+            raise NotImplementedError("quantize_from fills a q8 (torch.uint8) table")
+        t = src.tensor if isinstance(src, HostTable) else src
+        dim = self.tensor.shape[1] - _lib.CE_Q8_HEADER_BYTES
+        if t.dtype not in _lib.ACT_DTYPES:
+            raise NotImplementedError(f"rows of dtype {t.dtype} cannot be quantized: torch.float32, torch.bfloat16 and "
+                                      "torch.float16 are implemented")
+        if t.dim() != 2 or tuple(t.shape) != (self.tensor.shape[0], dim):
+            raise ValueError(f"quantize_from needs [{self.tensor.shape[0]}, {dim}] rows (got {tuple(t.shape)})")
+        assert t.device.type == "cpu" and t.is_contiguous()
+        check(lib.ce_host_quantize_q8(ctypes.c_void_p(t.data_ptr()), _lib.ACT_DTYPES[t.dtype], t.shape[0], dim,
+                                      ctypes.c_void_p(self.host_ptr), threads or _default_threads()))
+        return self
+
     def fill_uniform_(self, lo: float, hi: float, seed: int, threads: int = 0):
+        if self.tensor.dtype == _lib.Q8:
+            raise NotImplementedError("a q8 (torch.uint8) table is built from trained rows (quantize_from), not filled")
         if self.tensor.dtype != torch.float32:
             # the round-to-nearest-even cast of the fp32 fill of the same seed, element by element
             check(lib.ce_host_fill_uniform_w16(ctypes.c_void_p(self.host_ptr), self.tensor.numel(), lo, hi, seed,
@@ -133,10 +165,15 @@ class CachedParamMgr(torch.nn.Module):
             raise NotImplementedError("cuda_row_num == 0 (no cache) is not implemented")
         self._table = weight if isinstance(weight, HostTable) else HostTable.wrap(weight)
         self._weight = self._table.tensor
-        self.num_embeddings, self.embedding_dim = self._weight.shape
+        self.num_embeddings, self._row_width = self._weight.shape
         self.table_dtype = self._weight.dtype
-        # what the library is told a row is: fp32 elements (a 16-bit row of D elements = D / 2 of them, bit for bit)
-        self._lib_dim = self.embedding_dim // 2 if self.table_dtype in _lib.W16_DTYPES else self.embedding_dim
+        q8 = self.table_dtype == _lib.Q8
+        # a q8 table's rows are 16 + D bytes wide; embedding_dim keeps meaning D
+        self.embedding_dim = self._row_width - _lib.CE_Q8_HEADER_BYTES if q8 else self._row_width
+        # what the library is told a row is: fp32 elements (a 16-bit row of D elements = D / 2 of them, a q8 row
+        # (16 + D) / 4 of them, bit for bit)
+        self._lib_dim = self._row_width // 4 if q8 else (
+            self.embedding_dim // 2 if self.table_dtype in _lib.W16_DTYPES else self.embedding_dim)
         self.cuda_row_num = int(cuda_row_num)
         self.buffer_size = buffer_size
         self.pin_weight = pin_weight
@@ -148,7 +185,9 @@ class CachedParamMgr(torch.nn.Module):
         assert N < 2 ** 31 - 1, "row ids are int32 on the device"
         dev = self.device
         # the only trainable parameter the optimiser sees (A.1)
-        self.cuda_cached_weight = torch.nn.Parameter(torch.zeros(C, D, device=dev, dtype=self.table_dtype))
+        # (a q8 cache: [C, 16 + D] uint8, never trained)
+        self.cuda_cached_weight = torch.nn.Parameter(
+            torch.zeros(C, self._row_width, device=dev, dtype=self.table_dtype), requires_grad=not q8)
         # DATASET+freq re-rank needs idx_map; identity otherwise (kept None = no array, no gather)
         self._idx_map: Optional[torch.Tensor] = None
         if use_idx_map:
@@ -502,7 +541,7 @@ class CachedParamMgr(torch.nn.Module):
         state_dict that holds it serialises the whole storage, tail included (clone the parameter before saving, or
         save the host table after flush(), which is what a checkpoint of this module is anyway)."""
         rows = int(rows)
-        C, D = self.cuda_row_num, self.embedding_dim
+        C, D = self.cuda_row_num, self._row_width
         full = getattr(self, "_cache_full", None)
         if full is None or full.shape[0] < C + rows:
             with torch.cuda.device(self.device):

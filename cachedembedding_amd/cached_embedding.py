@@ -17,6 +17,11 @@ from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
 from .functional import FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_lr, check_lr_path, embedding_bag
 
 
+def _refuse_q8_update(module, what: str, lr) -> None:
+    if lr is not None and getattr(module, "table_dtype", None) == _lib.Q8:
+        raise NotImplementedError(f"{what}(lr) with a q8 (torch.uint8) table: a quantized table is never updated")
+
+
 class CachedEmbeddingBag(nn.Module):
     def __init__(self, num_embeddings: int, embedding_dim: int, padding_idx: Optional[int] = None,
                  max_norm: Optional[float] = None, norm_type: float = 2.0, scale_grad_by_freq: bool = False,
@@ -25,7 +30,8 @@ class CachedEmbeddingBag(nn.Module):
                  ids_freq_mapping=None, warmup_ratio: float = 0.7, buffer_size: int = 0, pin_weight: bool = False,
                  evict_strategy: EvictionStrategy = EvictionStrategy.DATASET, *, cuda_row_num: Optional[int] = None,
                  init_seed: int = 1024, strict: bool = True, output_dtype: Optional[torch.dtype] = None,
-                 table_dtype: Optional[torch.dtype] = None):
+                 table_dtype: Optional[torch.dtype] = None, _table: Optional[HostTable] = None,
+                 _idx_map: Optional[torch.Tensor] = None):
         super().__init__()
         # output_dtype (addition): dtype of the pooled output and of the gradient coming back -- None / torch.float32,
         # torch.bfloat16 or torch.float16 (functional.embedding_bag(output_dtype=...)).  `dtype` is the TABLE's dtype.
@@ -36,8 +42,23 @@ class CachedEmbeddingBag(nn.Module):
         # table AND the cache hold 16-bit rows (half the host DRAM, half of every admission and write-back); sums and
         # updates stay fp32 and a row is rounded once per step (set_weight_rounding).  The pooled output then defaults
         # to the table's dtype.
-        self.table_dtype = torch.float32 if _lib.table_code(table_dtype) == _lib.CE_ACT_F32 else table_dtype
-        w16 = self.table_dtype != torch.float32
+        # table_dtype=torch.uint8 (addition): an 8-bit row-wise quantized table (q8: rows of 16 + D bytes)
+        # for evaluation and serving -- built from trained rows (from_pretrained(..., table_dtype=torch.uint8) or
+        # quantized() of a trained module: _table / _idx_map are theirs), never updated; the output defaults to fp32.
+        q8 = table_dtype == _lib.Q8
+        self.table_dtype = _lib.Q8 if q8 else (
+            torch.float32 if _lib.table_code(table_dtype) == _lib.CE_ACT_F32 else table_dtype)
+        w16 = self.table_dtype in _lib.W16_DTYPES
+        if q8:
+            _lib.check_q8_dim(embedding_dim)
+            for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
+                             ("sparse=True", bool(sparse))):
+                if on:
+                    raise NotImplementedError(f"{what} with a q8 (torch.uint8) table: it is forward only")
+            if _weight is None and _table is None:
+                raise NotImplementedError("a q8 (torch.uint8) table is built from trained rows, it cannot be "
+                                          "initialised: CachedEmbeddingBag.from_pretrained(embeddings, "
+                                          "table_dtype=torch.uint8) or quantized() of a trained module")
         if w16:
             _lib.check_w16_dim(embedding_dim)
             for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
@@ -71,7 +92,21 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_sgd = FusedSGD(None)
         self.fused_adagrad = FusedRowwiseAdagrad(None)
 
-        if _weight is None:
+        if _table is not None:
+            table = _table
+            assert table.tensor.dtype == self.table_dtype and table.tensor.shape[0] == num_embeddings
+        elif q8:
+            w = _weight.detach()
+            if w.dtype == _lib.Q8:                          # already q8 rows: pinned in place
+                assert tuple(w.shape) == (num_embeddings, _lib.q8_row_bytes(embedding_dim))
+                table = HostTable.wrap(w if w.device.type == "cpu" and w.is_contiguous() else w.cpu().contiguous())
+            else:
+                assert tuple(w.shape) == (num_embeddings, embedding_dim)
+                if w.dtype not in _lib.ACT_DTYPES:
+                    w = w.float()
+                table = HostTable.allocate(num_embeddings, embedding_dim, dtype=_lib.Q8).quantize_from(
+                    w.cpu().contiguous())
+        elif _weight is None:
             table = HostTable.allocate(num_embeddings, embedding_dim, dtype=self.table_dtype)
             table.fill_uniform_(-1.0 / num_embeddings, 1.0 / num_embeddings, init_seed)
             if padding_idx is not None:
@@ -84,8 +119,13 @@ class CachedEmbeddingBag(nn.Module):
                 w = w.to("cpu", self.table_dtype).contiguous()
             table = HostTable.wrap(w)
         self.cache_weight_mgr = CachedParamMgr(table, self.cuda_row_num, buffer_size, pin_weight,
-                                               evict_strategy=evict_strategy, device=device, strict=strict)
+                                               evict_strategy=evict_strategy, device=device, strict=strict,
+                                               use_idx_map=True if _idx_map is not None else None)
+        if _idx_map is not None:                            # quantized(): the source module's id -> row map
+            self.cache_weight_mgr._idx_map.copy_(_idx_map)
         self.cache_weight_mgr.reorder(ids_freq_mapping, warmup_ratio)
+        if q8:
+            self.eval()
         if w16:
             self.set_weight_rounding(self.weight_rounding, self.weight_rounding_seed)
 
@@ -115,7 +155,8 @@ class CachedEmbeddingBag(nn.Module):
         lr may be a tensor (functional.check_lr: one fp32 element on the cache's device): it is kept by reference and
         read by the kernels when they run, so fill_ / copy_ into it changes the rate of the next step -- also of a
         step replayed from a hipGraph.  Not with deterministic=True."""
-        if isinstance(lr, torch.Tensor):                        # (a float or None: nothing new is looked at)
+        _refuse_q8_update(self, "set_fused_sgd", lr)
+        if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
             check_accumulator("sgd", self.table_dtype, accumulator, bool(deterministic), self.weight_rounding)
@@ -140,7 +181,8 @@ class CachedEmbeddingBag(nn.Module):
         instead of one as large as the cache (FusedRowwiseAdagrad); not with deterministic=True, and a 16-bit table
         needs set_weight_rounding("nearest") first.
         lr may be a tensor, as in set_fused_sgd; not with deterministic=True."""
-        if isinstance(lr, torch.Tensor):                        # (a float or None: nothing new is looked at)
+        _refuse_q8_update(self, "set_fused_rowwise_adagrad", lr)
+        if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
             check_accumulator("rowwise_adagrad", self.table_dtype, accumulator, bool(deterministic),
@@ -161,7 +203,7 @@ class CachedEmbeddingBag(nn.Module):
         """How the fused updates round a row of a 16-bit table: "nearest" (round-to-nearest-even) or "stochastic" (the
         default: one of the two 16-bit neighbours, with probabilities that make the rounding unbiased; the random bits
         are a hash of seed, step, host-table row and element).  A ValueError for an fp32 table."""
-        if self.table_dtype == torch.float32:
+        if self.table_dtype not in _lib.W16_DTYPES:
             raise ValueError("set_weight_rounding is meaningful only with a 16-bit table (table_dtype=)")
         if rounding not in ("nearest", "stochastic"):
             raise ValueError(f"rounding={rounding!r}: 'nearest' or 'stochastic'")
@@ -238,6 +280,45 @@ class CachedEmbeddingBag(nn.Module):
     @classmethod
     def from_pretrained(cls, embeddings: torch.Tensor, freeze: bool = True, **kwargs) -> "CachedEmbeddingBag":
         rows, cols = embeddings.shape
+        if kwargs.get("table_dtype") == _lib.Q8:
+            # table_dtype=torch.uint8: the fp32 / bf16 / fp16 rows are quantized (functional.quantize_rows), or q8 rows
+            # ([rows, 16 + D] uint8) are taken as they are; the module is eval-only
+            if not freeze:
+                raise NotImplementedError("from_pretrained(freeze=False) with a q8 (torch.uint8) table: a quantized "
+                                          "table is never updated")
+            if embeddings.dtype == _lib.Q8:
+                cols -= _lib.CE_Q8_HEADER_BYTES
+            return cls(rows, cols, _weight=embeddings, **kwargs)
         m = cls(rows, cols, _weight=embeddings, **kwargs)
         m.cache_weight_mgr.cuda_cached_weight.requires_grad_(not freeze)
         return m
+
+    def quantized(self, **overrides) -> "CachedEmbeddingBag":
+        """An eval-only module over the 8-bit row-wise quantized (q8) copy of this module's table: this module is
+        flushed, its host table is quantized row by row -- in row space, so the id -> row map (idx_map) carries over --
+        into a new pinned table, and the new module has this one's mode, include_last_offset, padding_idx, eviction
+        strategy, cuda_row_num, output dtype and idx_map.  overrides: cuda_row_num (a q8 row of D elements is 16 + D
+        bytes: the same HBM holds more rows), output_dtype, warmup_ratio, buffer_size, strict.  This module is left as it
+        is and trains on."""
+        if self.table_dtype == _lib.Q8:
+            raise NotImplementedError("quantized() of a q8 (torch.uint8) module: it is quantized already")
+        if getattr(self, "world_size", 1) > 1:
+            _lib.refuse_q8(f"{type(self).__name__}.quantized() on {self.world_size} ranks", _lib.Q8)
+        bad = set(overrides) - {"cuda_row_num", "output_dtype", "warmup_ratio", "buffer_size", "strict"}
+        if bad:
+            raise TypeError(f"quantized() got unexpected overrides {sorted(bad)}")
+        for what, on in (("mode='max'", self.mode == "max"), ("max_norm", self.max_norm is not None)):
+            if on:
+                raise NotImplementedError(f"{what} with a q8 (torch.uint8) table: it is forward only")
+        _lib.check_q8_dim(self.embedding_dim)
+        mgr = self.cache_weight_mgr
+        self.flush()
+        src = self.weight                                   # (waits for the write-backs of the worker transport)
+        table = HostTable.allocate(self.num_embeddings, self.embedding_dim, dtype=_lib.Q8).quantize_from(src)
+        kw = dict(cuda_row_num=self.cuda_row_num, output_dtype=self.output_dtype, warmup_ratio=0.7,
+                  buffer_size=mgr.buffer_size, strict=mgr.strict)
+        kw.update(overrides)
+        return CachedEmbeddingBag(self.num_embeddings, self.embedding_dim, padding_idx=self.padding_idx, mode=self.mode,
+                                  include_last_offset=self.include_last_offset, device=mgr.device,
+                                  evict_strategy=self.evict_strategy, table_dtype=_lib.Q8, _table=table,
+                                  _idx_map=mgr._idx_map, **kw)

@@ -288,6 +288,71 @@ class _BagFn(torch.autograd.Function):
         return gw, None, None, gpsw, None, None, None, None, None, None, None, None, None, None
 
 
+def _forward_q8(weight, indices, offsets, psw, mode, include_last, hook_features, presorted, out, out_dtype):
+    """The forward over an 8-bit row-wise quantized table (ce_bag_forward_q8 / ce_bag_forward_src_keys_q8): weight is
+    [R, 16 + D] uint8.  No autograd node: there is no backward, the output never requires grad."""
+    _lib.require_gpu()
+    assert weight.is_cuda and weight.is_contiguous()
+    num_bags = offsets.numel() - 1 if include_last else offsets.numel()
+    dim = weight.shape[1] - _lib.CE_Q8_HEADER_BYTES
+    shape = (num_bags // hook_features, hook_features, dim) if hook_features else (num_bags, dim)
+    if out is not None:
+        if tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous() or out.device != weight.device:
+            raise ValueError(f"out= must be a contiguous {_DTYPE_NAMES[out_dtype]} tensor of shape {shape} on "
+                             f"{weight.device}")
+    else:
+        out = torch.empty(shape, device=weight.device, dtype=out_dtype)
+    act = _lib.ACT_DTYPES[out_dtype]
+    from_keys = FORWARD_FROM_KEYS and isinstance(presorted, SrcKeys) and presorted.identity and psw is None \
+        and mode == _lib.CE_MODE_SUM and num_bags == indices.numel()
+    if psw is not None:
+        psw = psw.detach()
+    if from_keys:
+        check(lib.ce_bag_forward_src_keys_q8(ptr(weight), weight.shape[0], dim, indices.numel(), ptr(presorted.keys),
+                                             ptr(out), act, stream_ptr()))
+    else:
+        check(lib.ce_bag_forward_q8(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(), ptr(offsets),
+                                    int(offsets.dtype == torch.int64), num_bags, int(include_last), ptr(psw), mode,
+                                    hook_features, ptr(out), act, stream_ptr()))
+    return out
+
+
+def _q8_host_src(t: torch.Tensor):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in _lib.ACT_DTYPES:
+        raise NotImplementedError("quantize_rows takes a 2-D torch.float32, torch.bfloat16 or torch.float16 tensor")
+    _lib.check_q8_dim(t.shape[1])
+    return t.detach().cpu().contiguous()
+
+
+def quantize_rows(t: torch.Tensor, threads: int = 0) -> torch.Tensor:
+    """[N, D] fp32 / bf16 / fp16 rows (any device; quantized on the host) -> [N, 16 + D] uint8 q8 rows on the CPU
+    (ce_host_quantize_q8: scale = (max - min) / 255, bias = min, code = rint((x - min) / scale)).  A row holding a NaN
+    or an infinity raises (CE_ERR_INVALID names the first one).  Needs no GPU."""
+    src = _q8_host_src(t)
+    n, dim = src.shape
+    q = torch.empty(n, _lib.q8_row_bytes(dim), dtype=torch.uint8)
+    check(lib.ce_host_quantize_q8(ptr(src), _lib.ACT_DTYPES[src.dtype], n, dim, ptr(q), threads or _q8_threads()))
+    return q
+
+
+def dequantize_rows(q: torch.Tensor, dim: Optional[int] = None, threads: int = 0) -> torch.Tensor:
+    """[N, 16 + dim] uint8 q8 rows -> [N, dim] fp32 on the CPU: fmaf(code, scale, bias), the value the kernels use"""
+    if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.dtype != _lib.Q8:
+        raise NotImplementedError("dequantize_rows takes a 2-D torch.uint8 tensor of q8 rows")
+    if dim is None:
+        dim = q.shape[1] - _lib.CE_Q8_HEADER_BYTES
+    if q.shape[1] != _lib.q8_row_bytes(dim):
+        raise ValueError(f"q8 rows of dim {dim} are {_lib.CE_Q8_HEADER_BYTES + dim} bytes wide (got {q.shape[1]})")
+    src = q.detach().cpu().contiguous()
+    out = torch.empty(src.shape[0], dim, dtype=torch.float32)
+    check(lib.ce_host_dequantize_q8(ptr(src), src.shape[0], dim, ptr(out), threads or _q8_threads()))
+    return out
+
+
+def _q8_threads() -> int:
+    return int(lib.ce_cpu_budget())
+
+
 def check_lr(lr):
     """What a fused update's learning rate may be: None (the update is off), a number, or a tensor of ONE fp32 element,
     contiguous, that does not require grad.  The tensor is kept by reference and never read on the host: the kernels
@@ -583,7 +648,22 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     # and hence of the gradient autograd hands back; the weight, the sums and every update stay fp32, the kernels
     # round once on the store and read the 16-bit gradient in place.  out= must then have that dtype.
     _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
-    if fused_sgd is not None and fused_sgd.lr is not None:
+    q8 = weight.dtype == _lib.Q8
+    if q8:
+        # an 8-bit row-wise quantized table ([R, 16 + D] uint8 rows): forward only, the output defaults to fp32.  What it
+        # does not take is refused here, before any kernel has run.
+        if weight.dim() != 2:
+            raise ValueError("a q8 (torch.uint8) weight is a [rows, 16 + embedding_dim] tensor")
+        _lib.check_q8_dim(weight.shape[1] - _lib.CE_Q8_HEADER_BYTES)
+        for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
+                         ("a fused SGD / row-wise Adagrad update (a quantized table is never updated)",
+                          fused_sgd is not None and fused_sgd.lr is not None),
+                         ("a gradient w.r.t. per_sample_weights",
+                          per_sample_weights is not None and per_sample_weights.requires_grad
+                          and torch.is_grad_enabled())):
+            if on:
+                raise NotImplementedError(f"{what} with a q8 (torch.uint8) table: it is forward only")
+    elif fused_sgd is not None and fused_sgd.lr is not None:
         check_accumulator("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
                           fused_sgd.accumulator, bool(fused_sgd.deterministic), fused_sgd.rounding)
         if fused_sgd.accumulator == "step" and mode == "max":
@@ -722,6 +802,9 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     if masked_indices and mode != "sum":
         raise NotImplementedError("masked (padding) lookups are implemented for mode='sum' only (mean would need "
                                   "the per-bag count of non-padding entries)")
+    if q8:
+        return _forward_q8(weight, indices, offsets, per_sample_weights, _MODES[mode], bool(include_last_offset),
+                           int(hook_features), presorted, out, output_dtype)
     return _BagFn.apply(weight, indices, offsets, per_sample_weights, _MODES[mode], bool(include_last_offset),
                         int(hook_features), bool(sparse), fused_sgd, presorted, bwd_scale,
                         padding_idx is not None or bool(masked_indices), None if out is None else [out], output_dtype)

@@ -55,6 +55,11 @@ def parse_args(argv=None):
     p.add_argument("--eval_acc", action="store_true",
                    help="AUROC and accuracy over the val set after every epoch and over the test set at the end "
                         "(recsys/dlrm_main.py:168,358-371)")
+    p.add_argument("--eval_q8", action="store_true",
+                   help="with --eval_acc, one process, no --use_tablewise: after the final test evaluation the trained "
+                        "table is quantized to 8-bit rows (CachedEmbeddingBag.quantized()), the test set is evaluated "
+                        "again through it, and test_auroc_q8 / test_accuracy_q8 / the two table sizes are printed as "
+                        "one JSON line (and merged into --json_out)")
     p.add_argument("--batch_size", type=int, default=16384)
     p.add_argument("--num_dense_features", type=int, default=13)
     p.add_argument("--embedding_dim", type=int, default=128)
@@ -635,6 +640,13 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     check_output_dtype(args, world)
+    if args.eval_q8:
+        if not args.eval_acc:
+            raise ValueError("--eval_q8 needs --eval_acc: it evaluates the test set a second time, through the "
+                             "quantized table")
+        if world > 1 or args.use_tablewise:
+            raise NotImplementedError("--eval_q8 is implemented for one process without --use_tablewise (the sharded "
+                                      "classes do not take a q8 table)")
     if args.adagrad:
         if args.fused_sgd:
             raise ValueError("--adagrad takes the place of --fused_sgd: pass one of them")
@@ -759,6 +771,25 @@ def main(argv=None):
                               "val_batches": _evaluate.batches} if args.eval_acc else None)}, indent=1))
     if args.eval_acc:                                            # recsys/dlrm_main.py:365-369
         results["test_auroc"], results["test_accuracy"] = _evaluate(model, test_loader, "test", args, device, rank, world)
+    if args.eval_q8:
+        # serve what was trained at a quarter of the memory: the same dense weights over the 8-bit row-wise quantized
+        # copy of the table (a new pinned table and a cache of its own; the trained module is only flushed)
+        import json
+        sparse = model.sparse_modules
+        q8 = embed.quantized()
+        sparse.embed = q8
+        try:
+            auroc, acc = _evaluate(model, test_loader, "test (q8 table)", args, device, rank, world)
+        finally:
+            sparse.embed = embed
+        table, table_q8 = embed.weight, q8.weight
+        extra = {"test_auroc_q8": auroc, "test_accuracy_q8": acc,
+                 "table_bytes": table.numel() * table.element_size(), "table_bytes_q8": table_q8.numel()}
+        results.update(extra)
+        print(json.dumps({"script": "examples/dlrm_main.py", "test_auroc": results["test_auroc"],
+                          "test_accuracy": results["test_accuracy"], **extra}))
+        if args.json_out and Path(args.json_out).exists():
+            Path(args.json_out).write_text(json.dumps(json.loads(Path(args.json_out).read_text()) | extra, indent=1))
     if world > 1:
         dist.destroy_process_group()
 

@@ -551,6 +551,36 @@ int ce_bag_backward_update_src_lrdev(void* weight, int32_t weight_dtype, int64_t
                                      const float* lr, float eps, int32_t optimizer, int32_t rounding, uint64_t seed,
                                      int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
+/* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
+ * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
+ * A row of `dim` elements is 16 + dim bytes:
+ *   bytes 0..3 scale (fp32) | 4..7 bias (fp32) | 8..15 zero | 16..16+dim-1: dim codes, uint8
+ * dim % 16 == 0, 16 <= dim <= 1024 and the table 16-byte aligned, so every row is a whole number of 16-byte units
+ * and its codes start 16-byte aligned (the cache op, which only moves rows, is driven with embedding_dim =
+ * (16 + dim) / 4).  Any other dim: CE_ERR_UNSUPPORTED before any launch; ce_q8_row_bytes returns 0 for it.
+ * Element value: v = fmaf((float)q, scale, bias) -- ONE explicit fused multiply-add, in the kernels and on the host.
+ * Quantizer (fp32 IEEE throughout, every operation rounded to fp32, no contraction), per row: lo = min, hi = max,
+ * scale = (hi - lo) / 255, bias = lo, q = clamp(rintf((x - lo) / scale), 0, 255) (ties to even).  If the fp32
+ * quotient (hi - lo) / 255 is 0 (a constant row, a denormal range) all codes are 0 and scale is stored as 0: the row
+ * reproduces lo.  A row holding a NaN or an infinity: CE_ERR_INVALID, ce_last_error names the first such row, and
+ * the destination is unspecified.  The result does not depend on `threads` (capped by ce_cpu_budget()).
+ * src_dtype: CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16 (16-bit sources are up-converted exactly first).  Both host
+ * entries work on host memory and need no GPU.
+ * The two forwards are ce_bag_forward_w16 / ce_bag_forward_src_keys_w16 in every respect but the row type: sum /
+ * mean, per-sample weights, hook_features, int32 / int64 offsets, offsets == NULL for one id per bag; lookups outside
+ * [0, num_rows) take no part (the key-driven form writes a zero row for them); fp32 sums, one rounding on the store
+ * to act_dtype; capture-safe; everything refusable is refused before the first launch. */
+#define CE_Q8_HEADER_BYTES 16
+size_t ce_q8_row_bytes(int32_t dim);
+int ce_host_quantize_q8(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, void* dst, int threads);
+int ce_host_dequantize_q8(const void* src, int64_t n_rows, int32_t dim, float* dst, int threads);
+int ce_bag_forward_q8(const void* weight, int64_t num_rows, int32_t dim,
+                      const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                      int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                      int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_forward_src_keys_q8(const void* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                               const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6]. Device state arrays are owned by the caller (so the Python
  * mirror can expose them as tensors: cached_idx_map, inverted_cached_idx, idx_map,
