@@ -21,7 +21,9 @@
 // L2 / Infinity Cache.
 // The sums and the updates are fp32; the forward's output and the backward's grad_out have the activation
 // type AT (fp32, bf16, fp16: Act<AT, VT> in ce_common.h) the four bag kernels are templated on.  The table is fp32, or
-// -- the two forwards only (WT; ce_bag_forward_w16 / _src_keys_w16) -- bf16 / fp16; its update is ce_bag_adagrad.hip's.
+// -- the two forwards only (WT, read through Row<WT, VT>) -- bf16 / fp16 (ce_bag_forward_w16 / _src_keys_w16; its update
+// is ce_bag_adagrad.hip's) or 8-bit row-wise quantized (Q8; ce_bag_forward_q8 / _src_keys_q8: evaluation and serving
+// only, no backward).
 #include <algorithm>
 
 #include "ce_common.h"
@@ -107,15 +109,54 @@ __device__ __forceinline__ void store_out(T* p, T v) {
   __builtin_nontemporal_store(v, p);
 }
 
+// How the two forwards read a table row of type WT with lanes of VT: a row is kHeader + rowlen elements V, a lane's
+// chunk ch is element kHeader + ch.  While its loads are in flight a lane keeps a `Held` per chunk (up() of the V) and a
+// `Hdr` per row (header() of the row's start, where kHeader != 0); value() turns them into the chunk's fp32 elements at
+// the point of use.  The index expressions stay in the kernels, in the order they always had: moved in here, the fp32
+// and 16-bit instantiations come out of the compiler scheduled differently (profiles/q8_row_type_refactor.md).
+// fp32 / bf16 / fp16 rows: rowlen chunks, the chunk itself is held (up-converted exactly on load), no header.
+template <typename WT, typename VT> struct Row {
+  typedef typename Act<WT, VT>::V V;
+  typedef VT Held;
+  struct Hdr {};
+  static constexpr int kHeader = 0;
+  static __device__ __forceinline__ Held zero() { return vzero<VT>(); }
+  static __device__ __forceinline__ Held up(V a) { return Act<WT, VT>::up(a); }
+  static __device__ __forceinline__ VT value(Held v, Hdr) { return v; }
+};
+// q8 rows (include/ce_api.h): 4 + rowlen dwords -- scale, bias (fp32), 8 zero bytes, then a dword of 4 codes per chunk.
+// A lane holds the codes (1 dword per chunk, not 4: fewer registers than the fp32 rows at the same depth); element k is
+// byte k (v_cvt_f32_ubyte0..3) and ONE explicit fma.  scale and bias are one 8-byte load per row that EVERY lane of the
+// group issues at the same address: the lanes of one load instruction that hit one address are served by one request,
+// and it sits in the same 128-byte line as the row's first codes, which the group fetches anyway -- while one lane
+// loading and the others shuffling would put a ds_bpermute (G up to 64 lanes: no DPP form) between every row load and
+// its first use.  A 144-byte row (D = 128) always spans two 128-byte lines: the format's price.
+struct Q8 {};
+constexpr int kTableQ8 = 8;   // "q8" in the launchers' weight_dtype, beside CE_ACT_*: library-internal, no entry takes it
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <> struct Row<Q8, f32x4> {
+  typedef uint32_t V;
+  typedef uint32_t Held;
+  typedef f32x2 Hdr;      // {scale, bias}; {0, 0} for a row that takes no part
+  static constexpr int kHeader = CE_Q8_HEADER_BYTES / 4;
+  static __device__ __forceinline__ Held zero() { return 0u; }
+  static __device__ __forceinline__ Held up(V a) { return a; }
+  static __device__ __forceinline__ Hdr header(const V* row) { return *(const Hdr*)row; }
+  static __device__ __forceinline__ f32x4 value(Held c, Hdr sb) {
+    return f32x4{__builtin_fmaf((float)(c & 0xffu), sb.x, sb.y), __builtin_fmaf((float)((c >> 8) & 0xffu), sb.x, sb.y),
+                 __builtin_fmaf((float)((c >> 16) & 0xffu), sb.x, sb.y), __builtin_fmaf((float)(c >> 24), sb.x, sb.y)};
+  }
+};
+
 // STAGE: tiles with multi-id bags stage their indices in LDS (32 KB per workgroup); the launcher picks the
 // LDS-free variant when nnz == num_bags (single-id batches) so occupancy is set by registers alone.
 // AT: the output's element type (Act<AT, VT>, ce_common.h): sums stay fp32, the store rounds.
-// WT: the table's element type (float, or bf16 / fp16 with f32x4 lanes: a lane's chunk is then 8 bytes of the row,
-// up-converted exactly on load).
+// WT: the table's row type (Row<WT, VT>: float; bf16 / fp16 with f32x4 lanes, a lane's chunk is then 8 bytes of the row;
+// Q8 with f32x4 lanes).  A row that takes no part is held as zeros: chunks and header.
 template <typename VT, int NCH, bool STAGE, int U, typename AT, typename WT = float>
 __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   using A = Act<AT, VT>;
-  using T = Act<WT, VT>;
+  using T = Row<WT, VT>;
   __shared__ int lds_idx[STAGE ? 4 : 1][STAGE ? kIdxStage : 1];
   const int lane = threadIdx.x & 63;
   const int G = 1 << p.g_log2;
@@ -128,6 +169,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   const typename T::V* __restrict__ W = (const typename T::V*)p.weight;
   typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const int rowlen = p.rowlen;
+  const int stride = T::kHeader + rowlen;
   // tiles are dealt round-robin to the waves of an oversubscribed grid (an even contiguous split over a
   // resident-sized grid measured 15 % slower: 0.060 -> 0.069 ms)
   const int ntiles = (p.num_bags + 63) >> 6;
@@ -150,16 +192,22 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
         if (p.psw) w = p.psw[lo];
       }
       for (int base = 0; base < nb; base += gpw * U) {
-        VT v[U][NCH];
+        typename T::Held v[U][NCH];
+        typename T::Hdr h[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int bi = base + u * gpw + grp;
           const int ri = __shfl(idx, bi & 63);
+          h[u] = typename T::Hdr{};
+          if constexpr (T::kHeader != 0) {      // every lane of the group reads it; the chunk loads share the row's product
+            const typename T::V* row = &W[(int64_t)ri * stride];
+            if (bi < nb && (uint32_t)ri < p.num_rows) h[u] = T::header(row);
+          }
 #pragma unroll
           for (int c = 0; c < NCH; ++c) {
             const int ch = gl + c * G;
-            v[u][c] = vzero<VT>();
-            if (bi < nb && ch < rowlen && (uint32_t)ri < p.num_rows) v[u][c] = T::up(W[(int64_t)ri * rowlen + ch]);
+            v[u][c] = T::zero();
+            if (bi < nb && ch < rowlen && (uint32_t)ri < p.num_rows) v[u][c] = T::up(W[(int64_t)ri * stride + T::kHeader + ch]);
           }
         }
 #pragma unroll
@@ -172,7 +220,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
             for (int c = 0; c < NCH; ++c) {
               const int ch = gl + c * G;
               if (ch < rowlen) {
-                VT val = p.psw ? v[u][c] * wi : v[u][c];
+                VT val = p.psw ? T::value(v[u][c], h[u]) * wi : T::value(v[u][c], h[u]);
                 store_out(&O[orow * rowlen + ch], A::down(val));
               }
             }
@@ -212,21 +260,32 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
               if (p.psw) w[t] = p.psw[j + t];
             }
           }
-          VT v[8][NCH];
+          typename T::Held v[8][NCH];
+          typename T::Hdr h[8];
 #pragma unroll
           for (int t = 0; t < 8; ++t) {
+            h[t] = typename T::Hdr{};
+            if constexpr (T::kHeader != 0) {
+              // (the row's first element is worked out HERE, for every lane, so that the chunk loads below share the
+              // 64-bit product: left alone, the compiler sinks it into this branch and multiplies again for the chunks --
+              // 2 % of the 20-ids-per-bag q8 forward, profiles/q8_row_type_refactor.md)
+              const int64_t first = (int64_t)r[t] * stride;
+              asm volatile("" :: "v"(first));
+              if ((uint32_t)r[t] < p.num_rows) h[t] = T::header(&W[first]);
+            }
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
               const int ch = gl + c * G;
-              v[t][c] = vzero<VT>();
-              if (ch < rowlen && (uint32_t)r[t] < p.num_rows) v[t][c] = T::up(W[(int64_t)r[t] * rowlen + ch]);
+              v[t][c] = T::zero();
+              if (ch < rowlen && (uint32_t)r[t] < p.num_rows) v[t][c] = T::up(W[(int64_t)r[t] * stride + T::kHeader + ch]);
             }
           }
 #pragma unroll
           for (int t = 0; t < 8; ++t) {
             if (j + t < bhi) {
 #pragma unroll
-              for (int c = 0; c < NCH; ++c) acc[c] = p.psw ? acc[c] + v[t][c] * w[t] : acc[c] + v[t][c];
+              for (int c = 0; c < NCH; ++c)
+                acc[c] = p.psw ? acc[c] + T::value(v[t][c], h[t]) * w[t] : acc[c] + T::value(v[t][c], h[t]);
             }
           }
         }
@@ -1007,11 +1066,12 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
 // An ignored lookup (row 0xffffffff, see k_bag_presort_seg) gets a zero row; padding keys (~0) are skipped.
 // AT: the output's element type; the row is rounded once per store, so `prev` stays the fp32 row.
 // PAIR (16-bit AT, f32x4 lanes): the stores of two keys are ONE 16-byte store per lane (see u32x4 above).
-// WT: the table's element type (a 16-bit table whose type differs from AT: the row is up-converted on load).
+// WT: the table's row type (a 16-bit table whose type differs from AT: the row is up-converted on load; Q8: the row is
+// dequantized ONCE per run, `prev` is the fp32 row).  PAIR is never instantiated for Q8.
 template <typename VT, int NCH, int R, typename AT, bool PAIR = false, typename WT = float>
 __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t total) {      // 4 waves per SIMD: <= 128 VGPRs
   using A = Act<AT, VT>;
-  using T = Act<WT, VT>;
+  using T = Row<WT, VT>;
   static_assert(!PAIR || (sizeof(typename A::V) == 8 && R % 2 == 0), "PAIR: 4 x 16 bit per lane, keys two at a time");
   __shared__ unsigned long long lk[256 * (R > 4 ? R : 4)];
   const int tid = threadIdx.x;
@@ -1020,6 +1080,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
   const int grp = tid >> p.g_log2;
   const int gl = tid & (G - 1);
   const int rowlen = p.rowlen;
+  const int stride = T::kHeader + rowlen;
   const typename T::V* __restrict__ W = (const typename T::V*)p.weight;
   typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const unsigned long long* __restrict__ keys = p.presorted;
@@ -1039,7 +1100,8 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
     for (int k = gl; k < kc; k += G) mylk[k] = c0 + k < s1 ? keys[c0 + k] : ~0ull;
     const int64_t c1 = min(s1, c0 + kc);
     for (int64_t q = c0; q < c1; q += R) {
-      VT v[R][NCH];
+      typename T::Held v[R][NCH];
+      typename T::Hdr h[R];
       uint32_t heads = 0;
       uint32_t last = prev_row;
 #pragma unroll
@@ -1050,11 +1112,16 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
         const bool head = on && rw != last;
         if (on) last = rw;
         if (head) heads |= 1u << t;
+        h[t] = typename T::Hdr{};
+        if constexpr (T::kHeader != 0) {
+          const typename T::V* row = &W[(int64_t)rw * stride];
+          if (head && rw < p.num_rows) h[t] = T::header(row);
+        }
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const int ch = gl + c * G;
-          v[t][c] = vzero<VT>();
-          if (head && ch < rowlen && rw < p.num_rows) v[t][c] = T::up(W[(int64_t)rw * rowlen + ch]);
+          v[t][c] = T::zero();
+          if (head && ch < rowlen && rw < p.num_rows) v[t][c] = T::up(W[(int64_t)rw * stride + T::kHeader + ch]);
         }
       }
       __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): every head of the step has arrived
@@ -1068,13 +1135,13 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
           u32x2 r0[NCH], r1[NCH];
           if ((heads >> t) & 1) {
 #pragma unroll
-            for (int c = 0; c < NCH; ++c) prev[c] = v[t][c];
+            for (int c = 0; c < NCH; ++c) prev[c] = T::value(v[t][c], h[t]);
           }
 #pragma unroll
           for (int c = 0; c < NCH; ++c) r0[c] = __builtin_bit_cast(u32x2, A::down(prev[c]));
           if ((heads >> (t + 1)) & 1) {
 #pragma unroll
-            for (int c = 0; c < NCH; ++c) prev[c] = v[t + 1][c];
+            for (int c = 0; c < NCH; ++c) prev[c] = T::value(v[t + 1][c], h[t + 1]);
           }
 #pragma unroll
           for (int c = 0; c < NCH; ++c) r1[c] = __builtin_bit_cast(u32x2, A::down(prev[c]));
@@ -1100,7 +1167,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
         if (k == ~0ull) continue;              // padding (group-uniform)
         if ((heads >> t) & 1) {
 #pragma unroll
-          for (int c = 0; c < NCH; ++c) prev[c] = v[t][c];       // a new run: its row stays in `prev` until the next head
+          for (int c = 0; c < NCH; ++c) prev[c] = T::value(v[t][c], h[t]);   // a new run: its fp32 row stays in `prev`
         }
         // (owner-exclusive keys -- presort_window(ids=...) -- carry kExclFlag in bit 31 of the low word: not part of the row)
         const int64_t orow = (int64_t)((uint32_t)k & ~kExclFlag);
@@ -1198,9 +1265,11 @@ static int fill_params_keys(BagParams& p, RowGeom& r, int32_t dim, bool aligned,
 template <typename F> static void for_lanes_act(const RowGeom& r, int act, F&& f) {
   for_lanes(r.vec, r.nch, [&](auto l) { for_act(act, [&](auto a) { f(l, a); }); });
 }
-// ... and with the table's type (the two forwards): f(Lanes<VT, N>, ActTag<WT>, ActTag<AT>)
+// ... and with the table's type (the two forwards): f(Lanes<VT, N>, ActTag<WT>, ActTag<AT>); q8: vector lanes only
 template <typename F> static void for_table_act(int weight_dtype, const RowGeom& r, int act, F&& f) {
-  for_table(weight_dtype, r, [&](auto l, auto w) { for_act(act, [&](auto a) { f(l, w, a); }); });
+  auto acts = [&](auto l, auto w) { for_act(act, [&](auto a) { f(l, w, a); }); };
+  if (weight_dtype == kTableQ8) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<Q8>{}); });
+  else for_table(weight_dtype, r, acts);
 }
 
 // rows in flight per lane group, by lane shape: k_bag_fwd's U and k_bag_bwd_tile's R ...
@@ -1260,8 +1329,8 @@ static int launch_bwd_scatter(BagParams& p, const RowGeom& r, int act, const flo
   return CE_OK;
 }
 
-// The gather-shaped forward over filled BagParams.  weight_dtype: CE_ACT_F32, or a 16-bit table's type -- the same
-// kernel with the row type WT; only the vector lane shape exists there, a lane's chunk is 8 bytes of the row.
+// The gather-shaped forward over filled BagParams.  weight_dtype: CE_ACT_F32, or a 16-bit table's type or kTableQ8 --
+// the same kernel with the row type WT; only the vector lane shape exists there.
 static int launch_fwd(BagParams& p, const RowGeom& r, const void* weight, int weight_dtype, int64_t num_rows, void* out,
                       int act, hipStream_t s) {
   p.weight = (const float*)weight;
@@ -1284,7 +1353,7 @@ static int launch_fwd(BagParams& p, const RowGeom& r, const void* weight, int we
 
 // The key-driven forward.  An fp32 table has the PAIR form for a 16-bit output; a 16-bit table only the converting
 // instantiation (WT != AT: exact up-conversion, one rounding on the store) -- equal types never get here, see
-// ce_bag_forward_src_keys_w16.
+// ce_bag_forward_src_keys_w16.  A q8 table (kTableQ8) always converts: it takes that arm too.
 static int launch_fwd_keys(const void* weight, int weight_dtype, int64_t num_rows, int32_t dim, bool aligned, int64_t nnz,
                            const uint64_t* src_keys, void* out, int act, hipStream_t s) {
   BagParams p{};
@@ -1598,6 +1667,44 @@ extern "C" int ce_bag_forward_src_keys_w16(const void* weight, int32_t weight_dt
     return ce_bag_forward_src_keys_act((const float*)weight, num_rows, dim / 2, nnz, src_keys, out, CE_ACT_F32, stream);
   }
   return launch_fwd_keys(weight, weight_dtype, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
+}
+
+// ---- forward from a q8 table (dim % 16 == 0, 16 <= dim <= 1024, everything aligned): the row type Q8 of the same kernels
+#define CE_REQUIRE_Q8_DIM(dim)                                                         \
+  CE_REQUIRE(ce_q8_row_bytes(dim) != 0, CE_ERR_UNSUPPORTED,                            \
+             "a q8 table needs dim %% 16 == 0 and 16 <= dim <= 1024 (got %d)", (int)(dim))
+#define CE_REQUIRE_Q8_ALIGNED(weight, out, act)                                        \
+  CE_REQUIRE(al16(weight) && act_aligned(out, act), CE_ERR_INVALID,                    \
+             "a q8 table must be 16-byte aligned and its output on the vector boundary")
+
+extern "C" int ce_bag_forward_q8(const void* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                 const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                 int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                 int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_Q8_DIM(dim);
+  if (num_bags == 0) return CE_OK;
+  CE_REQUIRE(weight && out && (indices || nnz == 0), CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(offsets || num_bags == nnz, CE_ERR_INVALID,
+             "offsets == NULL states one id per bag (offsets = arange): num_bags must equal nnz");
+  CE_REQUIRE_Q8_ALIGNED(weight, out, act_dtype);
+  BagParams p{};
+  RowGeom r;
+  int rc = fill_params(p, r, dim, true, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                       per_sample_weights, mode, hook_features);
+  if (rc) return rc;
+  return launch_fwd(p, r, weight, kTableQ8, num_rows, out, act_dtype, (hipStream_t)stream);
+}
+
+extern "C" int ce_bag_forward_src_keys_q8(const void* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                          const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_Q8_DIM(dim);
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE_ROWS(num_rows);
+  CE_REQUIRE_Q8_ALIGNED(weight, out, act_dtype);
+  return launch_fwd_keys(weight, kTableQ8, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
 }
 
 extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : padded_keys(nnz); }

@@ -179,9 +179,14 @@ template <typename VT_, int NCH_> struct Lanes {
 };
 template <typename AT_> struct ActTag { typedef AT_ AT; };
 
+// the vector lane shapes alone (a table that has no scalar form): f(Lanes<f32x4, N>)
+template <typename F> static inline void for_vec_lanes(int nch, F&& f) {
+  if (nch == 1) f(Lanes<f32x4, 1>{}); else if (nch == 2) f(Lanes<f32x4, 2>{}); else f(Lanes<f32x4, 4>{});
+}
+
 template <typename F> static inline void for_lanes(bool vec, int nch, F&& f) {
   if (vec) {
-    if (nch == 1) f(Lanes<f32x4, 1>{}); else if (nch == 2) f(Lanes<f32x4, 2>{}); else f(Lanes<f32x4, 4>{});
+    for_vec_lanes(nch, f);
   } else {
     if (nch == 1) f(Lanes<float, 1>{}); else if (nch == 2) f(Lanes<float, 2>{}); else f(Lanes<float, 4>{});
   }
@@ -193,14 +198,13 @@ template <typename F> static inline void for_act(int act, F&& f) {
 
 // a 16-bit table's lanes (always f32x4 chunks) and row type: f(Lanes<f32x4, N>, ActTag<WT>)
 template <typename F> static inline void for_w16(int nch, int weight_dtype, F&& f) {
-  auto lanes = [&](auto w) {
-    if (nch == 1) f(Lanes<f32x4, 1>{}, w); else if (nch == 2) f(Lanes<f32x4, 2>{}, w); else f(Lanes<f32x4, 4>{}, w);
-  };
+  auto lanes = [&](auto w) { for_vec_lanes(nch, [&](auto l) { f(l, w); }); };
   if (weight_dtype == CE_ACT_BF16) lanes(ActTag<bf16_t>{}); else lanes(ActTag<f16_t>{});
 }
 
 // the one place that turns (weight_dtype, RowGeom) into the table's row type and the lane shape of a launch:
-// f(Lanes<VT, N>, ActTag<WT>) -- an fp32 table in either lane form, a 16-bit table in vector lanes
+// f(Lanes<VT, N>, ActTag<WT>) -- an fp32 table in either lane form, a 16-bit table in vector lanes.  (The q8 table,
+// forward only, is added by the forwards' own for_table_act in ce_bag.hip: the updates that dispatch here have no q8 form.)
 template <typename F> static inline void for_table(int weight_dtype, const RowGeom& r, F&& f) {
   if (weight_dtype == CE_ACT_F32) for_lanes(r.vec, r.nch, [&](auto l) { f(l, ActTag<float>{}); });
   else for_w16(r.nch, weight_dtype, f);

@@ -116,18 +116,24 @@ def test_forward_defaults_to_fp32_and_takes_out():
 
 # ---- 6. key-driven forward -------------------------------------------------------------------------------------------
 
+def _key_slots(D):
+    """two batches of 1000 slots into the R = 257 rows of _fwd_case(D)"""
+    rng = np.random.default_rng(1000 + D)
+    slots = rng.integers(0, 257, (2, 1000))
+    slots[:, :8] = [5, 6, 5, 5, 6, 0, 256, 5]                    # runs of equal rows, the first and the last row
+    slots[1, 11] = -1                                            # an ignored lookup: a zero row
+    return slots
+
+
 @pytest.mark.parametrize("D", [16, 128, 272])
 def test_key_driven_forward(D):
     """nnz = 1000: not a whole segment; two batches; keys from the window presort, with and without hook_features; one
     ignored lookup, whose output row is zero.  The 16-bit outputs are 16-byte aligned and D % 8 == 0."""
     from cachedembedding_amd.functional import embedding_bag, presort_window
     c = _fwd_case(D)
-    rng = np.random.default_rng(1000 + D)
     R, nnz, P = c["R"], 1000, 2
     w = c["q"].cuda()
-    slots = rng.integers(0, R, (P, nnz))
-    slots[:, :8] = [5, 6, 5, 5, 6, 0, 256, 5]                    # runs of equal rows, the first and the last row
-    slots[1, 11] = -1                                            # an ignored lookup: a zero row
+    slots = _key_slots(D)
     sl = torch.from_numpy(slots).cuda()
     off = torch.arange(nnz + 1, dtype=torch.int32, device="cuda")
     for hook in (0, 4):
@@ -146,6 +152,38 @@ def test_key_driven_forward(D):
                 if b == 1:
                     zero = out.view(-1, D)[(11 % (nnz // hook)) * hook + 11 // (nnz // hook) if hook else 11]
                     assert not _bits(zero).any()
+
+
+@pytest.mark.parametrize("D", [16, 272])
+def test_q8_forward_is_the_fp32_forward_over_the_dequantized_rows(D):
+    """q8 is a row type of the two forward kernels, not kernels of its own: an fp32 table that holds dequantize_rows(q)
+    gives the same output, bit for bit, in every output type.  D = 16: one chunk per lane; D = 272: two, the lanes' third
+    masked.  One id per bag: the general forward, with and without hook_features, and the key-driven forward over the
+    window presort's keys (nnz = 1000, one ignored lookup).  (Bags of several ids are not compared bit for bit: with
+    per-sample weights the compiler contracts `sum + value * weight` differently for the two row types, in the separate
+    q8 kernels before this as well -- profiles/q8_row_type_refactor.md; test_general_forward bounds those.)"""
+    from cachedembedding_amd.functional import embedding_bag, presort_window
+    c = _fwd_case(D)
+    nb, R = c["nb"], c["R"]
+    tables = (c["q"].cuda(), c["deq"].cuda())
+
+    def same(ids, off, **kw):
+        for ot in OUT:
+            o8, o32 = (embedding_bag(ids, w, off, include_last_offset=True, output_dtype=ot, **kw) for w in tables)
+            assert o8.dtype == ot and o32.dtype == ot and o8.shape == o32.shape
+            assert torch.equal(_bits(o8), _bits(o32)), (NAMES[ot], kw.get("mode"), kw.get("hook_features"))
+
+    ids = torch.from_numpy(c["single"]).cuda()
+    for hook in (0, 5):
+        same(ids, torch.arange(nb + 1, device="cuda"), mode="sum", hook_features=hook)
+    slots = _key_slots(D)
+    sl = torch.from_numpy(slots).cuda()
+    nnz = slots.shape[1]
+    off = torch.arange(nnz + 1, dtype=torch.int32, device="cuda")
+    for hook in (0, 4):
+        keys = presort_window(sl, R, offsets=off, include_last_offset=True, hook_features=hook, identity_bags=True)
+        for b in range(len(slots)):
+            same(sl[b], off, mode="sum", hook_features=hook, presorted=keys[b])
 
 
 # ---- 7. through the cache --------------------------------------------------------------------------------------------
