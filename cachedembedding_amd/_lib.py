@@ -48,6 +48,7 @@ CE_CALL_PREPARE = 0
 CE_CALL_PRELOAD = 1
 CE_CALL_FLUSH = 2
 CE_Q8_HEADER_BYTES = 16
+CE_Q4_HEADER_BYTES = 16
 
 
 class CeCacheConfig(Structure):
@@ -183,6 +184,12 @@ SIGNATURES = {
     "ce_host_dequantize_q8": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int]),
     "ce_bag_forward_q8": (c_int, _BAG + _ACT + _STREAM),
     "ce_bag_forward_src_keys_q8": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    # the 4-bit row-wise quantized table (q4): rows of 16 + dim / 2 bytes; the q8 entries' argument lists
+    "ce_q4_row_bytes": (c_size_t, [c_int32]),
+    "ce_host_quantize_q4": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),
+    "ce_host_dequantize_q4": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int]),
+    "ce_bag_forward_q4": (c_int, _BAG + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_q4": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),
@@ -354,6 +361,48 @@ def refuse_q8(what: str, table_dtype) -> None:
 def q8_row_bytes(dim: int) -> int:
     check_q8_dim(dim)
     return CE_Q8_HEADER_BYTES + dim
+
+
+# the 4-bit row-wise quantized table (q4) is SPELLED torch.quint4x2 where a table_dtype is given; its storage is a
+# [N, 16 + D / 2] torch.uint8 tensor of whole rows (nothing allocates a quint4x2 tensor).  A uint8 tensor's width cannot
+# tell the two formats apart, so whoever holds q4 rows carries quant_bits = 4 beside them; torch.uint8 alone means q8.
+Q4 = torch.quint4x2
+
+
+def check_q4_dim(dim: int) -> None:
+    """a q4 row is 16 + dim / 2 bytes, whole 16-byte units with 16-byte aligned codes: refused before the GPU is asked for"""
+    if dim % 32 != 0 or dim < 32 or dim > 1024:
+        raise NotImplementedError(f"a q4 (torch.quint4x2) table needs embedding_dim % 32 == 0 and 32 <= embedding_dim <= "
+                                  f"1024 (got {dim})")
+
+
+def refuse_q4(what: str, table_dtype) -> None:
+    """refuse_q8 for a q4 table"""
+    if table_dtype == Q4:
+        raise NotImplementedError(f"{what} with a q4 (torch.quint4x2) table: a quantized table is served by a "
+                                  "single-process CachedEmbeddingBag (from_pretrained(..., table_dtype=torch.quint4x2) or "
+                                  "quantized(bits=4))")
+
+
+def refuse_quantized(what: str, table_dtype) -> None:
+    refuse_q8(what, table_dtype)
+    refuse_q4(what, table_dtype)
+
+
+def q4_row_bytes(dim: int) -> int:
+    check_q4_dim(dim)
+    return CE_Q4_HEADER_BYTES + dim // 2
+
+
+def quant_bits_of(table_dtype) -> int:
+    """8 for a q8, 4 for a q4 table_dtype, 0 for any other"""
+    return 8 if table_dtype == Q8 else (4 if table_dtype == Q4 else 0)
+
+
+def check_quant_bits(bits) -> int:
+    if bits not in (4, 8):
+        raise NotImplementedError(f"quantized rows of {bits!r} bits: 8 (q8) and 4 (q4) are implemented")
+    return bits
 
 
 def ptr(t) -> int:

@@ -52,8 +52,10 @@ class HostTable:
     """[N, D] fp32, bf16 or fp16 table in pinned, device-mapped host DRAM (CachedParamMgr.weight, A.1).  A 16-bit table
     needs D % 8 == 0 and D <= 1024: its rows are whole 16-byte units, the bytes of an fp32 [N, D / 2] table."""
 
-    def __init__(self, tensor: torch.Tensor, host_ptr: int, dev_ptr: int, registered: bool):
+    def __init__(self, tensor: torch.Tensor, host_ptr: int, dev_ptr: int, registered: bool, quant_bits: int = 0):
         self.tensor = tensor
+        # 8 / 4: the rows are q8 / q4 rows (torch.uint8 storage either way; uint8 alone means q8), 0: they are elements
+        self.quant_bits = quant_bits or (8 if tensor.dtype == _lib.Q8 else 0)
         self.host_ptr = host_ptr
         self.dev_ptr = dev_ptr
         self._fin = weakref.finalize(self, HostTable._release, host_ptr, registered)
@@ -70,9 +72,10 @@ class HostTable:
     def allocate(cls, num_embeddings: int, dim: int, threads=0, dtype: torch.dtype = torch.float32) -> "HostTable":
         if not isinstance(threads, int):              # allocate(N, D, dtype)
             threads, dtype = 0, threads
-        if dtype == _lib.Q8:
-            # an 8-bit row-wise quantized table: [N, 16 + D] uint8, whole rows (filled by quantize_from)
-            width = _lib.q8_row_bytes(dim)
+        if dtype == _lib.Q8 or dtype == _lib.Q4:
+            # a row-wise quantized table: [N, 16 + D] (q8) or [N, 16 + D / 2] (q4, spelled torch.quint4x2) uint8, whole
+            # rows (filled by quantize_from)
+            width = _lib.q4_row_bytes(dim) if dtype == _lib.Q4 else _lib.q8_row_bytes(dim)
             _lib.require_gpu()
             hp, dp = ctypes.c_void_p(), ctypes.c_void_p()
             check(lib.ce_host_alloc(num_embeddings * width, threads or _default_threads(), ctypes.byref(hp),
@@ -80,7 +83,8 @@ class HostTable:
             carr = (ctypes.c_uint8 * (num_embeddings * width)).from_address(hp.value)
             carr._ce_block = _PinnedBlock(hp.value)
             t = torch.from_numpy(np.ctypeslib.as_array(carr))
-            return cls(t.view(num_embeddings, width), hp.value, dp.value, registered=False)
+            return cls(t.view(num_embeddings, width), hp.value, dp.value, registered=False,
+                       quant_bits=_lib.quant_bits_of(dtype))
         w16 = _lib.table_code(dtype) != _lib.CE_ACT_F32
         if w16:
             _lib.check_w16_dim(dim)
@@ -98,9 +102,12 @@ class HostTable:
         return cls(t.view(num_embeddings, dim), hp.value, dp.value, registered=False)
 
     @classmethod
-    def wrap(cls, weight: torch.Tensor) -> "HostTable":
-        """Pin + map a tensor the caller owns (the `_weight` / from_pretrained path)."""
-        if weight.dtype == _lib.Q8:
+    def wrap(cls, weight: torch.Tensor, quant_bits: int = 8) -> "HostTable":
+        """Pin + map a tensor the caller owns (the `_weight` / from_pretrained path).  quant_bits: looked at for a
+        torch.uint8 tensor only -- 8: [N, 16 + D] q8 rows, 4: [N, 16 + D / 2] q4 rows."""
+        if weight.dtype == _lib.Q8 and _lib.check_quant_bits(quant_bits) == 4:
+            _lib.check_q4_dim(2 * (weight.shape[-1] - _lib.CE_Q4_HEADER_BYTES))
+        elif weight.dtype == _lib.Q8:
             _lib.check_q8_dim(weight.shape[-1] - _lib.CE_Q8_HEADER_BYTES)      # [N, 16 + D] uint8: whole q8 rows
         elif _lib.table_code(weight.dtype) != _lib.CE_ACT_F32:
             _lib.check_w16_dim(weight.shape[-1])
@@ -109,26 +116,34 @@ class HostTable:
         dp = ctypes.c_void_p()
         check(lib.ce_host_register(ctypes.c_void_p(weight.data_ptr()), weight.numel() * weight.element_size(),
                                    ctypes.byref(dp)))
-        return cls(weight, weight.data_ptr(), dp.value, registered=True)
+        return cls(weight, weight.data_ptr(), dp.value, registered=True,
+                   quant_bits=quant_bits if weight.dtype == _lib.Q8 else 0)
 
     def quantize_from(self, src, threads: int = 0) -> "HostTable":
         """Fill this q8 table ([N, 16 + D] uint8) with the quantized rows of `src`: a HostTable or a CPU tensor, [N, D]
-        fp32 / bf16 / fp16 (ce_host_quantize_q8; a row holding a NaN or an infinity raises).  Host work only."""
+        fp32 / bf16 / fp16 (ce_host_quantize_q8; a row holding a NaN or an infinity raises).  Host work only.  A q4
+        table ([N, 16 + D / 2] uint8, quant_bits == 4) is filled by ce_host_quantize_q4."""
         if self.tensor.dtype != _lib.Q8:
             raise NotImplementedError("quantize_from fills a q8 (torch.uint8) table")
         t = src.tensor if isinstance(src, HostTable) else src
-        dim = self.tensor.shape[1] - _lib.CE_Q8_HEADER_BYTES
+        q4 = self.quant_bits == 4
+        width = self.tensor.shape[1]
+        dim = 2 * (width - _lib.CE_Q4_HEADER_BYTES) if q4 else width - _lib.CE_Q8_HEADER_BYTES
         if t.dtype not in _lib.ACT_DTYPES:
             raise NotImplementedError(f"rows of dtype {t.dtype} cannot be quantized: torch.float32, torch.bfloat16 and "
                                       "torch.float16 are implemented")
         if t.dim() != 2 or tuple(t.shape) != (self.tensor.shape[0], dim):
             raise ValueError(f"quantize_from needs [{self.tensor.shape[0]}, {dim}] rows (got {tuple(t.shape)})")
         assert t.device.type == "cpu" and t.is_contiguous()
-        check(lib.ce_host_quantize_q8(ctypes.c_void_p(t.data_ptr()), _lib.ACT_DTYPES[t.dtype], t.shape[0], dim,
-                                      ctypes.c_void_p(self.host_ptr), threads or _default_threads()))
+        quantize = lib.ce_host_quantize_q4 if q4 else lib.ce_host_quantize_q8
+        check(quantize(ctypes.c_void_p(t.data_ptr()), _lib.ACT_DTYPES[t.dtype], t.shape[0], dim,
+                       ctypes.c_void_p(self.host_ptr), threads or _default_threads()))
         return self
 
     def fill_uniform_(self, lo: float, hi: float, seed: int, threads: int = 0):
+        if self.quant_bits == 4:
+            raise NotImplementedError("a q4 (torch.quint4x2) table is built from trained rows (quantize_from), not "
+                                      "filled")
         if self.tensor.dtype == _lib.Q8:
             raise NotImplementedError("a q8 (torch.uint8) table is built from trained rows (quantize_from), not filled")
         if self.tensor.dtype != torch.float32:
@@ -166,12 +181,15 @@ class CachedParamMgr(torch.nn.Module):
         self._table = weight if isinstance(weight, HostTable) else HostTable.wrap(weight)
         self._weight = self._table.tensor
         self.num_embeddings, self._row_width = self._weight.shape
-        self.table_dtype = self._weight.dtype
-        q8 = self.table_dtype == _lib.Q8
-        # a q8 table's rows are 16 + D bytes wide; embedding_dim keeps meaning D
-        self.embedding_dim = self._row_width - _lib.CE_Q8_HEADER_BYTES if q8 else self._row_width
+        # (a q4 table reports torch.quint4x2; its storage, like the cache's, is torch.uint8)
+        self.quant_bits = self._table.quant_bits
+        self.table_dtype = _lib.Q4 if self.quant_bits == 4 else self._weight.dtype
+        q8 = self.quant_bits != 0
+        # a q8 table's rows are 16 + D bytes wide, a q4 table's 16 + D / 2; embedding_dim keeps meaning D
+        self.embedding_dim = (2 * (self._row_width - _lib.CE_Q4_HEADER_BYTES) if self.quant_bits == 4
+                              else self._row_width - _lib.CE_Q8_HEADER_BYTES) if q8 else self._row_width
         # what the library is told a row is: fp32 elements (a 16-bit row of D elements = D / 2 of them, a q8 row
-        # (16 + D) / 4 of them, bit for bit)
+        # (16 + D) / 4 and a q4 row (16 + D / 2) / 4 of them, bit for bit)
         self._lib_dim = self._row_width // 4 if q8 else (
             self.embedding_dim // 2 if self.table_dtype in _lib.W16_DTYPES else self.embedding_dim)
         self.cuda_row_num = int(cuda_row_num)
@@ -185,9 +203,9 @@ class CachedParamMgr(torch.nn.Module):
         assert N < 2 ** 31 - 1, "row ids are int32 on the device"
         dev = self.device
         # the only trainable parameter the optimiser sees (A.1)
-        # (a q8 cache: [C, 16 + D] uint8, never trained)
+        # (a q8 cache: [C, 16 + D] uint8, a q4 cache: [C, 16 + D / 2] uint8; never trained)
         self.cuda_cached_weight = torch.nn.Parameter(
-            torch.zeros(C, self._row_width, device=dev, dtype=self.table_dtype), requires_grad=not q8)
+            torch.zeros(C, self._row_width, device=dev, dtype=self._weight.dtype), requires_grad=not q8)
         # DATASET+freq re-rank needs idx_map; identity otherwise (kept None = no array, no gather)
         self._idx_map: Optional[torch.Tensor] = None
         if use_idx_map:

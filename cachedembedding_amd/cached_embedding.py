@@ -20,6 +20,12 @@ from .functional import FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_
 def _refuse_q8_update(module, what: str, lr) -> None:
     if lr is not None and getattr(module, "table_dtype", None) == _lib.Q8:
         raise NotImplementedError(f"{what}(lr) with a q8 (torch.uint8) table: a quantized table is never updated")
+    if lr is not None and getattr(module, "table_dtype", None) == _lib.Q4:
+        raise NotImplementedError(f"{what}(lr) with a q4 (torch.quint4x2) table: a quantized table is never updated")
+
+
+def _quant_name(bits: int) -> str:
+    return "q4 (torch.quint4x2)" if bits == 4 else "q8 (torch.uint8)"
 
 
 class CachedEmbeddingBag(nn.Module):
@@ -45,20 +51,24 @@ class CachedEmbeddingBag(nn.Module):
         # table_dtype=torch.uint8 (addition): an 8-bit row-wise quantized table (q8: rows of 16 + D bytes)
         # for evaluation and serving -- built from trained rows (from_pretrained(..., table_dtype=torch.uint8) or
         # quantized() of a trained module: _table / _idx_map are theirs), never updated; the output defaults to fp32.
-        q8 = table_dtype == _lib.Q8
-        self.table_dtype = _lib.Q8 if q8 else (
+        # table_dtype=torch.quint4x2 (addition): the same with 4-bit codes (q4: rows of 16 + D / 2 bytes, DESIGN.md
+        # 3.10; quantized(bits=4)).  torch.quint4x2 only spells the format: host table and cache are torch.uint8.
+        bits = _lib.quant_bits_of(table_dtype)
+        q8 = bits != 0                                      # a quantized table, of either width
+        self.table_dtype = table_dtype if q8 else (
             torch.float32 if _lib.table_code(table_dtype) == _lib.CE_ACT_F32 else table_dtype)
         w16 = self.table_dtype in _lib.W16_DTYPES
         if q8:
-            _lib.check_q8_dim(embedding_dim)
+            (_lib.check_q4_dim if bits == 4 else _lib.check_q8_dim)(embedding_dim)
             for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
                              ("sparse=True", bool(sparse))):
                 if on:
-                    raise NotImplementedError(f"{what} with a q8 (torch.uint8) table: it is forward only")
+                    raise NotImplementedError(f"{what} with a {_quant_name(bits)} table: it is forward only")
             if _weight is None and _table is None:
-                raise NotImplementedError("a q8 (torch.uint8) table is built from trained rows, it cannot be "
+                raise NotImplementedError(f"a {_quant_name(bits)} table is built from trained rows, it cannot be "
                                           "initialised: CachedEmbeddingBag.from_pretrained(embeddings, "
-                                          "table_dtype=torch.uint8) or quantized() of a trained module")
+                                          f"table_dtype={self.table_dtype}) or quantized({'bits=4' if bits == 4 else ''}) "
+                                          "of a trained module")
         if w16:
             _lib.check_w16_dim(embedding_dim)
             for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
@@ -94,17 +104,20 @@ class CachedEmbeddingBag(nn.Module):
 
         if _table is not None:
             table = _table
-            assert table.tensor.dtype == self.table_dtype and table.tensor.shape[0] == num_embeddings
+            assert table.tensor.dtype == (torch.uint8 if q8 else self.table_dtype) and table.quant_bits == bits \
+                and table.tensor.shape[0] == num_embeddings
         elif q8:
             w = _weight.detach()
-            if w.dtype == _lib.Q8:                          # already q8 rows: pinned in place
-                assert tuple(w.shape) == (num_embeddings, _lib.q8_row_bytes(embedding_dim))
-                table = HostTable.wrap(w if w.device.type == "cpu" and w.is_contiguous() else w.cpu().contiguous())
+            if w.dtype == torch.uint8:                      # already q8 / q4 rows: pinned in place
+                width = _lib.q4_row_bytes(embedding_dim) if bits == 4 else _lib.q8_row_bytes(embedding_dim)
+                assert tuple(w.shape) == (num_embeddings, width)
+                table = HostTable.wrap(w if w.device.type == "cpu" and w.is_contiguous() else w.cpu().contiguous(),
+                                       quant_bits=bits)
             else:
                 assert tuple(w.shape) == (num_embeddings, embedding_dim)
                 if w.dtype not in _lib.ACT_DTYPES:
                     w = w.float()
-                table = HostTable.allocate(num_embeddings, embedding_dim, dtype=_lib.Q8).quantize_from(
+                table = HostTable.allocate(num_embeddings, embedding_dim, dtype=self.table_dtype).quantize_from(
                     w.cpu().contiguous())
         elif _weight is None:
             table = HostTable.allocate(num_embeddings, embedding_dim, dtype=self.table_dtype)
@@ -247,7 +260,7 @@ class CachedEmbeddingBag(nn.Module):
                             self.norm_type, self.scale_grad_by_freq, self.mode, self.sparse, per_sample_weights,
                             self.include_last_offset, None, hook_features=hook_features,
                             fused_sgd=self._fused(), presorted=presorted, masked_indices=masked, out=out,
-                            output_dtype=self.output_dtype)
+                            output_dtype=self.output_dtype, quant_bits=4 if self.table_dtype == _lib.Q4 else 8)
         if shape_hook is not None:
             out = shape_hook(out)
         return out
@@ -280,45 +293,50 @@ class CachedEmbeddingBag(nn.Module):
     @classmethod
     def from_pretrained(cls, embeddings: torch.Tensor, freeze: bool = True, **kwargs) -> "CachedEmbeddingBag":
         rows, cols = embeddings.shape
-        if kwargs.get("table_dtype") == _lib.Q8:
+        bits = _lib.quant_bits_of(kwargs.get("table_dtype"))
+        if bits:
             # table_dtype=torch.uint8: the fp32 / bf16 / fp16 rows are quantized (functional.quantize_rows), or q8 rows
-            # ([rows, 16 + D] uint8) are taken as they are; the module is eval-only
+            # ([rows, 16 + D] uint8) are taken as they are; the module is eval-only.  table_dtype=torch.quint4x2: the
+            # same with q4 rows -- a uint8 tensor is then taken as [rows, 16 + D / 2] q4 rows
             if not freeze:
-                raise NotImplementedError("from_pretrained(freeze=False) with a q8 (torch.uint8) table: a quantized "
+                raise NotImplementedError(f"from_pretrained(freeze=False) with a {_quant_name(bits)} table: a quantized "
                                           "table is never updated")
-            if embeddings.dtype == _lib.Q8:
-                cols -= _lib.CE_Q8_HEADER_BYTES
+            if embeddings.dtype == torch.uint8:
+                cols = 2 * (cols - _lib.CE_Q4_HEADER_BYTES) if bits == 4 else cols - _lib.CE_Q8_HEADER_BYTES
             return cls(rows, cols, _weight=embeddings, **kwargs)
         m = cls(rows, cols, _weight=embeddings, **kwargs)
         m.cache_weight_mgr.cuda_cached_weight.requires_grad_(not freeze)
         return m
 
-    def quantized(self, **overrides) -> "CachedEmbeddingBag":
+    def quantized(self, bits: int = 8, **overrides) -> "CachedEmbeddingBag":
         """An eval-only module over the 8-bit row-wise quantized (q8) copy of this module's table: this module is
         flushed, its host table is quantized row by row -- in row space, so the id -> row map (idx_map) carries over --
         into a new pinned table, and the new module has this one's mode, include_last_offset, padding_idx, eviction
         strategy, cuda_row_num, output dtype and idx_map.  overrides: cuda_row_num (a q8 row of D elements is 16 + D
         bytes: the same HBM holds more rows), output_dtype, warmup_ratio, buffer_size, strict.  This module is left as it
-        is and trains on."""
+        is and trains on.  bits=4: the 4-bit (q4) copy, rows of 16 + D / 2 bytes."""
         if self.table_dtype == _lib.Q8:
             raise NotImplementedError("quantized() of a q8 (torch.uint8) module: it is quantized already")
+        if self.table_dtype == _lib.Q4:
+            raise NotImplementedError("quantized() of a q4 (torch.quint4x2) module: it is quantized already")
+        dtype = _lib.Q4 if _lib.check_quant_bits(bits) == 4 else _lib.Q8
         if getattr(self, "world_size", 1) > 1:
-            _lib.refuse_q8(f"{type(self).__name__}.quantized() on {self.world_size} ranks", _lib.Q8)
+            _lib.refuse_quantized(f"{type(self).__name__}.quantized() on {self.world_size} ranks", dtype)
         bad = set(overrides) - {"cuda_row_num", "output_dtype", "warmup_ratio", "buffer_size", "strict"}
         if bad:
             raise TypeError(f"quantized() got unexpected overrides {sorted(bad)}")
         for what, on in (("mode='max'", self.mode == "max"), ("max_norm", self.max_norm is not None)):
             if on:
-                raise NotImplementedError(f"{what} with a q8 (torch.uint8) table: it is forward only")
-        _lib.check_q8_dim(self.embedding_dim)
+                raise NotImplementedError(f"{what} with a {_quant_name(bits)} table: it is forward only")
+        (_lib.check_q4_dim if bits == 4 else _lib.check_q8_dim)(self.embedding_dim)
         mgr = self.cache_weight_mgr
         self.flush()
         src = self.weight                                   # (waits for the write-backs of the worker transport)
-        table = HostTable.allocate(self.num_embeddings, self.embedding_dim, dtype=_lib.Q8).quantize_from(src)
+        table = HostTable.allocate(self.num_embeddings, self.embedding_dim, dtype=dtype).quantize_from(src)
         kw = dict(cuda_row_num=self.cuda_row_num, output_dtype=self.output_dtype, warmup_ratio=0.7,
                   buffer_size=mgr.buffer_size, strict=mgr.strict)
         kw.update(overrides)
         return CachedEmbeddingBag(self.num_embeddings, self.embedding_dim, padding_idx=self.padding_idx, mode=self.mode,
                                   include_last_offset=self.include_last_offset, device=mgr.device,
-                                  evict_strategy=self.evict_strategy, table_dtype=_lib.Q8, _table=table,
+                                  evict_strategy=self.evict_strategy, table_dtype=dtype, _table=table,
                                   _idx_map=mgr._idx_map, **kw)

@@ -22,8 +22,8 @@
 // The sums and the updates are fp32; the forward's output and the backward's grad_out have the activation
 // type AT (fp32, bf16, fp16: Act<AT, VT> in ce_common.h) the four bag kernels are templated on.  The table is fp32, or
 // -- the two forwards only (WT, read through Row<WT, VT>) -- bf16 / fp16 (ce_bag_forward_w16 / _src_keys_w16; its update
-// is ce_bag_adagrad.hip's) or 8-bit row-wise quantized (Q8; ce_bag_forward_q8 / _src_keys_q8: evaluation and serving
-// only, no backward).
+// is ce_bag_adagrad.hip's) or 8-bit / 4-bit row-wise quantized (Q8, Q4; ce_bag_forward_q8 / _src_keys_q8 and the _q4
+// pair: evaluation and serving only, no backward).
 #include <algorithm>
 
 #include "ce_common.h"
@@ -148,11 +148,35 @@ template <> struct Row<Q8, f32x4> {
   }
 };
 
+// q4 rows (include/ce_api.h): 8 + rowlen uint16 -- q8's 16-byte header, then 16 bits of 4 codes per chunk, nibble k the
+// chunk's element k.  A lane holds them in a dword; the even and the odd nibbles are masked into two bytes each
+// (c & 0x0f0f, (c >> 4) & 0x0f0f), so the four conversions are the byte forms q8 uses, then ONE explicit fma each.
+// An 80-byte row (D = 128) lies in one 128-byte line at 4 of its 8 possible offsets and in two otherwise.
+// Every lane loads its own 2 bytes (global_load_ushort).  That is not slower than q8's dword per lane at any measured
+// shape, and the alternative that was built -- the lanes gl and gl ^ 1 load the aligned dword they share and shift
+// their half out -- took 1.2-1.8 times q8's time (profiles/q4_table.md); it is not in the tree.
+struct Q4 {};
+constexpr int kTableQ4 = 4;   // like kTableQ8
+template <> struct Row<Q4, f32x4> {
+  typedef uint16_t V;
+  typedef uint32_t Held;  // the chunk's 16 bits of codes in the low half; value() does not look at the high half
+  typedef f32x2 Hdr;
+  static constexpr int kHeader = CE_Q4_HEADER_BYTES / 2;
+  static __device__ __forceinline__ Held zero() { return 0u; }
+  static __device__ __forceinline__ Held up(V a) { return a; }
+  static __device__ __forceinline__ Hdr header(const V* row) { return *(const Hdr*)row; }
+  static __device__ __forceinline__ f32x4 value(Held c, Hdr sb) {
+    const uint32_t e = c & 0x0f0fu, o = (c >> 4) & 0x0f0fu;
+    return f32x4{__builtin_fmaf((float)(e & 0xffu), sb.x, sb.y), __builtin_fmaf((float)(o & 0xffu), sb.x, sb.y),
+                 __builtin_fmaf((float)(e >> 8), sb.x, sb.y), __builtin_fmaf((float)(o >> 8), sb.x, sb.y)};
+  }
+};
+
 // STAGE: tiles with multi-id bags stage their indices in LDS (32 KB per workgroup); the launcher picks the
 // LDS-free variant when nnz == num_bags (single-id batches) so occupancy is set by registers alone.
 // AT: the output's element type (Act<AT, VT>, ce_common.h): sums stay fp32, the store rounds.
 // WT: the table's row type (Row<WT, VT>: float; bf16 / fp16 with f32x4 lanes, a lane's chunk is then 8 bytes of the row;
-// Q8 with f32x4 lanes).  A row that takes no part is held as zeros: chunks and header.
+// Q8 and Q4 with f32x4 lanes).  A row that takes no part is held as zeros: chunks and header.
 template <typename VT, int NCH, bool STAGE, int U, typename AT, typename WT = float>
 __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   using A = Act<AT, VT>;
@@ -1067,7 +1091,7 @@ __global__ __launch_bounds__(256) void k_bag_bwd_stream(BagParams p, int64_t tot
 // AT: the output's element type; the row is rounded once per store, so `prev` stays the fp32 row.
 // PAIR (16-bit AT, f32x4 lanes): the stores of two keys are ONE 16-byte store per lane (see u32x4 above).
 // WT: the table's row type (a 16-bit table whose type differs from AT: the row is up-converted on load; Q8: the row is
-// dequantized ONCE per run, `prev` is the fp32 row).  PAIR is never instantiated for Q8.
+// dequantized ONCE per run, `prev` is the fp32 row; Q4 likewise).  PAIR is never instantiated for Q8 and Q4.
 template <typename VT, int NCH, int R, typename AT, bool PAIR = false, typename WT = float>
 __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t total) {      // 4 waves per SIMD: <= 128 VGPRs
   using A = Act<AT, VT>;
@@ -1265,10 +1289,11 @@ static int fill_params_keys(BagParams& p, RowGeom& r, int32_t dim, bool aligned,
 template <typename F> static void for_lanes_act(const RowGeom& r, int act, F&& f) {
   for_lanes(r.vec, r.nch, [&](auto l) { for_act(act, [&](auto a) { f(l, a); }); });
 }
-// ... and with the table's type (the two forwards): f(Lanes<VT, N>, ActTag<WT>, ActTag<AT>); q8: vector lanes only
+// ... and with the table's type (the two forwards): f(Lanes<VT, N>, ActTag<WT>, ActTag<AT>); q8, q4: vector lanes only
 template <typename F> static void for_table_act(int weight_dtype, const RowGeom& r, int act, F&& f) {
   auto acts = [&](auto l, auto w) { for_act(act, [&](auto a) { f(l, w, a); }); };
   if (weight_dtype == kTableQ8) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<Q8>{}); });
+  else if (weight_dtype == kTableQ4) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<Q4>{}); });
   else for_table(weight_dtype, r, acts);
 }
 
@@ -1329,8 +1354,8 @@ static int launch_bwd_scatter(BagParams& p, const RowGeom& r, int act, const flo
   return CE_OK;
 }
 
-// The gather-shaped forward over filled BagParams.  weight_dtype: CE_ACT_F32, or a 16-bit table's type or kTableQ8 --
-// the same kernel with the row type WT; only the vector lane shape exists there.
+// The gather-shaped forward over filled BagParams.  weight_dtype: CE_ACT_F32, or a 16-bit table's type, kTableQ8 or
+// kTableQ4 -- the same kernel with the row type WT; only the vector lane shape exists there.
 static int launch_fwd(BagParams& p, const RowGeom& r, const void* weight, int weight_dtype, int64_t num_rows, void* out,
                       int act, hipStream_t s) {
   p.weight = (const float*)weight;
@@ -1353,7 +1378,7 @@ static int launch_fwd(BagParams& p, const RowGeom& r, const void* weight, int we
 
 // The key-driven forward.  An fp32 table has the PAIR form for a 16-bit output; a 16-bit table only the converting
 // instantiation (WT != AT: exact up-conversion, one rounding on the store) -- equal types never get here, see
-// ce_bag_forward_src_keys_w16.  A q8 table (kTableQ8) always converts: it takes that arm too.
+// ce_bag_forward_src_keys_w16.  A q8 or q4 table (kTableQ8, kTableQ4) always converts: it takes that arm too.
 static int launch_fwd_keys(const void* weight, int weight_dtype, int64_t num_rows, int32_t dim, bool aligned, int64_t nnz,
                            const uint64_t* src_keys, void* out, int act, hipStream_t s) {
   BagParams p{};
@@ -1705,6 +1730,44 @@ extern "C" int ce_bag_forward_src_keys_q8(const void* weight, int64_t num_rows, 
   CE_REQUIRE_ROWS(num_rows);
   CE_REQUIRE_Q8_ALIGNED(weight, out, act_dtype);
   return launch_fwd_keys(weight, kTableQ8, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
+}
+
+// ---- forward from a q4 table (dim % 32 == 0, 32 <= dim <= 1024): the q8 entries with the row type Q4
+#define CE_REQUIRE_Q4_DIM(dim)                                                         \
+  CE_REQUIRE(ce_q4_row_bytes(dim) != 0, CE_ERR_UNSUPPORTED,                            \
+             "a q4 table needs dim %% 32 == 0 and 32 <= dim <= 1024 (got %d)", (int)(dim))
+#define CE_REQUIRE_Q4_ALIGNED(weight, out, act)                                        \
+  CE_REQUIRE(al16(weight) && act_aligned(out, act), CE_ERR_INVALID,                    \
+             "a q4 table must be 16-byte aligned and its output on the vector boundary")
+
+extern "C" int ce_bag_forward_q4(const void* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                 const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                 int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                 int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_Q4_DIM(dim);
+  if (num_bags == 0) return CE_OK;
+  CE_REQUIRE(weight && out && (indices || nnz == 0), CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(offsets || num_bags == nnz, CE_ERR_INVALID,
+             "offsets == NULL states one id per bag (offsets = arange): num_bags must equal nnz");
+  CE_REQUIRE_Q4_ALIGNED(weight, out, act_dtype);
+  BagParams p{};
+  RowGeom r;
+  int rc = fill_params(p, r, dim, true, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                       per_sample_weights, mode, hook_features);
+  if (rc) return rc;
+  return launch_fwd(p, r, weight, kTableQ4, num_rows, out, act_dtype, (hipStream_t)stream);
+}
+
+extern "C" int ce_bag_forward_src_keys_q4(const void* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                          const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_Q4_DIM(dim);
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE_ROWS(num_rows);
+  CE_REQUIRE_Q4_ALIGNED(weight, out, act_dtype);
+  return launch_fwd_keys(weight, kTableQ4, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
 }
 
 extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : padded_keys(nnz); }

@@ -288,13 +288,16 @@ class _BagFn(torch.autograd.Function):
         return gw, None, None, gpsw, None, None, None, None, None, None, None, None, None, None
 
 
-def _forward_q8(weight, indices, offsets, psw, mode, include_last, hook_features, presorted, out, out_dtype):
-    """The forward over an 8-bit row-wise quantized table (ce_bag_forward_q8 / ce_bag_forward_src_keys_q8): weight is
-    [R, 16 + D] uint8.  No autograd node: there is no backward, the output never requires grad."""
+def _forward_q8(weight, indices, offsets, psw, mode, include_last, hook_features, presorted, out, out_dtype, bits=8):
+    """The forward over a row-wise quantized table: weight is [R, 16 + D] uint8 (q8: ce_bag_forward_q8 /
+    ce_bag_forward_src_keys_q8) or, with bits=4, [R, 16 + D / 2] uint8 (q4: the _q4 pair).  No autograd node: there is
+    no backward, the output never requires grad."""
     _lib.require_gpu()
     assert weight.is_cuda and weight.is_contiguous()
     num_bags = offsets.numel() - 1 if include_last else offsets.numel()
-    dim = weight.shape[1] - _lib.CE_Q8_HEADER_BYTES
+    dim = _quant_dim(weight.shape[1], bits)
+    fwd, fwd_keys = (lib.ce_bag_forward_q4, lib.ce_bag_forward_src_keys_q4) if bits == 4 else \
+        (lib.ce_bag_forward_q8, lib.ce_bag_forward_src_keys_q8)
     shape = (num_bags // hook_features, hook_features, dim) if hook_features else (num_bags, dim)
     if out is not None:
         if tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous() or out.device != weight.device:
@@ -308,44 +311,56 @@ def _forward_q8(weight, indices, offsets, psw, mode, include_last, hook_features
     if psw is not None:
         psw = psw.detach()
     if from_keys:
-        check(lib.ce_bag_forward_src_keys_q8(ptr(weight), weight.shape[0], dim, indices.numel(), ptr(presorted.keys),
-                                             ptr(out), act, stream_ptr()))
+        check(fwd_keys(ptr(weight), weight.shape[0], dim, indices.numel(), ptr(presorted.keys), ptr(out), act,
+                       stream_ptr()))
     else:
-        check(lib.ce_bag_forward_q8(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(), ptr(offsets),
-                                    int(offsets.dtype == torch.int64), num_bags, int(include_last), ptr(psw), mode,
-                                    hook_features, ptr(out), act, stream_ptr()))
+        check(fwd(ptr(weight), weight.shape[0], dim, ptr(indices), indices.numel(), ptr(offsets),
+                  int(offsets.dtype == torch.int64), num_bags, int(include_last), ptr(psw), mode, hook_features, ptr(out),
+                  act, stream_ptr()))
     return out
 
 
-def _q8_host_src(t: torch.Tensor):
+def _quant_dim(width: int, bits: int) -> int:
+    """elements of a quantized row that is `width` bytes wide"""
+    return 2 * (width - _lib.CE_Q4_HEADER_BYTES) if bits == 4 else width - _lib.CE_Q8_HEADER_BYTES
+
+
+def _q8_host_src(t: torch.Tensor, bits: int = 8):
     if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in _lib.ACT_DTYPES:
         raise NotImplementedError("quantize_rows takes a 2-D torch.float32, torch.bfloat16 or torch.float16 tensor")
-    _lib.check_q8_dim(t.shape[1])
+    (_lib.check_q4_dim if bits == 4 else _lib.check_q8_dim)(t.shape[1])
     return t.detach().cpu().contiguous()
 
 
-def quantize_rows(t: torch.Tensor, threads: int = 0) -> torch.Tensor:
+def quantize_rows(t: torch.Tensor, threads: int = 0, bits: int = 8) -> torch.Tensor:
     """[N, D] fp32 / bf16 / fp16 rows (any device; quantized on the host) -> [N, 16 + D] uint8 q8 rows on the CPU
     (ce_host_quantize_q8: scale = (max - min) / 255, bias = min, code = rint((x - min) / scale)).  A row holding a NaN
-    or an infinity raises (CE_ERR_INVALID names the first one).  Needs no GPU."""
-    src = _q8_host_src(t)
+    or an infinity raises (CE_ERR_INVALID names the first one).  Needs no GPU.
+    bits=4: [N, 16 + D / 2] uint8 q4 rows (ce_host_quantize_q4: 15 in place of 255, two codes per byte)."""
+    src = _q8_host_src(t, _lib.check_quant_bits(bits))
     n, dim = src.shape
-    q = torch.empty(n, _lib.q8_row_bytes(dim), dtype=torch.uint8)
-    check(lib.ce_host_quantize_q8(ptr(src), _lib.ACT_DTYPES[src.dtype], n, dim, ptr(q), threads or _q8_threads()))
+    row_bytes, quantize = (_lib.q4_row_bytes, lib.ce_host_quantize_q4) if bits == 4 else \
+        (_lib.q8_row_bytes, lib.ce_host_quantize_q8)
+    q = torch.empty(n, row_bytes(dim), dtype=torch.uint8)
+    check(quantize(ptr(src), _lib.ACT_DTYPES[src.dtype], n, dim, ptr(q), threads or _q8_threads()))
     return q
 
 
-def dequantize_rows(q: torch.Tensor, dim: Optional[int] = None, threads: int = 0) -> torch.Tensor:
-    """[N, 16 + dim] uint8 q8 rows -> [N, dim] fp32 on the CPU: fmaf(code, scale, bias), the value the kernels use"""
+def dequantize_rows(q: torch.Tensor, dim: Optional[int] = None, threads: int = 0, bits: int = 8) -> torch.Tensor:
+    """[N, 16 + dim] uint8 q8 rows -> [N, dim] fp32 on the CPU: fmaf(code, scale, bias), the value the kernels use.
+    bits=4: [N, 16 + dim / 2] uint8 q4 rows (a uint8 tensor's width cannot tell the two apart)."""
+    name = "q4" if _lib.check_quant_bits(bits) == 4 else "q8"
+    row_bytes, dequantize = (_lib.q4_row_bytes, lib.ce_host_dequantize_q4) if bits == 4 else \
+        (_lib.q8_row_bytes, lib.ce_host_dequantize_q8)
     if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.dtype != _lib.Q8:
-        raise NotImplementedError("dequantize_rows takes a 2-D torch.uint8 tensor of q8 rows")
+        raise NotImplementedError(f"dequantize_rows takes a 2-D torch.uint8 tensor of {name} rows")
     if dim is None:
-        dim = q.shape[1] - _lib.CE_Q8_HEADER_BYTES
-    if q.shape[1] != _lib.q8_row_bytes(dim):
-        raise ValueError(f"q8 rows of dim {dim} are {_lib.CE_Q8_HEADER_BYTES + dim} bytes wide (got {q.shape[1]})")
+        dim = _quant_dim(q.shape[1], bits)
+    if q.shape[1] != row_bytes(dim):
+        raise ValueError(f"{name} rows of dim {dim} are {row_bytes(dim)} bytes wide (got {q.shape[1]})")
     src = q.detach().cpu().contiguous()
     out = torch.empty(src.shape[0], dim, dtype=torch.float32)
-    check(lib.ce_host_dequantize_q8(ptr(src), src.shape[0], dim, ptr(out), threads or _q8_threads()))
+    check(dequantize(ptr(src), src.shape[0], dim, ptr(out), threads or _q8_threads()))
     return out
 
 
@@ -640,7 +655,10 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                   include_last_offset: bool = False, padding_idx: Optional[int] = None, *,
                   hook_features: int = 0, fused_sgd: Union[FusedSGD, FusedRowwiseAdagrad, None] = None,
                   presorted: Union[torch.Tensor, SrcKeys, None] = None, masked_indices: bool = False,
-                  out: Optional[torch.Tensor] = None, output_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, output_dtype: Optional[torch.dtype] = None,
+                  quant_bits: int = 8) -> torch.Tensor:
+    # quant_bits: looked at for a torch.uint8 weight only -- 8: q8 rows [R, 16 + D]; 4: q4 rows [R, 16 + D / 2] (a uint8
+    # tensor's width cannot tell the two apart)
     # out: write the pooled output into this tensor (contiguous, of the output dtype and the shape the call would
     # allocate) and return it --
     # a static output buffer for steps replayed from a hipGraph, possibly one chosen by pick_fast_buffer
@@ -650,11 +668,12 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
     q8 = weight.dtype == _lib.Q8
     if q8:
-        # an 8-bit row-wise quantized table ([R, 16 + D] uint8 rows): forward only, the output defaults to fp32.  What it
-        # does not take is refused here, before any kernel has run.
+        # a row-wise quantized table ([R, 16 + D] uint8 q8 rows, or [R, 16 + D / 2] q4 rows with quant_bits=4): forward
+        # only, the output defaults to fp32.  What it does not take is refused here, before any kernel has run.
+        name = "q4 (torch.quint4x2)" if _lib.check_quant_bits(quant_bits) == 4 else "q8 (torch.uint8)"
         if weight.dim() != 2:
-            raise ValueError("a q8 (torch.uint8) weight is a [rows, 16 + embedding_dim] tensor")
-        _lib.check_q8_dim(weight.shape[1] - _lib.CE_Q8_HEADER_BYTES)
+            raise ValueError(f"a {name} weight is a [rows, 16 + embedding_dim{' / 2' if quant_bits == 4 else ''}] tensor")
+        (_lib.check_q4_dim if quant_bits == 4 else _lib.check_q8_dim)(_quant_dim(weight.shape[1], quant_bits))
         for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
                          ("a fused SGD / row-wise Adagrad update (a quantized table is never updated)",
                           fused_sgd is not None and fused_sgd.lr is not None),
@@ -662,7 +681,7 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                           per_sample_weights is not None and per_sample_weights.requires_grad
                           and torch.is_grad_enabled())):
             if on:
-                raise NotImplementedError(f"{what} with a q8 (torch.uint8) table: it is forward only")
+                raise NotImplementedError(f"{what} with a {name} table: it is forward only")
     elif fused_sgd is not None and fused_sgd.lr is not None:
         check_accumulator("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
                           fused_sgd.accumulator, bool(fused_sgd.deterministic), fused_sgd.rounding)
@@ -804,7 +823,7 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                                   "the per-bag count of non-padding entries)")
     if q8:
         return _forward_q8(weight, indices, offsets, per_sample_weights, _MODES[mode], bool(include_last_offset),
-                           int(hook_features), presorted, out, output_dtype)
+                           int(hook_features), presorted, out, output_dtype, quant_bits)
     return _BagFn.apply(weight, indices, offsets, per_sample_weights, _MODES[mode], bool(include_last_offset),
                         int(hook_features), bool(sparse), fused_sgd, presorted, bwd_scale,
                         padding_idx is not None or bool(masked_indices), None if out is None else [out], output_dtype)

@@ -135,7 +135,7 @@ class FusedSparseModules(nn.Module):
             raise ValueError("FusedSparseModules: give evict_strategy or use_lfu_eviction, not both")
         # table_dtype (addition): torch.bfloat16 / torch.float16 rows in the host table and in the cache
         # (CachedEmbeddingBag(table_dtype=...)); single-rank column-wise operator only
-        _lib.refuse_q8("FusedSparseModules", table_dtype)
+        _lib.refuse_quantized("FusedSparseModules", table_dtype)
         if use_tablewise_parallel and _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"FusedSparseModules(use_tablewise_parallel=True, table_dtype={table_dtype}): "
                                       "the table-wise module keeps fp32 tables")

@@ -529,7 +529,7 @@ class RowwiseShardedEmbeddingBag(nn.Module):
                  cuda_row_num: Optional[int] = None, output_dtype: Optional[torch.dtype] = None,
                  table_dtype: Optional[torch.dtype] = None):
         super().__init__()
-        _lib.refuse_q8("RowwiseShardedEmbeddingBag", table_dtype)
+        _lib.refuse_quantized("RowwiseShardedEmbeddingBag", table_dtype)
         if _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"RowwiseShardedEmbeddingBag with table_dtype={table_dtype}: the row-wise "
                                       "exchange buffers and the owner-side update are fp32")
@@ -739,7 +739,7 @@ class GraphedShardedWindow:
                  arrangement: Optional[str] = None, arrangement_trial: Optional[dict] = None,
                  static_out_candidates: int = 0, before_capture=None, output_dtype: Optional[torch.dtype] = None,
                  table_dtype: Optional[torch.dtype] = None):
-        _lib.refuse_q8("GraphedShardedWindow", table_dtype)
+        _lib.refuse_quantized("GraphedShardedWindow", table_dtype)
         if _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"GraphedShardedWindow with table_dtype={table_dtype}: the row-wise exchange "
                                       "buffers and the owner-side update are fp32")
@@ -1415,7 +1415,7 @@ class ParallelCachedEmbeddingBag(CachedEmbeddingBag):
         self.rank = dist.get_rank(self.group) if self.group is not None else 0
         self.world_size = dist.get_world_size(self.group) if self.group is not None else 1
         self._refuse_act16(kw.get("output_dtype"))            # before anything is allocated
-        _lib.refuse_q8("ParallelCachedEmbeddingBag", kw.get("table_dtype"))
+        _lib.refuse_quantized("ParallelCachedEmbeddingBag", kw.get("table_dtype"))
         if self.world_size > 1 and _lib.table_code(kw.get("table_dtype")) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"ParallelCachedEmbeddingBag with table_dtype={kw.get('table_dtype')} on "
                                       f"{self.world_size} ranks: the all-to-all of the pooled output is fp32")

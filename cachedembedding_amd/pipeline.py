@@ -251,7 +251,7 @@ class PrefetchWindow:
         # bag_layout = (offsets, include_last_offset, hook_features) of the batches (presort=True, mode='sum' without
         # per-sample weights): the window's keys become source-row keys (functional.SrcKeys), which the backward
         # streams over without a per-tile bag search
-        _lib.refuse_q8("PrefetchWindow", getattr(embed, "table_dtype", None))
+        _lib.refuse_quantized("PrefetchWindow", getattr(embed, "table_dtype", None))
         self._layout = None if bag_layout is None else dict(offsets=bag_layout[0],
                                                             include_last_offset=bool(bag_layout[1]),
                                                             hook_features=int(bag_layout[2]),
@@ -459,7 +459,7 @@ class GraphedWindow:
         # _finish) -- so its kernels never run BESIDE the bag kernels (side by side they cost each other more than the
         # cache op's own kernel time: every one of them is bound by the same memory system), while the PCIe admission of
         # window k+1's rows still overlaps with window k's steps.  Same protection rule as overlap (protect_depth 1).
-        _lib.refuse_q8("GraphedWindow", getattr(embed, "table_dtype", None))
+        _lib.refuse_quantized("GraphedWindow", getattr(embed, "table_dtype", None))
         assert not (interleaved and (overlap or graph_cache_op or plan_ahead != 1)), \
             "interleaved replaces overlap (one stream, plan_ahead 1)"
         self.interleaved = interleaved

@@ -71,7 +71,7 @@ class ParallelCachedEmbeddingBagTablewise(nn.Module):
                  evict_strategy: EvictionStrategy = EvictionStrategy.LFU, group=None, output_dtype=None,
                  table_dtype=None):
         super().__init__()
-        _lib.refuse_q8("ParallelCachedEmbeddingBagTablewise", table_dtype)
+        _lib.refuse_quantized("ParallelCachedEmbeddingBagTablewise", table_dtype)
         if _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"ParallelCachedEmbeddingBagTablewise with table_dtype={table_dtype}: the "
                                       "table-wise module keeps fp32 tables")

@@ -60,6 +60,9 @@ def parse_args(argv=None):
                         "table is quantized to 8-bit rows (CachedEmbeddingBag.quantized()), the test set is evaluated "
                         "again through it, and test_auroc_q8 / test_accuracy_q8 / the two table sizes are printed as "
                         "one JSON line (and merged into --json_out)")
+    p.add_argument("--eval_q4", action="store_true",
+                   help="like --eval_q8 (and beside it, if both are given) with the 4-bit row-wise quantized table "
+                        "(CachedEmbeddingBag.quantized(bits=4)): test_auroc_q4 / test_accuracy_q4 / table_bytes_q4")
     p.add_argument("--batch_size", type=int, default=16384)
     p.add_argument("--num_dense_features", type=int, default=13)
     p.add_argument("--embedding_dim", type=int, default=128)
@@ -647,6 +650,13 @@ def main(argv=None):
         if world > 1 or args.use_tablewise:
             raise NotImplementedError("--eval_q8 is implemented for one process without --use_tablewise (the sharded "
                                       "classes do not take a q8 table)")
+    if args.eval_q4:
+        if not args.eval_acc:
+            raise ValueError("--eval_q4 needs --eval_acc: it evaluates the test set once more, through the "
+                             "quantized table")
+        if world > 1 or args.use_tablewise:
+            raise NotImplementedError("--eval_q4 is implemented for one process without --use_tablewise (the sharded "
+                                      "classes do not take a q4 table)")
     if args.adagrad:
         if args.fused_sgd:
             raise ValueError("--adagrad takes the place of --fused_sgd: pass one of them")
@@ -771,25 +781,28 @@ def main(argv=None):
                               "val_batches": _evaluate.batches} if args.eval_acc else None)}, indent=1))
     if args.eval_acc:                                            # recsys/dlrm_main.py:365-369
         results["test_auroc"], results["test_accuracy"] = _evaluate(model, test_loader, "test", args, device, rank, world)
-    if args.eval_q8:
-        # serve what was trained at a quarter of the memory: the same dense weights over the 8-bit row-wise quantized
-        # copy of the table (a new pinned table and a cache of its own; the trained module is only flushed)
+    for bits in [b for b, on in ((8, args.eval_q8), (4, args.eval_q4)) if on]:
+        # serve what was trained at a quarter (q8) or a sixth (q4, D = 128) of the memory: the same dense weights over
+        # the row-wise quantized copy of the table (a new pinned table and a cache of its own; the trained module is
+        # only flushed)
         import json
         sparse = model.sparse_modules
-        q8 = embed.quantized()
-        sparse.embed = q8
+        tag = f"q{bits}"
+        quant = embed.quantized() if bits == 8 else embed.quantized(bits=bits)
+        sparse.embed = quant
         try:
-            auroc, acc = _evaluate(model, test_loader, "test (q8 table)", args, device, rank, world)
+            auroc, acc = _evaluate(model, test_loader, f"test ({tag} table)", args, device, rank, world)
         finally:
             sparse.embed = embed
-        table, table_q8 = embed.weight, q8.weight
-        extra = {"test_auroc_q8": auroc, "test_accuracy_q8": acc,
-                 "table_bytes": table.numel() * table.element_size(), "table_bytes_q8": table_q8.numel()}
+        table, table_q = embed.weight, quant.weight
+        extra = {f"test_auroc_{tag}": auroc, f"test_accuracy_{tag}": acc,
+                 "table_bytes": table.numel() * table.element_size(), f"table_bytes_{tag}": table_q.numel()}
         results.update(extra)
         print(json.dumps({"script": "examples/dlrm_main.py", "test_auroc": results["test_auroc"],
                           "test_accuracy": results["test_accuracy"], **extra}))
         if args.json_out and Path(args.json_out).exists():
             Path(args.json_out).write_text(json.dumps(json.loads(Path(args.json_out).read_text()) | extra, indent=1))
+        del quant
     if world > 1:
         dist.destroy_process_group()
 

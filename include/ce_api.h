@@ -581,6 +581,33 @@ int ce_bag_forward_q8(const void* weight, int64_t num_rows, int32_t dim,
 int ce_bag_forward_src_keys_q8(const void* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
 
+/* 4-bit row-wise quantized table, `q4` (additions to API 6): q8 with 16 levels -- evaluation and serving only, no
+ * backward, no update, never written by a kernel.  A row of `dim` elements is 16 + dim / 2 bytes:
+ *   bytes 0..3 scale (fp32) | 4..7 bias (fp32) | 8..15 zero | 16..16+dim/2-1: dim codes, two per byte
+ * Element i is in code byte i / 2: the low nibble for even i, the high nibble for odd i.  The four elements
+ * 4ch .. 4ch+3 of a lane's chunk ch are therefore one little-endian uint16 at code offset 2ch, nibble k of it is
+ * element 4ch + k.
+ * dim % 32 == 0, 32 <= dim <= 1024 and the table 16-byte aligned, so every row is a whole number of 16-byte units and
+ * its codes start 16-byte aligned (the cache op is driven with embedding_dim = (16 + dim / 2) / 4).  Any other dim:
+ * CE_ERR_UNSUPPORTED before any launch; ce_q4_row_bytes returns 0 for it.
+ * The header is q8's 16 bytes (fp32 scale and bias, 8 zero bytes) for the same alignment reason: the fp16 scale / bias
+ * that FBGEMM's 4-bit rows carry BEHIND the codes is not followed, and such rows are not read.
+ * Element value: v = fmaf((float)q, scale, bias) -- ONE explicit fused multiply-add, in the kernels and on the host.
+ * Quantizer: q8's with 15 in place of 255 -- scale = (hi - lo) / 15, bias = lo, q = clamp(rintf((x - lo) / scale), 0,
+ * 15); a zero quotient stores scale 0 and codes 0; a NaN or an infinity is CE_ERR_INVALID naming the first such row;
+ * the result does not depend on `threads`; both nibbles of every code byte and the pad bytes are written.
+ * Every entry has the argument list of its q8 twin and behaves like it in every respect but the row type. */
+#define CE_Q4_HEADER_BYTES 16
+size_t ce_q4_row_bytes(int32_t dim);
+int ce_host_quantize_q4(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, void* dst, int threads);
+int ce_host_dequantize_q4(const void* src, int64_t n_rows, int32_t dim, float* dst, int threads);
+int ce_bag_forward_q4(const void* weight, int64_t num_rows, int32_t dim,
+                      const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                      int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                      int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_forward_src_keys_q4(const void* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                               const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6]. Device state arrays are owned by the caller (so the Python
  * mirror can expose them as tensors: cached_idx_map, inverted_cached_idx, idx_map,
