@@ -457,14 +457,16 @@ __global__ __launch_bounds__(256) void k_bag_bwd_rows(BagParams p) {
 constexpr int kBwdTile = 1024;
 
 __device__ __forceinline__ int find_bag(const BagParams& p, int j) {
-  // bag whose [offsets[b], end(b)) holds lookup j; single-id layouts (offsets == arange) hit the first test
+  // bag whose [offsets[b], end(b)) holds lookup j; single-id layouts (offsets == arange) hit the first test.
+  // -1: no bag covers j (j < offsets[0], or j >= the end of the last bag) -- the forward never saw such a lookup, and
+  // the callers skip it like an ignored one
   if (j < p.num_bags && ld_off(p, j) == j && bag_end(p, j) == j + 1) return j;
   int lo = 0, hi = p.num_bags - 1;
   while (lo < hi) {                       // last b with offsets[b] <= j
     const int mid = (lo + hi + 1) >> 1;
     if (ld_off(p, mid) <= j) lo = mid; else hi = mid - 1;
   }
-  return lo;
+  return (ld_off(p, lo) <= j && j < bag_end(p, lo)) ? lo : -1;
 }
 
 // sort keys: (row, lookup-in-tile).  32-bit keys (row < 2^22, i.e. caches up to 4 M rows) halve the LDS traffic
@@ -567,6 +569,7 @@ constexpr int kSegBuckets = CE_SEG_BUCKETS;
 // SRC: the low word of a key is not the lookup's place in its segment but the row of grad_out the lookup reads
 // (out_row(bag of the lookup), from the batch's offsets): everything the streaming backward needs, resolved here
 // once per window instead of in every backward launch.  lay.offsets of batch b = offsets + b * off_stride elements.
+// A lookup that no bag covers (find_bag: -1) has no such row and gets the all-ones key of the padding.
 // EXCL (with SRC): the keys are staged in LDS at their grouped positions, every bucket of at most kExclRun keys is
 // sorted by row there (a handful of keys: insertion sort by the thread that owns the bucket's first position), and
 // the first key of every run that lies inside ONE 16-position block of the segment gets bit 31 of its low word set:
@@ -637,12 +640,18 @@ __global__ __launch_bounds__(1024) void k_bag_presort_seg(const int64_t* __restr
       if (e < n_here) {
         const int64_t row = ROWS ? (int64_t)slot_r[ROWS ? r : 0] : indices[in_base + e];
         const bool valid = (uint64_t)row < (uint64_t)num_rows;
-        if (valid || SRC) {
+        // lay.offsets == nullptr: one id per bag, in order (bag of lookup j = j) -- what every Criteo / Avazu
+        // batch is; saves the two offset loads per lookup that find_bag needs to establish it (-12 us per window)
+        int bag = sib * kSegLen + e;
+        bool covered = true;
+        // SRC: a lookup that no bag covers has no output row: its key stays all ones, like the padding
+        if (SRC && lay.offsets) {
+          bag = find_bag(q, bag);
+          covered = bag >= 0;
+        }
+        if ((valid || SRC) && covered) {
           unsigned low = (unsigned)e;
-          // lay.offsets == nullptr: one id per bag, in order (bag of lookup j = j) -- what every Criteo / Avazu
-          // batch is; saves the two offset loads per lookup that find_bag needs to establish it (-12 us per window)
-          if (SRC)
-            low = (unsigned)out_row(q, lay.offsets ? find_bag(q, sib * kSegLen + e) : sib * kSegLen + e);
+          if (SRC) low = (unsigned)out_row(q, bag);
           // SRC: an ignored lookup (slot -1 / out of range) keeps its output row under the row 0xffffffff -- the
           // backward skips it like padding (row >= num_rows), the key-driven forward writes its zero row; it goes to
           // the last bucket with the padding
@@ -828,8 +837,8 @@ __global__ __launch_bounds__(256) void k_bag_bwd_tile(BagParams p, const float* 
       } else {
         j = -1;
       }
-      if (j >= 0) {
-        const int bag = find_bag(p, j);
+      const int bag = j >= 0 ? find_bag(p, j) : -1;
+      if (bag >= 0) {                        // (a lookup that no bag covers is skipped like an invalid key)
         float sc = alpha;
         if (p.psw) sc *= p.psw[j];
         if (p.mode == CE_MODE_MEAN) {

@@ -242,7 +242,11 @@ int ce_bag_backward_dense_presorted(float* grad_weight, int64_t num_rows, int32_
  * (67 vs 74 us at the bench shape); they trust the keys (grad_out row < num_bags) and ignore rows >= num_rows.
  * An ignored lookup (index outside [0, num_rows), e.g. slot -1) keeps its grad_out / output row in the low word under
  * the row 0xffffffff (API 4; all ones before) -- the backward skips it like padding, ce_bag_forward_src_keys writes its
- * zero row; only the positions beyond nnz_per_batch in the last segment are all ones.
+ * zero row.
+ * A lookup that NO BAG COVERS (see "Lookups that no bag covers" below) has no grad_out / output row at all: its key is
+ * all ones -- row half 0xffffffff, low word 0xffffffff -- whatever its index, so every consumer skips it as it skips
+ * padding (the backwards, the mark passes of the accumulator updates, and ce_bag_forward_src_keys, which writes
+ * nothing for it).  Apart from those, only the positions beyond nnz_per_batch in the last segment are all ones.
  * Replaces the same upstream call as the forms above (recsys/dlrm_main.py:274-279, loss.backward + optimizer.step). */
 int ce_bag_presort_window_src(const int64_t* indices, int64_t nnz_per_batch, int64_t n_batches, int64_t num_rows,
                               const void* offsets, int32_t offsets_are_i64, int64_t offsets_batch_stride,
@@ -287,7 +291,16 @@ int ce_bag_backward_sgd_presorted_src_excl(float* weight, int64_t num_rows, int3
  * order for sparse grads; bit-reproducible, slower for very hot rows.  Lookups of rows outside
  * [0, num_rows) (the -1 of padding or of an overflowing cache call) take no part.  Lookups that
  * no bag covers (before offsets[0], or behind offsets[num_bags] with include_last_offset) take no
- * part either.  Nothing in the workspace needs initialising. */
+ * part either.  Nothing in the workspace needs initialising.
+ *
+ * Lookups that no bag covers -- the rule for EVERY entry that takes offsets.  Lookup j belongs to the bag b with
+ * offsets[b] <= j < end(b), end(b) = offsets[b + 1], or nnz for the last bag without include_last_offset.  A lookup
+ * with j < offsets[0], or j >= end(last bag) (offsets[num_bags] < nnz with include_last_offset, which torch accepts
+ * and ignores the tail of), belongs to none.  The forward and ce_bag_backward_rows walk the bags and never see it;
+ * the lookup-driven backwards -- ce_bag_backward_dense* / _sgd* / _rowwise_adagrad* / _update_* from slots + offsets,
+ * with or without presorted keys -- skip it like a lookup outside [0, num_rows); the sorted updates skip it (above);
+ * and the source-row presorts write an all-ones key for it (see ce_bag_presort_window_src).  The row it names gets no
+ * gradient, no update and no momentum from it. */
 size_t ce_bag_backward_sgd_sorted_workspace(int64_t num_rows, int64_t nnz);
 int ce_bag_backward_sgd_sorted(float* weight, int64_t num_rows, int32_t dim,
                                const int64_t* indices, int64_t nnz,

@@ -293,7 +293,9 @@ def test_full_size_step_vs_torch_cpu(presort):
                                       (425984, 26, 200000, 32), (70000, 1, 5_000_000, 8)])
 def test_presorted_backward_matches_in_kernel_sort(nb, F, C, D):
     """ce_bag_presort (16384-lookup segments) + ce_bag_backward_sgd_presorted == ce_bag_backward_sgd up to fp32
-    summation order; the last case has more than 2^22 rows (64-bit tile keys)"""
+    summation order; the last case has more than 2^22 rows (64-bit tile keys).
+    (What a correct key array is -- for these keys, the source-row keys and the owner-exclusive flags -- is stated by
+    the model in tests/presort_ref.py and checked for every producer in tests/test_gpu_presort_keys.py.)"""
     ce = _ce()
     from cachedembedding_amd.functional import presort_len, presort_slots
     g = torch.Generator().manual_seed(nb)
@@ -362,7 +364,7 @@ def test_presorted_backward_multi_id_bags_mean_and_weights():
 def test_presort_window_equals_per_batch_presort_and_feeds_the_backward(P, n, C):
     """one launch for the P batches of a window: batch b's keys cover exactly its own lookups (segments never
     straddle batches, also when a batch is not a whole number of 16384-lookup segments) and drive the fused backward
-    to the same result as the in-kernel tile sort"""
+    to the same result as the in-kernel tile sort (the full key contract: tests/test_gpu_presort_keys.py)"""
     ce = _ce()
     from cachedembedding_amd.functional import presort_len, presort_window
     g = torch.Generator().manual_seed(P * n)
