@@ -106,6 +106,8 @@ _W16_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_int32, c_i
 # workspace_bytes, stream
 _LRDEV_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int32, c_int32, c_uint64, c_int32, c_void_p,
                        c_size_t] + _STREAM
+# keys, beta1, beta2, lr, lr_dev, eps, step, accumulator, workspace, workspace_bytes, stream
+_ADAM_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -178,6 +180,14 @@ SIGNATURES = {
     "ce_bag_backward_sgd_src_lrdev": (c_int, _SRC + _ACT + [c_void_p] + _KEYS + [c_void_p] + _STREAM),
     "ce_bag_backward_update_lrdev": (c_int, _W16 + _BAG[1:] + _ACT + _LRDEV_TAIL),
     "ce_bag_backward_update_src_lrdev": (c_int, _W16 + _SRC[1:] + _ACT + _LRDEV_TAIL),
+    # the Adam-layout table (rows w | m | v of 3 * dim fp32): the fp32 forwards' lists; the update's tail = keys, beta1,
+    # beta2, lr, lr_dev, eps, step, accumulator, workspace, workspace_bytes, stream
+    "ce_host_fill_uniform_adam": (c_int, [c_void_p, c_int64, c_int32, c_float, c_float, c_uint64, c_int]),
+    "ce_bag_forward_adam": (c_int, _BAG + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_adam": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    "ce_bag_backward_adam_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ce_bag_backward_adam": (c_int, _BAG + _ACT + _ADAM_TAIL),
+    "ce_bag_backward_adam_src": (c_int, _SRC + _ACT + _ADAM_TAIL),
     # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
     "ce_q8_row_bytes": (c_size_t, [c_int32]),
     "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),
@@ -403,6 +413,32 @@ def check_quant_bits(bits) -> int:
     if bits not in (4, 8):
         raise NotImplementedError(f"quantized rows of {bits!r} bits: 8 (q8) and 4 (q4) are implemented")
     return bits
+
+
+# the Adam layout (fused_optimizer="adam"): an fp32 table whose rows carry their moments, [N, 3 * D] = w | m | v
+LAYOUTS = (None, "adam")
+
+
+def check_layout(layout):
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout={layout!r}: None or 'adam'")
+    return layout
+
+
+def check_adam_dim(dim: int) -> None:
+    """the three parts of an Adam-layout row are whole 16-byte units, one lane group per row: refused before the GPU is
+    asked for"""
+    if dim % 4 != 0 or dim < 4 or dim > 1024:
+        raise NotImplementedError(f"an Adam-layout table needs embedding_dim % 4 == 0 and 4 <= embedding_dim <= 1024 "
+                                  f"(got {dim})")
+
+
+def check_adam_table(dim: int, table_dtype) -> None:
+    """what fused_optimizer="adam" needs of the table: fp32 rows (no 16-bit, no quantized table) and the dim rule"""
+    if quant_bits_of(table_dtype) or table_code(table_dtype) != CE_ACT_F32:
+        raise NotImplementedError(f"fused_optimizer='adam' with table_dtype={table_dtype}: the Adam layout is an fp32 "
+                                  "table (16-bit moments or tables are not implemented)")
+    check_adam_dim(dim)
 
 
 def ptr(t) -> int:

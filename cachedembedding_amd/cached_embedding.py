@@ -14,7 +14,8 @@ import torch.nn as nn
 
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
-from .functional import FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_lr, check_lr_path, embedding_bag
+from .functional import (FusedAdam, FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_lr, check_lr_path,
+                         embedding_bag)
 
 
 def _refuse_q8_update(module, what: str, lr) -> None:
@@ -22,6 +23,12 @@ def _refuse_q8_update(module, what: str, lr) -> None:
         raise NotImplementedError(f"{what}(lr) with a q8 (torch.uint8) table: a quantized table is never updated")
     if lr is not None and getattr(module, "table_dtype", None) == _lib.Q4:
         raise NotImplementedError(f"{what}(lr) with a q4 (torch.quint4x2) table: a quantized table is never updated")
+
+
+def _refuse_adam_layout(module, what: str, lr) -> None:
+    if lr is not None and getattr(module, "fused_optimizer", None) == "adam":
+        raise NotImplementedError(f"{what}(lr) on an Adam-layout module (fused_optimizer='adam'): its rows carry Adam's "
+                                  "moments, set_fused_adam(lr) is its fused update")
 
 
 def _quant_name(bits: int) -> str:
@@ -37,8 +44,21 @@ class CachedEmbeddingBag(nn.Module):
                  evict_strategy: EvictionStrategy = EvictionStrategy.DATASET, *, cuda_row_num: Optional[int] = None,
                  init_seed: int = 1024, strict: bool = True, output_dtype: Optional[torch.dtype] = None,
                  table_dtype: Optional[torch.dtype] = None, _table: Optional[HostTable] = None,
-                 _idx_map: Optional[torch.Tensor] = None):
+                 _idx_map: Optional[torch.Tensor] = None, fused_optimizer: Optional[str] = None):
         super().__init__()
+        # fused_optimizer="adam" (addition): the host table AND the cache hold rows w | m | v of 3 * D floats -- Adam's
+        # moments live where the table lives and travel with the rows through eviction and admission;
+        # set_fused_adam(lr) then applies Adam inside backward.  An fp32 table only; embedding_dim keeps meaning D.
+        if fused_optimizer not in (None, "adam"):
+            raise ValueError(f"fused_optimizer={fused_optimizer!r}: None or 'adam'")
+        self.fused_optimizer = fused_optimizer
+        adam = fused_optimizer == "adam"
+        if adam:
+            _lib.check_adam_table(embedding_dim, table_dtype)
+            for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
+                             ("sparse=True", bool(sparse))):
+                if on:
+                    raise NotImplementedError(f"{what} with an Adam-layout table (fused_optimizer='adam')")
         # output_dtype (addition): dtype of the pooled output and of the gradient coming back -- None / torch.float32,
         # torch.bfloat16 or torch.float16 (functional.embedding_bag(output_dtype=...)).  `dtype` is the TABLE's dtype.
         if dtype not in (None, torch.float32):
@@ -101,11 +121,21 @@ class CachedEmbeddingBag(nn.Module):
         self.cache_op = True
         self.fused_sgd = FusedSGD(None)
         self.fused_adagrad = FusedRowwiseAdagrad(None)
+        self.fused_adam = None
 
         if _table is not None:
             table = _table
             assert table.tensor.dtype == (torch.uint8 if q8 else self.table_dtype) and table.quant_bits == bits \
-                and table.tensor.shape[0] == num_embeddings
+                and table.tensor.shape[0] == num_embeddings and table.layout == fused_optimizer
+        elif adam:
+            table = HostTable.allocate(num_embeddings, embedding_dim, layout="adam")
+            if _weight is None:
+                table.fill_uniform_(-1.0 / num_embeddings, 1.0 / num_embeddings, init_seed)
+                if padding_idx is not None:
+                    table.tensor[padding_idx].zero_()
+            else:
+                assert tuple(_weight.shape) == (num_embeddings, embedding_dim)
+                table.set_weight_(_weight)                  # zero moments
         elif q8:
             w = _weight.detach()
             if w.dtype == torch.uint8:                      # already q8 / q4 rows: pinned in place
@@ -141,11 +171,33 @@ class CachedEmbeddingBag(nn.Module):
             self.eval()
         if w16:
             self.set_weight_rounding(self.weight_rounding, self.weight_rounding_seed)
+        if adam:
+            # the step count Adam's bias correction reads: on the device, so that a replayed graph counts on
+            self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.cache_weight_mgr.device)
+            self.fused_adam = FusedAdam(None, step=self.adam_step)
 
     # -- the host table (upstream `.weight`) and the parameter protocol (A.7) ------------
     @property
     def weight(self) -> torch.Tensor:
-        return self.cache_weight_mgr.weight
+        # (an Adam-layout table: the [N, D] view of the rows' w parts; current after flush(), like the moments)
+        w = self.cache_weight_mgr.weight
+        return w[:, :self.embedding_dim] if self.fused_optimizer == "adam" else w
+
+    def _adam_part(self, k: int, name: str) -> torch.Tensor:
+        if self.fused_optimizer != "adam":
+            raise AttributeError(f"{name} exists on a module built with fused_optimizer='adam'")
+        d = self.embedding_dim
+        return self.cache_weight_mgr.weight[:, k * d:(k + 1) * d]
+
+    @property
+    def exp_avg(self) -> torch.Tensor:
+        """Adam's first moment, the [N, D] view of the host table's m parts (torch.optim's name); current after flush()"""
+        return self._adam_part(1, "exp_avg")
+
+    @property
+    def exp_avg_sq(self) -> torch.Tensor:
+        """Adam's second moment, the [N, D] view of the host table's v parts; current after flush()"""
+        return self._adam_part(2, "exp_avg_sq")
 
     def named_parameters(self, prefix: str = "", recurse: bool = True, remove_duplicate: bool = True
                          ) -> Iterator[Tuple[str, nn.Parameter]]:
@@ -169,6 +221,7 @@ class CachedEmbeddingBag(nn.Module):
         read by the kernels when they run, so fill_ / copy_ into it changes the rate of the next step -- also of a
         step replayed from a hipGraph.  Not with deterministic=True."""
         _refuse_q8_update(self, "set_fused_sgd", lr)
+        _refuse_adam_layout(self, "set_fused_sgd", lr)
         if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
@@ -195,6 +248,7 @@ class CachedEmbeddingBag(nn.Module):
         needs set_weight_rounding("nearest") first.
         lr may be a tensor, as in set_fused_sgd; not with deterministic=True."""
         _refuse_q8_update(self, "set_fused_rowwise_adagrad", lr)
+        _refuse_adam_layout(self, "set_fused_rowwise_adagrad", lr)
         if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
@@ -211,6 +265,25 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_adagrad.accumulator = accumulator
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
+
+    def set_fused_adam(self, lr: Union[float, torch.Tensor, None], betas=(0.9, 0.999), eps: float = 1e-8,
+                       accumulator: str = "step", deterministic: bool = False):
+        """Apply Adam (torch.optim.SparseAdam's arithmetic: only the rows a step looks up move) to the cache rows inside
+        backward.  Needs a module built with fused_optimizer="adam": the moments are part of every row, in the host
+        table and in the cache, `.exp_avg` / `.exp_avg_sq` after flush(); the step count is `.adam_step` (device).
+        lr=None turns the update off (moments and step count are kept; a backward is then a RuntimeError).  lr may be
+        a tensor, as in set_fused_sgd.  accumulator: "step" (default) or "cache" -- the size of the fp32 accumulator the
+        step's gradient is folded into; both write the same bits given the same folded gradient.  Exclusive with
+        set_fused_sgd / set_fused_rowwise_adagrad: an Adam-layout module refuses those."""
+        if self.fused_optimizer != "adam":
+            raise ValueError("set_fused_adam needs a module built with fused_optimizer='adam': Adam's moments live in "
+                             "the rows of the table")
+        if isinstance(lr, torch.Tensor):
+            check_lr(lr)
+        elif lr is not None and not float(lr) >= 0.0:
+            raise ValueError(f"lr={lr!r}: must be >= 0")
+        self.fused_adam.set(betas, eps, accumulator, deterministic)      # (deterministic=True: not implemented)
+        self.fused_adam.lr = lr
 
     def set_weight_rounding(self, rounding: str = "stochastic", seed: int = 0):
         """How the fused updates round a row of a 16-bit table: "nearest" (round-to-nearest-even) or "stochastic" (the
@@ -234,6 +307,8 @@ class CachedEmbeddingBag(nn.Module):
         self.output_dtype = torch.float32 if dtype is None else dtype
 
     def _fused(self):
+        if self.fused_adam is not None:                     # an Adam-layout table: the forward needs the object too
+            return self.fused_adam
         return self.fused_adagrad if self.fused_adagrad.lr is not None else self.fused_sgd
 
     def forward(self, input: torch.Tensor, offsets: Optional[torch.Tensor] = None,
@@ -332,6 +407,8 @@ class CachedEmbeddingBag(nn.Module):
         mgr = self.cache_weight_mgr
         self.flush()
         src = self.weight                                   # (waits for the write-backs of the worker transport)
+        if self.fused_optimizer == "adam":
+            src = src.contiguous()                          # the w parts alone: the moments are not quantized
         table = HostTable.allocate(self.num_embeddings, self.embedding_dim, dtype=dtype).quantize_from(src)
         kw = dict(cuda_row_num=self.cuda_row_num, output_dtype=self.output_dtype, warmup_ratio=0.7,
                   buffer_size=mgr.buffer_size, strict=mgr.strict)

@@ -120,6 +120,7 @@ template <typename WT, typename VT> struct Row {
   typedef VT Held;
   struct Hdr {};
   static constexpr int kHeader = 0;
+  static constexpr int kSpan = 1;       // rows lie kSpan * (kHeader + rowlen) elements apart
   static __device__ __forceinline__ Held zero() { return vzero<VT>(); }
   static __device__ __forceinline__ Held up(V a) { return Act<WT, VT>::up(a); }
   static __device__ __forceinline__ VT value(Held v, Hdr) { return v; }
@@ -139,6 +140,7 @@ template <> struct Row<Q8, f32x4> {
   typedef uint32_t Held;
   typedef f32x2 Hdr;      // {scale, bias}; {0, 0} for a row that takes no part
   static constexpr int kHeader = CE_Q8_HEADER_BYTES / 4;
+  static constexpr int kSpan = 1;
   static __device__ __forceinline__ Held zero() { return 0u; }
   static __device__ __forceinline__ Held up(V a) { return a; }
   static __device__ __forceinline__ Hdr header(const V* row) { return *(const Hdr*)row; }
@@ -162,6 +164,7 @@ template <> struct Row<Q4, f32x4> {
   typedef uint32_t Held;  // the chunk's 16 bits of codes in the low half; value() does not look at the high half
   typedef f32x2 Hdr;
   static constexpr int kHeader = CE_Q4_HEADER_BYTES / 2;
+  static constexpr int kSpan = 1;
   static __device__ __forceinline__ Held zero() { return 0u; }
   static __device__ __forceinline__ Held up(V a) { return a; }
   static __device__ __forceinline__ Hdr header(const V* row) { return *(const Hdr*)row; }
@@ -172,11 +175,27 @@ template <> struct Row<Q4, f32x4> {
   }
 };
 
+// Adam-layout rows (include/ce_api.h): 3 * rowlen chunks -- w | m | v, fp32.  The forwards read the w part alone: an
+// fp32 row whose successor lies three rows' width away.  Nothing else differs from the fp32 row type, so the kernels
+// are the fp32 kernels with another stride; the moments are never loaded.
+struct AdamRow {};
+constexpr int kTableAdam = 3;   // like kTableQ8
+template <> struct Row<AdamRow, f32x4> {
+  typedef f32x4 V;
+  typedef f32x4 Held;
+  struct Hdr {};
+  static constexpr int kHeader = 0;
+  static constexpr int kSpan = 3;
+  static __device__ __forceinline__ Held zero() { return vzero<f32x4>(); }
+  static __device__ __forceinline__ Held up(V a) { return a; }
+  static __device__ __forceinline__ f32x4 value(Held v, Hdr) { return v; }
+};
+
 // STAGE: tiles with multi-id bags stage their indices in LDS (32 KB per workgroup); the launcher picks the
 // LDS-free variant when nnz == num_bags (single-id batches) so occupancy is set by registers alone.
 // AT: the output's element type (Act<AT, VT>, ce_common.h): sums stay fp32, the store rounds.
 // WT: the table's row type (Row<WT, VT>: float; bf16 / fp16 with f32x4 lanes, a lane's chunk is then 8 bytes of the row;
-// Q8 and Q4 with f32x4 lanes).  A row that takes no part is held as zeros: chunks and header.
+// Q8, Q4 and AdamRow with f32x4 lanes).  A row that takes no part is held as zeros: chunks and header.
 template <typename VT, int NCH, bool STAGE, int U, typename AT, typename WT = float>
 __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   using A = Act<AT, VT>;
@@ -193,7 +212,7 @@ __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   const typename T::V* __restrict__ W = (const typename T::V*)p.weight;
   typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const int rowlen = p.rowlen;
-  const int stride = T::kHeader + rowlen;
+  const int stride = (T::kHeader + rowlen) * T::kSpan;
   // tiles are dealt round-robin to the waves of an oversubscribed grid (an even contiguous split over a
   // resident-sized grid measured 15 % slower: 0.060 -> 0.069 ms)
   const int ntiles = (p.num_bags + 63) >> 6;
@@ -1113,7 +1132,7 @@ __global__ __launch_bounds__(256, 4) void k_bag_fwd_keys(BagParams p, int64_t to
   const int grp = tid >> p.g_log2;
   const int gl = tid & (G - 1);
   const int rowlen = p.rowlen;
-  const int stride = T::kHeader + rowlen;
+  const int stride = (T::kHeader + rowlen) * T::kSpan;
   const typename T::V* __restrict__ W = (const typename T::V*)p.weight;
   typename A::V* __restrict__ O = (typename A::V*)p.dst;
   const unsigned long long* __restrict__ keys = p.presorted;
@@ -1303,6 +1322,7 @@ template <typename F> static void for_table_act(int weight_dtype, const RowGeom&
   auto acts = [&](auto l, auto w) { for_act(act, [&](auto a) { f(l, w, a); }); };
   if (weight_dtype == kTableQ8) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<Q8>{}); });
   else if (weight_dtype == kTableQ4) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<Q4>{}); });
+  else if (weight_dtype == kTableAdam) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<AdamRow>{}); });
   else for_table(weight_dtype, r, acts);
 }
 
@@ -1387,7 +1407,8 @@ static int launch_fwd(BagParams& p, const RowGeom& r, const void* weight, int we
 
 // The key-driven forward.  An fp32 table has the PAIR form for a 16-bit output; a 16-bit table only the converting
 // instantiation (WT != AT: exact up-conversion, one rounding on the store) -- equal types never get here, see
-// ce_bag_forward_src_keys_w16.  A q8 or q4 table (kTableQ8, kTableQ4) always converts: it takes that arm too.
+// ce_bag_forward_src_keys_w16.  A q8 or q4 table (kTableQ8, kTableQ4) always converts: it takes that arm too, and so
+// does an Adam-layout table (kTableAdam: the arm's kernel with an identity conversion; it has no PAIR form).
 static int launch_fwd_keys(const void* weight, int weight_dtype, int64_t num_rows, int32_t dim, bool aligned, int64_t nnz,
                            const uint64_t* src_keys, void* out, int act, hipStream_t s) {
   BagParams p{};
@@ -1777,6 +1798,43 @@ extern "C" int ce_bag_forward_src_keys_q4(const void* weight, int64_t num_rows, 
   CE_REQUIRE_ROWS(num_rows);
   CE_REQUIRE_Q4_ALIGNED(weight, out, act_dtype);
   return launch_fwd_keys(weight, kTableQ4, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
+}
+
+// ---- forward from an Adam-layout table (rows w | m | v of 3 * dim fp32; dim % 4 == 0, 4 <= dim <= 1024, everything
+// aligned): the row type AdamRow of the same kernels, which reads the w part alone
+#define CE_REQUIRE_ADAM_ALIGNED(weight, out, act)                                      \
+  CE_REQUIRE(al16(weight) && act_aligned(out, act), CE_ERR_INVALID,                    \
+             "an Adam-layout table must be 16-byte aligned and its output on the vector boundary")
+
+extern "C" int ce_bag_forward_adam(const float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                   int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                   int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                   int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_ADAM_DIM(dim);
+  if (num_bags == 0) return CE_OK;
+  CE_REQUIRE(weight && out && (indices || nnz == 0), CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(offsets || num_bags == nnz, CE_ERR_INVALID,
+             "offsets == NULL states one id per bag (offsets = arange): num_bags must equal nnz");
+  CE_REQUIRE_ADAM_ALIGNED(weight, out, act_dtype);
+  BagParams p{};
+  RowGeom r;
+  int rc = fill_params(p, r, dim, true, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                       per_sample_weights, mode, hook_features);
+  if (rc) return rc;
+  return launch_fwd(p, r, weight, kTableAdam, num_rows, out, act_dtype, (hipStream_t)stream);
+}
+
+extern "C" int ce_bag_forward_src_keys_adam(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                            const uint64_t* src_keys, void* out, int32_t act_dtype,
+                                            ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_ADAM_DIM(dim);
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE_ROWS(num_rows);
+  CE_REQUIRE_ADAM_ALIGNED(weight, out, act_dtype);
+  return launch_fwd_keys(weight, kTableAdam, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
 }
 
 extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : padded_keys(nnz); }

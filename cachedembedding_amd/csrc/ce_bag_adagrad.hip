@@ -17,6 +17,8 @@
 // the entry): DESIGN.md 3.5 says why.  No host synchronisation, no allocation, launch shapes fixed by the arguments (a
 // backward can be captured into a hipGraph).  The momentum is indexed by host-table row (row_of_slot = cached_idx_map)
 // and never moves with the cache; a slot maps to one row for the whole step, so folding by slot is folding by row.
+// Adam (ce_bag_backward_adam*) is a third arithmetic of update_row on an fp32 table whose rows carry
+// their own moments (w | m | v): the two atomic folds above, unchanged, hand it the same folded gradient.
 #include "ce_common.h"
 
 namespace ce {
@@ -38,10 +40,22 @@ struct UpdateArgs {
   float lr;
   float eps;
   const float* lr_dev;                // non-NULL (the ce_*_lrdev entries): the learning rate is *lr_dev, `lr` is not read
+  // Adam only (`weight` is then [num_rows, 3 * D]: w | m | v; `counter` is the caller's step count)
+  double beta1, beta2;
+  float omb1, omb2;                   // (float)(1.0 - beta): the fp64 difference, rounded once
 };
 
 // the launch's learning rate: uniform, so a kernel reads it once per thread, at its top, and hands it to update_row
 __device__ __forceinline__ float learning_rate(const UpdateArgs& a) { return a.lr_dev ? *a.lr_dev : a.lr; }
+
+// Adam's step size lr * c_t, c_t = sqrt(1 - beta2^t) / (1 - beta1^t) in fp64 from the step count as the call's first
+// launch left it, rounded once: uniform like the learning rate, so a kernel works it out once per thread, at its top
+__device__ __forceinline__ float adam_step_size(const UpdateArgs& a) {
+#pragma clang fp contract(off)
+  const double t = (double)*a.counter;
+  const float c = (float)(sqrt(1.0 - pow(a.beta2, t)) / (1.0 - pow(a.beta1, t)));
+  return learning_rate(a) * c;
+}
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -122,12 +136,41 @@ template <bool STOCH> __device__ __forceinline__ uint64_t step_key(const UpdateA
 //            happens; m[r] = m[r] + ss / D (lane 0 writes); mult = lr / (sqrt(m[r]) + eps).   sgd: mult = lr.
 //   x = fma(-g, mult, up(W[s])) per element; W[s] = x (fp32), nearest(x), or round_stochastic(x, 16 bits of
 //   mix64(mix64(step_key ^ r) + chunk index) per element).
-template <typename VT, typename WT, int NCH, bool STOCH>
+//   ADAM (an fp32 table of rows w | m | v, vector lanes; lr is adam_step_size; `adagrad` is not looked at), per element:
+//     m' = m + omb1 * (g - m) ; v' = v + omb2 * (g * g - v) ; w' = w - lr * (m' / (sqrtf(v') + eps))
+//   every operation rounded on its own (torch.optim.SparseAdam's); no reduction, no state outside the row.
+// the step of one element from its new moments: lr * (m / (sqrtf(v) + eps)), division and square root correctly rounded
+__device__ __forceinline__ float adam_delta(float lr, float eps, float m, float v) {
+#pragma clang fp contract(off)
+  const float q = m / (sqrtf(v) + eps);
+  return lr * q;
+}
+
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false>
 __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64_t step_key, int64_t s,
                                            const VT (&g)[NCH], int gl, int G, bool adagrad) {
 #pragma clang fp contract(off)
   using T = Act<WT, VT>;
   static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
+  if constexpr (ADAM) {
+    static_assert(std::is_same<WT, float>::value && sizeof(VT) == 16 && !STOCH, "Adam: an fp32 table, vector lanes");
+    f32x4* R = (f32x4*)a.weight + s * 3 * (int64_t)a.rowlen;      // w: [0, rowlen), m: [rowlen, 2 rowlen), v behind it
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      if (idx >= a.rowlen) continue;
+      const f32x4 gc = g[c];
+      f32x4 w = R[idx], m = R[a.rowlen + idx], v = R[2 * a.rowlen + idx];
+      m = m + (gc - m) * a.omb1;                 // (elementwise, each operation rounded: contraction is off)
+      v = v + (gc * gc - v) * a.omb2;
+      w = w - f32x4{adam_delta(lr, a.eps, m.x, v.x), adam_delta(lr, a.eps, m.y, v.y), adam_delta(lr, a.eps, m.z, v.z),
+                    adam_delta(lr, a.eps, m.w, v.w)};
+      R[idx] = w;
+      R[a.rowlen + idx] = m;
+      R[2 * a.rowlen + idx] = v;
+    }
+    return;
+  }
   typename T::V* W = (typename T::V*)a.weight + s * a.rowlen;
   const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
   float mult = lr;
@@ -225,6 +268,25 @@ __global__ __launch_bounds__(256) void k_mark_slots(const int64_t* __restrict__ 
   }
 }
 
+// k_mark_slots for Adam, where a row that is merely flagged CHANGES (its moments decay): only the lookups some bag covers
+// -- positions [offsets[0], end of the last bag) -- flag their slot.  The counter is the caller's step count.
+__global__ __launch_bounds__(256) void k_mark_slots_covered(const int64_t* __restrict__ slots, int64_t n,
+                                                            uint32_t num_rows, const void* __restrict__ offsets,
+                                                            int off64, int64_t num_bags, int include_last,
+                                                            uint8_t* __restrict__ flags, unsigned long long* counter) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
+  int64_t lo = off64 ? ((const int64_t*)offsets)[0] : ((const int32_t*)offsets)[0];
+  int64_t hi = n;
+  if (include_last) hi = off64 ? ((const int64_t*)offsets)[num_bags] : ((const int32_t*)offsets)[num_bags];
+  if (lo < 0) lo = 0;
+  if (hi > n) hi = n;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += stride) {
+    const int64_t s = slots[i];
+    if (s >= 0 && s < (int64_t)num_rows) flags[s] = 1;
+  }
+}
+
 // source-row keys (row << 32 | grad_out row); row 0xffffffff = ignored lookup / padding of the last segment
 __global__ __launch_bounds__(256) void k_mark_keys(const unsigned long long* __restrict__ keys, int64_t n,
                                                    uint32_t num_rows, uint8_t* __restrict__ flags,
@@ -246,12 +308,12 @@ struct ApplyArgs {
 
 // a wave reads 64 flags at once, and a lane group per flagged slot reads acc, updates the row and writes acc and the
 // flag back to zero
-template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH>
+template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH, bool ADAM = false>
 __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
   const LaneGroup l = lane_group(a.u.g_log2);
   VT* A = (VT*)a.acc;
   const uint64_t key = step_key<STOCH>(a.u);
-  const float lr = learning_rate(a.u);
+  const float lr = ADAM ? adam_step_size(a.u) : learning_rate(a.u);
   for (int64_t base = l.wave * 64; base < (int64_t)a.num_rows; base += l.nwaves * 64) {
     const int64_t mine = base + l.lane;
     const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
@@ -259,7 +321,7 @@ __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
       const int64_t s = base + i;
       VT g[NCH];
       load_row(g, A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
-      update_row<VT, WT, NCH, STOCH>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD);
+      update_row<VT, WT, NCH, STOCH, ADAM>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD);
       zero_row<VT, NCH>(A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
     });
     if (flagged) a.flags[mine] = 0;
@@ -601,7 +663,7 @@ struct CompactArgs {
 };
 
 // one lane group per list entry (grid-stride over u < U; the grid is sized by cap)
-template <typename VT, typename WT, int NCH, bool STOCH>
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false>
 __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   const int G = 1 << a.u.g_log2;
   const int gl = threadIdx.x & (G - 1);
@@ -610,11 +672,11 @@ __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   VT* A = (VT*)a.acc;
   const int64_t n = *a.n_list;
   const uint64_t key = step_key<STOCH>(a.u);
-  const float lr = learning_rate(a.u);
+  const float lr = ADAM ? adam_step_size(a.u) : learning_rate(a.u);
   for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
     VT g[NCH];
     load_row(g, A + u * a.u.rowlen, gl, G, a.u.rowlen);
-    update_row<VT, WT, NCH, STOCH>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad);
+    update_row<VT, WT, NCH, STOCH, ADAM>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad);
     zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
   }
 }
@@ -697,6 +759,8 @@ static CompactWs carve_compact(void* ws, int64_t num_rows, int64_t nnz, int32_t 
   return w;
 }
 
+constexpr int32_t kOptAdam = 2;       // beside CE_OPT_*: library-internal, no `optimizer` argument takes it
+
 // the arguments every update entry has (the fp32 Adagrad entries: CE_ACT_F32, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST)
 struct UpdateCall {
   void* weight;
@@ -715,8 +779,13 @@ struct UpdateCall {
   void* workspace;
   size_t workspace_bytes;
   const float* lr_dev = nullptr;      // the ce_*_lrdev entries: the learning rate in device memory (`lr` is then 0)
+  // the ce_bag_backward_adam* entries (optimizer = kOptAdam, an fp32 table of rows w | m | v): the caller's step count
+  // takes the place of the workspace's counter
+  unsigned long long* step = nullptr;
+  double beta1 = 0.0, beta2 = 0.0;
   bool w16() const { return weight_dtype != CE_ACT_F32; }
   bool adagrad() const { return optimizer == CE_OPT_ROWWISE_ADAGRAD; }
+  bool adam() const { return optimizer == kOptAdam; }
   bool stochastic() const { return rounding == CE_ROUND_STOCHASTIC; }
 };
 
@@ -734,6 +803,10 @@ static UpdateArgs update_args(const UpdateCall& c, const RowGeom& r, const unsig
   u.lr = c.lr;
   u.eps = c.eps;
   u.lr_dev = c.lr_dev;
+  u.beta1 = c.beta1;
+  u.beta2 = c.beta2;
+  u.omb1 = (float)(1.0 - c.beta1);
+  u.omb2 = (float)(1.0 - c.beta2);
   return u;
 }
 
@@ -791,25 +864,53 @@ static void launch_mark(const void* src, bool keys, int64_t n, int64_t num_rows,
     hipLaunchKernelGGL(k_mark_slots, g, b, 0, s, (const int64_t*)src, n, (uint32_t)num_rows, flags, counter);
 }
 
+// the lookups of the slots + offsets entries
+struct SlotLookups {
+  const int64_t* indices;
+  const void* offsets;
+  int32_t off64;
+  int64_t num_bags;
+  int32_t include_last;
+  const float* psw;
+  int32_t mode;
+  int64_t hookF;
+  const uint64_t* presorted;
+};
+
+// the mark pass of a call: the slots of L (Adam: of the lookups a bag covers) or, L == NULL, the row halves of `keys`
+static void launch_mark_call(const UpdateCall& c, const SlotLookups* L, const void* keys, int64_t n, uint8_t* flags,
+                             unsigned long long* counter, hipStream_t s) {
+  if (L && c.adam())
+    hipLaunchKernelGGL(k_mark_slots_covered, dim3(grid_for(n, 256)), dim3(256), 0, s, L->indices, n,
+                       (uint32_t)c.num_rows, L->offsets, (int)L->off64, L->num_bags, (int)L->include_last, flags, counter);
+  else
+    launch_mark(L ? (const void*)L->indices : keys, !L, n, c.num_rows, flags, counter, s);
+}
+
 // The cache-sized update after its check: mark `n` slots / keys of `src`, scatter(acc) = the caller's dense backward,
 // apply.  An fp32 table is row-wise Adagrad with its rows stored as they are; a 16-bit table takes either optimizer and
 // either rounding.
 template <typename Scatter>
-static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const void* src, bool keys, int64_t n,
+static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const SlotLookups* L, const void* keys, int64_t n,
                               hipStream_t s, Scatter&& scatter) {
   const ApplyWs ws = carve_apply(c.workspace, c.num_rows, c.dim, c.w16());
-  launch_mark(src, keys, n, c.num_rows, ws.flags, ws.counter, s);
+  unsigned long long* counter = c.adam() ? c.step : ws.counter;
+  launch_mark_call(c, L, keys, n, ws.flags, counter, s);
   CE_LAUNCH_CHECK();
   int rc = scatter(ws.acc);
   if (rc) return rc;
   ApplyArgs a{};
-  a.u = update_args(c, r, ws.counter);
+  a.u = update_args(c, r, counter);
   a.acc = ws.acc;
   a.flags = ws.flags;
   a.num_rows = (uint32_t)c.num_rows;
   const dim3 g(grid_for(cdiv(c.num_rows, 64), 4)), b(256);
   const bool ada = c.adagrad(), st = c.stochastic();
-  for_table(c.weight_dtype, r, [&](auto l, auto w) {
+  if (c.adam())
+    for_vec_lanes(r.nch, [&](auto l) {
+      hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true>), g, b, 0, s, a);
+    });
+  else for_table(c.weight_dtype, r, [&](auto l, auto w) {
     using VT = typename decltype(l)::VT;
     using WT = typename decltype(w)::AT;
     constexpr int N = decltype(l)::NCH;
@@ -835,13 +936,17 @@ static int launch_compact_scan(int64_t num_rows, const CompactWs& ws, hipStream_
 
 static int launch_compact_apply(const UpdateCall& c, const RowGeom& r, const CompactWs& ws, hipStream_t s) {
   CompactArgs a{};
-  a.u = update_args(c, r, ws.counter);
+  a.u = update_args(c, r, c.adam() ? c.step : ws.counter);
   a.acc = ws.acc;
   a.list = ws.list;
   a.n_list = ws.n_list;
   a.adagrad = c.adagrad();
   const dim3 g(grid_for(ws.cap, 256 >> r.g_log2)), b(256);
-  for_table(c.weight_dtype, r, [&](auto l, auto w) {
+  if (c.adam())
+    for_vec_lanes(r.nch, [&](auto l) {
+      hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true>), g, b, 0, s, a);
+    });
+  else for_table(c.weight_dtype, r, [&](auto l, auto w) {
     using VT = typename decltype(l)::VT;
     using WT = typename decltype(w)::AT;
     constexpr int N = decltype(l)::NCH;
@@ -880,19 +985,6 @@ static EntryRules compact_rules(const UpdateCall& c) {
           [](int64_t R, int64_t n, int32_t D) { return carve_compact(nullptr, R, n, D).bytes; }};
 }
 
-// the lookups of the slots + offsets entries
-struct SlotLookups {
-  const int64_t* indices;
-  const void* offsets;
-  int32_t off64;
-  int64_t num_bags;
-  int32_t include_last;
-  const float* psw;
-  int32_t mode;
-  int64_t hookF;
-  const uint64_t* presorted;
-};
-
 // the dense backward of the call's lookups into acc[rows, dim], reading `idx` / `keys` in place of the caller's
 static int scatter_slots(float* acc, int64_t rows, const UpdateCall& c, const SlotLookups& L, const int64_t* idx,
                          const uint64_t* keys, ce_stream_t stream) {
@@ -912,7 +1004,7 @@ static int adagrad_fp32_slots(const UpdateCall& c, const SlotLookups& L, ce_stre
   int rc = update_check(c, fp32_rules(c), r);
   if (rc) return rc;
   CE_REQUIRE(L.indices && L.offsets, CE_ERR_INVALID, "null pointer");
-  return update_cache_sized(c, r, L.indices, false, c.nnz, (hipStream_t)stream, [&](float* acc) {
+  return update_cache_sized(c, r, &L, nullptr, c.nnz, (hipStream_t)stream, [&](float* acc) {
     return scatter_slots(acc, c.num_rows, c, L, L.indices, L.presorted, stream);
   });
 }
@@ -924,7 +1016,7 @@ static int adagrad_fp32_src(const UpdateCall& c, const uint64_t* src_keys, ce_st
   int rc = update_check(c, fp32_rules(c), r);
   if (rc) return rc;
   CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
-  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(c.nnz), (hipStream_t)stream, [&](float* acc) {
+  return update_cache_sized(c, r, nullptr, src_keys, ce_bag_presort_len(c.nnz), (hipStream_t)stream, [&](float* acc) {
     return ce_bag_backward_dense_src_act(acc, c.num_rows, c.dim, c.nnz, c.grad_out, c.act, src_keys, stream);
   });
 }
@@ -942,7 +1034,7 @@ static int update_w16_slots(const UpdateCall& c, const SlotLookups& L, ce_stream
              "mode must be sum, or mean without per_sample_weights");
   CE_REQUIRE(L.hookF >= 0 && (L.hookF == 0 || L.num_bags % L.hookF == 0), CE_ERR_INVALID,
              "hook_features must divide num_bags");
-  return update_cache_sized(c, r, L.indices, false, c.nnz, (hipStream_t)stream, [&](float* acc) {
+  return update_cache_sized(c, r, &L, nullptr, c.nnz, (hipStream_t)stream, [&](float* acc) {
     return scatter_slots(acc, c.num_rows, c, L, L.indices, L.presorted, stream);
   });
 }
@@ -953,16 +1045,14 @@ static int update_w16_src(const UpdateCall& c, const uint64_t* src_keys, ce_stre
   if (rc) return rc;
   if (c.nnz == 0) return CE_OK;
   CE_REQUIRE(src_keys && c.nnz > 0 && c.nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "null keys or nnz out of range");
-  return update_cache_sized(c, r, src_keys, true, ce_bag_presort_len(c.nnz), (hipStream_t)stream, [&](float* acc) {
+  return update_cache_sized(c, r, nullptr, src_keys, ce_bag_presort_len(c.nnz), (hipStream_t)stream, [&](float* acc) {
     return ce_bag_backward_dense_src_act(acc, c.num_rows, c.dim, c.nnz, c.grad_out, c.act, src_keys, stream);
   });
 }
 
 // step-sized accumulator: mark, compact, remap, the dense backward into acc[cap, D], apply over the list
-static int update_compact_slots(const UpdateCall& c, const SlotLookups& L, ce_stream_t stream) {
-  RowGeom r;
-  int rc = update_check(c, compact_rules(c), r);
-  if (rc) return rc;
+static int compact_slots_run(const UpdateCall& c, const RowGeom& r, const SlotLookups& L, ce_stream_t stream) {
+  int rc;
   if (L.num_bags == 0 || c.nnz == 0) return CE_OK;
   CE_REQUIRE(L.indices && L.offsets, CE_ERR_INVALID, "null pointer");
   CE_REQUIRE(L.num_bags > 0 && L.num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "sizes out of range");
@@ -972,7 +1062,7 @@ static int update_compact_slots(const UpdateCall& c, const SlotLookups& L, ce_st
              "hook_features must divide num_bags");
   hipStream_t s = (hipStream_t)stream;
   const CompactWs ws = carve_compact(c.workspace, c.num_rows, c.nnz, c.dim);
-  launch_mark(L.indices, false, c.nnz, c.num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
+  launch_mark_call(c, &L, nullptr, c.nnz, ws.flags, c.adam() ? c.step : (c.w16() ? ws.counter : nullptr), s);
   rc = launch_compact_scan(c.num_rows, ws, s);
   if (rc) return rc;
   // segment-sorted keys hold the rows themselves: with them the scatter never reads `indices`, so only they are remapped
@@ -995,16 +1085,21 @@ static int update_compact_slots(const UpdateCall& c, const SlotLookups& L, ce_st
   return launch_compact_apply(c, r, ws, s);
 }
 
-static int update_compact_src(const UpdateCall& c, const uint64_t* src_keys, ce_stream_t stream) {
+static int update_compact_slots(const UpdateCall& c, const SlotLookups& L, ce_stream_t stream) {
   RowGeom r;
   int rc = update_check(c, compact_rules(c), r);
   if (rc) return rc;
+  return compact_slots_run(c, r, L, stream);
+}
+
+static int compact_src_run(const UpdateCall& c, const RowGeom& r, const uint64_t* src_keys, ce_stream_t stream) {
+  int rc;
   if (c.nnz == 0) return CE_OK;
   CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
   hipStream_t s = (hipStream_t)stream;
   const CompactWs ws = carve_compact(c.workspace, c.num_rows, c.nnz, c.dim);
   const int64_t total = ce_bag_presort_len(c.nnz);
-  launch_mark(src_keys, true, total, c.num_rows, ws.flags, c.w16() ? ws.counter : nullptr, s);
+  launch_mark_call(c, nullptr, src_keys, total, ws.flags, c.adam() ? c.step : (c.w16() ? ws.counter : nullptr), s);
   rc = launch_compact_scan(c.num_rows, ws, s);
   if (rc) return rc;
   hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
@@ -1014,6 +1109,56 @@ static int update_compact_src(const UpdateCall& c, const uint64_t* src_keys, ce_
   rc = ce_bag_backward_dense_src_act(ws.acc, ws.cap, c.dim, c.nnz, c.grad_out, c.act, (const uint64_t*)ws.remap, stream);
   if (rc) return rc;
   return launch_compact_apply(c, r, ws, s);
+}
+
+static int update_compact_src(const UpdateCall& c, const uint64_t* src_keys, ce_stream_t stream) {
+  RowGeom r;
+  int rc = update_check(c, compact_rules(c), r);
+  if (rc) return rc;
+  return compact_src_run(c, r, src_keys, stream);
+}
+
+// ---- Adam (ce_bag_backward_adam / _adam_src): an fp32 table whose rows are w | m | v.  Either
+// accumulator's pipeline as it stands -- the accumulators are [., dim] as for any fp32 table -- with the mark pass
+// counting the caller's step and update_row's Adam arithmetic in the apply pass.
+
+static size_t adam_workspace(int64_t num_rows, int64_t nnz, int32_t dim, int32_t accumulator) {
+  return accumulator == CE_ACC_STEP ? carve_compact(nullptr, num_rows, nnz, dim).bytes
+                                    : carve_apply(nullptr, num_rows, dim, false).bytes;
+}
+
+// Everything an Adam entry refuses, from the arguments alone, before its first launch and before any HIP call; the
+// order is the header's.  r: the lane shape of the apply pass (vector lanes: the dim rule and the alignment see to it).
+static int adam_check(const UpdateCall& c, int32_t accumulator, RowGeom& r) {
+  CE_REQUIRE(c.step, CE_ERR_INVALID, "step: null device pointer");
+  CE_REQUIRE(accumulator == CE_ACC_CACHE || accumulator == CE_ACC_STEP, CE_ERR_INVALID,
+             "unknown accumulator %d (CE_ACC_CACHE / CE_ACC_STEP)", (int)accumulator);
+  CE_REQUIRE(c.beta1 >= 0.0 && c.beta1 < 1.0 && c.beta2 >= 0.0 && c.beta2 < 1.0, CE_ERR_INVALID,
+             "beta1 and beta2 must lie in [0, 1)");
+  CE_REQUIRE(c.eps >= 0.f, CE_ERR_INVALID, "eps must be >= 0");
+  CE_REQUIRE(c.lr_dev || c.lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
+  CE_REQUIRE_ACT(c.act);
+  CE_REQUIRE_ADAM_DIM(c.dim);
+  CE_REQUIRE(c.weight && c.grad_out && c.workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(c.num_rows > 0 && c.num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE(c.nnz >= 0 && c.nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "nnz out of range");
+  CE_REQUIRE(al16(c.weight) && (((uintptr_t)c.step) & 7) == 0, CE_ERR_INVALID,
+             "an Adam-layout table must be 16-byte aligned (and step 8-byte aligned)");
+  CE_REQUIRE((((uintptr_t)c.workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
+  CE_REQUIRE(c.workspace_bytes >= adam_workspace(c.num_rows, c.nnz, c.dim, accumulator), CE_ERR_INVALID,
+             "workspace too small");
+  return row_geometry(c.dim, true, r);
+}
+
+static UpdateCall adam_call(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act,
+                            double beta1, double beta2, float lr, const float* lr_dev, float eps, int64_t* step,
+                            void* workspace, size_t workspace_bytes) {
+  UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act, nullptr, nullptr, 0, lr_dev ? 0.f : lr, eps,
+               kOptAdam, CE_ROUND_NEAREST, 0, workspace, workspace_bytes, lr_dev};
+  c.step = (unsigned long long*)step;
+  c.beta1 = beta1;
+  c.beta2 = beta2;
+  return c;
 }
 
 // Which covered entry a ce_*_lrdev call is, from its accumulator and its table; `run` gets the call as that entry
@@ -1299,4 +1444,56 @@ extern "C" int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype,
   }
   CE_LAUNCH_CHECK();
   return CE_OK;
+}
+
+// ---- Adam on an Adam-layout table (rows w | m | v)
+
+extern "C" size_t ce_bag_backward_adam_workspace(int64_t num_rows, int64_t nnz, int32_t dim, int32_t accumulator) {
+  if (num_rows < 0 || num_rows >= (int64_t)INT32_MAX || nnz < 0 || nnz >= (int64_t)INT32_MAX || dim < 0) return 0;
+  if (accumulator != CE_ACC_CACHE && accumulator != CE_ACC_STEP) return 0;
+  return adam_workspace(num_rows, nnz, dim, accumulator);
+}
+
+extern "C" int ce_bag_backward_adam(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                    const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                    int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                    int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                    const uint64_t* presorted, double beta1, double beta2, float lr, const float* lr_dev,
+                                    float eps, int64_t* step, int32_t accumulator, void* workspace,
+                                    size_t workspace_bytes, ce_stream_t stream) {
+  const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
+                                 workspace, workspace_bytes);
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, presorted};
+  RowGeom r;
+  int rc = adam_check(c, accumulator, r);
+  if (rc) return rc;
+  if (accumulator == CE_ACC_STEP) return compact_slots_run(c, r, L, stream);
+  if (num_bags == 0 || nnz == 0) return CE_OK;
+  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(num_bags > 0 && num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "sizes out of range");
+  CE_REQUIRE(mode == CE_MODE_SUM || (mode == CE_MODE_MEAN && !per_sample_weights), CE_ERR_INVALID,
+             "mode must be sum, or mean without per_sample_weights");
+  CE_REQUIRE(hook_features >= 0 && (hook_features == 0 || num_bags % hook_features == 0), CE_ERR_INVALID,
+             "hook_features must divide num_bags");
+  return update_cache_sized(c, r, &L, nullptr, nnz, (hipStream_t)stream, [&](float* acc) {
+    return scatter_slots(acc, num_rows, c, L, indices, presorted, stream);
+  });
+}
+
+extern "C" int ce_bag_backward_adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out,
+                                        int32_t act_dtype, const uint64_t* src_keys, double beta1, double beta2, float lr,
+                                        const float* lr_dev, float eps, int64_t* step, int32_t accumulator,
+                                        void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
+                                 workspace, workspace_bytes);
+  RowGeom r;
+  int rc = adam_check(c, accumulator, r);
+  if (rc) return rc;
+  if (accumulator == CE_ACC_STEP) return compact_src_run(c, r, src_keys, stream);
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
+  return update_cache_sized(c, r, nullptr, src_keys, ce_bag_presort_len(nnz), (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_src_act(acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
+  });
 }

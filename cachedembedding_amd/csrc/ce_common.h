@@ -171,6 +171,12 @@ static inline int w16_check(int32_t weight_dtype, int32_t dim) {
   return CE_OK;
 }
 
+// An ADAM-LAYOUT table (ce_*_adam): fp32 rows w | m | v of 3 * dim elements whose three parts are whole 16-byte
+// units, vector lanes only.  The argument alone decides.
+#define CE_REQUIRE_ADAM_DIM(dim)                                                                 \
+  CE_REQUIRE((dim) % 4 == 0 && (dim) >= 4 && (dim) <= 1024, CE_ERR_UNSUPPORTED,                  \
+             "an Adam-layout table needs dim %% 4 == 0 and 4 <= dim <= 1024 (got %d)", (int)(dim))
+
 // The one place that turns the run-time lane shape and activation code into template arguments: f is a generic lambda
 // and gets a tag to read the types from (typename decltype(l)::VT, decltype(l)::NCH, typename decltype(a)::AT).
 template <typename VT_, int NCH_> struct Lanes {

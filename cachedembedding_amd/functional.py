@@ -71,6 +71,7 @@ class _BagFn(torch.autograd.Function):
         _lib.require_gpu()
         w16 = weight.dtype in _lib.W16_DTYPES
         assert weight.is_cuda and (w16 or weight.dtype == torch.float32) and weight.is_contiguous()
+        adam = isinstance(fused, FusedAdam)      # the weight is then [rows, 3 * D]: w | m | v
         if psw is not None and ctx.needs_input_grad[3] and fused is not None and fused.lr is not None:
             # d loss / d per_sample_weights[j] = <grad_out[bag of j], weight[indices[j]]> needs the rows as the forward
             # saw them, and the fused update moves them inside backward: refused HERE, before any kernel has run (a
@@ -78,7 +79,7 @@ class _BagFn(torch.autograd.Function):
             raise NotImplementedError("gradient w.r.t. per_sample_weights with the fused SGD / row-wise Adagrad "
                                       "update")
         num_bags = offsets.numel() - 1 if include_last else offsets.numel()
-        dim = weight.shape[1]
+        dim = weight.shape[1] // 3 if adam else weight.shape[1]
         shape = (num_bags // hook_features, hook_features, dim) if hook_features else (num_bags, dim)
         if out_box is not None:
             # the caller's buffer (embedding_bag(out=...)): a static output for graph-captured steps, or one chosen by
@@ -105,6 +106,10 @@ class _BagFn(torch.autograd.Function):
             # fp32 sums, one rounding on the store; from keys with out_dtype == the table's dtype: a bit copy)
             fn = lib.ce_bag_forward_src_keys_w16 if from_keys else lib.ce_bag_forward_w16
             check(fn(ptr(weight), _lib.ACT_DTYPES[weight.dtype], weight.shape[0], dim, *args))
+        elif adam:
+            # the fp32 kernels with the Adam row type: the w part of every row, the rows three times as far apart
+            fn = lib.ce_bag_forward_src_keys_adam if from_keys else lib.ce_bag_forward_adam
+            check(fn(ptr(weight), weight.shape[0], dim, *args))
         else:
             fn = lib.ce_bag_forward_src_keys_act if from_keys else lib.ce_bag_forward_act
             check(fn(ptr(weight), weight.shape[0], dim, *args))
@@ -122,13 +127,38 @@ class _BagFn(torch.autograd.Function):
         weight = ctx.weight
         mode, include_last, hook_features, sparse, fused, num_bags = ctx.args
         grad_out = grad_out.contiguous()
-        dim = weight.shape[1]
+        adam = isinstance(fused, FusedAdam)
+        if adam and fused.lr is None:
+            raise RuntimeError("backward through an Adam-layout table with no fused Adam set: an autograd gradient in "
+                               "slot space over 3 * D columns means nothing (set_fused_adam(lr) first, or run the "
+                               "forward under torch.no_grad())")
+        dim = weight.shape[1] // 3 if adam else weight.shape[1]
         off64 = int(offsets.dtype == torch.int64)
         nnz = indices.numel()
         R = weight.shape[0]
         gw = None
         pre = ctx.presorted
         src = isinstance(pre, SrcKeys)
+        if adam:
+            # Adam inside backward (ce_bag_backward_adam*): either accumulator's fold, then one apply pass that updates
+            # w, m and v of every row the step looked up; the step count lives on the device (fused.step)
+            act = _lib.ACT_DTYPES.get(grad_out.dtype)
+            if act is None:
+                raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
+            with torch.no_grad():
+                ws = fused.workspace(R, nnz, dim, weight.device)
+                lr_t = isinstance(fused.lr, torch.Tensor)
+                tail = (float(fused.betas[0]), float(fused.betas[1]), 0.0 if lr_t else float(fused.lr),
+                        ptr(fused.lr) if lr_t else None, float(fused.eps), ptr(fused.step),
+                        _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws), ws.numel(),
+                        stream_ptr())
+                if src:
+                    check(lib.ce_bag_backward_adam_src(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                else:
+                    check(lib.ce_bag_backward_adam(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags,
+                                                   int(include_last), ptr(psw), mode, hook_features, ptr(grad_out), act,
+                                                   ptr(pre), *tail))
+            return (None,) * 14
         rowwise = isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None
         sgd = not rowwise and fused is not None and fused.lr is not None
         # the hot paths -- row-wise Adagrad, fused SGD by atomics, the dense gradient -- read grad_out as it comes
@@ -649,11 +679,69 @@ class FusedRowwiseAdagrad(_CheckedLr):
         return _cached_bytes(self, "_ws", need, device, zero=True)
 
 
+class FusedAdam(_CheckedLr):
+    """Switch for the fused backward + Adam update of one embedding module whose table carries its moments: the weight
+    the kernels see is [rows, 3 * D] fp32, every row w | m | v.  torch.optim.SparseAdam's arithmetic,
+    per step and per UNIQUE row the step looks up, g the sum of the row's gradient rows in the batch, t the step count:
+        m += (1 - beta1) (g - m) ;  v += (1 - beta2) (g g - v) ;
+        w -= lr sqrt(1 - beta2^t) / (1 - beta1^t) * m / (sqrt(v) + eps)
+    Rows no lookup names keep all three parts.  Handing this object to embedding_bag is what says the weight has the
+    layout, so the forward needs it too; lr=None leaves the forward working and makes a backward a RuntimeError.
+
+    step: ONE int64 on the weight's device, zero before the first step; the first kernel of every backward adds 1 to it
+    (a replayed graph counts on).  accumulator: "step" (the default: an fp32 accumulator of min(lookups of the step,
+    rows) rows) or "cache" (one row per row of the weight).  lr may be a tensor, as for FusedSGD (check_lr)."""
+
+    deterministic = False                                   # (the sorted fold has no Adam form)
+    rounding, seed = "nearest", 0
+
+    def __init__(self, lr: Union[float, torch.Tensor, None] = None, betas=(0.9, 0.999), eps: float = 1e-8,
+                 accumulator: str = "step", step: Optional[torch.Tensor] = None, deterministic: bool = False):
+        self.lr = lr
+        self.set(betas, eps, accumulator, deterministic)
+        self.step = step
+        self._ws_step, self._ws_step_key = None, None
+        self._ws = None
+
+    def set(self, betas, eps: float, accumulator: str, deterministic: bool = False) -> None:
+        if deterministic:
+            raise NotImplementedError("fused Adam with deterministic=True: the sorted fold has no Adam form")
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas={tuple(betas)!r}: both must lie in [0, 1)")
+        if not float(eps) >= 0.0:
+            raise ValueError(f"eps={eps!r}: must be >= 0")
+        if accumulator not in ACCUMULATORS:
+            raise ValueError(f"accumulator={accumulator!r}: 'cache' or 'step'")
+        self.betas, self.eps, self.accumulator = (b1, b2), float(eps), accumulator
+
+    def check(self, weight: torch.Tensor) -> None:
+        """refusals that must come before any kernel of the step has run"""
+        if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] % 3 != 0:
+            raise NotImplementedError("FusedAdam needs an fp32 weight of Adam-layout rows, [rows, 3 * embedding_dim] "
+                                      f"(got {tuple(weight.shape)} {weight.dtype})")
+        _lib.check_adam_dim(weight.shape[1] // 3)
+        if self.lr is None:
+            return
+        if not isinstance(self.lr, torch.Tensor) and not float(self.lr) >= 0.0:
+            raise ValueError(f"lr={self.lr!r}: must be >= 0")
+        st = self.step
+        if st is None or not st.is_cuda or st.dtype != torch.int64 or st.numel() != 1 or st.device != weight.device:
+            raise ValueError("fused Adam needs its step count: one int64 element on the weight's device")
+
+    def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
+        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again
+        if self.accumulator == "step":
+            return _workspace_step(self, num_rows, nnz, dim, device)
+        need = lib.ce_bag_backward_adam_workspace(num_rows, nnz, dim, _lib.CE_ACC_CACHE)
+        return _cached_bytes(self, "_ws", need, device, zero=True)
+
+
 def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional[torch.Tensor] = None,
                   max_norm: Optional[float] = None, norm_type: float = 2.0, scale_grad_by_freq: bool = False,
                   mode: str = "mean", sparse: bool = False, per_sample_weights: Optional[torch.Tensor] = None,
                   include_last_offset: bool = False, padding_idx: Optional[int] = None, *,
-                  hook_features: int = 0, fused_sgd: Union[FusedSGD, FusedRowwiseAdagrad, None] = None,
+                  hook_features: int = 0, fused_sgd: Union[FusedSGD, FusedRowwiseAdagrad, FusedAdam, None] = None,
                   presorted: Union[torch.Tensor, SrcKeys, None] = None, masked_indices: bool = False,
                   out: Optional[torch.Tensor] = None, output_dtype: Optional[torch.dtype] = None,
                   quant_bits: int = 8) -> torch.Tensor:
@@ -667,6 +755,20 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     # round once on the store and read the 16-bit gradient in place.  out= must then have that dtype.
     _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
     q8 = weight.dtype == _lib.Q8
+    adam = isinstance(fused_sgd, FusedAdam)
+    if adam:
+        # an Adam-layout table ([R, 3 * D] fp32 rows w | m | v; the FusedAdam object is what says so): what it does not
+        # take is refused here, before any kernel has run
+        fused_sgd.check(weight)
+        for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
+                         ("a gradient w.r.t. per_sample_weights",
+                          per_sample_weights is not None and per_sample_weights.requires_grad
+                          and torch.is_grad_enabled())):
+            if on:
+                raise NotImplementedError(f"{what} with an Adam-layout table")
+        if isinstance(fused_sgd.lr, torch.Tensor) and check_lr(fused_sgd.lr).device != weight.device:
+            raise ValueError(f"the learning-rate tensor is on {fused_sgd.lr.device}, the weight on "
+                             f"{weight.device}: the kernels read it from device memory")
     if q8:
         # a row-wise quantized table ([R, 16 + D] uint8 q8 rows, or [R, 16 + D / 2] q4 rows with quant_bits=4): forward
         # only, the output defaults to fp32.  What it does not take is refused here, before any kernel has run.
@@ -682,7 +784,7 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                           and torch.is_grad_enabled())):
             if on:
                 raise NotImplementedError(f"{what} with a {name} table: it is forward only")
-    elif fused_sgd is not None and fused_sgd.lr is not None:
+    elif not adam and fused_sgd is not None and fused_sgd.lr is not None:
         check_accumulator("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
                           fused_sgd.accumulator, bool(fused_sgd.deterministic), fused_sgd.rounding)
         if fused_sgd.accumulator == "step" and mode == "max":

@@ -128,8 +128,15 @@ class FusedSparseModules(nn.Module):
                  is_dist_dataloader: bool = True, use_lfu_eviction: bool = False, use_tablewise_parallel: bool = False,
                  dataset: Optional[str] = None, fold_hook: bool = False, group=None,
                  output_dtype: Optional[torch.dtype] = None, table_dtype: Optional[torch.dtype] = None,
-                 evict_strategy: Optional[EvictionStrategy] = None):
+                 evict_strategy: Optional[EvictionStrategy] = None, fused_optimizer: Optional[str] = None):
         super().__init__()
+        # fused_optimizer="adam" (addition): an Adam-layout table (CachedEmbeddingBag(fused_optimizer="adam"): the rows
+        # carry Adam's moments).  One process, the plain module: the sharded classes do not take the layout.
+        if fused_optimizer is not None and (use_tablewise_parallel or (
+                torch.distributed.is_initialized() and torch.distributed.get_world_size(group) > 1)):
+            raise NotImplementedError(f"FusedSparseModules(fused_optimizer={fused_optimizer!r}) on several ranks or with "
+                                      "use_tablewise_parallel=True: an Adam-layout table is served by a single-process "
+                                      "CachedEmbeddingBag")
         # evict_strategy (addition): any EvictionStrategy, LRU included; None keeps use_lfu_eviction's meaning
         if evict_strategy is not None and use_lfu_eviction:
             raise ValueError("FusedSparseModules: give evict_strategy or use_lfu_eviction, not both")
@@ -159,6 +166,14 @@ class FusedSparseModules(nn.Module):
                                                              buffer_size=buffer_size, evict_strategy=strategy, group=group)
             self.shape_hook = sparse_embedding_shape_hook_for_tablewise
             self.fold_hook = False
+        elif fused_optimizer is not None:
+            from .cached_embedding import CachedEmbeddingBag
+            self.embed = CachedEmbeddingBag(sum(num_embeddings_per_feature), embedding_dim, sparse=sparse,
+                                            mode=reduction_mode, include_last_offset=True, cache_ratio=cache_ratio,
+                                            ids_freq_mapping=id_freq_map, warmup_ratio=warmup_ratio,
+                                            buffer_size=buffer_size, evict_strategy=strategy, output_dtype=output_dtype,
+                                            table_dtype=table_dtype, fused_optimizer=fused_optimizer)
+            self.shape_hook = sparse_embedding_shape_hook
         else:
             self.embed = ParallelCachedEmbeddingBag(sum(num_embeddings_per_feature), embedding_dim, sparse=sparse,
                                                     mode=reduction_mode, include_last_offset=True,

@@ -1416,6 +1416,9 @@ class ParallelCachedEmbeddingBag(CachedEmbeddingBag):
         self.world_size = dist.get_world_size(self.group) if self.group is not None else 1
         self._refuse_act16(kw.get("output_dtype"))            # before anything is allocated
         _lib.refuse_quantized("ParallelCachedEmbeddingBag", kw.get("table_dtype"))
+        if kw.get("fused_optimizer") is not None:
+            raise NotImplementedError(f"ParallelCachedEmbeddingBag with fused_optimizer={kw.get('fused_optimizer')!r}: an "
+                                      "Adam-layout table is served by a single-process CachedEmbeddingBag")
         if self.world_size > 1 and _lib.table_code(kw.get("table_dtype")) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"ParallelCachedEmbeddingBag with table_dtype={kw.get('table_dtype')} on "
                                       f"{self.world_size} ranks: the all-to-all of the pooled output is fp32")

@@ -69,9 +69,12 @@ class ParallelCachedEmbeddingBagTablewise(nn.Module):
                  mode: str = "mean", include_last_offset: bool = False, dtype=None, device=None,
                  warmup_ratio: float = 0.7, buffer_size: int = 50_000, pin_weight: bool = False,
                  evict_strategy: EvictionStrategy = EvictionStrategy.LFU, group=None, output_dtype=None,
-                 table_dtype=None):
+                 table_dtype=None, fused_optimizer=None):
         super().__init__()
         _lib.refuse_quantized("ParallelCachedEmbeddingBagTablewise", table_dtype)
+        if fused_optimizer is not None:
+            raise NotImplementedError(f"ParallelCachedEmbeddingBagTablewise with fused_optimizer={fused_optimizer!r}: an "
+                                      "Adam-layout table is served by a single-process CachedEmbeddingBag")
         if _lib.table_code(table_dtype) != _lib.CE_ACT_F32:
             raise NotImplementedError(f"ParallelCachedEmbeddingBagTablewise with table_dtype={table_dtype}: the "
                                       "table-wise module keeps fp32 tables")

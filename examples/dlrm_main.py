@@ -113,6 +113,15 @@ def parse_args(argv=None):
                    help="exact row-wise Adagrad for the embedding, fused into backward (FBGEMM's EXACT_ROWWISE_ADAGRAD, "
                         "as baselines/dlrm_main.py:698-702 maps --adagrad), torch.optim.Adagrad for the dense part "
                         "(:799-802); takes the place of --fused_sgd (one process)")
+    p.add_argument("--adam", action="store_true",
+                   help="Adam for the embedding, fused into backward, with the moments carried in the table's rows "
+                        "(CachedEmbeddingBag(fused_optimizer='adam') + set_fused_adam: torch.optim.SparseAdam's "
+                        "arithmetic; the moments travel with the rows between host table and cache), torch.optim.Adam "
+                        "for the dense part.  One process, an fp32 table, without --use_tablewise; not with --adagrad or "
+                        "--fused_sgd")
+    p.add_argument("--adam_beta1", type=float, default=0.9, help="with --adam: beta1 of both Adams")
+    p.add_argument("--adam_beta2", type=float, default=0.999, help="with --adam: beta2 of both Adams")
+    p.add_argument("--eps", type=float, default=1e-8, help="with --adam: eps of both Adams")
     p.add_argument("--adagrad_deterministic", action="store_true",
                    help="with --adagrad: fold a row's gradient in lookup order over the step's sorted lookups instead "
                         "of by atomics -- bit-reproducible, and without the [cache rows, D] fp32 accumulator")
@@ -219,7 +228,7 @@ class HybridParallelDLRM(nn.Module):
             # (a 16-bit table's output would default to the table's dtype: the flag's fp32 stays fp32)
             output_dtype=_OUTPUT_DTYPES[args.embedding_output_dtype] or
             (torch.float32 if args.table_dtype != "fp32" else None),
-            table_dtype=_TABLE_DTYPES[args.table_dtype])
+            table_dtype=_TABLE_DTYPES[args.table_dtype], fused_optimizer="adam" if args.adam else None)
         self.autocast = args.embedding_output_dtype == "bf16"
         dense = DenseModules(args.num_dense_features, len(sizes), args.embedding_dim,
                              [int(x) for x in args.dense_arch_layer_sizes.split(",")],
@@ -360,6 +369,9 @@ def make_optimizer(model, args, device, world: int):
         lr_t = torch.full((1,), args.learning_rate, dtype=torch.float32, device=device)
     lr = args.learning_rate if lr_t is None else lr_t
     groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world, "lr_scale": world}]
+    if args.adam:
+        embed.set_fused_adam(lr, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc)
+        return torch.optim.Adam(groups, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps), None
     if args.adagrad:
         embed.set_fused_rowwise_adagrad(lr, deterministic=args.adagrad_deterministic, accumulator=acc)
     elif args.fused_sgd:
@@ -393,7 +405,9 @@ class LrChange:
         for g in self.optimizer.param_groups:
             g["lr"] = new * g.get("lr_scale", 1)
         acc = "step" if args.step_accumulator else "cache"
-        if args.adagrad:
+        if args.adam:
+            self.embed.set_fused_adam(new, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc)
+        elif args.adagrad:
             self.embed.set_fused_rowwise_adagrad(new, deterministic=args.adagrad_deterministic, accumulator=acc)
         elif args.fused_sgd:
             self.embed.set_fused_sgd(new, accumulator=acc)
@@ -463,8 +477,8 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None, lr_
     embed = model.sparse_modules.embed
     layout = None
     if args.window_keys:
-        if not ((args.fused_sgd or args.adagrad) and args.fold_hook) or world > 1:
-            raise ValueError("--window_keys needs --fused_sgd (or --adagrad) --fold_hook (one process)")
+        if not ((args.fused_sgd or args.adagrad or args.adam) and args.fold_hook) or world > 1:
+            raise ValueError("--window_keys needs --fused_sgd (or --adagrad, or --adam) --fold_hook (one process)")
         F = model.sparse_modules.sparse_feature_num
         offsets = torch.arange(F * args.batch_size + 1, dtype=torch.int32, device=device)     # one id per bag (KJT lengths = 1)
         layout = (offsets, True, F)
@@ -475,7 +489,7 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None, lr_
     train.window = win
     graphed = None
     train.graph_captures = 0
-    if args.graph_step and (world > 1 or not ((args.fused_sgd or args.adagrad) and args.fold_hook)):
+    if args.graph_step and (world > 1 or not ((args.fused_sgd or args.adagrad or args.adam) and args.fold_hook)):
         raise ValueError("--graph_step needs --fused_sgd (or --adagrad) --fold_hook and one process (DDP's bucket hooks "
                          "and the sparse "
                          "COO gradient of the unfused path are not captured)")
@@ -618,6 +632,8 @@ def _evaluate(model, loader, stage, args, device, rank, world):
 def check_step_accumulator(args):
     """--step_accumulator: refused here, before a device is touched, with the library's own refusals"""
     from cachedembedding_amd.functional import check_accumulator
+    if args.adam:
+        return                                      # (both accumulators serve Adam)
     if not (args.adagrad or args.fused_sgd):
         raise ValueError("--step_accumulator sizes the accumulator of a fused update: pass --adagrad, or --fused_sgd "
                          "with a 16-bit --table_dtype")
@@ -657,6 +673,19 @@ def main(argv=None):
         if world > 1 or args.use_tablewise:
             raise NotImplementedError("--eval_q4 is implemented for one process without --use_tablewise (the sharded "
                                       "classes do not take a q4 table)")
+    if args.adam:
+        if args.adagrad or args.fused_sgd:
+            raise ValueError("--adam takes the place of --adagrad and of --fused_sgd: pass one of them")
+        if world > 1 or args.use_tablewise:
+            raise NotImplementedError("--adam is implemented for one process without --use_tablewise (the sharded "
+                                      "classes do not take an Adam-layout table)")
+        if args.table_dtype != "fp32":
+            raise NotImplementedError("--adam needs --table_dtype fp32: the Adam layout is an fp32 table")
+        if args.use_sparse_embed_grad:
+            raise NotImplementedError("--adam with --use_sparse_embed_grad: the fused update hands torch no gradient")
+        if args.graph_step and args.change_lr:
+            raise NotImplementedError("--adam with --graph_step --change_lr: torch.optim.Adam of the dense part reads "
+                                      "its rate on the host")
     if args.adagrad:
         if args.fused_sgd:
             raise ValueError("--adagrad takes the place of --fused_sgd: pass one of them")

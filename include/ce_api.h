@@ -564,6 +564,78 @@ int ce_bag_backward_update_src_lrdev(void* weight, int32_t weight_dtype, int64_t
                                      const float* lr, float eps, int32_t optimizer, int32_t rounding, uint64_t seed,
                                      int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
+/* Fused Adam with the moments carried in the row, layout `adam` (additions to API 6).  Adam's two moments are as large
+ * as the table, so they cannot stay in HBM beside a cache of 1 % of it: they live where the table lives and travel
+ * with the rows.  An fp32 table only.  A row of `dim` elements is 3 * dim floats:
+ *   w[0 .. dim) | m[dim .. 2 dim) | v[2 dim .. 3 dim)        (weights, first moment, second moment)
+ * dim % 4 == 0, 4 <= dim <= 1024 and the table 16-byte aligned, so all three parts of every row start on a 16-byte
+ * boundary and only the vector lane form exists (the cache op, which only moves rows, is driven with embedding_dim =
+ * 3 * dim: the moments survive eviction and admission with no cache kernel knowing of them).  Any other dim:
+ * CE_ERR_UNSUPPORTED before any launch.  `weight` is [num_rows, 3 * dim] in every entry below; `dim` stays D.
+ *
+ * ce_host_fill_uniform_adam: row r's w part = what ce_host_fill_uniform gives row r of an [n_rows, dim] table for the
+ * same (lo, hi, seed) -- element r * dim + d of that fill --, its moments zero.  Host memory, no GPU; the result does
+ * not depend on `threads`.
+ *
+ * The two forwards are ce_bag_forward_act / ce_bag_forward_src_keys_act in every respect but the row type (the same
+ * kernels with a row stride of three rows' width): they read the w part alone -- sum / mean, per-sample weights,
+ * hook_features, int32 / int64 / NULL offsets, act_dtype, a zero row for an ignored key; capture-safe; the dim rule,
+ * then null pointers, then misalignment (the table 16 bytes, `out` its vector boundary) are refused before the first
+ * launch.  The result is bit-equal to the fp32 sibling's over a contiguous copy of the w parts.
+ *
+ * ce_bag_backward_adam (slots + offsets, optional segment-sorted keys) and ce_bag_backward_adam_src (source-row keys)
+ * take the lists of ce_bag_backward_update_lrdev / _src_lrdev without weight_dtype, row_of_slot, momentum,
+ * momentum_rows, optimizer, rounding and seed, and with beta1, beta2, `float lr` TOGETHER WITH `const float* lr_dev`,
+ * and `int64_t* step`.
+ *   - lr_dev == NULL: the learning rate is `lr`.  Otherwise it points to ONE fp32 in device memory that the kernels
+ *     read when they run, as the ce_*_lrdev entries read theirs, and `lr` is ignored.
+ *   - `step` is ONE int64 in device memory, 8-byte aligned, owned by the caller (zero before the first step).  The
+ *     first launch of a call adds 1 to it; t below is its value after that.  It lives outside the workspace so that it
+ *     outlives it, and on the device so that a replayed graph counts on.
+ *   - accumulator: CE_ACC_CACHE -- the pipeline of ce_bag_backward_rowwise_adagrad* (mark, the dense backward into
+ *     acc[num_rows, dim], one apply pass over the flags) -- or CE_ACC_STEP -- that of ce_bag_backward_update_compact*
+ *     (mark, compaction, rewrite, the dense backward into acc[min(nnz, num_rows), dim], one apply pass over the list).
+ *     Workspace: ce_bag_backward_adam_workspace(num_rows, nnz, dim, accumulator) bytes = what
+ *     ce_bag_backward_rowwise_adagrad_workspace(num_rows, dim) / ce_bag_backward_update_compact_workspace(num_rows,
+ *     nnz, dim) return, 256-byte aligned, with the same contract: zero-filled by its owner once, left zero-filled by
+ *     every call (the step-sized one: flags and acc; its own counter is not used).
+ *   - The arithmetic is torch.optim.SparseAdam's, every operation rounded on its own (no contraction).  For every
+ *     UNIQUE row the call looks up, g its folded gradient of the call:
+ *         omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2)                       (fp64 difference, rounded)
+ *         c_t  = (float)(sqrt(1.0 - pow(beta2, t)) / (1.0 - pow(beta1, t)))              (fp64, on the device)
+ *         m' = m + omb1 * (g - m) ;  v' = v + omb2 * (g * g - v) ;  w' = w - (lr * c_t) * (m' / (sqrtf(v') + eps))
+ *     Rows no lookup names keep w, m and v bit for bit.  Lookups outside [0, num_rows) and lookups no bag covers take
+ *     no part ("Lookups that no bag covers" above) -- the mark pass skips them too, because here a row that is merely
+ *     flagged changes.  A row named only by zero-weight lookups has g = 0 and still decays its moments, as in torch.
+ *     Given the same folded gradient both accumulators write the same bits (one update_row).
+ *   - No host synchronisation, no allocation, launch shapes fixed by the arguments (capture-safe).
+ *   - Refused before the first launch, in this order: step == NULL (CE_ERR_INVALID; the first check), an unknown
+ *     accumulator, a beta outside [0, 1), eps < 0, a by-value lr < 0 (or NaN), an unknown act_dtype, the dim rule
+ *     (CE_ERR_UNSUPPORTED), null pointers and sizes beyond 2^31, misalignment (table 16 bytes, step 8, workspace 256),
+ *     a workspace that is too small; then, for a call with lookups, what the covered pipeline refuses (null indices /
+ *     offsets / keys, mean with per-sample weights, hook_features that does not divide num_bags).
+ *   - nnz == 0 (or num_bags == 0) returns after those checks with no launch: it does not count a step.
+ * Not built: 16-bit moments or tables, the sorted (deterministic) fold, weight decay. */
+int ce_host_fill_uniform_adam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed, int threads);
+int ce_bag_forward_adam(const float* weight, int64_t num_rows, int32_t dim,
+                        const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                        int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                        int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_forward_src_keys_adam(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                 const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+size_t ce_bag_backward_adam_workspace(int64_t num_rows, int64_t nnz, int32_t dim, int32_t accumulator);
+int ce_bag_backward_adam(float* weight, int64_t num_rows, int32_t dim,
+                         const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                         int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                         int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                         const uint64_t* presorted, double beta1, double beta2, float lr, const float* lr_dev,
+                         float eps, int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                         ce_stream_t stream);
+int ce_bag_backward_adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                             const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                             double beta1, double beta2, float lr, const float* lr_dev, float eps, int64_t* step,
+                             int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+
 /* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
  * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
  * A row of `dim` elements is 16 + dim bytes:
