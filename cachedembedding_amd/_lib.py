@@ -41,6 +41,9 @@ CE_SORTED_CHUNK = 64
 CE_COMPACT_BLOCK = 4096
 CE_ACC_CACHE = 0
 CE_ACC_STEP = 1
+CE_WD_NONE = 0
+CE_WD_L2 = 1
+CE_WD_DECOUPLED = 2
 CE_TRANSPORT_ZEROCOPY = 0
 CE_TRANSPORT_STAGED = 1
 CE_TRANSPORT_WORKER = 2
@@ -108,6 +111,17 @@ _LRDEV_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int32, 
                        c_size_t] + _STREAM
 # keys, beta1, beta2, lr, lr_dev, eps, step, accumulator, workspace, workspace_bytes, stream
 _ADAM_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
+# weight decay: `weight_decay, weight_decay_mode` directly behind eps --
+# keys, row_of_slot, momentum, momentum_rows, lr, lr_dev, eps, weight_decay, weight_decay_mode, optimizer, rounding, seed,
+# accumulator, workspace, workspace_bytes, stream
+_WD = [c_float, c_int32]
+_UPDATE_WD_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_float] + _WD + \
+    [c_int32, c_int32, c_uint64, c_int32, c_void_p, c_size_t] + _STREAM
+# row_of_slot, momentum, momentum_rows, lr, eps, weight_decay, weight_decay_mode, optimizer, rounding, seed, workspace, ...
+_SORTED_WD_TAIL = [c_void_p, c_void_p, c_int64, c_float, c_float] + _WD + \
+    [c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
+_ADAM_WD_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD + \
+    [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -188,6 +202,12 @@ SIGNATURES = {
     "ce_bag_backward_adam_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
     "ce_bag_backward_adam": (c_int, _BAG + _ACT + _ADAM_TAIL),
     "ce_bag_backward_adam_src": (c_int, _SRC + _ACT + _ADAM_TAIL),
+    # weight decay (L2 / decoupled, lazy) for the fused updates: the covered lists with the decay behind eps
+    "ce_bag_backward_update_wd": (c_int, _W16 + _BAG[1:] + _ACT + _UPDATE_WD_TAIL),
+    "ce_bag_backward_update_src_wd": (c_int, _W16 + _SRC[1:] + _ACT + _UPDATE_WD_TAIL),
+    "ce_bag_backward_update_sorted_wd": (c_int, _W16 + _BAG[1:] + _ACT + _SORTED_WD_TAIL),
+    "ce_bag_backward_adam_wd": (c_int, _BAG + _ACT + _ADAM_WD_TAIL),
+    "ce_bag_backward_adam_src_wd": (c_int, _SRC + _ACT + _ADAM_WD_TAIL),
     # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
     "ce_q8_row_bytes": (c_size_t, [c_int32]),
     "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),

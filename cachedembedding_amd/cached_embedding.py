@@ -15,7 +15,16 @@ import torch.nn as nn
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
 from .functional import (FusedAdam, FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_lr, check_lr_path,
-                         embedding_bag)
+                         check_weight_decay, check_weight_decay_path, embedding_bag, refuse_weight_decay)
+
+
+def _checked_weight_decay(module, optimizer: str, lr, deterministic: bool, weight_decay, weight_decay_mode) -> float:
+    """the checked decay of a set_fused_* call, with everything it is refused for known at that point"""
+    wd = check_weight_decay(weight_decay, weight_decay_mode)
+    refuse_weight_decay(getattr(module, "_no_weight_decay", None), wd)
+    if lr is not None and wd:
+        check_weight_decay_path(optimizer, module.table_dtype, wd, bool(deterministic), lr, module.mode)
+    return wd
 
 
 def _refuse_q8_update(module, what: str, lr) -> None:
@@ -212,16 +221,23 @@ class CachedEmbeddingBag(nn.Module):
     def set_cache_mgr_async_copy(self, flag: bool):
         self.cache_weight_mgr.set_async_copy(flag)
 
+    # the sharded / table-wise modules name themselves here: their owner-side update (ce_rows_axpy) has no decay
+    _no_weight_decay: Optional[str] = None
+
     def set_fused_sgd(self, lr: Union[float, torch.Tensor, None], deterministic: bool = False,
-                      accumulator: str = "cache"):
+                      accumulator: str = "cache", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
         """Apply SGD(lr) to the cache rows inside backward (K13+K14 fused).  lr=None restores
         the plain autograd behaviour (grad handed to torch.optim).  accumulator="step" (a 16-bit table only): the
         update's fp32 accumulator has a row per lookup of the step at most instead of one per cache row.
         lr may be a tensor (functional.check_lr: one fp32 element on the cache's device): it is kept by reference and
         read by the kernels when they run, so fill_ / copy_ into it changes the rate of the next step -- also of a
-        step replayed from a hipGraph.  Not with deterministic=True."""
+        step replayed from a hipGraph.  Not with deterministic=True.
+        weight_decay / weight_decay_mode ("l2" or "decoupled"; functional.FusedSGD): lazy decay of the rows a step
+        looks up.  An fp32 table takes it with deterministic=True only -- the atomic scatter has no per-row pass --,
+        which is refused here, before the first step."""
         _refuse_q8_update(self, "set_fused_sgd", lr)
         _refuse_adam_layout(self, "set_fused_sgd", lr)
+        wd = _checked_weight_decay(self, "sgd", lr, deterministic, weight_decay, weight_decay_mode)
         if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
@@ -233,11 +249,14 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_sgd.lr = lr
         self.fused_sgd.deterministic = deterministic
         self.fused_sgd.accumulator = accumulator
+        self.fused_sgd.set_weight_decay(wd, weight_decay_mode)
 
     def set_fused_rowwise_adagrad(self, lr: Union[float, torch.Tensor, None], eps: float = 1e-8,
-                                  deterministic: bool = False, accumulator: str = "cache"):
-        """Apply exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0; the reference's baseline
-        --adagrad) to the cache rows inside backward.  The state is one fp32 accumulator per row of the host table,
+                                  deterministic: bool = False, accumulator: str = "cache", *,
+                                  weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
+        """Apply exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD; the reference's baseline --adagrad; with
+        weight_decay / weight_decay_mode "l2" or "decoupled" FBGEMM's L2 / DECOUPLE, lazy: the rows a step looks up
+        decay once, at that step, wherever they sit) to the cache rows inside backward.  The state is one fp32 accumulator per row of the host table,
         `cache_weight_mgr.momentum1` (device, zeroed when first enabled, indexed like `weight`); it stays in HBM and
         never moves with the cache.  lr=None turns the update off (the state is kept).  Exclusive with
         set_fused_sgd(lr).  deterministic=True: the sorted, bit-reproducible fold (FusedRowwiseAdagrad), fp32 and
@@ -249,6 +268,7 @@ class CachedEmbeddingBag(nn.Module):
         lr may be a tensor, as in set_fused_sgd; not with deterministic=True."""
         _refuse_q8_update(self, "set_fused_rowwise_adagrad", lr)
         _refuse_adam_layout(self, "set_fused_rowwise_adagrad", lr)
+        wd = _checked_weight_decay(self, "rowwise_adagrad", lr, deterministic, weight_decay, weight_decay_mode)
         if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
@@ -263,17 +283,21 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_adagrad.eps = float(eps)
         self.fused_adagrad.deterministic = bool(deterministic)
         self.fused_adagrad.accumulator = accumulator
+        self.fused_adagrad.set_weight_decay(wd, weight_decay_mode)
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
 
     def set_fused_adam(self, lr: Union[float, torch.Tensor, None], betas=(0.9, 0.999), eps: float = 1e-8,
-                       accumulator: str = "step", deterministic: bool = False):
+                       accumulator: str = "step", deterministic: bool = False, *, weight_decay: float = 0.0,
+                       weight_decay_mode: str = "l2"):
         """Apply Adam (torch.optim.SparseAdam's arithmetic: only the rows a step looks up move) to the cache rows inside
         backward.  Needs a module built with fused_optimizer="adam": the moments are part of every row, in the host
         table and in the cache, `.exp_avg` / `.exp_avg_sq` after flush(); the step count is `.adam_step` (device).
         lr=None turns the update off (moments and step count are kept; a backward is then a RuntimeError).  lr may be
         a tensor, as in set_fused_sgd.  accumulator: "step" (default) or "cache" -- the size of the fp32 accumulator the
-        step's gradient is folded into; both write the same bits given the same folded gradient.  Exclusive with
+        step's gradient is folded into; both write the same bits given the same folded gradient.  weight_decay with
+        weight_decay_mode "l2" is torch.optim.Adam(weight_decay=), with "decoupled" torch.optim.AdamW, both lazy: the
+        rows a step looks up decay once, at that step (functional.FusedAdam).  Exclusive with
         set_fused_sgd / set_fused_rowwise_adagrad: an Adam-layout module refuses those."""
         if self.fused_optimizer != "adam":
             raise ValueError("set_fused_adam needs a module built with fused_optimizer='adam': Adam's moments live in "
@@ -282,7 +306,9 @@ class CachedEmbeddingBag(nn.Module):
             check_lr(lr)
         elif lr is not None and not float(lr) >= 0.0:
             raise ValueError(f"lr={lr!r}: must be >= 0")
-        self.fused_adam.set(betas, eps, accumulator, deterministic)      # (deterministic=True: not implemented)
+        wd = _checked_weight_decay(self, "adam", lr, False, weight_decay, weight_decay_mode)
+        self.fused_adam.set(betas, eps, accumulator, deterministic, weight_decay=wd,       # (deterministic=True: not
+                            weight_decay_mode=weight_decay_mode)                           # implemented)
         self.fused_adam.lr = lr
 
     def set_weight_rounding(self, rounding: str = "stochastic", seed: int = 0):

@@ -1,6 +1,7 @@
-// Fused optimizer updates of the cached table: exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD, weight_decay = 0;
-// the reference's baseline maps --adagrad to it: baselines/dlrm_main.py:698-702) on fp32, bf16 and fp16 rows, and SGD
-// on bf16 / fp16 rows.  Per step and per UNIQUE row r looked up:
+// Fused optimizer updates of the cached table: exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD; the reference's
+// baseline maps --adagrad to it: baselines/dlrm_main.py:698-702) on fp32, bf16 and fp16 rows, and SGD on bf16 / fp16
+// rows; each, and Adam, also with a lazy weight decay -- L2 or decoupled: the ce_*_wd entries, the WD = true
+// instantiations, DESIGN.md 3.12.  Per step and per UNIQUE row r looked up (without decay):
 //   g = sum of the step's gradient rows of r ;  m[r] += sum_d g[d]^2 / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps)
 // (SGD: W[r] -= lr * g).  "Exact": the non-linear update sees the row's whole gradient of the batch, so duplicate
 // lookups are folded across the whole batch first.  Three ways to fold:
@@ -43,6 +44,9 @@ struct UpdateArgs {
   // Adam only (`weight` is then [num_rows, 3 * D]: w | m | v; `counter` is the caller's step count)
   double beta1, beta2;
   float omb1, omb2;                   // (float)(1.0 - beta): the fp64 difference, rounded once
+  // weight decay (the ce_*_wd entries, the WD = true instantiations): CE_WD_L2 or CE_WD_DECOUPLED
+  float wd;
+  int32_t wd_mode;
 };
 
 // the launch's learning rate: uniform, so a kernel reads it once per thread, at its top, and hands it to update_row
@@ -56,6 +60,11 @@ __device__ __forceinline__ float adam_step_size(const UpdateArgs& a) {
   const float c = (float)(sqrt(1.0 - pow(a.beta2, t)) / (1.0 - pow(a.beta1, t)));
   return learning_rate(a) * c;
 }
+
+// The decoupled decay's factor f = (float)(1.0 - (double)lr * (double)wd), lr the launch's learning rate (Adam: lr, not
+// lr * c_t): uniform like the learning rate -- and read from *lr_dev with it, so a replayed graph follows a schedule in
+// the decay as well -- so a kernel works it out once per thread, at its top.  The L2 form does not look at it.
+__device__ __forceinline__ float decay_factor(float lr, float wd) { return (float)(1.0 - (double)lr * (double)wd); }
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -139,6 +148,12 @@ template <bool STOCH> __device__ __forceinline__ uint64_t step_key(const UpdateA
 //   ADAM (an fp32 table of rows w | m | v, vector lanes; lr is adam_step_size; `adagrad` is not looked at), per element:
 //     m' = m + omb1 * (g - m) ; v' = v + omb2 * (g * g - v) ; w' = w - lr * (m' / (sqrtf(v') + eps))
 //   every operation rounded on its own (torch.optim.SparseAdam's); no reduction, no state outside the row.
+//   WD (weight decay, lazy: the rows a step names decay once, in that step; f is decay_factor), with w = up(W[s]) read
+//   ONCE, before the reduction, and kept in registers up to the store:
+//     CE_WD_L2:        h = g + wd * w per element (the product rounded, then the sum); the update above with h for g
+//                      everywhere -- the sum of squares, the momentum, the moments, the step;
+//     CE_WD_DECOUPLED: w_d = w * f per element; the update above with w_d for w and the raw g.
+//   A slot the Adagrad update does not touch (r outside the momentum) gets no decay either.
 // the step of one element from its new moments: lr * (m / (sqrtf(v) + eps)), division and square root correctly rounded
 __device__ __forceinline__ float adam_delta(float lr, float eps, float m, float v) {
 #pragma clang fp contract(off)
@@ -146,11 +161,12 @@ __device__ __forceinline__ float adam_delta(float lr, float eps, float m, float 
   return lr * q;
 }
 
-template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false>
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false>
 __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64_t step_key, int64_t s,
-                                           const VT (&g)[NCH], int gl, int G, bool adagrad) {
+                                           const VT (&g)[NCH], int gl, int G, bool adagrad, float f = 1.f) {
 #pragma clang fp contract(off)
   using T = Act<WT, VT>;
+  const bool l2 = WD && a.wd_mode == CE_WD_L2;               // uniform
   static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
   if constexpr (ADAM) {
     static_assert(std::is_same<WT, float>::value && sizeof(VT) == 16 && !STOCH, "Adam: an fp32 table, vector lanes");
@@ -159,8 +175,11 @@ __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64
     for (int c = 0; c < NCH; ++c) {
       const int idx = gl + c * G;
       if (idx >= a.rowlen) continue;
-      const f32x4 gc = g[c];
+      f32x4 gc = g[c];
       f32x4 w = R[idx], m = R[a.rowlen + idx], v = R[2 * a.rowlen + idx];
+      if constexpr (WD) {
+        if (l2) gc = gc + w * a.wd; else w = w * f;
+      }
       m = m + (gc - m) * a.omb1;                 // (elementwise, each operation rounded: contraction is off)
       v = v + (gc * gc - v) * a.omb2;
       w = w - f32x4{adam_delta(lr, a.eps, m.x, v.x), adam_delta(lr, a.eps, m.y, v.y), adam_delta(lr, a.eps, m.z, v.z),
@@ -174,8 +193,20 @@ __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64
   typename T::V* W = (typename T::V*)a.weight + s * a.rowlen;
   const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
   float mult = lr;
+  // WD: the row as it was (zero past rowlen, so h is zero there as g is) and hg, the gradient the update sees
+  VT w0[WD ? NCH : 1], hg[WD ? NCH : 1];
+  if constexpr (WD) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      w0[c] = idx < a.rowlen ? T::up(W[idx]) : vzero<VT>();
+      hg[c] = g[c];
+      if (l2) hg[c] = g[c] + w0[c] * a.wd; else w0[c] = w0[c] * f;
+    }
+  }
   if (adagrad) {
-    float ss = lane_sq_sum<WT, NCH>(g);
+    float ss;
+    if constexpr (WD) ss = lane_sq_sum<WT, NCH>(hg); else ss = lane_sq_sum<WT, NCH>(g);
     for (int off = G >> 1; off > 0; off >>= 1) ss = ss + __shfl_xor(ss, off, G);
     if (r < 0 || r >= a.momentum_rows) return;
     const float mr = a.momentum[r] + ss / (float)a.dim;
@@ -188,7 +219,8 @@ __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64
   for (int c = 0; c < NCH; ++c) {
     const int idx = gl + c * G;
     if (idx >= a.rowlen) continue;
-    const VT x = fnma(g[c], mult, T::up(W[idx]));
+    VT x;
+    if constexpr (WD) x = fnma(hg[c], mult, w0[c]); else x = fnma(g[c], mult, T::up(W[idx]));
     if constexpr (STOCH) {
       const uint64_t h = mix64(row_key + (uint64_t)idx);         // 16 bits for each of the chunk's 4 elements
       typename T::V o;
@@ -268,13 +300,14 @@ __global__ __launch_bounds__(256) void k_mark_slots(const int64_t* __restrict__ 
   }
 }
 
-// k_mark_slots for Adam, where a row that is merely flagged CHANGES (its moments decay): only the lookups some bag covers
-// -- positions [offsets[0], end of the last bag) -- flag their slot.  The counter is the caller's step count.
+// k_mark_slots for Adam and for every update with weight decay, where a row that is merely flagged CHANGES (its moments
+// decay, its weights decay): only the lookups some bag covers -- positions [offsets[0], end of the last bag) -- flag
+// their slot.  The counter is the caller's step count (Adam), the workspace's, or NULL.
 __global__ __launch_bounds__(256) void k_mark_slots_covered(const int64_t* __restrict__ slots, int64_t n,
                                                             uint32_t num_rows, const void* __restrict__ offsets,
                                                             int off64, int64_t num_bags, int include_last,
                                                             uint8_t* __restrict__ flags, unsigned long long* counter) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
+  if (counter && blockIdx.x == 0 && threadIdx.x == 0) *counter = *counter + 1;
   int64_t lo = off64 ? ((const int64_t*)offsets)[0] : ((const int32_t*)offsets)[0];
   int64_t hi = n;
   if (include_last) hi = off64 ? ((const int64_t*)offsets)[num_bags] : ((const int32_t*)offsets)[num_bags];
@@ -308,12 +341,13 @@ struct ApplyArgs {
 
 // a wave reads 64 flags at once, and a lane group per flagged slot reads acc, updates the row and writes acc and the
 // flag back to zero
-template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH, bool ADAM = false>
+template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH, bool ADAM = false, bool WD = false>
 __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
   const LaneGroup l = lane_group(a.u.g_log2);
   VT* A = (VT*)a.acc;
   const uint64_t key = step_key<STOCH>(a.u);
   const float lr = ADAM ? adam_step_size(a.u) : learning_rate(a.u);
+  const float f = WD ? decay_factor(learning_rate(a.u), a.u.wd) : 1.f;
   for (int64_t base = l.wave * 64; base < (int64_t)a.num_rows; base += l.nwaves * 64) {
     const int64_t mine = base + l.lane;
     const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
@@ -321,7 +355,7 @@ __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
       const int64_t s = base + i;
       VT g[NCH];
       load_row(g, A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
-      update_row<VT, WT, NCH, STOCH, ADAM>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD);
+      update_row<VT, WT, NCH, STOCH, ADAM, WD>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD, f);
       zero_row<VT, NCH>(A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
     });
     if (flagged) a.flags[mine] = 0;
@@ -359,6 +393,8 @@ struct SortedArgs {
   int32_t rowlen, g_log2, dim, off64, include_last, mode, hookF, hookB, adagrad;
   float lr;
   float eps;
+  float wd;                    // weight decay (the WD = true instantiations): CE_WD_L2 or CE_WD_DECOUPLED
+  int32_t wd_mode;
 };
 
 // first position of the run of `row` that holds position p (rows ascending, rows[p] == row): gallop back, then bisect
@@ -377,11 +413,70 @@ __device__ __forceinline__ int64_t run_start(const int32_t* __restrict__ rows, i
   return hi;
 }
 
-// the update of one row by its lane group: g = the row's whole gradient of the step (zero in chunks past rowlen)
-template <typename VT, typename WT, int NCH>
-__device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s, const VT (&g)[NCH], int gl, int G) {
+// The decay's three uniform values of a sorted launch, worked out once per thread at the top of the kernel.  parked():
+// the same values moved into VECTOR registers.  k_sorted_fold without decay already uses every scalar register the
+// compiler may hand out (NCH = 4: 106), so three more scalars that live across its fold loop would be spilled; a lane
+// has vector registers to spare, and a value the compiler cannot see to be uniform stays in one.
+struct SortedDecay {
+  float wd = 0.f, f = 1.f;     // CE_WD_L2's factor of w in h; CE_WD_DECOUPLED's factor of w (decay_factor of the float lr)
+  int l2 = 0;
+};
+__device__ __forceinline__ float parked(float x) {
+  float v;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(x));
+  return v;
+}
+__device__ __forceinline__ SortedDecay sorted_decay(const SortedArgs& a, bool park) {
+  SortedDecay d;
+  d.wd = a.wd;
+  d.f = decay_factor(a.lr, a.wd);
+  d.l2 = a.wd_mode == CE_WD_L2;
+  if (park) {
+    d.wd = parked(d.wd);
+    d.f = parked(d.f);
+    d.l2 = __float_as_int(parked(__int_as_float(d.l2)));
+  }
+  return d;
+}
+
+// the update of one row by its lane group: g = the row's whole gradient of the step (zero in chunks past rowlen).
+// WD: the decayed update, its terms spelled as update_row spells them (the row read once, before the reduction; f is
+// decay_factor of the float lr) -- a row looked up once gets the bits of the atomic forms.
+template <typename VT, typename WT, int NCH, bool WD = false>
+__device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s, const VT (&g)[NCH], int gl, int G,
+                                                 SortedDecay d = SortedDecay{}) {
   using T = Act<WT, VT>;
   typename T::V* W = (typename T::V*)a.weight;
+  if constexpr (WD) {
+#pragma clang fp contract(off)
+    const bool l2 = d.l2 != 0;
+    const float f = d.f;
+    typename T::V* Ws = W + s * a.rowlen;
+    const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
+    VT w0[NCH], hg[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      w0[c] = idx < a.rowlen ? T::up(Ws[idx]) : vzero<VT>();
+      hg[c] = g[c];
+      if (l2) hg[c] = g[c] + w0[c] * d.wd; else w0[c] = w0[c] * f;
+    }
+    float mult = a.lr;
+    if (a.adagrad) {
+      float ss = lane_sq_sum<WT, NCH>(hg);
+      for (int off = G >> 1; off > 0; off >>= 1) ss = ss + __shfl_xor(ss, off, G);
+      if (r < 0 || r >= a.momentum_rows) return;
+      const float mr = a.momentum[r] + ss / (float)a.dim;
+      mult = a.lr / (sqrtf(mr) + a.eps);
+      if (gl == 0) a.momentum[r] = mr;
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      if (idx < a.rowlen) Ws[idx] = T::down(fnma(hg[c], mult, w0[c]));
+    }
+    return;
+  }
   float ss = lane_sq_sum<WT, NCH>(g);
   const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
   float mult = a.lr;
@@ -405,9 +500,11 @@ __device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s,
 
 // one wave per 64 consecutive sorted positions (grid-stride): every lane finds out whether its position starts a chunk,
 // the chunk heads are handed to the wave's lane groups in rounds (the walk for_each_flagged wraps, written out)
-template <typename VT, typename AT, typename WT, int NCH>
+template <typename VT, typename AT, typename WT, int NCH, bool WD = false>
 __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
   using TA = Act<AT, VT>;
+  SortedDecay dec;
+  if constexpr (WD) dec = sorted_decay(a, true);
   const int G = 1 << a.g_log2;
   const int lane = threadIdx.x & 63;
   const int q = lane >> a.g_log2;
@@ -471,7 +568,7 @@ __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
         }
       }
       if (first && !more) {
-        sorted_apply_row<VT, WT, NCH>(a, (int64_t)row, g, gl, G);
+        sorted_apply_row<VT, WT, NCH, WD>(a, (int64_t)row, g, gl, G, dec);
       } else {
         const int64_t prow = 2 * (p >> 6) + (first ? 1 : 0);
 #pragma unroll
@@ -485,8 +582,10 @@ __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
 }
 
 // the runs of more than one chunk: the head of such a run adds its partial rows in ascending chunk order and applies
-template <typename VT, typename WT, int NCH>
+template <typename VT, typename WT, int NCH, bool WD = false>
 __global__ __launch_bounds__(256) void k_sorted_combine(SortedArgs a) {
+  SortedDecay dec;
+  if constexpr (WD) dec = sorted_decay(a, false);
   const int G = 1 << a.g_log2;
   const int lane = threadIdx.x & 63;
   const int q = lane >> a.g_log2;
@@ -525,7 +624,7 @@ __global__ __launch_bounds__(256) void k_sorted_combine(SortedArgs a) {
           if (idx < a.rowlen) g[c] = g[c] + P[(2 * (t >> 6)) * a.rowlen + idx];
         }
       }
-      sorted_apply_row<VT, WT, NCH>(a, (int64_t)row, g, gl, G);
+      sorted_apply_row<VT, WT, NCH, WD>(a, (int64_t)row, g, gl, G, dec);
     }
   }
 }
@@ -663,7 +762,7 @@ struct CompactArgs {
 };
 
 // one lane group per list entry (grid-stride over u < U; the grid is sized by cap)
-template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false>
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false>
 __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   const int G = 1 << a.u.g_log2;
   const int gl = threadIdx.x & (G - 1);
@@ -673,10 +772,11 @@ __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   const int64_t n = *a.n_list;
   const uint64_t key = step_key<STOCH>(a.u);
   const float lr = ADAM ? adam_step_size(a.u) : learning_rate(a.u);
+  const float f = WD ? decay_factor(learning_rate(a.u), a.u.wd) : 1.f;
   for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
     VT g[NCH];
     load_row(g, A + u * a.u.rowlen, gl, G, a.u.rowlen);
-    update_row<VT, WT, NCH, STOCH, ADAM>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad);
+    update_row<VT, WT, NCH, STOCH, ADAM, WD>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad, f);
     zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
   }
 }
@@ -783,6 +883,10 @@ struct UpdateCall {
   // takes the place of the workspace's counter
   unsigned long long* step = nullptr;
   double beta1 = 0.0, beta2 = 0.0;
+  // the ce_*_wd entries: weight decay (decay() false: the call is the covered entry's, kernels and all)
+  float wd = 0.f;
+  int32_t wd_mode = CE_WD_NONE;
+  bool decay() const { return wd_mode != CE_WD_NONE && wd != 0.f; }
   bool w16() const { return weight_dtype != CE_ACT_F32; }
   bool adagrad() const { return optimizer == CE_OPT_ROWWISE_ADAGRAD; }
   bool adam() const { return optimizer == kOptAdam; }
@@ -807,7 +911,22 @@ static UpdateArgs update_args(const UpdateCall& c, const RowGeom& r, const unsig
   u.beta2 = c.beta2;
   u.omb1 = (float)(1.0 - c.beta1);
   u.omb2 = (float)(1.0 - c.beta2);
+  u.wd = c.wd;
+  u.wd_mode = c.wd_mode;
   return u;
+}
+
+// the two checks the ce_*_wd entries add, behind their leading checks and before everything else (also for nnz == 0)
+static int wd_check(float wd, int32_t wd_mode) {
+  CE_REQUIRE(wd_mode == CE_WD_NONE || wd_mode == CE_WD_L2 || wd_mode == CE_WD_DECOUPLED, CE_ERR_INVALID,
+             "unknown weight_decay_mode %d (CE_WD_NONE / CE_WD_L2 / CE_WD_DECOUPLED)", (int)wd_mode);
+  CE_REQUIRE(wd >= 0.f, CE_ERR_INVALID, "weight_decay must be >= 0");
+  return CE_OK;
+}
+
+// f(std::true_type) for a call that decays, f(std::false_type) -- the instantiations from before the decay -- otherwise
+template <typename F> static inline void for_decay(bool decay, F&& f) {
+  if (decay) f(std::true_type{}); else f(std::false_type{});
 }
 
 // How the entries' checks differ -- everything else is the same conditions in the same order.
@@ -877,10 +996,11 @@ struct SlotLookups {
   const uint64_t* presorted;
 };
 
-// the mark pass of a call: the slots of L (Adam: of the lookups a bag covers) or, L == NULL, the row halves of `keys`
+// the mark pass of a call: the slots of L (Adam, weight decay: of the lookups a bag covers -- there a row that is
+// merely flagged changes) or, L == NULL, the row halves of `keys` (an uncovered lookup's key is all ones already)
 static void launch_mark_call(const UpdateCall& c, const SlotLookups* L, const void* keys, int64_t n, uint8_t* flags,
                              unsigned long long* counter, hipStream_t s) {
-  if (L && c.adam())
+  if (L && (c.adam() || c.decay()))
     hipLaunchKernelGGL(k_mark_slots_covered, dim3(grid_for(n, 256)), dim3(256), 0, s, L->indices, n,
                        (uint32_t)c.num_rows, L->offsets, (int)L->off64, L->num_bags, (int)L->include_last, flags, counter);
   else
@@ -906,20 +1026,23 @@ static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const SlotL
   a.num_rows = (uint32_t)c.num_rows;
   const dim3 g(grid_for(cdiv(c.num_rows, 64), 4)), b(256);
   const bool ada = c.adagrad(), st = c.stochastic();
-  if (c.adam())
-    for_vec_lanes(r.nch, [&](auto l) {
-      hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true>), g, b, 0, s, a);
+  for_decay(c.decay(), [&](auto d) {
+    constexpr bool WD = decltype(d)::value;
+    if (c.adam())
+      for_vec_lanes(r.nch, [&](auto l) {
+        hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD>), g, b, 0, s, a);
+      });
+    else for_table(c.weight_dtype, r, [&](auto l, auto w) {
+      using VT = typename decltype(l)::VT;
+      using WT = typename decltype(w)::AT;
+      constexpr int N = decltype(l)::NCH;
+      if constexpr (std::is_same<WT, float>::value)
+        hipLaunchKernelGGL((k_rows_apply<VT, float, N, true, false, false, WD>), g, b, 0, s, a);
+      else if (ada && st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, true, false, WD>), g, b, 0, s, a);
+      else if (ada) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, false, false, WD>), g, b, 0, s, a);
+      else if (st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, true, false, WD>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, false, false, WD>), g, b, 0, s, a);
     });
-  else for_table(c.weight_dtype, r, [&](auto l, auto w) {
-    using VT = typename decltype(l)::VT;
-    using WT = typename decltype(w)::AT;
-    constexpr int N = decltype(l)::NCH;
-    if constexpr (std::is_same<WT, float>::value)
-      hipLaunchKernelGGL((k_rows_apply<VT, float, N, true, false>), g, b, 0, s, a);
-    else if (ada && st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, true>), g, b, 0, s, a);
-    else if (ada) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, false>), g, b, 0, s, a);
-    else if (st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, false>), g, b, 0, s, a);
   });
   CE_LAUNCH_CHECK();
   return CE_OK;
@@ -942,20 +1065,23 @@ static int launch_compact_apply(const UpdateCall& c, const RowGeom& r, const Com
   a.n_list = ws.n_list;
   a.adagrad = c.adagrad();
   const dim3 g(grid_for(ws.cap, 256 >> r.g_log2)), b(256);
-  if (c.adam())
-    for_vec_lanes(r.nch, [&](auto l) {
-      hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true>), g, b, 0, s, a);
+  for_decay(c.decay(), [&](auto d) {
+    constexpr bool WD = decltype(d)::value;
+    if (c.adam())
+      for_vec_lanes(r.nch, [&](auto l) {
+        hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD>), g, b, 0, s, a);
+      });
+    else for_table(c.weight_dtype, r, [&](auto l, auto w) {
+      using VT = typename decltype(l)::VT;
+      using WT = typename decltype(w)::AT;
+      constexpr int N = decltype(l)::NCH;
+      if constexpr (std::is_same<WT, float>::value)
+        hipLaunchKernelGGL((k_compact_apply<VT, float, N, false, false, WD>), g, b, 0, s, a);
+      else if (c.stochastic())
+        hipLaunchKernelGGL((k_compact_apply<VT, WT, N, true, false, WD>), g, b, 0, s, a);
+      else
+        hipLaunchKernelGGL((k_compact_apply<VT, WT, N, false, false, WD>), g, b, 0, s, a);
     });
-  else for_table(c.weight_dtype, r, [&](auto l, auto w) {
-    using VT = typename decltype(l)::VT;
-    using WT = typename decltype(w)::AT;
-    constexpr int N = decltype(l)::NCH;
-    if constexpr (std::is_same<WT, float>::value)
-      hipLaunchKernelGGL((k_compact_apply<VT, float, N, false>), g, b, 0, s, a);
-    else if (c.stochastic())
-      hipLaunchKernelGGL((k_compact_apply<VT, WT, N, true>), g, b, 0, s, a);
-    else
-      hipLaunchKernelGGL((k_compact_apply<VT, WT, N, false>), g, b, 0, s, a);
   });
   CE_LAUNCH_CHECK();
   return CE_OK;
@@ -1133,6 +1259,8 @@ static int adam_check(const UpdateCall& c, int32_t accumulator, RowGeom& r) {
   CE_REQUIRE(c.step, CE_ERR_INVALID, "step: null device pointer");
   CE_REQUIRE(accumulator == CE_ACC_CACHE || accumulator == CE_ACC_STEP, CE_ERR_INVALID,
              "unknown accumulator %d (CE_ACC_CACHE / CE_ACC_STEP)", (int)accumulator);
+  int rc = wd_check(c.wd, c.wd_mode);       // (the ce_*_adam_wd entries: the entries without decay pass 0 / CE_WD_NONE)
+  if (rc) return rc;
   CE_REQUIRE(c.beta1 >= 0.0 && c.beta1 < 1.0 && c.beta2 >= 0.0 && c.beta2 < 1.0, CE_ERR_INVALID,
              "beta1 and beta2 must lie in [0, 1)");
   CE_REQUIRE(c.eps >= 0.f, CE_ERR_INVALID, "eps must be >= 0");
@@ -1152,12 +1280,14 @@ static int adam_check(const UpdateCall& c, int32_t accumulator, RowGeom& r) {
 
 static UpdateCall adam_call(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act,
                             double beta1, double beta2, float lr, const float* lr_dev, float eps, int64_t* step,
-                            void* workspace, size_t workspace_bytes) {
+                            void* workspace, size_t workspace_bytes, float wd = 0.f, int32_t wd_mode = CE_WD_NONE) {
   UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act, nullptr, nullptr, 0, lr_dev ? 0.f : lr, eps,
                kOptAdam, CE_ROUND_NEAREST, 0, workspace, workspace_bytes, lr_dev};
   c.step = (unsigned long long*)step;
   c.beta1 = beta1;
   c.beta2 = beta2;
+  c.wd = wd;
+  c.wd_mode = wd_mode;
   return c;
 }
 
@@ -1171,6 +1301,21 @@ static int lrdev_dispatch(UpdateCall c, int32_t accumulator, Fp32&& fp32, W16&& 
   if (accumulator == CE_ACC_STEP) return compact(c);
   if (c.weight_dtype != CE_ACT_F32) return w16(c);
   c.rounding = CE_ROUND_NEAREST;      // an fp32 row is stored as it is: the covered entry has neither argument
+  c.seed = 0;
+  return fp32(c);
+}
+
+// a ce_*_wd update call: the accumulator code, the two decay checks, then the covered entry as lrdev_dispatch picks it
+// (lr_dev == NULL: the learning rate by value)
+template <typename Fp32, typename W16, typename Compact>
+static int wd_dispatch(UpdateCall c, int32_t accumulator, Fp32&& fp32, W16&& w16, Compact&& compact) {
+  CE_REQUIRE(accumulator == CE_ACC_CACHE || accumulator == CE_ACC_STEP, CE_ERR_INVALID,
+             "unknown accumulator %d (CE_ACC_CACHE / CE_ACC_STEP)", (int)accumulator);
+  int rc = wd_check(c.wd, c.wd_mode);
+  if (rc) return rc;
+  if (accumulator == CE_ACC_STEP) return compact(c);
+  if (c.weight_dtype != CE_ACT_F32) return w16(c);
+  c.rounding = CE_ROUND_NEAREST;
   c.seed = 0;
   return fp32(c);
 }
@@ -1340,15 +1485,20 @@ extern "C" size_t ce_bag_backward_update_sorted_workspace(int64_t num_rows, int6
   return carve_sorted(nullptr, nnz, dim).bytes;
 }
 
-extern "C" int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
-                                             const int64_t* indices, int64_t nnz, const void* offsets,
-                                             int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
-                                             const float* per_sample_weights, int32_t mode, int64_t hook_features,
-                                             const void* grad_out, int32_t act_dtype, const int32_t* row_of_slot,
-                                             float* momentum, int64_t momentum_rows, float lr, float eps,
-                                             int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
-                                             size_t workspace_bytes, ce_stream_t stream) {
+// ce_bag_backward_update_sorted (weight_decay 0, CE_WD_NONE) and ce_bag_backward_update_sorted_wd are this one function
+static int update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, const int64_t* indices,
+                         int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                         int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                         int64_t hook_features, const void* grad_out, int32_t act_dtype, const int32_t* row_of_slot,
+                         float* momentum, int64_t momentum_rows, float lr, float eps, float weight_decay,
+                         int32_t weight_decay_mode, int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                         size_t workspace_bytes, ce_stream_t stream) {
   // everything that can be refused, from the arguments alone: no launch, no HIP call before the last check
+  {
+    int rc = wd_check(weight_decay, weight_decay_mode);
+    if (rc) return rc;
+  }
+  const bool decay = weight_decay_mode != CE_WD_NONE && weight_decay != 0.f;
   CE_REQUIRE_ACT(act_dtype);
   CE_REQUIRE(weight_dtype == CE_ACT_F32 || weight_dtype == CE_ACT_BF16 || weight_dtype == CE_ACT_F16, CE_ERR_INVALID,
              "unknown weight_dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)weight_dtype);
@@ -1393,8 +1543,9 @@ extern "C" int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype,
   hipStream_t s = (hipStream_t)stream;
   const SortedWs ws = carve_sorted(workspace, nnz, dim);
   SortedRows sr{};
+  // with decay a row that merely heads a run changes: the lookups no bag covers must head none
   rc = sorted_rows(indices, nnz, num_rows, offsets, offsets_are_i64, num_bags, include_last_offset, ws.sort,
-                   s, sr);
+                   s, sr, decay);
   if (rc) return rc;
   SortedArgs a{};
   a.weight = weight;
@@ -1422,28 +1573,101 @@ extern "C" int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype,
   a.adagrad = optimizer == CE_OPT_ROWWISE_ADAGRAD;
   a.lr = lr;
   a.eps = eps;
+  a.wd = weight_decay;
+  a.wd_mode = weight_decay_mode;
   const dim3 g(grid_for(cdiv(nnz, 64), 4)), b(256);
-  if (w16) {
-    for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
-      using WT = typename decltype(w)::AT;
-      constexpr int N = decltype(l)::NCH;
-      for_act(act_dtype, [&](auto at) {
-        hipLaunchKernelGGL((k_sorted_fold<f32x4, typename decltype(at)::AT, WT, N>), g, b, 0, s, a);
+  for_decay(decay, [&](auto d) {
+    constexpr bool WD = decltype(d)::value;
+    if (w16) {
+      for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
+        using WT = typename decltype(w)::AT;
+        constexpr int N = decltype(l)::NCH;
+        for_act(act_dtype, [&](auto at) {
+          hipLaunchKernelGGL((k_sorted_fold<f32x4, typename decltype(at)::AT, WT, N, WD>), g, b, 0, s, a);
+        });
+        hipLaunchKernelGGL((k_sorted_combine<f32x4, WT, N, WD>), g, b, 0, s, a);
       });
-      hipLaunchKernelGGL((k_sorted_combine<f32x4, WT, N>), g, b, 0, s, a);
-    });
-  } else {
-    for_lanes(r.vec, r.nch, [&](auto l) {
-      using VT = typename decltype(l)::VT;
-      constexpr int N = decltype(l)::NCH;
-      for_act(act_dtype, [&](auto at) {
-        hipLaunchKernelGGL((k_sorted_fold<VT, typename decltype(at)::AT, float, N>), g, b, 0, s, a);
+    } else {
+      for_lanes(r.vec, r.nch, [&](auto l) {
+        using VT = typename decltype(l)::VT;
+        constexpr int N = decltype(l)::NCH;
+        for_act(act_dtype, [&](auto at) {
+          hipLaunchKernelGGL((k_sorted_fold<VT, typename decltype(at)::AT, float, N, WD>), g, b, 0, s, a);
+        });
+        hipLaunchKernelGGL((k_sorted_combine<VT, float, N, WD>), g, b, 0, s, a);
       });
-      hipLaunchKernelGGL((k_sorted_combine<VT, float, N>), g, b, 0, s, a);
-    });
-  }
+    }
+  });
   CE_LAUNCH_CHECK();
   return CE_OK;
+}
+
+extern "C" int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                             const int64_t* indices, int64_t nnz, const void* offsets,
+                                             int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                             const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                             const void* grad_out, int32_t act_dtype, const int32_t* row_of_slot,
+                                             float* momentum, int64_t momentum_rows, float lr, float eps,
+                                             int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                             size_t workspace_bytes, ce_stream_t stream) {
+  return update_sorted(weight, weight_dtype, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                       include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype, row_of_slot,
+                       momentum, momentum_rows, lr, eps, 0.f, CE_WD_NONE, optimizer, rounding, seed, workspace,
+                       workspace_bytes, stream);
+}
+
+extern "C" int ce_bag_backward_update_sorted_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                                const int64_t* indices, int64_t nnz, const void* offsets,
+                                                int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                                const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                                const void* grad_out, int32_t act_dtype, const int32_t* row_of_slot,
+                                                float* momentum, int64_t momentum_rows, float lr, float eps,
+                                                float weight_decay, int32_t weight_decay_mode, int32_t optimizer,
+                                                int32_t rounding, uint64_t seed, void* workspace,
+                                                size_t workspace_bytes, ce_stream_t stream) {
+  return update_sorted(weight, weight_dtype, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                       include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype, row_of_slot,
+                       momentum, momentum_rows, lr, eps, weight_decay, weight_decay_mode, optimizer, rounding, seed,
+                       workspace, workspace_bytes, stream);
+}
+
+// ---- weight decay for the atomic updates: the pair of ce_bag_backward_update_lrdev / _src_lrdev with the learning
+// rate in Adam's convention (lr_dev == NULL: by value) and the decay behind eps
+
+extern "C" int ce_bag_backward_update_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                         const int64_t* indices, int64_t nnz, const void* offsets,
+                                         int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                         const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                         const void* grad_out, int32_t act_dtype, const uint64_t* presorted,
+                                         const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                         const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
+                                         int32_t optimizer, int32_t rounding, uint64_t seed, int32_t accumulator,
+                                         void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+               momentum_rows, lr_dev ? 0.f : lr, eps, optimizer, rounding, seed, workspace, workspace_bytes, lr_dev};
+  c.wd = weight_decay;
+  c.wd_mode = weight_decay_mode;
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, presorted};
+  return wd_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_slots(u, L, stream); },
+                     [&](const UpdateCall& u) { return update_w16_slots(u, L, stream); },
+                     [&](const UpdateCall& u) { return update_compact_slots(u, L, stream); });
+}
+
+extern "C" int ce_bag_backward_update_src_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                             int64_t nnz, const void* grad_out, int32_t act_dtype,
+                                             const uint64_t* src_keys, const int32_t* row_of_slot, float* momentum,
+                                             int64_t momentum_rows, float lr, const float* lr_dev, float eps,
+                                             float weight_decay, int32_t weight_decay_mode, int32_t optimizer,
+                                             int32_t rounding, uint64_t seed, int32_t accumulator, void* workspace,
+                                             size_t workspace_bytes, ce_stream_t stream) {
+  UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+               momentum_rows, lr_dev ? 0.f : lr, eps, optimizer, rounding, seed, workspace, workspace_bytes, lr_dev};
+  c.wd = weight_decay;
+  c.wd_mode = weight_decay_mode;
+  return wd_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_src(u, src_keys, stream); },
+                     [&](const UpdateCall& u) { return update_w16_src(u, src_keys, stream); },
+                     [&](const UpdateCall& u) { return update_compact_src(u, src_keys, stream); });
 }
 
 // ---- Adam on an Adam-layout table (rows w | m | v)
@@ -1454,15 +1678,15 @@ extern "C" size_t ce_bag_backward_adam_workspace(int64_t num_rows, int64_t nnz, 
   return adam_workspace(num_rows, nnz, dim, accumulator);
 }
 
-extern "C" int ce_bag_backward_adam(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
-                                    const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
-                                    int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
-                                    int64_t hook_features, const void* grad_out, int32_t act_dtype,
-                                    const uint64_t* presorted, double beta1, double beta2, float lr, const float* lr_dev,
-                                    float eps, int64_t* step, int32_t accumulator, void* workspace,
-                                    size_t workspace_bytes, ce_stream_t stream) {
+// ce_bag_backward_adam (weight_decay 0, CE_WD_NONE) and ce_bag_backward_adam_wd are one function; the _src pair likewise
+static int adam_slots(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                      const void* offsets, int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                      const float* per_sample_weights, int32_t mode, int64_t hook_features, const void* grad_out,
+                      int32_t act_dtype, const uint64_t* presorted, double beta1, double beta2, float lr,
+                      const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode, int64_t* step,
+                      int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream) {
   const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
-                                 workspace, workspace_bytes);
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode);
   const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
                       hook_features, presorted};
   RowGeom r;
@@ -1481,12 +1705,12 @@ extern "C" int ce_bag_backward_adam(float* weight, int64_t num_rows, int32_t dim
   });
 }
 
-extern "C" int ce_bag_backward_adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out,
-                                        int32_t act_dtype, const uint64_t* src_keys, double beta1, double beta2, float lr,
-                                        const float* lr_dev, float eps, int64_t* step, int32_t accumulator,
-                                        void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+static int adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act_dtype,
+                    const uint64_t* src_keys, double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                    float weight_decay, int32_t weight_decay_mode, int64_t* step, int32_t accumulator, void* workspace,
+                    size_t workspace_bytes, ce_stream_t stream) {
   const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
-                                 workspace, workspace_bytes);
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode);
   RowGeom r;
   int rc = adam_check(c, accumulator, r);
   if (rc) return rc;
@@ -1496,4 +1720,47 @@ extern "C" int ce_bag_backward_adam_src(float* weight, int64_t num_rows, int32_t
   return update_cache_sized(c, r, nullptr, src_keys, ce_bag_presort_len(nnz), (hipStream_t)stream, [&](float* acc) {
     return ce_bag_backward_dense_src_act(acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
   });
+}
+
+extern "C" int ce_bag_backward_adam(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                    const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                    int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                    int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                    const uint64_t* presorted, double beta1, double beta2, float lr, const float* lr_dev,
+                                    float eps, int64_t* step, int32_t accumulator, void* workspace,
+                                    size_t workspace_bytes, ce_stream_t stream) {
+  return adam_slots(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                    per_sample_weights, mode, hook_features, grad_out, act_dtype, presorted, beta1, beta2, lr, lr_dev, eps,
+                    0.f, CE_WD_NONE, step, accumulator, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ce_bag_backward_adam_wd(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                       const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                       int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                       int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                       const uint64_t* presorted, double beta1, double beta2, float lr,
+                                       const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
+                                       int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                       ce_stream_t stream) {
+  return adam_slots(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                    per_sample_weights, mode, hook_features, grad_out, act_dtype, presorted, beta1, beta2, lr, lr_dev, eps,
+                    weight_decay, weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ce_bag_backward_adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out,
+                                        int32_t act_dtype, const uint64_t* src_keys, double beta1, double beta2, float lr,
+                                        const float* lr_dev, float eps, int64_t* step, int32_t accumulator,
+                                        void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, 0.f,
+                  CE_WD_NONE, step, accumulator, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ce_bag_backward_adam_src_wd(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                           const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                           double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                                           float weight_decay, int32_t weight_decay_mode, int64_t* step,
+                                           int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                           ce_stream_t stream) {
+  return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, weight_decay,
+                  weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream);
 }

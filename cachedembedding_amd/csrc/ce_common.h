@@ -123,7 +123,7 @@ struct SortedRows {
 size_t sorted_rows_bytes(int64_t nnz);
 int sorted_rows(const int64_t* indices, int64_t nnz, int64_t num_rows, const void* offsets, int off64,
                 int64_t num_bags, int include_last, void* workspace, hipStream_t s,
-                SortedRows& out);
+                SortedRows& out, bool covered_only = false);
 
 // How the lanes of a launch hold one embedding row.  Vector form: a lane's chunk is 16 B (f32x4); it needs dim % 4 == 0
 // and `aligned` -- every row pointer of the launch on its vector boundary.  Scalar form otherwise: one float per chunk.

@@ -632,12 +632,22 @@ static SortWs carve(void* ws, int64_t nnz) {
 // only as many bits as the rows need, so a raw -1 key would share all of them with the last row of a power-of-two
 // table and interleave with it; the first launch therefore writes key = num_rows for such lookups and the passes sort
 // bits(num_rows + 1) bits.
+// offsets != NULL (the update with weight decay, where a row that merely heads a run changes): a lookup no bag covers
+// -- a position outside [offsets[0], end of the last bag) -- is ignored too, so it names no row.
 __global__ __launch_bounds__(256) void k_sorted_keys(const int64_t* __restrict__ ids, int64_t n, int64_t num_rows,
-                                                     int32_t* __restrict__ keys, int32_t* __restrict__ vals) {
+                                                     int32_t* __restrict__ keys, int32_t* __restrict__ vals,
+                                                     const void* __restrict__ offsets, int off64, int64_t num_bags,
+                                                     int include_last) {
+  int64_t lo = 0, hi = n;
+  if (offsets) {
+    lo = off64 ? ((const int64_t*)offsets)[0] : ((const int32_t*)offsets)[0];
+    if (include_last) hi = off64 ? ((const int64_t*)offsets)[num_bags] : ((const int32_t*)offsets)[num_bags];
+  }
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int64_t id = ids[i];
-    keys[i] = (unsigned long long)id < (unsigned long long)num_rows ? (int32_t)id : (int32_t)num_rows;
+    const bool valid = (unsigned long long)id < (unsigned long long)num_rows && i >= lo && i < hi;
+    keys[i] = valid ? (int32_t)id : (int32_t)num_rows;
     vals[i] = (int32_t)i;
   }
 }
@@ -647,14 +657,14 @@ size_t sorted_rows_bytes(int64_t nnz) { return carve(nullptr, std::max<int64_t>(
 // nnz in [1, 2^31 - 1), num_rows in [1, 2^31 - 1): checked by the caller.  bag_of is -1 for a lookup no bag covers.
 int sorted_rows(const int64_t* indices, int64_t nnz, int64_t num_rows, const void* offsets, int off64,
                 int64_t num_bags, int include_last, void* workspace, hipStream_t s,
-                SortedRows& out) {
+                SortedRows& out, bool covered_only) {
   SortWs ws = carve(workspace, nnz);
   const int ntiles = (int)cdiv(nnz, kTile);
   int bits = 1;
   while ((1ll << bits) <= num_rows) ++bits;            // the sentinel key num_rows itself must fit
   const int passes = (bits + 7) / 8;
   hipLaunchKernelGGL(k_sorted_keys, dim3(grid_for(nnz, 256)), dim3(256), 0, s, indices, nnz, num_rows, ws.keys[0],
-                     ws.vals[0]);
+                     ws.vals[0], covered_only ? offsets : nullptr, off64, num_bags, include_last);
   CE_HIP_CHECK(hipMemsetAsync(ws.bag_of, 0xff, (size_t)nnz * 4, s));
   hipLaunchKernelGGL(k_expand_bags, dim3(grid_for(num_bags, 256)), dim3(256), 0, s, offsets, off64, num_bags, nnz,
                      include_last, ws.bag_of);

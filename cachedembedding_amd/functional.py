@@ -148,16 +148,20 @@ class _BagFn(torch.autograd.Function):
             with torch.no_grad():
                 ws = fused.workspace(R, nnz, dim, weight.device)
                 lr_t = isinstance(fused.lr, torch.Tensor)
+                # weight decay: the ce_*_wd pair, the decay and its mode directly behind eps; without it today's entries
+                decay = fused.weight_decay != 0.0
                 tail = (float(fused.betas[0]), float(fused.betas[1]), 0.0 if lr_t else float(fused.lr),
-                        ptr(fused.lr) if lr_t else None, float(fused.eps), ptr(fused.step),
-                        _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws), ws.numel(),
-                        stream_ptr())
+                        ptr(fused.lr) if lr_t else None, float(fused.eps)) + \
+                    ((float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) if decay else ()) + \
+                    (ptr(fused.step), _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws),
+                     ws.numel(), stream_ptr())
                 if src:
-                    check(lib.ce_bag_backward_adam_src(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                    fn = lib.ce_bag_backward_adam_src_wd if decay else lib.ce_bag_backward_adam_src
+                    check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                 else:
-                    check(lib.ce_bag_backward_adam(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags,
-                                                   int(include_last), ptr(psw), mode, hook_features, ptr(grad_out), act,
-                                                   ptr(pre), *tail))
+                    fn = lib.ce_bag_backward_adam_wd if decay else lib.ce_bag_backward_adam
+                    check(fn(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last),
+                             ptr(psw), mode, hook_features, ptr(grad_out), act, ptr(pre), *tail))
             return (None,) * 14
         rowwise = isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None
         sgd = not rowwise and fused is not None and fused.lr is not None
@@ -168,7 +172,9 @@ class _BagFn(torch.autograd.Function):
         act = _lib.ACT_DTYPES.get(grad_out.dtype)
         if act is None:
             raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
-        fp32_only = fused.deterministic if sgd else (sparse and not rowwise)
+        # (deterministic SGD WITH weight decay is ce_bag_backward_update_sorted_wd, which reads `act` in place like the
+        # other update entries: no upcast there, so `act` goes on describing the buffer that is handed over)
+        fp32_only = (fused.deterministic and fused.weight_decay == 0.0) if sgd else (sparse and not rowwise)
         if fp32_only and act != _lib.CE_ACT_F32:
             grad_out = grad_out.float()
         slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
@@ -176,6 +182,37 @@ class _BagFn(torch.autograd.Function):
         # a tensor learning rate goes to the ce_*_lrdev entries, whose kernels read it when they run (nothing here
         # does); a float to the by-value entries.  What the tensor form does not take was refused before the forward.
         lr_dev = (rowwise or sgd) and isinstance(fused.lr, torch.Tensor)
+        if (rowwise or sgd) and fused.weight_decay != 0.0:
+            # weight decay: the ce_*_wd entries -- the sorted one for deterministic=True (fp32 SGD has
+            # no other), else the atomic pair with either accumulator.  What they do not take was refused before the
+            # forward (check_weight_decay_path).  Without decay nothing below has changed.
+            with torch.no_grad():
+                w16 = weight.dtype in _lib.W16_DTYPES
+                wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
+                mom = fused.momentum if rowwise else None
+                head = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel())
+                decay = (float(fused.eps) if rowwise else 0.0, float(fused.weight_decay),
+                         WEIGHT_DECAY_MODES[fused.weight_decay_mode],
+                         _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
+                         _lib.CE_ROUND_STOCHASTIC if w16 and fused.rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
+                         int(fused.seed) & (2 ** 64 - 1))
+                if fused.deterministic:
+                    ws = _workspace_sorted(fused, R, nnz, dim, weight.device)
+                    check(lib.ce_bag_backward_update_sorted_wd(*wd, *slots_args, act, *head, float(fused.lr), *decay,
+                                                               ptr(ws), ws.numel(), stream_ptr()))
+                    return (None,) * 14
+                if fused.accumulator == "step":
+                    ws, acc = fused.workspace_step(R, nnz, dim, weight.device), _lib.CE_ACC_STEP
+                else:
+                    ws = fused.workspace_w16(R, dim, weight.device) if w16 else fused.workspace(R, dim, weight.device)
+                    acc = _lib.CE_ACC_CACHE
+                tail = head + (0.0 if lr_dev else float(fused.lr), ptr(fused.lr) if lr_dev else None) + decay + \
+                    (acc, ptr(ws), ws.numel(), stream_ptr())
+                if src:
+                    check(lib.ce_bag_backward_update_src_wd(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                else:
+                    check(lib.ce_bag_backward_update_wd(*wd, *slots_args, act, ptr(pre), *tail))
+            return (None,) * 14
         if (rowwise or sgd) and fused.accumulator == "step":
             # the atomic update with an accumulator of min(nnz, rows) rows (ce_bag_backward_update_compact*): mark, an
             # ordered compaction of the flagged slots, the slots / keys renumbered, the same dense backward, one apply
@@ -577,7 +614,63 @@ def check_lr_path(lr, deterministic: bool, mode: Optional[str] = None) -> None:
         raise NotImplementedError("a tensor learning rate with mode='max'")
 
 
-class FusedSGD(_CheckedLr):
+WEIGHT_DECAY_MODES = {"l2": _lib.CE_WD_L2, "decoupled": _lib.CE_WD_DECOUPLED}
+
+
+def check_weight_decay(weight_decay, weight_decay_mode) -> float:
+    """weight_decay: a number >= 0 (a negative or NaN one is a ValueError); weight_decay_mode: "l2" (the decay joins the
+    gradient: torch.optim.{SGD, Adagrad, Adam}(weight_decay=), FBGEMM's L2) or "decoupled" (the row is scaled by
+    1 - lr * weight_decay first: torch.optim.AdamW, FBGEMM's DECOUPLE).  Returns the decay as a float."""
+    if weight_decay_mode not in WEIGHT_DECAY_MODES:
+        raise ValueError(f"weight_decay_mode={weight_decay_mode!r}: 'l2' or 'decoupled'")
+    if isinstance(weight_decay, torch.Tensor):
+        raise ValueError("weight_decay is a float: only the learning rate may live in device memory")
+    wd = float(weight_decay)
+    if not wd >= 0.0:
+        raise ValueError(f"weight_decay={weight_decay!r}: must be >= 0")
+    return wd
+
+
+def check_weight_decay_path(optimizer: str, table_dtype, weight_decay: float, deterministic: bool = False, lr=None,
+                            mode: Optional[str] = None) -> None:
+    """Refusals of weight_decay != 0 (optimizer: "sgd", "rowwise_adagrad" or "adam"; table_dtype: the weight's, None:
+    not known yet -- what depends on it is asked again before the forward).  Host logic only -- it is asked before the
+    forward, so that nothing is refused after a kernel has run."""
+    if not weight_decay:
+        return
+    if mode == "max":
+        raise NotImplementedError("weight_decay with mode='max': that update has no per-row pass")
+    if isinstance(lr, torch.Tensor) and deterministic:
+        raise NotImplementedError("weight_decay with a tensor learning rate and deterministic=True: the sorted updates "
+                                  "take a float")
+    if optimizer == "sgd" and table_dtype == torch.float32 and not deterministic:
+        raise NotImplementedError("weight_decay with fused SGD on an fp32 table: the atomic scatter has no per-row "
+                                  "pass that could decay a row once -- set deterministic=True (the sorted update)")
+
+
+def refuse_weight_decay(who: Optional[str], weight_decay) -> None:
+    """the sharded and table-wise modules: their owner-side update is ce_rows_axpy, which has no decay"""
+    if who and weight_decay:
+        raise NotImplementedError(f"weight_decay is not implemented for {who}: its owner-side update is ce_rows_axpy, "
+                                  "which has no per-row decay")
+
+
+def _workspace_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
+    """workspace of ce_bag_backward_update_sorted* (sort arrays, partial rows): nothing in it needs initialising"""
+    need = lib.ce_bag_backward_update_sorted_workspace(num_rows, nnz, dim)
+    return _cached_bytes(self, "_ws_sorted", need, device, zero=False)
+
+
+class _WeightDecay:
+    """`weight_decay` / `weight_decay_mode` of the fused switches: checked on every set_weight_decay"""
+    weight_decay, weight_decay_mode = 0.0, "l2"
+
+    def set_weight_decay(self, weight_decay: float = 0.0, weight_decay_mode: str = "l2") -> None:
+        self.weight_decay = check_weight_decay(weight_decay, weight_decay_mode)
+        self.weight_decay_mode = weight_decay_mode
+
+
+class FusedSGD(_CheckedLr, _WeightDecay):
     """Switch for the fused backward+SGD path of one embedding module.
 
     lr=None disables fusion (the module behaves exactly like nn.EmbeddingBag under
@@ -586,12 +679,18 @@ class FusedSGD(_CheckedLr):
     min(lookups of the step, rows) rows instead of one per row of the weight.
     lr may be a tensor (check_lr): one fp32 element on the weight's device, kept by reference and read by the kernels
     when they run -- rewrite it in place (fill_ / copy_) between steps or between replays of a captured step.  Not
-    with deterministic=True and not with mode='max'."""
+    with deterministic=True and not with mode='max'.
+    weight_decay, weight_decay_mode ("l2": w -= lr (g + wd w); "decoupled": w = w (1 - lr wd) - lr g), lazy: the rows a
+    step looks up decay once, in that step.  A 16-bit table with either accumulator; an fp32 table
+    with deterministic=True only (the atomic scatter has no per-row pass); not with mode='max'."""
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, deterministic: bool = False,
-                 accumulator: str = "cache"):
+                 accumulator: str = "cache", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
         check_accumulator("sgd", None, accumulator, bool(deterministic))
         check_lr_path(check_lr(lr), bool(deterministic))
+        self.set_weight_decay(weight_decay, weight_decay_mode)
+        check_weight_decay_path("sgd", None, self.weight_decay, bool(deterministic), lr)
+        self._ws_sorted = None
         self.lr = lr
         self.deterministic = deterministic
         self.accumulator = accumulator
@@ -609,9 +708,9 @@ class FusedSGD(_CheckedLr):
         return _cached_bytes(self, "_ws", lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz), device, zero=False)
 
 
-class FusedRowwiseAdagrad(_CheckedLr):
+class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay):
     """Switch for the fused backward + exact row-wise Adagrad update of one embedding module (FBGEMM's
-    EXACT_ROWWISE_ADAGRAD, weight_decay = 0).  Per step and per UNIQUE row r the step looks up, with g the sum of the
+    EXACT_ROWWISE_ADAGRAD; weight_decay_mode "l2" / "decoupled" are its L2 / DECOUPLE).  Per step and per UNIQUE row r the step looks up, with g the sum of the
     row's gradient rows in the batch:  m[r] += sum(g * g) / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps).
 
     momentum: fp32 [rows] on the device -- one accumulator per row of the table the momentum follows; row_of_slot:
@@ -629,13 +728,20 @@ class FusedRowwiseAdagrad(_CheckedLr):
     the weight ("cache", the default).  Not with deterministic=True, and on a 16-bit table with rounding="nearest"
     only: both are refused before any kernel runs.
 
-    lr may be a tensor, as for FusedSGD (check_lr); not with deterministic=True."""
+    lr may be a tensor, as for FusedSGD (check_lr); not with deterministic=True.
+
+    weight_decay, weight_decay_mode, lazy (the rows a step looks up decay once, in that step):
+    "l2": h = g + weight_decay * w takes the place of g everywhere, in sum(h * h) / D too; "decoupled": w is scaled by
+    1 - lr * weight_decay first.  Every path above takes it."""
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, eps: float = 1e-8,
                  momentum: Optional[torch.Tensor] = None, row_of_slot: Optional[torch.Tensor] = None,
-                 deterministic: bool = False, accumulator: str = "cache"):
+                 deterministic: bool = False, accumulator: str = "cache", *, weight_decay: float = 0.0,
+                 weight_decay_mode: str = "l2"):
         check_accumulator("rowwise_adagrad", None, accumulator, bool(deterministic))
         check_lr_path(check_lr(lr), bool(deterministic))
+        self.set_weight_decay(weight_decay, weight_decay_mode)
+        check_weight_decay_path("rowwise_adagrad", None, self.weight_decay, bool(deterministic), lr)
         self.lr = lr
         self.deterministic = bool(deterministic)
         self.accumulator = accumulator
@@ -668,10 +774,7 @@ class FusedRowwiseAdagrad(_CheckedLr):
         elif rmap.dtype != torch.int32 or not rmap.is_contiguous() or rmap.device != weight.device:
             raise ValueError("row_of_slot must be a contiguous int32 tensor on the weight's device")
 
-    def workspace_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
-        """workspace of the deterministic path (sort arrays, partial rows): nothing in it needs initialising"""
-        need = lib.ce_bag_backward_update_sorted_workspace(num_rows, nnz, dim)
-        return _cached_bytes(self, "_ws_sorted", need, device, zero=False)
+    workspace_sorted = _workspace_sorted         # the deterministic path (sort arrays, partial rows)
 
     def workspace(self, num_rows: int, dim: int, device) -> torch.Tensor:
         # zero-filled once; every call of the kernels leaves it zero-filled again
@@ -679,7 +782,7 @@ class FusedRowwiseAdagrad(_CheckedLr):
         return _cached_bytes(self, "_ws", need, device, zero=True)
 
 
-class FusedAdam(_CheckedLr):
+class FusedAdam(_CheckedLr, _WeightDecay):
     """Switch for the fused backward + Adam update of one embedding module whose table carries its moments: the weight
     the kernels see is [rows, 3 * D] fp32, every row w | m | v.  torch.optim.SparseAdam's arithmetic,
     per step and per UNIQUE row the step looks up, g the sum of the row's gradient rows in the batch, t the step count:
@@ -690,20 +793,27 @@ class FusedAdam(_CheckedLr):
 
     step: ONE int64 on the weight's device, zero before the first step; the first kernel of every backward adds 1 to it
     (a replayed graph counts on).  accumulator: "step" (the default: an fp32 accumulator of min(lookups of the step,
-    rows) rows) or "cache" (one row per row of the weight).  lr may be a tensor, as for FusedSGD (check_lr)."""
+    rows) rows) or "cache" (one row per row of the weight).  lr may be a tensor, as for FusedSGD (check_lr).
+
+    weight_decay, weight_decay_mode, lazy like the moments (the rows a step looks up decay once, in that step):
+    "l2" is torch.optim.Adam(weight_decay=) -- g + weight_decay * w feeds both moments --, "decoupled" torch.optim.AdamW
+    -- w is scaled by 1 - lr * weight_decay (lr, not the bias-corrected step size) first."""
 
     deterministic = False                                   # (the sorted fold has no Adam form)
     rounding, seed = "nearest", 0
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, betas=(0.9, 0.999), eps: float = 1e-8,
-                 accumulator: str = "step", step: Optional[torch.Tensor] = None, deterministic: bool = False):
+                 accumulator: str = "step", step: Optional[torch.Tensor] = None, deterministic: bool = False, *,
+                 weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
         self.lr = lr
-        self.set(betas, eps, accumulator, deterministic)
+        self.set(betas, eps, accumulator, deterministic, weight_decay=weight_decay, weight_decay_mode=weight_decay_mode)
         self.step = step
         self._ws_step, self._ws_step_key = None, None
         self._ws = None
 
-    def set(self, betas, eps: float, accumulator: str, deterministic: bool = False) -> None:
+    def set(self, betas, eps: float, accumulator: str, deterministic: bool = False, *, weight_decay: float = 0.0,
+            weight_decay_mode: str = "l2") -> None:
+        wd = check_weight_decay(weight_decay, weight_decay_mode)
         if deterministic:
             raise NotImplementedError("fused Adam with deterministic=True: the sorted fold has no Adam form")
         b1, b2 = (float(b) for b in betas)
@@ -714,6 +824,7 @@ class FusedAdam(_CheckedLr):
         if accumulator not in ACCUMULATORS:
             raise ValueError(f"accumulator={accumulator!r}: 'cache' or 'step'")
         self.betas, self.eps, self.accumulator = (b1, b2), float(eps), accumulator
+        self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
 
     def check(self, weight: torch.Tensor) -> None:
         """refusals that must come before any kernel of the step has run"""
@@ -789,6 +900,8 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                           fused_sgd.accumulator, bool(fused_sgd.deterministic), fused_sgd.rounding)
         if fused_sgd.accumulator == "step" and mode == "max":
             raise NotImplementedError("accumulator='step' with mode='max'")
+        check_weight_decay_path("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
+                                fused_sgd.weight_decay, bool(fused_sgd.deterministic), fused_sgd.lr, mode)
         if isinstance(fused_sgd.lr, torch.Tensor):
             # asked again here: .lr, .deterministic and the weight can all change after the switch was built
             check_lr_path(check_lr(fused_sgd.lr), bool(fused_sgd.deterministic), mode)

@@ -32,7 +32,7 @@ from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
 from .cached_embedding import CachedEmbeddingBag
-from .functional import _MODES, FORWARD_FROM_KEYS, SrcKeys
+from .functional import _MODES, FORWARD_FROM_KEYS, SrcKeys, check_weight_decay, refuse_weight_decay
 
 
 def get_partition(embedding_dim: int, rank: int, world_size: int) -> Tuple[int, int, bool]:
@@ -577,15 +577,20 @@ class RowwiseShardedEmbeddingBag(nn.Module):
     def weight(self):
         return self.cache_weight_mgr.weight
 
-    def set_fused_sgd(self, lr: Optional[float]):
+    def set_fused_sgd(self, lr: Optional[float], *, weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
+        refuse_weight_decay("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
+                            check_weight_decay(weight_decay, weight_decay_mode))
         if isinstance(lr, torch.Tensor):
             raise NotImplementedError("a tensor learning rate is not implemented for the row-wise sharded embedding "
                                       "(RowwiseShardedEmbeddingBag / GraphedShardedWindow): its owner-side update "
                                       "takes a float")
         self._lr[0] = lr
 
-    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8):
+    def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8, *, weight_decay: float = 0.0,
+                                  weight_decay_mode: str = "l2"):
         """Refused: the owner-side update of the row exchange is SGD only (GraphedShardedWindow replays it too)."""
+        refuse_weight_decay("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
+                            check_weight_decay(weight_decay, weight_decay_mode))
         if lr is not None:
             raise NotImplementedError("fused row-wise Adagrad is not implemented for the row-wise sharded embedding "
                                       "(RowwiseShardedEmbeddingBag / GraphedShardedWindow); use set_fused_sgd(lr)")
@@ -1406,6 +1411,8 @@ class ParallelCachedEmbeddingBag(CachedEmbeddingBag):
     """Column-wise parallel cached EmbeddingBag -- the class recsys/models/dlrm.py:70-81 builds.
     Every rank holds num_embeddings x (embedding_dim / W) and receives the GLOBAL batch; forward returns
     shape_hook(local pooled) exchanged with dual_all_to_all(scatter batch, gather dim)."""
+
+    _no_weight_decay = "ParallelCachedEmbeddingBag"          # set_fused_*(weight_decay != 0) is refused
 
     def __init__(self, num_embeddings, embedding_dim, padding_idx=None, max_norm=None, norm_type=2.0,
                  scale_grad_by_freq=False, sparse=False, _weight=None, mode="mean", include_last_offset=False,

@@ -109,6 +109,7 @@ class ParallelCachedEmbeddingBagTablewise(nn.Module):
                                                           warmup_ratio=warmup_ratio, buffer_size=buffer_size,
                                                           pin_weight=pin_weight, evict_strategy=evict_strategy)
         self.cache_weight_mgr = self.cache_weight_mgr_module.cache_weight_mgr
+        self.cache_weight_mgr_module._no_weight_decay = "ParallelCachedEmbeddingBagTablewise"      # (set_fused_* refuse it)
         # features per rank, for the feature gather of the output exchange
         self._feat_per_rank = [sum(1 for r in self.rank_of_tables if r == p) for p in range(self.world_size)]
 

@@ -130,6 +130,13 @@ def parse_args(argv=None):
                         "accumulator has a row per lookup of a step at most instead of one per cache row "
                         "(accumulator='step'); not with --adagrad_deterministic, and --adagrad on a 16-bit table needs "
                         "--weight_rounding nearest with it")
+    p.add_argument("--embed_weight_decay", type=float, default=0.0,
+                   help="weight decay of the embedding's fused update (--adagrad, --adam or --fused_sgd), lazy: the "
+                        "rows a step looks up decay once, in that step; the dense part is not touched.  --fused_sgd on "
+                        "an fp32 table has no per-row pass and refuses it")
+    p.add_argument("--embed_weight_decay_mode", choices=("l2", "decoupled"), default="l2",
+                   help="l2: the decay joins the gradient (torch.optim.Adam / Adagrad / SGD weight_decay, FBGEMM L2); "
+                        "decoupled: the row is scaled by 1 - lr * decay first (torch.optim.AdamW, FBGEMM DECOUPLE)")
     p.add_argument("--fold_hook", action="store_true", help="write [B,F,D] from the gather kernel")
     p.add_argument("--window_keys", action="store_true",
                    help="the window's cache op also groups every batch's slots by row (source-row keys): the forward "
@@ -370,12 +377,12 @@ def make_optimizer(model, args, device, world: int):
     lr = args.learning_rate if lr_t is None else lr_t
     groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world, "lr_scale": world}]
     if args.adam:
-        embed.set_fused_adam(lr, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc)
+        embed.set_fused_adam(lr, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc, **_decay(args))
         return torch.optim.Adam(groups, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps), None
     if args.adagrad:
-        embed.set_fused_rowwise_adagrad(lr, deterministic=args.adagrad_deterministic, accumulator=acc)
+        embed.set_fused_rowwise_adagrad(lr, deterministic=args.adagrad_deterministic, accumulator=acc, **_decay(args))
     elif args.fused_sgd:
-        embed.set_fused_sgd(lr, accumulator=acc)
+        embed.set_fused_sgd(lr, accumulator=acc, **_decay(args))
     else:
         groups.insert(0, {"params": list(model.sparse_modules.parameters()), "lr": args.learning_rate, "lr_scale": 1})
     if lr_t is not None:
@@ -406,11 +413,13 @@ class LrChange:
             g["lr"] = new * g.get("lr_scale", 1)
         acc = "step" if args.step_accumulator else "cache"
         if args.adam:
-            self.embed.set_fused_adam(new, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc)
+            self.embed.set_fused_adam(new, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc,
+                                      **_decay(args))
         elif args.adagrad:
-            self.embed.set_fused_rowwise_adagrad(new, deterministic=args.adagrad_deterministic, accumulator=acc)
+            self.embed.set_fused_rowwise_adagrad(new, deterministic=args.adagrad_deterministic, accumulator=acc,
+                                                 **_decay(args))
         elif args.fused_sgd:
-            self.embed.set_fused_sgd(new, accumulator=acc)
+            self.embed.set_fused_sgd(new, accumulator=acc, **_decay(args))
 
 
 class _GraphedStep:
@@ -629,6 +638,25 @@ def _evaluate(model, loader, stage, args, device, rank, world):
     return auroc, acc
 
 
+def _decay(args) -> dict:
+    """the keywords every set_fused_* takes for --embed_weight_decay / --embed_weight_decay_mode"""
+    return {"weight_decay": args.embed_weight_decay, "weight_decay_mode": args.embed_weight_decay_mode}
+
+
+def check_embed_weight_decay(args):
+    """--embed_weight_decay: refused here, before a device is touched, with the library's own refusals"""
+    from cachedembedding_amd.functional import check_weight_decay, check_weight_decay_path
+    wd = check_weight_decay(args.embed_weight_decay, args.embed_weight_decay_mode)
+    if not wd:
+        return
+    if not (args.adagrad or args.adam or args.fused_sgd):
+        raise ValueError("--embed_weight_decay decays the rows inside a fused update: pass --adagrad, --adam or "
+                         "--fused_sgd")
+    table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
+    check_weight_decay_path("adam" if args.adam else "rowwise_adagrad" if args.adagrad else "sgd", table, wd,
+                            bool(args.adagrad_deterministic))
+
+
 def check_step_accumulator(args):
     """--step_accumulator: refused here, before a device is touched, with the library's own refusals"""
     from cachedembedding_amd.functional import check_accumulator
@@ -650,6 +678,7 @@ def main(argv=None):
         raise NotImplementedError("--adagrad_deterministic rounds a 16-bit table to nearest: pass --weight_rounding nearest")
     if args.step_accumulator:
         check_step_accumulator(args)
+    check_embed_weight_decay(args)
     if args.change_lr and args.graph_step and args.adagrad_deterministic:
         raise NotImplementedError("--graph_step --change_lr keeps the learning rate in a device tensor, which the "
                                   "sorted update (--adagrad_deterministic) does not read")

@@ -309,7 +309,7 @@ int ce_bag_backward_sgd_sorted(float* weight, int64_t num_rows, int32_t dim,
                                int32_t mode, int64_t hook_features, const float* grad_out, float lr,
                                void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
-/* Fused exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD with weight_decay = 0).  For every UNIQUE row of the
+/* Fused exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD; weight decay: the ce_*_wd entries further down).  For every UNIQUE row of the
  * call, g = the sum of its lookups' gradient rows (as the SGD entries scale them), then
  *   momentum[m] += sum_d g[d]^2 / dim ;  weight[slot] -= lr * g / (sqrt(momentum[m]) + eps)
  * with m = row_of_slot[slot] (row_of_slot: device int32[num_rows], the cache's cached_idx_map; NULL = the slot itself)
@@ -615,7 +615,8 @@ int ce_bag_backward_update_src_lrdev(void* weight, int32_t weight_dtype, int64_t
  *     a workspace that is too small; then, for a call with lookups, what the covered pipeline refuses (null indices /
  *     offsets / keys, mean with per-sample weights, hook_features that does not divide num_bags).
  *   - nnz == 0 (or num_bags == 0) returns after those checks with no launch: it does not count a step.
- * Not built: 16-bit moments or tables, the sorted (deterministic) fold, weight decay. */
+ * Not built: 16-bit moments or tables, the sorted (deterministic) fold.  Weight decay (L2 as torch.optim.Adam's,
+ * decoupled as torch.optim.AdamW's): ce_bag_backward_adam_wd / _adam_src_wd below. */
 int ce_host_fill_uniform_adam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed, int threads);
 int ce_bag_forward_adam(const float* weight, int64_t num_rows, int32_t dim,
                         const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
@@ -635,6 +636,83 @@ int ce_bag_backward_adam_src(float* weight, int64_t num_rows, int32_t dim, int64
                              const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
                              double beta1, double beta2, float lr, const float* lr_dev, float eps, int64_t* step,
                              int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+
+/* Weight decay for the fused updates (additions to API 6): L2 and decoupled, lazy.  Five entries; each is an existing
+ * argument list with `float weight_decay, int32_t weight_decay_mode` directly behind `eps`:
+ *   ce_bag_backward_update_wd        the list of ce_bag_backward_update_lrdev with `float lr, const float* lr_dev` in
+ *                                    place of `const float* lr` (Adam's convention: lr_dev == NULL means by value):
+ *                                    row-wise Adagrad on fp32 / bf16 / fp16 tables, SGD on 16-bit tables, CE_ACC_CACHE
+ *                                    and CE_ACC_STEP
+ *   ce_bag_backward_update_src_wd    the same from source-row keys (the list of ce_bag_backward_update_src_lrdev)
+ *   ce_bag_backward_update_sorted_wd the list of ce_bag_backward_update_sorted (float lr only): the deterministic fold,
+ *                                    Adagrad and SGD, fp32 and 16-bit tables with CE_ROUND_NEAREST
+ *   ce_bag_backward_adam_wd          the list of ce_bag_backward_adam (Adam-layout table, both accumulators)
+ *   ce_bag_backward_adam_src_wd      the list of ce_bag_backward_adam_src
+ * The workspaces are those of the covered entries, with the same contracts; so are the refusals, their codes, messages
+ * and order, capture-safety, no host synchronisation, no allocation.
+ *
+ * The decay is LAZY, as FBGEMM's and torch.optim.SparseAdam's state updates are: in a call exactly the rows the call
+ * NAMES are decayed, once, however often they are named.  A row is named if some lookup that a bag covers has its slot
+ * in [0, num_rows) (a source-row key: a row half below num_rows).  A row named only by zero-weight lookups (g = 0) still
+ * decays; rows no covered lookup names keep their bits -- w, momentum and moments.  (So the mark pass of the slots +
+ * offsets forms flags covered lookups only here, and the sorted form gives uncovered lookups the ignored key.)
+ * All arithmetic is fp32 with contraction off, every operation rounded on its own.  w: the row before the call (a 16-bit
+ * row up-converted exactly), g: its folded gradient:
+ *   CE_WD_L2        (torch.optim.{SGD, Adagrad, Adam}(weight_decay=), FBGEMM L2):  h = g + wd * w per element (the
+ *                   product rounded, then the sum); the covered entry's update with h in place of g EVERYWHERE: row-wise
+ *                   Adagrad's sum h^2 / dim, the momentum and the step; Adam's m' and v'; SGD's w - lr * h.
+ *   CE_WD_DECOUPLED (torch.optim.AdamW, FBGEMM DECOUPLE):  f = (float)(1.0 - (double)lr * (double)wd), lr the call's
+ *                   learning rate -- *lr_dev when that is given, read when the kernels run, so a replayed graph follows
+ *                   a schedule in the decay too; for Adam lr, not lr * c_t --;  w_d = w * f per element; the covered
+ *                   entry's update with w_d in place of w and the raw g.
+ *   CE_WD_NONE, or weight_decay == 0 with any mode: the covered entry's update, by the covered entry's kernels: the
+ *                   bits are those of the covered entry.
+ * Row-wise Adagrad: a slot whose momentum index lies outside [0, momentum_rows) is not touched, so it does not decay.
+ * A 16-bit row is rounded once per call, nearest or stochastic (same hash of seed, step counter, row and element).
+ * A row looked up once in a call gets the same bits from CE_ACC_CACHE, CE_ACC_STEP and the sorted entry.
+ * Refusals: an unknown weight_decay_mode, then a weight_decay that is negative or NaN, are CE_ERR_INVALID.  The two
+ * checks stand directly behind the entry's leading checks -- the accumulator code in the update entries; step == NULL
+ * and the accumulator code in the Adam entries; nothing in the sorted entry, where they come first -- before every
+ * other refusal, and also for nnz == 0.  CE_OPT_SGD on an fp32 table stays CE_ERR_UNSUPPORTED in the two atomic entries
+ * (that scatter has no per-row pass): fp32 SGD with decay exists through the sorted entry only.
+ * Not built: FBGEMM's COUNTER / COWCLIP modes, a decay read from device memory, decay in ce_rows_axpy. */
+#define CE_WD_NONE 0
+#define CE_WD_L2 1
+#define CE_WD_DECOUPLED 2
+int ce_bag_backward_update_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                              const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                              int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                              int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                              const uint64_t* presorted, const int32_t* row_of_slot, float* momentum,
+                              int64_t momentum_rows, float lr, const float* lr_dev, float eps, float weight_decay,
+                              int32_t weight_decay_mode, int32_t optimizer, int32_t rounding, uint64_t seed,
+                              int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_update_src_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
+                                  const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                  const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                  const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
+                                  int32_t optimizer, int32_t rounding, uint64_t seed, int32_t accumulator,
+                                  void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_update_sorted_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                     const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                     int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                     int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                     const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                     float eps, float weight_decay, int32_t weight_decay_mode, int32_t optimizer,
+                                     int32_t rounding, uint64_t seed, void* workspace, size_t workspace_bytes,
+                                     ce_stream_t stream);
+int ce_bag_backward_adam_wd(float* weight, int64_t num_rows, int32_t dim,
+                            const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                            int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                            int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                            const uint64_t* presorted, double beta1, double beta2, float lr, const float* lr_dev,
+                            float eps, float weight_decay, int32_t weight_decay_mode, int64_t* step,
+                            int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_adam_src_wd(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                                float weight_decay, int32_t weight_decay_mode, int64_t* step, int32_t accumulator,
+                                void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
 /* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
  * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
