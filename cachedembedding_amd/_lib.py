@@ -122,6 +122,7 @@ _SORTED_WD_TAIL = [c_void_p, c_void_p, c_int64, c_float, c_float] + _WD + \
     [c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
 _ADAM_WD_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD + \
     [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
+_ROW_MOMENT = [c_void_p, c_void_p, c_int64]      # row_of_slot, v, v_rows (partial row-wise Adam), behind the keys
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -208,6 +209,14 @@ SIGNATURES = {
     "ce_bag_backward_update_sorted_wd": (c_int, _W16 + _BAG[1:] + _ACT + _SORTED_WD_TAIL),
     "ce_bag_backward_adam_wd": (c_int, _BAG + _ACT + _ADAM_WD_TAIL),
     "ce_bag_backward_adam_src_wd": (c_int, _SRC + _ACT + _ADAM_WD_TAIL),
+    # partial row-wise Adam (rows w | m of 2 * dim fp32, the second moment one fp32 per table row): the Adam layout's
+    # lists; the update's = the _adam_wd lists with row_of_slot, v, v_rows behind the keys
+    "ce_host_fill_uniform_pradam": (c_int, [c_void_p, c_int64, c_int32, c_float, c_float, c_uint64, c_int]),
+    "ce_bag_forward_pradam": (c_int, _BAG + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_pradam": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    "ce_bag_backward_pradam_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ce_bag_backward_pradam": (c_int, _BAG + _ACT + _KEYS + _ROW_MOMENT + _ADAM_WD_TAIL[1:]),
+    "ce_bag_backward_pradam_src": (c_int, _SRC + _ACT + _KEYS + _ROW_MOMENT + _ADAM_WD_TAIL[1:]),
     # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
     "ce_q8_row_bytes": (c_size_t, [c_int32]),
     "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),
@@ -436,12 +445,15 @@ def check_quant_bits(bits) -> int:
 
 
 # the Adam layout (fused_optimizer="adam"): an fp32 table whose rows carry their moments, [N, 3 * D] = w | m | v
-LAYOUTS = (None, "adam")
+# partial row-wise Adam (fused_optimizer="partial_rowwise_adam"): [N, 2 * D] = w | m, the second moment one fp32 per row
+# in device memory
+LAYOUTS = (None, "adam", "partial_rowwise_adam")
+LAYOUT_SPAN = {None: 1, "adam": 3, "partial_rowwise_adam": 2}      # row parts of D floats
 
 
 def check_layout(layout):
     if layout not in LAYOUTS:
-        raise ValueError(f"layout={layout!r}: None or 'adam'")
+        raise ValueError(f"layout={layout!r}: None, 'adam' or 'partial_rowwise_adam'")
     return layout
 
 
@@ -453,11 +465,12 @@ def check_adam_dim(dim: int) -> None:
                                   f"(got {dim})")
 
 
-def check_adam_table(dim: int, table_dtype) -> None:
-    """what fused_optimizer="adam" needs of the table: fp32 rows (no 16-bit, no quantized table) and the dim rule"""
+def check_adam_table(dim: int, table_dtype, layout: str = "adam") -> None:
+    """what fused_optimizer="adam" / "partial_rowwise_adam" needs of the table: fp32 rows (no 16-bit, no quantized
+    table) and the dim rule"""
     if quant_bits_of(table_dtype) or table_code(table_dtype) != CE_ACT_F32:
-        raise NotImplementedError(f"fused_optimizer='adam' with table_dtype={table_dtype}: the Adam layout is an fp32 "
-                                  "table (16-bit moments or tables are not implemented)")
+        raise NotImplementedError(f"fused_optimizer={layout!r} with table_dtype={table_dtype}: the Adam layout is an "
+                                  "fp32 table (16-bit moments or tables are not implemented)")
     check_adam_dim(dim)
 
 

@@ -58,7 +58,9 @@ class HostTable:
         # "adam": an fp32 table whose rows carry their Adam moments, [N, 3 * D] = w | m | v; None: rows
         # of elements (or quantized rows, quant_bits)
         self.layout = _lib.check_layout(layout)
-        assert layout is None or (tensor.dtype == torch.float32 and tensor.shape[1] % 3 == 0 and not quant_bits)
+        # "partial_rowwise_adam": [N, 2 * D] = w | m, the second moment is not the table's
+        self.span = _lib.LAYOUT_SPAN[layout]
+        assert layout is None or (tensor.dtype == torch.float32 and tensor.shape[1] % self.span == 0 and not quant_bits)
         # 8 / 4: the rows are q8 / q4 rows (torch.uint8 storage either way; uint8 alone means q8), 0: they are elements
         self.quant_bits = quant_bits or (8 if tensor.dtype == _lib.Q8 else 0)
         self.host_ptr = host_ptr
@@ -78,17 +80,19 @@ class HostTable:
                  layout: Optional[str] = None) -> "HostTable":
         if not isinstance(threads, int):              # allocate(N, D, dtype)
             threads, dtype = 0, threads
-        if _lib.check_layout(layout) == "adam":
-            # [N, 3 * D] fp32: the rows' w parts are filled by fill_uniform_ / set_weight_, the moments start at zero
-            _lib.check_adam_table(dim, dtype)
+        if _lib.check_layout(layout) is not None:
+            # [N, 3 * D] (adam) or [N, 2 * D] (partial_rowwise_adam) fp32: the rows' w parts are filled by fill_uniform_ /
+            # set_weight_, the moments start at zero
+            span = _lib.LAYOUT_SPAN[layout]
+            _lib.check_adam_table(dim, dtype, layout)
             _lib.require_gpu()
-            n = num_embeddings * 3 * dim
+            n = num_embeddings * span * dim
             hp, dp = ctypes.c_void_p(), ctypes.c_void_p()
             check(lib.ce_host_alloc(n * 4, threads or _default_threads(), ctypes.byref(hp), ctypes.byref(dp)))
             carr = (ctypes.c_float * n).from_address(hp.value)
             carr._ce_block = _PinnedBlock(hp.value)
             t = torch.from_numpy(np.ctypeslib.as_array(carr))
-            return cls(t.view(num_embeddings, 3 * dim), hp.value, dp.value, registered=False, layout="adam")
+            return cls(t.view(num_embeddings, span * dim), hp.value, dp.value, registered=False, layout=layout)
         if dtype == _lib.Q8 or dtype == _lib.Q4:
             # a row-wise quantized table: [N, 16 + D] (q8) or [N, 16 + D / 2] (q4, spelled torch.quint4x2) uint8, whole
             # rows (filled by quantize_from)
@@ -159,17 +163,30 @@ class HostTable:
 
     def set_weight_(self, w: torch.Tensor) -> "HostTable":
         """an Adam-layout table: the w parts = `w` ([N, D], cast to fp32), the moments zero"""
-        assert self.layout == "adam" and tuple(w.shape) == (self.tensor.shape[0], self.tensor.shape[1] // 3)
+        assert self.layout is not None and tuple(w.shape) == (self.tensor.shape[0], self.tensor.shape[1] // self.span)
         d = w.shape[1]
         self.tensor.zero_()
         self.tensor[:, :d].copy_(w.detach().to("cpu", torch.float32))
         return self
 
+    def set_moments_(self, exp_avg: torch.Tensor, exp_avg_sq: Optional[torch.Tensor] = None) -> "HostTable":
+        """an Adam-layout table: the m parts = `exp_avg` ([N, D]) and, for rows w | m | v, the v parts = `exp_avg_sq`;
+        the w parts are not touched"""
+        n, d = self.tensor.shape[0], self.tensor.shape[1] // self.span
+        assert self.layout is not None and tuple(exp_avg.shape) == (n, d)
+        assert (exp_avg_sq is not None) == (self.span == 3)
+        self.tensor[:, d:2 * d].copy_(exp_avg.detach().to("cpu", torch.float32))
+        if exp_avg_sq is not None:
+            assert tuple(exp_avg_sq.shape) == (n, d)
+            self.tensor[:, 2 * d:].copy_(exp_avg_sq.detach().to("cpu", torch.float32))
+        return self
+
     def fill_uniform_(self, lo: float, hi: float, seed: int, threads: int = 0):
-        if self.layout == "adam":
+        if self.layout is not None:
             # row r's w part = row r of the plain fp32 fill of the same seed; zero moments
-            check(lib.ce_host_fill_uniform_adam(ctypes.c_void_p(self.host_ptr), self.tensor.shape[0],
-                                                self.tensor.shape[1] // 3, lo, hi, seed, threads or _default_threads()))
+            fill = lib.ce_host_fill_uniform_adam if self.layout == "adam" else lib.ce_host_fill_uniform_pradam
+            check(fill(ctypes.c_void_p(self.host_ptr), self.tensor.shape[0], self.tensor.shape[1] // self.span, lo, hi,
+                       seed, threads or _default_threads()))
             return self
         if self.quant_bits == 4:
             raise NotImplementedError("a q4 (torch.quint4x2) table is built from trained rows (quantize_from), not "
@@ -219,8 +236,8 @@ class CachedParamMgr(torch.nn.Module):
         # a q8 table's rows are 16 + D bytes wide, a q4 table's 16 + D / 2; embedding_dim keeps meaning D
         self.embedding_dim = (2 * (self._row_width - _lib.CE_Q4_HEADER_BYTES) if self.quant_bits == 4
                               else self._row_width - _lib.CE_Q8_HEADER_BYTES) if q8 else self._row_width
-        if self.layout == "adam":                     # rows w | m | v of 3 * D floats: D keeps meaning D
-            self.embedding_dim = self._row_width // 3
+        if self.layout is not None:                   # rows w | m | v of 3 * D floats, or w | m of 2 * D: D keeps meaning D
+            self.embedding_dim = self._row_width // self._table.span
         # what the library is told a row is: fp32 elements (a 16-bit row of D elements = D / 2 of them, a q8 row
         # (16 + D) / 4 and a q4 row (16 + D / 2) / 4 of them, bit for bit)
         self._lib_dim = self._row_width // 4 if q8 else (

@@ -35,9 +35,10 @@ def _refuse_q8_update(module, what: str, lr) -> None:
 
 
 def _refuse_adam_layout(module, what: str, lr) -> None:
-    if lr is not None and getattr(module, "fused_optimizer", None) == "adam":
-        raise NotImplementedError(f"{what}(lr) on an Adam-layout module (fused_optimizer='adam'): its rows carry Adam's "
-                                  "moments, set_fused_adam(lr) is its fused update")
+    layout = getattr(module, "fused_optimizer", None)
+    if lr is not None and layout is not None:
+        raise NotImplementedError(f"{what}(lr) on an Adam-layout module (fused_optimizer={layout!r}): its rows carry "
+                                  "Adam's moments, set_fused_adam(lr) is its fused update")
 
 
 def _quant_name(bits: int) -> str:
@@ -58,16 +59,20 @@ class CachedEmbeddingBag(nn.Module):
         # fused_optimizer="adam" (addition): the host table AND the cache hold rows w | m | v of 3 * D floats -- Adam's
         # moments live where the table lives and travel with the rows through eviction and admission;
         # set_fused_adam(lr) then applies Adam inside backward.  An fp32 table only; embedding_dim keeps meaning D.
-        if fused_optimizer not in (None, "adam"):
-            raise ValueError(f"fused_optimizer={fused_optimizer!r}: None or 'adam'")
+        # fused_optimizer="partial_rowwise_adam" (addition; FBGEMM's PARTIAL_ROWWISE_ADAM): rows w | m of
+        # 2 * D floats -- the first moment travels with the row --, and the second moment is one fp32 per host-table row
+        # in device memory (`.exp_avg_sq`, [N]), fed by the mean of the row's squared gradient.  Everything else is the
+        # Adam layout's: set_fused_adam(lr), an fp32 table only, the same refusals.
+        if fused_optimizer not in _lib.LAYOUTS:
+            raise ValueError(f"fused_optimizer={fused_optimizer!r}: None, 'adam' or 'partial_rowwise_adam'")
         self.fused_optimizer = fused_optimizer
-        adam = fused_optimizer == "adam"
+        adam = fused_optimizer is not None
         if adam:
-            _lib.check_adam_table(embedding_dim, table_dtype)
+            _lib.check_adam_table(embedding_dim, table_dtype, fused_optimizer)
             for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
                              ("sparse=True", bool(sparse))):
                 if on:
-                    raise NotImplementedError(f"{what} with an Adam-layout table (fused_optimizer='adam')")
+                    raise NotImplementedError(f"{what} with an Adam-layout table (fused_optimizer={fused_optimizer!r})")
         # output_dtype (addition): dtype of the pooled output and of the gradient coming back -- None / torch.float32,
         # torch.bfloat16 or torch.float16 (functional.embedding_bag(output_dtype=...)).  `dtype` is the TABLE's dtype.
         if dtype not in (None, torch.float32):
@@ -137,7 +142,7 @@ class CachedEmbeddingBag(nn.Module):
             assert table.tensor.dtype == (torch.uint8 if q8 else self.table_dtype) and table.quant_bits == bits \
                 and table.tensor.shape[0] == num_embeddings and table.layout == fused_optimizer
         elif adam:
-            table = HostTable.allocate(num_embeddings, embedding_dim, layout="adam")
+            table = HostTable.allocate(num_embeddings, embedding_dim, layout=fused_optimizer)
             if _weight is None:
                 table.fill_uniform_(-1.0 / num_embeddings, 1.0 / num_embeddings, init_seed)
                 if padding_idx is not None:
@@ -183,18 +188,27 @@ class CachedEmbeddingBag(nn.Module):
         if adam:
             # the step count Adam's bias correction reads: on the device, so that a replayed graph counts on
             self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.cache_weight_mgr.device)
-            self.fused_adam = FusedAdam(None, step=self.adam_step)
+            mgr = self.cache_weight_mgr
+            if fused_optimizer == "partial_rowwise_adam":
+                # the rows' second moments: one fp32 per host-table row, resident in HBM like row-wise Adagrad's
+                # momentum1, indexed through cached_idx_map and never moved by the cache
+                mgr.exp_avg_sq = torch.zeros(mgr.num_embeddings, device=mgr.device, dtype=torch.float32)
+                self.fused_adam = FusedAdam(None, step=self.adam_step, layout=fused_optimizer,
+                                            exp_avg_sq=mgr.exp_avg_sq, row_of_slot=mgr.cached_idx_map)
+            else:
+                self.fused_adam = FusedAdam(None, step=self.adam_step)
 
     # -- the host table (upstream `.weight`) and the parameter protocol (A.7) ------------
     @property
     def weight(self) -> torch.Tensor:
         # (an Adam-layout table: the [N, D] view of the rows' w parts; current after flush(), like the moments)
         w = self.cache_weight_mgr.weight
-        return w[:, :self.embedding_dim] if self.fused_optimizer == "adam" else w
+        return w[:, :self.embedding_dim] if self.fused_optimizer is not None else w
 
     def _adam_part(self, k: int, name: str) -> torch.Tensor:
-        if self.fused_optimizer != "adam":
-            raise AttributeError(f"{name} exists on a module built with fused_optimizer='adam'")
+        if self.fused_optimizer is None:
+            raise AttributeError(f"{name} exists on a module built with fused_optimizer='adam' or "
+                                 "'partial_rowwise_adam'")
         d = self.embedding_dim
         return self.cache_weight_mgr.weight[:, k * d:(k + 1) * d]
 
@@ -205,8 +219,34 @@ class CachedEmbeddingBag(nn.Module):
 
     @property
     def exp_avg_sq(self) -> torch.Tensor:
-        """Adam's second moment, the [N, D] view of the host table's v parts; current after flush()"""
+        """Adam's second moment, the [N, D] view of the host table's v parts; current after flush().  Partial row-wise
+        Adam: the [N] fp32 DEVICE tensor of the rows' second moments, indexed by host-table row (in row space, like
+        cache_weight_mgr.momentum1; with ids_freq_mapping row = idx_map[id]); the kernels write it in place."""
+        if self.fused_optimizer == "partial_rowwise_adam":
+            return self.cache_weight_mgr.exp_avg_sq
         return self._adam_part(2, "exp_avg_sq")
+
+    def load_adam_state(self, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int) -> None:
+        """Restore Adam's state, as read from `.exp_avg` / `.exp_avg_sq` / `.adam_step` of a module with the same layout
+        and the same id -> row map: exp_avg [N, D]; exp_avg_sq [N, D] (Adam layout) or [N] (partial row-wise Adam); step
+        the step count.  Flushes first, then writes the host table's moment parts (the partial layout: the device
+        tensor) and sets the step count; the weights are not touched."""
+        if self.fused_optimizer is None:
+            raise ValueError("load_adam_state needs a module built with fused_optimizer='adam' or 'partial_rowwise_adam'")
+        n, d = self.num_embeddings, self.embedding_dim
+        partial = self.fused_optimizer == "partial_rowwise_adam"
+        if tuple(exp_avg.shape) != (n, d):
+            raise ValueError(f"exp_avg must be [{n}, {d}] (got {tuple(exp_avg.shape)})")
+        if tuple(exp_avg_sq.shape) != ((n,) if partial else (n, d)):
+            raise ValueError(f"exp_avg_sq must be {[n] if partial else [n, d]} (got {tuple(exp_avg_sq.shape)})")
+        if int(step) < 0:
+            raise ValueError(f"step={step!r}: must be >= 0")
+        self.flush()
+        self.cache_weight_mgr.writeback_wait()              # (the write-backs of the worker transport have landed)
+        self.cache_weight_mgr._table.set_moments_(exp_avg, None if partial else exp_avg_sq)
+        if partial:
+            self.cache_weight_mgr.exp_avg_sq.copy_(exp_avg_sq.detach().to(torch.float32))
+        self.adam_step.fill_(int(step))
 
     def named_parameters(self, prefix: str = "", recurse: bool = True, remove_duplicate: bool = True
                          ) -> Iterator[Tuple[str, nn.Parameter]]:
@@ -299,9 +339,9 @@ class CachedEmbeddingBag(nn.Module):
         weight_decay_mode "l2" is torch.optim.Adam(weight_decay=), with "decoupled" torch.optim.AdamW, both lazy: the
         rows a step looks up decay once, at that step (functional.FusedAdam).  Exclusive with
         set_fused_sgd / set_fused_rowwise_adagrad: an Adam-layout module refuses those."""
-        if self.fused_optimizer != "adam":
-            raise ValueError("set_fused_adam needs a module built with fused_optimizer='adam': Adam's moments live in "
-                             "the rows of the table")
+        if self.fused_optimizer is None:
+            raise ValueError("set_fused_adam needs a module built with fused_optimizer='adam' (or 'partial_rowwise_adam'): "
+                             "Adam's moments live in the rows of the table")
         if isinstance(lr, torch.Tensor):
             check_lr(lr)
         elif lr is not None and not float(lr) >= 0.0:
@@ -433,7 +473,7 @@ class CachedEmbeddingBag(nn.Module):
         mgr = self.cache_weight_mgr
         self.flush()
         src = self.weight                                   # (waits for the write-backs of the worker transport)
-        if self.fused_optimizer == "adam":
+        if self.fused_optimizer is not None:
             src = src.contiguous()                          # the w parts alone: the moments are not quantized
         table = HostTable.allocate(self.num_embeddings, self.embedding_dim, dtype=dtype).quantize_from(src)
         kw = dict(cuda_row_num=self.cuda_row_num, output_dtype=self.output_dtype, warmup_ratio=0.7,

@@ -191,11 +191,19 @@ template <> struct Row<AdamRow, f32x4> {
   static __device__ __forceinline__ f32x4 value(Held v, Hdr) { return v; }
 };
 
+// Partial row-wise Adam rows (include/ce_api.h): 2 * rowlen chunks -- w | m, fp32; the second moment is one fp32 per
+// table row outside the row.  The Adam row type with a stride of two rows' width.
+struct PartialAdamRow {};
+constexpr int kTablePartialAdam = 5;   // like kTableQ8
+template <> struct Row<PartialAdamRow, f32x4> : Row<AdamRow, f32x4> {
+  static constexpr int kSpan = 2;
+};
+
 // STAGE: tiles with multi-id bags stage their indices in LDS (32 KB per workgroup); the launcher picks the
 // LDS-free variant when nnz == num_bags (single-id batches) so occupancy is set by registers alone.
 // AT: the output's element type (Act<AT, VT>, ce_common.h): sums stay fp32, the store rounds.
 // WT: the table's row type (Row<WT, VT>: float; bf16 / fp16 with f32x4 lanes, a lane's chunk is then 8 bytes of the row;
-// Q8, Q4 and AdamRow with f32x4 lanes).  A row that takes no part is held as zeros: chunks and header.
+// Q8, Q4, AdamRow and PartialAdamRow with f32x4 lanes).  A row that takes no part is held as zeros: chunks and header.
 template <typename VT, int NCH, bool STAGE, int U, typename AT, typename WT = float>
 __global__ __launch_bounds__(256) void k_bag_fwd(BagParams p) {
   using A = Act<AT, VT>;
@@ -1323,6 +1331,8 @@ template <typename F> static void for_table_act(int weight_dtype, const RowGeom&
   if (weight_dtype == kTableQ8) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<Q8>{}); });
   else if (weight_dtype == kTableQ4) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<Q4>{}); });
   else if (weight_dtype == kTableAdam) for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<AdamRow>{}); });
+  else if (weight_dtype == kTablePartialAdam)
+    for_vec_lanes(r.nch, [&](auto l) { acts(l, ActTag<PartialAdamRow>{}); });
   else for_table(weight_dtype, r, acts);
 }
 
@@ -1408,7 +1418,8 @@ static int launch_fwd(BagParams& p, const RowGeom& r, const void* weight, int we
 // The key-driven forward.  An fp32 table has the PAIR form for a 16-bit output; a 16-bit table only the converting
 // instantiation (WT != AT: exact up-conversion, one rounding on the store) -- equal types never get here, see
 // ce_bag_forward_src_keys_w16.  A q8 or q4 table (kTableQ8, kTableQ4) always converts: it takes that arm too, and so
-// does an Adam-layout table (kTableAdam: the arm's kernel with an identity conversion; it has no PAIR form).
+// does an Adam-layout table (kTableAdam, kTablePartialAdam: the arm's kernel with an identity conversion; it has no PAIR
+// form).
 static int launch_fwd_keys(const void* weight, int weight_dtype, int64_t num_rows, int32_t dim, bool aligned, int64_t nnz,
                            const uint64_t* src_keys, void* out, int act, hipStream_t s) {
   BagParams p{};
@@ -1835,6 +1846,40 @@ extern "C" int ce_bag_forward_src_keys_adam(const float* weight, int64_t num_row
   CE_REQUIRE_ROWS(num_rows);
   CE_REQUIRE_ADAM_ALIGNED(weight, out, act_dtype);
   return launch_fwd_keys(weight, kTableAdam, num_rows, dim, true, nnz, src_keys, out, act_dtype, (hipStream_t)stream);
+}
+
+// ---- forward from a partial row-wise Adam table (rows w | m of 2 * dim fp32; the Adam layout's rules): the row type
+// PartialAdamRow, which reads the w part alone
+extern "C" int ce_bag_forward_pradam(const float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                     int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                     int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                     int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_ADAM_DIM(dim);
+  if (num_bags == 0) return CE_OK;
+  CE_REQUIRE(weight && out && (indices || nnz == 0), CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(offsets || num_bags == nnz, CE_ERR_INVALID,
+             "offsets == NULL states one id per bag (offsets = arange): num_bags must equal nnz");
+  CE_REQUIRE_ADAM_ALIGNED(weight, out, act_dtype);
+  BagParams p{};
+  RowGeom r;
+  int rc = fill_params(p, r, dim, true, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                       per_sample_weights, mode, hook_features);
+  if (rc) return rc;
+  return launch_fwd(p, r, weight, kTablePartialAdam, num_rows, out, act_dtype, (hipStream_t)stream);
+}
+
+extern "C" int ce_bag_forward_src_keys_pradam(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                              const uint64_t* src_keys, void* out, int32_t act_dtype,
+                                              ce_stream_t stream) {
+  CE_REQUIRE_ACT(act_dtype);
+  CE_REQUIRE_ADAM_DIM(dim);
+  if (nnz == 0) return CE_OK;
+  CE_REQUIRE(weight && src_keys && out, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE_ROWS(num_rows);
+  CE_REQUIRE_ADAM_ALIGNED(weight, out, act_dtype);
+  return launch_fwd_keys(weight, kTablePartialAdam, num_rows, dim, true, nnz, src_keys, out, act_dtype,
+                         (hipStream_t)stream);
 }
 
 extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : padded_keys(nnz); }

@@ -19,7 +19,9 @@
 // backward can be captured into a hipGraph).  The momentum is indexed by host-table row (row_of_slot = cached_idx_map)
 // and never moves with the cache; a slot maps to one row for the whole step, so folding by slot is folding by row.
 // Adam (ce_bag_backward_adam*) is a third arithmetic of update_row on an fp32 table whose rows carry
-// their own moments (w | m | v): the two atomic folds above, unchanged, hand it the same folded gradient.
+// their own moments (w | m | v): the two atomic folds above, unchanged, hand it the same folded gradient.  Partial
+// row-wise Adam (ce_bag_backward_pradam*) is a fourth: rows w | m, the second moment one fp32 per table
+// row where row-wise Adagrad keeps its momentum, fed by the mean of the row's squared gradient.
 #include "ce_common.h"
 
 namespace ce {
@@ -161,13 +163,55 @@ __device__ __forceinline__ float adam_delta(float lr, float eps, float m, float 
   return lr * q;
 }
 
-template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false>
+//   ROWV (with ADAM: partial row-wise Adam, an fp32 table of rows w | m; the second moment is momentum[r], one fp32 per
+//   table row as in adagrad, and r outside it: nothing happens, no decay either), h the gradient after the decay:
+//     ss = sum of the group's lane_sq_sum<float> of h (xor tree, widest stride first) ;
+//     v' = v[r] + omb2 * (ss / D - v[r]) (lane 0 writes) ; m' = m + omb1 * (h - m) ; w' = w - lr * (m' / (sqrtf(v') + eps))
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false>
 __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64_t step_key, int64_t s,
                                            const VT (&g)[NCH], int gl, int G, bool adagrad, float f = 1.f) {
 #pragma clang fp contract(off)
   using T = Act<WT, VT>;
   const bool l2 = WD && a.wd_mode == CE_WD_L2;               // uniform
   static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
+  static_assert(!ROWV || ADAM, "a row-wise second moment: Adam only");
+  if constexpr (ADAM && ROWV) {
+    static_assert(std::is_same<WT, float>::value && sizeof(VT) == 16 && !STOCH, "Adam: an fp32 table, vector lanes");
+    f32x4* R = (f32x4*)a.weight + s * 2 * (int64_t)a.rowlen;      // w: [0, rowlen), m: [rowlen, 2 rowlen)
+    const int64_t r = a.row_of_slot ? (int64_t)a.row_of_slot[s] : s;
+    // WD: the row as it was (zero past rowlen, so h is zero there as g is) and hg, the gradient the update sees
+    f32x4 w0[WD ? NCH : 1], hg[WD ? NCH : 1];
+    if constexpr (WD) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        w0[c] = idx < a.rowlen ? R[idx] : vzero<f32x4>();
+        hg[c] = g[c];
+        if (l2) hg[c] = g[c] + w0[c] * a.wd; else w0[c] = w0[c] * f;
+      }
+    }
+    float ss;
+    if constexpr (WD) ss = lane_sq_sum<float, NCH>(hg); else ss = lane_sq_sum<float, NCH>(g);
+    for (int off = G >> 1; off > 0; off >>= 1) ss = ss + __shfl_xor(ss, off, G);
+    if (r < 0 || r >= a.momentum_rows) return;
+    const float v0 = a.momentum[r];
+    const float v = v0 + (ss / (float)a.dim - v0) * a.omb2;
+    if (gl == 0) a.momentum[r] = v;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      if (idx >= a.rowlen) continue;
+      f32x4 gc, w;
+      if constexpr (WD) { gc = hg[c]; w = w0[c]; } else { gc = g[c]; w = R[idx]; }
+      f32x4 m = R[a.rowlen + idx];
+      m = m + (gc - m) * a.omb1;
+      w = w - f32x4{adam_delta(lr, a.eps, m.x, v), adam_delta(lr, a.eps, m.y, v), adam_delta(lr, a.eps, m.z, v),
+                    adam_delta(lr, a.eps, m.w, v)};
+      R[idx] = w;
+      R[a.rowlen + idx] = m;
+    }
+    return;
+  }
   if constexpr (ADAM) {
     static_assert(std::is_same<WT, float>::value && sizeof(VT) == 16 && !STOCH, "Adam: an fp32 table, vector lanes");
     f32x4* R = (f32x4*)a.weight + s * 3 * (int64_t)a.rowlen;      // w: [0, rowlen), m: [rowlen, 2 rowlen), v behind it
@@ -341,7 +385,8 @@ struct ApplyArgs {
 
 // a wave reads 64 flags at once, and a lane group per flagged slot reads acc, updates the row and writes acc and the
 // flag back to zero
-template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH, bool ADAM = false, bool WD = false>
+template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH, bool ADAM = false, bool WD = false,
+          bool ROWV = false>
 __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
   const LaneGroup l = lane_group(a.u.g_log2);
   VT* A = (VT*)a.acc;
@@ -355,7 +400,7 @@ __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
       const int64_t s = base + i;
       VT g[NCH];
       load_row(g, A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
-      update_row<VT, WT, NCH, STOCH, ADAM, WD>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD, f);
+      update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD, f);
       zero_row<VT, NCH>(A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
     });
     if (flagged) a.flags[mine] = 0;
@@ -762,7 +807,7 @@ struct CompactArgs {
 };
 
 // one lane group per list entry (grid-stride over u < U; the grid is sized by cap)
-template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false>
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false>
 __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   const int G = 1 << a.u.g_log2;
   const int gl = threadIdx.x & (G - 1);
@@ -776,7 +821,7 @@ __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
     VT g[NCH];
     load_row(g, A + u * a.u.rowlen, gl, G, a.u.rowlen);
-    update_row<VT, WT, NCH, STOCH, ADAM, WD>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad, f);
+    update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad, f);
     zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
   }
 }
@@ -860,6 +905,7 @@ static CompactWs carve_compact(void* ws, int64_t num_rows, int64_t nnz, int32_t 
 }
 
 constexpr int32_t kOptAdam = 2;       // beside CE_OPT_*: library-internal, no `optimizer` argument takes it
+constexpr int32_t kOptPartialAdam = 3;   // partial row-wise Adam (rows w | m, the second moment in `momentum`): likewise
 
 // the arguments every update entry has (the fp32 Adagrad entries: CE_ACT_F32, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST)
 struct UpdateCall {
@@ -889,7 +935,8 @@ struct UpdateCall {
   bool decay() const { return wd_mode != CE_WD_NONE && wd != 0.f; }
   bool w16() const { return weight_dtype != CE_ACT_F32; }
   bool adagrad() const { return optimizer == CE_OPT_ROWWISE_ADAGRAD; }
-  bool adam() const { return optimizer == kOptAdam; }
+  bool adam() const { return optimizer == kOptAdam || optimizer == kOptPartialAdam; }
+  bool rowv() const { return optimizer == kOptPartialAdam; }     // (then adam() holds as well)
   bool stochastic() const { return rounding == CE_ROUND_STOCHASTIC; }
 };
 
@@ -1028,7 +1075,11 @@ static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const SlotL
   const bool ada = c.adagrad(), st = c.stochastic();
   for_decay(c.decay(), [&](auto d) {
     constexpr bool WD = decltype(d)::value;
-    if (c.adam())
+    if (c.rowv())
+      for_vec_lanes(r.nch, [&](auto l) {
+        hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD, true>), g, b, 0, s, a);
+      });
+    else if (c.adam())
       for_vec_lanes(r.nch, [&](auto l) {
         hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD>), g, b, 0, s, a);
       });
@@ -1067,7 +1118,11 @@ static int launch_compact_apply(const UpdateCall& c, const RowGeom& r, const Com
   const dim3 g(grid_for(ws.cap, 256 >> r.g_log2)), b(256);
   for_decay(c.decay(), [&](auto d) {
     constexpr bool WD = decltype(d)::value;
-    if (c.adam())
+    if (c.rowv())
+      for_vec_lanes(r.nch, [&](auto l) {
+        hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD, true>), g, b, 0, s, a);
+      });
+    else if (c.adam())
       for_vec_lanes(r.nch, [&](auto l) {
         hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD>), g, b, 0, s, a);
       });
@@ -1268,6 +1323,8 @@ static int adam_check(const UpdateCall& c, int32_t accumulator, RowGeom& r) {
   CE_REQUIRE_ACT(c.act);
   CE_REQUIRE_ADAM_DIM(c.dim);
   CE_REQUIRE(c.weight && c.grad_out && c.workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(!c.rowv() || (c.momentum && c.momentum_rows > 0), CE_ERR_INVALID,
+             "partial row-wise Adam needs its second moment: v, v_rows > 0");
   CE_REQUIRE(c.num_rows > 0 && c.num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
   CE_REQUIRE(c.nnz >= 0 && c.nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "nnz out of range");
   CE_REQUIRE(al16(c.weight) && (((uintptr_t)c.step) & 7) == 0, CE_ERR_INVALID,
@@ -1278,11 +1335,21 @@ static int adam_check(const UpdateCall& c, int32_t accumulator, RowGeom& r) {
   return row_geometry(c.dim, true, r);
 }
 
+// the second moment of a partial row-wise Adam call (ce_bag_backward_pradam*): v[v_rows], indexed by table row
+struct RowMoment {
+  const int32_t* row_of_slot;
+  float* v;
+  int64_t v_rows;
+};
+
+// rv: NULL for the Adam layout (rows w | m | v), the row-wise second moment of a partial row-wise Adam call (rows w | m)
 static UpdateCall adam_call(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act,
                             double beta1, double beta2, float lr, const float* lr_dev, float eps, int64_t* step,
-                            void* workspace, size_t workspace_bytes, float wd = 0.f, int32_t wd_mode = CE_WD_NONE) {
-  UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act, nullptr, nullptr, 0, lr_dev ? 0.f : lr, eps,
-               kOptAdam, CE_ROUND_NEAREST, 0, workspace, workspace_bytes, lr_dev};
+                            void* workspace, size_t workspace_bytes, float wd = 0.f, int32_t wd_mode = CE_WD_NONE,
+                            const RowMoment* rv = nullptr) {
+  UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act, rv ? rv->row_of_slot : nullptr,
+               rv ? rv->v : nullptr, rv ? rv->v_rows : 0, lr_dev ? 0.f : lr, eps,
+               rv ? kOptPartialAdam : kOptAdam, CE_ROUND_NEAREST, 0, workspace, workspace_bytes, lr_dev};
   c.step = (unsigned long long*)step;
   c.beta1 = beta1;
   c.beta2 = beta2;
@@ -1684,9 +1751,10 @@ static int adam_slots(float* weight, int64_t num_rows, int32_t dim, const int64_
                       const float* per_sample_weights, int32_t mode, int64_t hook_features, const void* grad_out,
                       int32_t act_dtype, const uint64_t* presorted, double beta1, double beta2, float lr,
                       const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode, int64_t* step,
-                      int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+                      int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream,
+                      const RowMoment* rv = nullptr) {
   const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
-                                 workspace, workspace_bytes, weight_decay, weight_decay_mode);
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, rv);
   const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
                       hook_features, presorted};
   RowGeom r;
@@ -1708,9 +1776,9 @@ static int adam_slots(float* weight, int64_t num_rows, int32_t dim, const int64_
 static int adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act_dtype,
                     const uint64_t* src_keys, double beta1, double beta2, float lr, const float* lr_dev, float eps,
                     float weight_decay, int32_t weight_decay_mode, int64_t* step, int32_t accumulator, void* workspace,
-                    size_t workspace_bytes, ce_stream_t stream) {
+                    size_t workspace_bytes, ce_stream_t stream, const RowMoment* rv = nullptr) {
   const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
-                                 workspace, workspace_bytes, weight_decay, weight_decay_mode);
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, rv);
   RowGeom r;
   int rc = adam_check(c, accumulator, r);
   if (rc) return rc;
@@ -1763,4 +1831,37 @@ extern "C" int ce_bag_backward_adam_src_wd(float* weight, int64_t num_rows, int3
                                            ce_stream_t stream) {
   return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, weight_decay,
                   weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream);
+}
+
+// ---- partial row-wise Adam on a table of rows w | m: the Adam entries with decay, and the second
+// moment -- row_of_slot, v[v_rows], indexed by table row like row-wise Adagrad's momentum -- before beta1.  The
+// accumulators are [., dim] as for any fp32 table, so the workspace is the Adam entries'.
+
+extern "C" size_t ce_bag_backward_pradam_workspace(int64_t num_rows, int64_t nnz, int32_t dim, int32_t accumulator) {
+  return ce_bag_backward_adam_workspace(num_rows, nnz, dim, accumulator);
+}
+
+extern "C" int ce_bag_backward_pradam(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                      const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                      int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                      int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                      const uint64_t* presorted, const int32_t* row_of_slot, float* v, int64_t v_rows,
+                                      double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                                      float weight_decay, int32_t weight_decay_mode, int64_t* step, int32_t accumulator,
+                                      void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  const RowMoment rv{row_of_slot, v, v_rows};
+  return adam_slots(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                    per_sample_weights, mode, hook_features, grad_out, act_dtype, presorted, beta1, beta2, lr, lr_dev, eps,
+                    weight_decay, weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, &rv);
+}
+
+extern "C" int ce_bag_backward_pradam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out,
+                                          int32_t act_dtype, const uint64_t* src_keys, const int32_t* row_of_slot,
+                                          float* v, int64_t v_rows, double beta1, double beta2, float lr,
+                                          const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
+                                          int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                          ce_stream_t stream) {
+  const RowMoment rv{row_of_slot, v, v_rows};
+  return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, weight_decay,
+                  weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, &rv);
 }

@@ -260,24 +260,37 @@ extern "C" int ce_host_fill_uniform(float* dst, int64_t n, float lo, float hi, u
   return CE_OK;
 }
 
-// an Adam-layout table (rows w | m | v of 3 * dim floats): the w part of row r = row r of the fill above, zero moments
-extern "C" int ce_host_fill_uniform_adam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed,
-                                         int threads) {
+// a table whose rows carry optimizer state (rows of parts * dim floats, the w part first): the w part of row r = row r
+// of the fill above, the parts behind it zero
+static int fill_uniform_parts(float* dst, int64_t n_rows, int32_t dim, int parts, float lo, float hi, uint64_t seed,
+                              int threads) {
   CE_REQUIRE(dst && n_rows >= 0, CE_ERR_INVALID, "bad arguments");
   CE_REQUIRE_ADAM_DIM(dim);
   const float span = hi - lo;
   parallel_for(n_rows, threads, [=](int64_t a, int64_t b) {
     for (int64_t r = a; r < b; ++r) {
-      float* row = dst + r * 3 * (int64_t)dim;
+      float* row = dst + r * parts * (int64_t)dim;
       for (int32_t d = 0; d < dim; ++d) {
         const uint64_t x = splitmix64(seed * 0xD6E8FEB86659FD93ull + (uint64_t)(r * dim + d));
         const float u = (float)(x >> 40) * (1.0f / 16777216.0f);   // as ce_host_fill_uniform
         row[d] = lo + span * u;
       }
-      memset(row + dim, 0, (size_t)dim * 8);
+      memset(row + dim, 0, (size_t)dim * 4 * (size_t)(parts - 1));
     }
   });
   return CE_OK;
+}
+
+// an Adam-layout table: rows w | m | v of 3 * dim floats
+extern "C" int ce_host_fill_uniform_adam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed,
+                                         int threads) {
+  return fill_uniform_parts(dst, n_rows, dim, 3, lo, hi, seed, threads);
+}
+
+// a partial row-wise Adam table: rows w | m of 2 * dim floats
+extern "C" int ce_host_fill_uniform_pradam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed,
+                                           int threads) {
+  return fill_uniform_parts(dst, n_rows, dim, 2, lo, hi, seed, threads);
 }
 
 // round-to-nearest-even casts of a finite or non-finite fp32 value, in integer arithmetic (host code)

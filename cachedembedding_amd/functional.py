@@ -71,7 +71,9 @@ class _BagFn(torch.autograd.Function):
         _lib.require_gpu()
         w16 = weight.dtype in _lib.W16_DTYPES
         assert weight.is_cuda and (w16 or weight.dtype == torch.float32) and weight.is_contiguous()
-        adam = isinstance(fused, FusedAdam)      # the weight is then [rows, 3 * D]: w | m | v
+        # the weight is then [rows, 3 * D]: w | m | v, or [rows, 2 * D]: w | m (3.13)
+        adam = isinstance(fused, FusedAdam)
+        partial = adam and fused.layout == "partial_rowwise_adam"
         if psw is not None and ctx.needs_input_grad[3] and fused is not None and fused.lr is not None:
             # d loss / d per_sample_weights[j] = <grad_out[bag of j], weight[indices[j]]> needs the rows as the forward
             # saw them, and the fused update moves them inside backward: refused HERE, before any kernel has run (a
@@ -79,7 +81,7 @@ class _BagFn(torch.autograd.Function):
             raise NotImplementedError("gradient w.r.t. per_sample_weights with the fused SGD / row-wise Adagrad "
                                       "update")
         num_bags = offsets.numel() - 1 if include_last else offsets.numel()
-        dim = weight.shape[1] // 3 if adam else weight.shape[1]
+        dim = weight.shape[1] // fused.span if adam else weight.shape[1]
         shape = (num_bags // hook_features, hook_features, dim) if hook_features else (num_bags, dim)
         if out_box is not None:
             # the caller's buffer (embedding_bag(out=...)): a static output for graph-captured steps, or one chosen by
@@ -108,7 +110,10 @@ class _BagFn(torch.autograd.Function):
             check(fn(ptr(weight), _lib.ACT_DTYPES[weight.dtype], weight.shape[0], dim, *args))
         elif adam:
             # the fp32 kernels with the Adam row type: the w part of every row, the rows three times as far apart
-            fn = lib.ce_bag_forward_src_keys_adam if from_keys else lib.ce_bag_forward_adam
+            if partial:
+                fn = lib.ce_bag_forward_src_keys_pradam if from_keys else lib.ce_bag_forward_pradam
+            else:
+                fn = lib.ce_bag_forward_src_keys_adam if from_keys else lib.ce_bag_forward_adam
             check(fn(ptr(weight), weight.shape[0], dim, *args))
         else:
             fn = lib.ce_bag_forward_src_keys_act if from_keys else lib.ce_bag_forward_act
@@ -130,9 +135,9 @@ class _BagFn(torch.autograd.Function):
         adam = isinstance(fused, FusedAdam)
         if adam and fused.lr is None:
             raise RuntimeError("backward through an Adam-layout table with no fused Adam set: an autograd gradient in "
-                               "slot space over 3 * D columns means nothing (set_fused_adam(lr) first, or run the "
+                               f"slot space over {getattr(fused, 'span', 3)} * D columns means nothing (set_fused_adam(lr) first, or run the "
                                "forward under torch.no_grad())")
-        dim = weight.shape[1] // 3 if adam else weight.shape[1]
+        dim = weight.shape[1] // fused.span if adam else weight.shape[1]
         off64 = int(offsets.dtype == torch.int64)
         nnz = indices.numel()
         R = weight.shape[0]
@@ -155,7 +160,20 @@ class _BagFn(torch.autograd.Function):
                     ((float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) if decay else ()) + \
                     (ptr(fused.step), _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws),
                      ws.numel(), stream_ptr())
-                if src:
+                if fused.layout == "partial_rowwise_adam":
+                    # partial row-wise Adam (ce_bag_backward_pradam*): one entry with or without decay; the second
+                    # moment, one fp32 per table row, is named by row_of_slot, v, v_rows in front of beta1
+                    v = fused.exp_avg_sq
+                    tail = (ptr(fused.row_of_slot), ptr(v), v.numel()) + tail[:5] + \
+                        (float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + tail[-5:]
+                    if src:
+                        check(lib.ce_bag_backward_pradam_src(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys),
+                                                             *tail))
+                    else:
+                        check(lib.ce_bag_backward_pradam(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64,
+                                                         num_bags, int(include_last), ptr(psw), mode, hook_features,
+                                                         ptr(grad_out), act, ptr(pre), *tail))
+                elif src:
                     fn = lib.ce_bag_backward_adam_src_wd if decay else lib.ce_bag_backward_adam_src
                     check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                 else:
@@ -797,14 +815,25 @@ class FusedAdam(_CheckedLr, _WeightDecay):
 
     weight_decay, weight_decay_mode, lazy like the moments (the rows a step looks up decay once, in that step):
     "l2" is torch.optim.Adam(weight_decay=) -- g + weight_decay * w feeds both moments --, "decoupled" torch.optim.AdamW
-    -- w is scaled by 1 - lr * weight_decay (lr, not the bias-corrected step size) first."""
+    -- w is scaled by 1 - lr * weight_decay (lr, not the bias-corrected step size) first.
+
+    layout="partial_rowwise_adam" (FBGEMM's PARTIAL_ROWWISE_ADAM): the weight is [rows, 2 * D], every row
+    w | m, and the second moment is ONE fp32 per table row -- exp_avg_sq, [v_rows] fp32 on the weight's device, indexed by
+    row_of_slot[slot] (int32 [rows]; None: by slot), as FusedRowwiseAdagrad's momentum is:
+        v[r] += (1 - beta2) (mean_d (g_d g_d) - v[r]) ;  w -= lr c_t * m / (sqrt(v[r]) + eps)
+    A slot whose row_of_slot lies outside [0, v_rows) is left alone."""
 
     deterministic = False                                   # (the sorted fold has no Adam form)
     rounding, seed = "nearest", 0
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  accumulator: str = "step", step: Optional[torch.Tensor] = None, deterministic: bool = False, *,
-                 weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
+                 weight_decay: float = 0.0, weight_decay_mode: str = "l2", layout: str = "adam",
+                 exp_avg_sq: Optional[torch.Tensor] = None, row_of_slot: Optional[torch.Tensor] = None):
+        if layout not in ("adam", "partial_rowwise_adam"):
+            raise ValueError(f"layout={layout!r}: 'adam' or 'partial_rowwise_adam'")
+        self.layout, self.span = layout, _lib.LAYOUT_SPAN[layout]
+        self.exp_avg_sq, self.row_of_slot = exp_avg_sq, row_of_slot        # (the partial layout only)
         self.lr = lr
         self.set(betas, eps, accumulator, deterministic, weight_decay=weight_decay, weight_decay_mode=weight_decay_mode)
         self.step = step
@@ -828,10 +857,10 @@ class FusedAdam(_CheckedLr, _WeightDecay):
 
     def check(self, weight: torch.Tensor) -> None:
         """refusals that must come before any kernel of the step has run"""
-        if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] % 3 != 0:
-            raise NotImplementedError("FusedAdam needs an fp32 weight of Adam-layout rows, [rows, 3 * embedding_dim] "
-                                      f"(got {tuple(weight.shape)} {weight.dtype})")
-        _lib.check_adam_dim(weight.shape[1] // 3)
+        if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] % self.span != 0:
+            raise NotImplementedError(f"FusedAdam needs an fp32 weight of Adam-layout rows, [rows, {self.span} * "
+                                      f"embedding_dim] (got {tuple(weight.shape)} {weight.dtype})")
+        _lib.check_adam_dim(weight.shape[1] // self.span)
         if self.lr is None:
             return
         if not isinstance(self.lr, torch.Tensor) and not float(self.lr) >= 0.0:
@@ -839,6 +868,16 @@ class FusedAdam(_CheckedLr, _WeightDecay):
         st = self.step
         if st is None or not st.is_cuda or st.dtype != torch.int64 or st.numel() != 1 or st.device != weight.device:
             raise ValueError("fused Adam needs its step count: one int64 element on the weight's device")
+        if self.layout == "partial_rowwise_adam":
+            v, ros = self.exp_avg_sq, self.row_of_slot
+            if v is None or v.dtype != torch.float32 or v.device != weight.device or not v.is_contiguous() or \
+                    v.numel() == 0:
+                raise ValueError("partial row-wise Adam needs exp_avg_sq: a contiguous fp32 tensor, one element per "
+                                 "table row, on the weight's device")
+            if ros is not None and (ros.dtype != torch.int32 or ros.device != weight.device or not ros.is_contiguous()
+                                    or ros.numel() < weight.shape[0]):
+                raise ValueError("row_of_slot: a contiguous int32 tensor of one element per row of the weight, on its "
+                                 "device")
 
     def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
         # zero-filled once; every call of the kernels leaves what must be zero zero-filled again

@@ -130,8 +130,9 @@ class FusedSparseModules(nn.Module):
                  output_dtype: Optional[torch.dtype] = None, table_dtype: Optional[torch.dtype] = None,
                  evict_strategy: Optional[EvictionStrategy] = None, fused_optimizer: Optional[str] = None):
         super().__init__()
-        # fused_optimizer="adam" (addition): an Adam-layout table (CachedEmbeddingBag(fused_optimizer="adam"): the rows
-        # carry Adam's moments).  One process, the plain module: the sharded classes do not take the layout.
+        # fused_optimizer="adam" / "partial_rowwise_adam" (addition): an Adam-layout table
+        # (CachedEmbeddingBag(fused_optimizer=...): the rows carry Adam's moments, or the first of them).  One process,
+        # the plain module: the sharded classes do not take the layout.
         if fused_optimizer is not None and (use_tablewise_parallel or (
                 torch.distributed.is_initialized() and torch.distributed.get_world_size(group) > 1)):
             raise NotImplementedError(f"FusedSparseModules(fused_optimizer={fused_optimizer!r}) on several ranks or with "

@@ -25,7 +25,7 @@ import os
 import sys
 import time
 from pathlib import Path
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.distributed as dist
@@ -119,6 +119,11 @@ def parse_args(argv=None):
                         "arithmetic; the moments travel with the rows between host table and cache), torch.optim.Adam "
                         "for the dense part.  One process, an fp32 table, without --use_tablewise; not with --adagrad or "
                         "--fused_sgd")
+    p.add_argument("--adam_partial_rowwise", action="store_true",
+                   help="with --adam: partial row-wise Adam (FBGEMM's PARTIAL_ROWWISE_ADAM; "
+                        "CachedEmbeddingBag(fused_optimizer='partial_rowwise_adam')): the first moment travels in the "
+                        "row, the second moment is one fp32 per table row in device memory -- rows of 2 * D floats "
+                        "instead of 3 * D")
     p.add_argument("--adam_beta1", type=float, default=0.9, help="with --adam: beta1 of both Adams")
     p.add_argument("--adam_beta2", type=float, default=0.999, help="with --adam: beta2 of both Adams")
     p.add_argument("--eps", type=float, default=1e-8, help="with --adam: eps of both Adams")
@@ -181,6 +186,13 @@ _OUTPUT_DTYPES = {"fp32": None, "bf16": torch.bfloat16}
 _TABLE_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
 
 
+def _fused_optimizer(args) -> Optional[str]:
+    """the layout --adam builds the table with"""
+    if not args.adam:
+        return None
+    return "partial_rowwise_adam" if args.adam_partial_rowwise else "adam"
+
+
 def check_output_dtype(args, world: int) -> None:
     """--embedding_output_dtype bf16 is refused, before anything is built, where the pooled output crosses ranks"""
     if args.embedding_output_dtype != "fp32" and (world > 1 or args.use_tablewise):
@@ -235,7 +247,7 @@ class HybridParallelDLRM(nn.Module):
             # (a 16-bit table's output would default to the table's dtype: the flag's fp32 stays fp32)
             output_dtype=_OUTPUT_DTYPES[args.embedding_output_dtype] or
             (torch.float32 if args.table_dtype != "fp32" else None),
-            table_dtype=_TABLE_DTYPES[args.table_dtype], fused_optimizer="adam" if args.adam else None)
+            table_dtype=_TABLE_DTYPES[args.table_dtype], fused_optimizer=_fused_optimizer(args))
         self.autocast = args.embedding_output_dtype == "bf16"
         dense = DenseModules(args.num_dense_features, len(sizes), args.embedding_dim,
                              [int(x) for x in args.dense_arch_layer_sizes.split(",")],
@@ -702,6 +714,8 @@ def main(argv=None):
         if world > 1 or args.use_tablewise:
             raise NotImplementedError("--eval_q4 is implemented for one process without --use_tablewise (the sharded "
                                       "classes do not take a q4 table)")
+    if args.adam_partial_rowwise and not args.adam:
+        raise ValueError("--adam_partial_rowwise chooses the layout of --adam: pass --adam with it")
     if args.adam:
         if args.adagrad or args.fused_sgd:
             raise ValueError("--adam takes the place of --adagrad and of --fused_sgd: pass one of them")

@@ -714,6 +714,71 @@ int ce_bag_backward_adam_src_wd(float* weight, int64_t num_rows, int32_t dim, in
                                 float weight_decay, int32_t weight_decay_mode, int64_t* step, int32_t accumulator,
                                 void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
+/* Partial row-wise Adam, layout `partial_rowwise_adam` (additions to API 6; FBGEMM's PARTIAL_ROWWISE_ADAM).  The first
+ * moment is kept per element and travels in the row, as in the Adam layout; the second moment is ONE fp32 per table
+ * row, fed by the mean of the row's squared gradient, and stays in device memory where row-wise Adagrad keeps its
+ * momentum.  An fp32 table only.  A row of `dim` elements is 2 * dim floats:
+ *   w[0 .. dim) | m[dim .. 2 dim)                             (weights, first moment)
+ * The dim rule and the alignment are the Adam layout's (dim % 4 == 0, 4 <= dim <= 1024, the table 16-byte aligned;
+ * vector lanes only; the cache op is driven with embedding_dim = 2 * dim).  `weight` is [num_rows, 2 * dim] in every
+ * entry below; `dim` stays D.
+ *
+ * ce_host_fill_uniform_pradam is ce_host_fill_uniform_adam for rows of 2 * dim floats: the same w parts, a zero m.
+ *
+ * ce_bag_forward_pradam / ce_bag_forward_src_keys_pradam are ce_bag_forward_adam / _src_keys_adam with a row stride of
+ * two rows' width: they read the w part alone, the result is bit-equal to the fp32 sibling's over a contiguous copy
+ * of the w parts, the refusals and their order are the same.  No PAIR form.
+ *
+ * ce_bag_backward_pradam / ce_bag_backward_pradam_src take the lists of ce_bag_backward_adam_wd / _adam_src_wd with
+ * `const int32_t* row_of_slot, float* v, int64_t v_rows` directly before beta1 -- the three arguments row-wise Adagrad
+ * calls row_of_slot, momentum, momentum_rows: v is [v_rows] fp32 in device memory, indexed by r = row_of_slot[s] for
+ * the row in slot s (row_of_slot == NULL: r = s), zero before the first step, never moved by the cache.  lr / lr_dev,
+ * `step`, the accumulators, the workspace (ce_bag_backward_pradam_workspace = ce_bag_backward_adam_workspace), the
+ * decay (weight_decay_mode CE_WD_NONE or weight_decay == 0: the instantiations without decay) and capture safety are
+ * those entries'.  The arithmetic, every operation rounded on its own (no contraction), for every UNIQUE row the call
+ * looks up, in slot s, g its folded gradient of the call, t the step count after the call's first launch:
+ *     omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2)                         (fp64 difference, rounded)
+ *     c_t  = (float)(sqrt(1.0 - pow(beta2, t)) / (1.0 - pow(beta1, t)))                (fp64, on the device)
+ *     h  = g                                                                            no decay
+ *     h  = g + weight_decay * w                                                         CE_WD_L2
+ *     w  = w * f, h = g ; f = (float)(1.0 - (double)lr * (double)weight_decay)          CE_WD_DECOUPLED
+ *     ss = sum of h_i^2 over the row: per lane as row-wise Adagrad's fp32 table sums it (the lane's last chunk
+ *          ((x^2 + y^2) + z^2) + w^2, the chunks before it fma chains, added in chunk order), then the xor tree across
+ *          the row's lane group, widest stride first
+ *     v' = v[r] + omb2 * (ss / D - v[r])                                                one scalar; lane 0 stores it
+ *     m' = m + omb1 * (h - m)                                                           per element
+ *     w' = w - (lr * c_t) * (m' / (sqrtf(v') + eps))                                    per element
+ *   - r outside [0, v_rows): nothing happens to the slot -- w and m keep their bits, no decay either (row-wise
+ *     Adagrad's rule).  Rows no lookup names keep w, m and v[r] bit for bit.  Lookups outside [0, num_rows) and
+ *     lookups no bag covers take no part and flag nothing.  A row named only by zero-weight lookups has g = 0 and
+ *     still decays m and v.  Given the same folded gradient both accumulators write the same bits.
+ *   - Refused before the first launch: what ce_bag_backward_adam_wd refuses, in its order, and v == NULL or
+ *     v_rows <= 0 (CE_ERR_INVALID) directly behind its null-pointer check.  nnz == 0 (or num_bags == 0) returns after
+ *     the checks with no launch: it does not count a step.
+ * Not built: 16-bit moments or tables, the sorted (deterministic) fold, a scalar lane form. */
+int ce_host_fill_uniform_pradam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed, int threads);
+int ce_bag_forward_pradam(const float* weight, int64_t num_rows, int32_t dim,
+                          const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                          int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                          int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_forward_src_keys_pradam(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                   const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+size_t ce_bag_backward_pradam_workspace(int64_t num_rows, int64_t nnz, int32_t dim, int32_t accumulator);
+int ce_bag_backward_pradam(float* weight, int64_t num_rows, int32_t dim,
+                           const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                           int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                           int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                           const uint64_t* presorted, const int32_t* row_of_slot, float* v, int64_t v_rows,
+                           double beta1, double beta2, float lr, const float* lr_dev, float eps, float weight_decay,
+                           int32_t weight_decay_mode, int64_t* step, int32_t accumulator, void* workspace,
+                           size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_pradam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                               const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                               const int32_t* row_of_slot, float* v, int64_t v_rows, double beta1, double beta2,
+                               float lr, const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
+                               int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                               ce_stream_t stream);
+
 /* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
  * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
  * A row of `dim` elements is 16 + dim bytes:
