@@ -30,17 +30,32 @@ def test_rows_regenerated_from_the_seed_equal_the_filled_table(N, D):
     assert float(want.abs().max()) <= 1.0 / N and float(want.std()) > 0.2 / N
 
 
-def test_gather_returns_zero_rows_for_rows_outside_the_table():
+# one lane | the width this test had | scalar, one float past the 64-lane group | 32 of 64 lanes | 65 16-byte units: a
+# second pass with one live lane | 12 passes
+@pytest.mark.parametrize("D", [4, 64, 66, 128, 260, 3072])
+def test_gather_returns_zero_rows_for_rows_outside_the_table(D):
+    """the gather's own pass loop over a row (a group of min(64, next power of two >= row length) lanes, 8 rows in
+    flight): every in-range row against the table, every out-of-range row against zeros, among 21 rows -- three groups
+    of 8, the last one partly empty"""
     from cachedembedding_amd import _lib
     from cachedembedding_amd.cache_mgr import HostTable
-    N, D = 4096, 64
+    N = 4096
     table = HostTable.allocate(N, D).fill_uniform_(-1.0, 1.0, 5)
-    rows = torch.tensor([3, -1, N, 10, 2 ** 40], device="cuda")
-    out = torch.full((5, D), 7.0, device="cuda")
-    _lib.check(_lib.lib.ce_host_rows_gather(table.dev_ptr, N, D, rows.data_ptr(), 5, out.data_ptr(), _lib.stream_ptr()))
+    listed = [3, -1, N, 10, 2 ** 40, N - 1, 0, -(2 ** 40), 77, N + 1, 4095, 2048, -2, 5, 6, 7, 2 ** 31, 1000, 9, N, 11]
+    rows = torch.tensor(listed, device="cuda")
+    n = len(listed)
+    out = torch.full((n, D), 7.0, device="cuda")
+    _lib.check(_lib.lib.ce_host_rows_gather(table.dev_ptr, N, D, rows.data_ptr(), n, out.data_ptr(), _lib.stream_ptr()))
     o = out.cpu()
     assert torch.equal(o[0], table.tensor[3]) and torch.equal(o[3], table.tensor[10])
     assert not o[1].any() and not o[2].any() and not o[4].any()
+    inside = [0 <= r < N for r in listed]
+    assert sum(inside) == 13 and table.tensor.abs().sum(dim=1).min() > 0
+    for k, r in enumerate(listed):
+        if inside[k]:
+            assert torch.equal(o[k].view(torch.int32), table.tensor[r].view(torch.int32)), (k, r)
+        else:
+            assert not o[k].any(), (k, r)
 
 
 def test_box_probe_reports_plausible_rates():

@@ -210,9 +210,10 @@ def _cache_case(D):
 
 @pytest.mark.parametrize("transport", ["zerocopy", "staged", "worker"])
 @pytest.mark.parametrize("strategy", ["DATASET", "LFU", "LRU"])
-@pytest.mark.parametrize("D", [32, 128])
+@pytest.mark.parametrize("D", [32, 128, 1024])
 def test_through_the_cache(D, strategy, transport):
-    """the cache op moves 32-byte (D = 32) and 80-byte (D = 128) rows intact while it evicts"""
+    """the cache op moves 32-byte (D = 32), 80-byte (D = 128) and 528-byte (D = 1024: 33 of a 64-lane group's lanes)
+    rows intact while it evicts"""
     import cachedembedding_amd as ce
     c = _cache_case(D)
     W = 16 + D // 2

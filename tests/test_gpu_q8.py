@@ -204,7 +204,7 @@ def _cache_batches():
 
 @pytest.mark.parametrize("transport", ["zerocopy", "staged", "worker"])
 @pytest.mark.parametrize("strategy", ["DATASET", "LFU", "LRU"])
-@pytest.mark.parametrize("D", [16, 128])
+@pytest.mark.parametrize("D", [16, 128, 1024])      # 1024: rows of 65 16-byte units, one past the movers' 64-lane group
 def test_through_the_cache(D, strategy, transport):
     import cachedembedding_amd as ce
     from cachedembedding_amd.functional import embedding_bag, quantize_rows

@@ -322,34 +322,34 @@ def test_update_stochastic(wt):
 N_TOY, D_TOY, B_TOY, LR_TOY, SEED_TOY = 2000, 32, 64, 2.0 ** -3, 77
 
 
-def _toy_batches(steps):
+def _toy_batches(steps, D=D_TOY):
     """ids unique within a step: half from 100 hot ids, half from the rest -- a 200-row cache evicts from step 4 on"""
     rng = np.random.default_rng(9)
     ids = [np.concatenate([rng.choice(100, B_TOY // 2, replace=False),
                            100 + rng.choice(N_TOY - 100, B_TOY // 2, replace=False)]) for _ in range(steps)]
-    grads = [rng.standard_normal((B_TOY, D_TOY)).astype(np.float32) for _ in range(steps)]
+    grads = [rng.standard_normal((B_TOY, D)).astype(np.float32) for _ in range(steps)]
     return ids, grads
 
 
-def _fp32_fill():
+def _fp32_fill(D=D_TOY):
     from cachedembedding_amd import _lib
-    f = np.zeros(N_TOY * D_TOY, np.float32)
+    f = np.zeros(N_TOY * D, np.float32)
     _lib.check(_lib.lib.ce_host_fill_uniform(f.ctypes.data, f.size, -1.0 / N_TOY, 1.0 / N_TOY, SEED_TOY, 1))
-    return torch.from_numpy(f).view(N_TOY, D_TOY)
+    return torch.from_numpy(f).view(N_TOY, D)
 
 
-def _replica(wt, ids, grads):
+def _replica(wt, ids, grads, D=D_TOY):
     """a torch-CPU 16-bit [N, D] tensor under the reference update, step by step"""
-    t = _fp32_fill().to(wt)
+    t = _fp32_fill(D).to(wt)
     for i, g in zip(ids, grads):
         ref.sgd_step_nearest(t, i, g, LR_TOY)
     return t
 
 
-def _toy_module(strategy, transport, table_dtype, C=200, **kw):
+def _toy_module(strategy, transport, table_dtype, C=200, D=D_TOY, **kw):
     import cachedembedding_amd as ce
     st = ce.EvictionStrategy.LFU if strategy == "lfu" else ce.EvictionStrategy.DATASET
-    emb = ce.CachedEmbeddingBag(N_TOY, D_TOY, mode="sum", include_last_offset=True, cuda_row_num=C, warmup_ratio=0.0,
+    emb = ce.CachedEmbeddingBag(N_TOY, D, mode="sum", include_last_offset=True, cuda_row_num=C, warmup_ratio=0.0,
                                 evict_strategy=st, init_seed=SEED_TOY, table_dtype=table_dtype, **kw)
     if transport is not None:
         emb.cache_weight_mgr.set_transport(transport)
@@ -385,6 +385,44 @@ def test_through_the_cache_sgd(strategy, transport):
     untouched = np.setdiff1d(np.arange(N_TOY), np.concatenate(ids))
     assert untouched.size > 0
     assert torch.equal(_bits(emb.weight[untouched]), _bits(_fp32_fill().to(wt)[untouched]))
+    assert emb.num_hits_history == plain.num_hits_history and emb.num_miss_history == plain.num_miss_history
+    assert emb.num_write_back_history == plain.num_write_back_history
+
+
+@pytest.mark.parametrize("transport", ["zerocopy", "worker"])
+@pytest.mark.parametrize("strategy", ["dataset", "lfu"])
+def test_through_the_cache_sgd_wide_rows(strategy, transport):
+    """test_through_the_cache_sgd at D = 1024, the top of the 16-bit dim rule: the cache op is driven with 512 fp32
+    elements per row, 128 16-byte units -- two whole passes of the row movers' 64-lane group, where D = 32 is 4 lanes of
+    one"""
+    wt, D = torch.bfloat16, 1024
+    ids, grads = _toy_batches(30, D)
+    emb = _toy_module(strategy, transport, wt, D=D)
+    assert emb.cache_weight_mgr._lib_dim == 512 and emb.cache_weight_mgr.transport_name == transport
+    assert emb.weight.dtype == wt and emb.element_size() == 2 and emb.output_dtype == wt
+    assert next(emb.parameters()).dtype == wt and next(emb.parameters()).shape == (200, D)
+    fill = _fp32_fill(D).to(wt)
+    assert torch.equal(_bits(emb.weight), _bits(fill)), "the 16-bit fill is the cast of the fp32 fill"
+    plain = _toy_module(strategy, transport, None, D=D)
+    off = torch.arange(B_TOY + 1, device="cuda")
+    for m in (emb, plain):
+        m.set_fused_sgd(LR_TOY)
+    emb.set_weight_rounding("nearest")
+    for i, g in zip(ids, grads):
+        out = emb(torch.from_numpy(i).cuda(), off)
+        out.backward(torch.from_numpy(g).cuda().to(out.dtype))
+        o32 = plain(torch.from_numpy(i).cuda(), off)
+        o32.backward(torch.from_numpy(g).cuda())
+    torch.cuda.synchronize()
+    assert sum(emb.num_write_back_history[:3]) == 0 and sum(emb.num_write_back_history[3:]) > 0
+    emb.flush()
+    plain.flush()
+    g16 = [torch.from_numpy(g).to(wt).float().numpy() for g in grads]        # the gradient as the bf16 output's autograd delivers it
+    want = _replica(wt, ids, g16, D)
+    assert torch.equal(_bits(emb.weight), _bits(want)), "residency must be invisible: the cache moves bits"
+    untouched = np.setdiff1d(np.arange(N_TOY), np.concatenate(ids))
+    assert untouched.size > 0
+    assert torch.equal(_bits(emb.weight[untouched]), _bits(fill[untouched]))
     assert emb.num_hits_history == plain.num_hits_history and emb.num_miss_history == plain.num_miss_history
     assert emb.num_write_back_history == plain.num_write_back_history
 
