@@ -44,6 +44,9 @@ CE_ACC_STEP = 1
 CE_WD_NONE = 0
 CE_WD_L2 = 1
 CE_WD_DECOUPLED = 2
+CE_CLIP_NONE = 0
+CE_CLIP_VALUE = 1
+CE_CLIP_ROW_NORM = 2
 CE_TRANSPORT_ZEROCOPY = 0
 CE_TRANSPORT_STAGED = 1
 CE_TRANSPORT_WORKER = 2
@@ -123,6 +126,14 @@ _SORTED_WD_TAIL = [c_void_p, c_void_p, c_int64, c_float, c_float] + _WD + \
 _ADAM_WD_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD + \
     [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
 _ROW_MOMENT = [c_void_p, c_void_p, c_int64]      # row_of_slot, v, v_rows (partial row-wise Adam), behind the keys
+# gradient clipping: `grad_clip, grad_clip_mode` directly behind weight_decay_mode
+_CLIP = [c_float, c_int32]
+_UPDATE_CLIP_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_float] + _WD + _CLIP + \
+    [c_int32, c_int32, c_uint64, c_int32, c_void_p, c_size_t] + _STREAM
+_SORTED_CLIP_TAIL = [c_void_p, c_void_p, c_int64, c_float, c_float] + _WD + _CLIP + \
+    [c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
+_ADAM_CLIP_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD + _CLIP + \
+    [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -217,6 +228,14 @@ SIGNATURES = {
     "ce_bag_backward_pradam_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
     "ce_bag_backward_pradam": (c_int, _BAG + _ACT + _KEYS + _ROW_MOMENT + _ADAM_WD_TAIL[1:]),
     "ce_bag_backward_pradam_src": (c_int, _SRC + _ACT + _KEYS + _ROW_MOMENT + _ADAM_WD_TAIL[1:]),
+    # gradient clipping (per value / per row norm) for the fused updates: the covered lists with the clip behind the decay
+    "ce_bag_backward_update_clip": (c_int, _W16 + _BAG[1:] + _ACT + _UPDATE_CLIP_TAIL),
+    "ce_bag_backward_update_src_clip": (c_int, _W16 + _SRC[1:] + _ACT + _UPDATE_CLIP_TAIL),
+    "ce_bag_backward_update_sorted_clip": (c_int, _W16 + _BAG[1:] + _ACT + _SORTED_CLIP_TAIL),
+    "ce_bag_backward_adam_clip": (c_int, _BAG + _ACT + _ADAM_CLIP_TAIL),
+    "ce_bag_backward_adam_src_clip": (c_int, _SRC + _ACT + _ADAM_CLIP_TAIL),
+    "ce_bag_backward_pradam_clip": (c_int, _BAG + _ACT + _KEYS + _ROW_MOMENT + _ADAM_CLIP_TAIL[1:]),
+    "ce_bag_backward_pradam_src_clip": (c_int, _SRC + _ACT + _KEYS + _ROW_MOMENT + _ADAM_CLIP_TAIL[1:]),
     # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
     "ce_q8_row_bytes": (c_size_t, [c_int32]),
     "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),

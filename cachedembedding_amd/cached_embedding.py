@@ -14,8 +14,9 @@ import torch.nn as nn
 
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
-from .functional import (FusedAdam, FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_lr, check_lr_path,
-                         check_weight_decay, check_weight_decay_path, embedding_bag, refuse_weight_decay)
+from .functional import (FusedAdam, FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_grad_clip,
+                         check_grad_clip_path, check_lr, check_lr_path, check_weight_decay, check_weight_decay_path,
+                         embedding_bag, refuse_grad_clip, refuse_weight_decay)
 
 
 def _checked_weight_decay(module, optimizer: str, lr, deterministic: bool, weight_decay, weight_decay_mode) -> float:
@@ -25,6 +26,15 @@ def _checked_weight_decay(module, optimizer: str, lr, deterministic: bool, weigh
     if lr is not None and wd:
         check_weight_decay_path(optimizer, module.table_dtype, wd, bool(deterministic), lr, module.mode)
     return wd
+
+
+def _checked_grad_clip(module, optimizer: str, lr, deterministic: bool, grad_clip, grad_clip_mode):
+    """the checked clip of a set_fused_* call (a float or None), with everything it is refused for known at that point"""
+    clip = check_grad_clip(grad_clip, grad_clip_mode)
+    refuse_grad_clip(getattr(module, "_no_weight_decay", None), clip)
+    if lr is not None and clip is not None:
+        check_grad_clip_path(optimizer, module.table_dtype, clip, bool(deterministic), lr, module.mode)
+    return clip
 
 
 def _refuse_q8_update(module, what: str, lr) -> None:
@@ -261,11 +271,13 @@ class CachedEmbeddingBag(nn.Module):
     def set_cache_mgr_async_copy(self, flag: bool):
         self.cache_weight_mgr.set_async_copy(flag)
 
-    # the sharded / table-wise modules name themselves here: their owner-side update (ce_rows_axpy) has no decay
+    # the sharded / table-wise modules name themselves here: their owner-side update (ce_rows_axpy) has no decay and no
+    # gradient clipping
     _no_weight_decay: Optional[str] = None
 
     def set_fused_sgd(self, lr: Union[float, torch.Tensor, None], deterministic: bool = False,
-                      accumulator: str = "cache", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
+                      accumulator: str = "cache", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2",
+                      grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
         """Apply SGD(lr) to the cache rows inside backward (K13+K14 fused).  lr=None restores
         the plain autograd behaviour (grad handed to torch.optim).  accumulator="step" (a 16-bit table only): the
         update's fp32 accumulator has a row per lookup of the step at most instead of one per cache row.
@@ -274,10 +286,13 @@ class CachedEmbeddingBag(nn.Module):
         step replayed from a hipGraph.  Not with deterministic=True.
         weight_decay / weight_decay_mode ("l2" or "decoupled"; functional.FusedSGD): lazy decay of the rows a step
         looks up.  An fp32 table takes it with deterministic=True only -- the atomic scatter has no per-row pass --,
-        which is refused here, before the first step."""
+        which is refused here, before the first step.
+        grad_clip / grad_clip_mode ("value" or "row_norm"; functional.check_grad_clip): a row's folded gradient of the
+        step is clipped before the decay and the step see it.  Taken where the decay is, refused where it is."""
         _refuse_q8_update(self, "set_fused_sgd", lr)
         _refuse_adam_layout(self, "set_fused_sgd", lr)
         wd = _checked_weight_decay(self, "sgd", lr, deterministic, weight_decay, weight_decay_mode)
+        clip = _checked_grad_clip(self, "sgd", lr, deterministic, grad_clip, grad_clip_mode)
         if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
@@ -290,10 +305,12 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_sgd.deterministic = deterministic
         self.fused_sgd.accumulator = accumulator
         self.fused_sgd.set_weight_decay(wd, weight_decay_mode)
+        self.fused_sgd.set_grad_clip(clip, grad_clip_mode)
 
     def set_fused_rowwise_adagrad(self, lr: Union[float, torch.Tensor, None], eps: float = 1e-8,
                                   deterministic: bool = False, accumulator: str = "cache", *,
-                                  weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
+                                  weight_decay: float = 0.0, weight_decay_mode: str = "l2",
+                                  grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
         """Apply exact row-wise Adagrad (FBGEMM's EXACT_ROWWISE_ADAGRAD; the reference's baseline --adagrad; with
         weight_decay / weight_decay_mode "l2" or "decoupled" FBGEMM's L2 / DECOUPLE, lazy: the rows a step looks up
         decay once, at that step, wherever they sit) to the cache rows inside backward.  The state is one fp32 accumulator per row of the host table,
@@ -305,10 +322,13 @@ class CachedEmbeddingBag(nn.Module):
         accumulator="step": the atomic update with an fp32 accumulator of min(lookups of a step, cache rows) rows
         instead of one as large as the cache (FusedRowwiseAdagrad); not with deterministic=True, and a 16-bit table
         needs set_weight_rounding("nearest") first.
-        lr may be a tensor, as in set_fused_sgd; not with deterministic=True."""
+        lr may be a tensor, as in set_fused_sgd; not with deterministic=True.
+        grad_clip / grad_clip_mode ("value" or "row_norm"; functional.check_grad_clip): the row's folded gradient is
+        clipped first; the decay, the sum of squares and the step see the clipped one.  Every path above takes it."""
         _refuse_q8_update(self, "set_fused_rowwise_adagrad", lr)
         _refuse_adam_layout(self, "set_fused_rowwise_adagrad", lr)
         wd = _checked_weight_decay(self, "rowwise_adagrad", lr, deterministic, weight_decay, weight_decay_mode)
+        clip = _checked_grad_clip(self, "rowwise_adagrad", lr, deterministic, grad_clip, grad_clip_mode)
         if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
             check_lr_path(check_lr(lr), bool(deterministic), self.mode)
         if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
@@ -324,12 +344,13 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_adagrad.deterministic = bool(deterministic)
         self.fused_adagrad.accumulator = accumulator
         self.fused_adagrad.set_weight_decay(wd, weight_decay_mode)
+        self.fused_adagrad.set_grad_clip(clip, grad_clip_mode)
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
 
     def set_fused_adam(self, lr: Union[float, torch.Tensor, None], betas=(0.9, 0.999), eps: float = 1e-8,
                        accumulator: str = "step", deterministic: bool = False, *, weight_decay: float = 0.0,
-                       weight_decay_mode: str = "l2"):
+                       weight_decay_mode: str = "l2", grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
         """Apply Adam (torch.optim.SparseAdam's arithmetic: only the rows a step looks up move) to the cache rows inside
         backward.  Needs a module built with fused_optimizer="adam": the moments are part of every row, in the host
         table and in the cache, `.exp_avg` / `.exp_avg_sq` after flush(); the step count is `.adam_step` (device).
@@ -337,7 +358,9 @@ class CachedEmbeddingBag(nn.Module):
         a tensor, as in set_fused_sgd.  accumulator: "step" (default) or "cache" -- the size of the fp32 accumulator the
         step's gradient is folded into; both write the same bits given the same folded gradient.  weight_decay with
         weight_decay_mode "l2" is torch.optim.Adam(weight_decay=), with "decoupled" torch.optim.AdamW, both lazy: the
-        rows a step looks up decay once, at that step (functional.FusedAdam).  Exclusive with
+        rows a step looks up decay once, at that step (functional.FusedAdam).  grad_clip / grad_clip_mode ("value" or
+        "row_norm"; functional.check_grad_clip): the row's folded gradient is clipped before the decay and the moments
+        see it -- clip_grad_value_ / a per-row clip_grad_norm_ in front of optimizer.step().  Exclusive with
         set_fused_sgd / set_fused_rowwise_adagrad: an Adam-layout module refuses those."""
         if self.fused_optimizer is None:
             raise ValueError("set_fused_adam needs a module built with fused_optimizer='adam' (or 'partial_rowwise_adam'): "
@@ -347,8 +370,10 @@ class CachedEmbeddingBag(nn.Module):
         elif lr is not None and not float(lr) >= 0.0:
             raise ValueError(f"lr={lr!r}: must be >= 0")
         wd = _checked_weight_decay(self, "adam", lr, False, weight_decay, weight_decay_mode)
+        clip = _checked_grad_clip(self, "adam", lr, False, grad_clip, grad_clip_mode)
         self.fused_adam.set(betas, eps, accumulator, deterministic, weight_decay=wd,       # (deterministic=True: not
-                            weight_decay_mode=weight_decay_mode)                           # implemented)
+                            weight_decay_mode=weight_decay_mode, grad_clip=clip,           # implemented)
+                            grad_clip_mode=grad_clip_mode)
         self.fused_adam.lr = lr
 
     def set_weight_rounding(self, rounding: str = "stochastic", seed: int = 0):

@@ -22,6 +22,19 @@
 // their own moments (w | m | v): the two atomic folds above, unchanged, hand it the same folded gradient.  Partial
 // row-wise Adam (ce_bag_backward_pradam*) is a fourth: rows w | m, the second moment one fp32 per table
 // row where row-wise Adagrad keeps its momentum, fed by the mean of the row's squared gradient.
+// Gradient clipping (the ce_*_clip entries, the CLIP = true instantiations) acts on a row's folded
+// gradient g -- what update_row / sorted_apply_row receive -- FIRST, and everything that used g then uses the clipped g:
+// the L2 decay's h = g + wd * w, row-wise Adagrad's sum h^2 / D, Adam's m' and v', partial row-wise Adam's ss, the step
+// (torch's order, clip_grad_* before optimizer.step(), and FBGEMM's).  fp32, contraction off, c the threshold by value:
+//   CE_CLIP_NONE      the covered entry's update, by the covered entry's kernels: its bits
+//   CE_CLIP_VALUE     per element:  g = g < -c ? -c : (g > c ? c : g)                   (a NaN stays a NaN, as torch.clamp)
+//   CE_CLIP_ROW_NORM  ss = sum_d g[d]^2 in lane_sq_sum's spelled-out order for the table's type, then the xor tree across
+//                     the lane group, widest stride first (the reduction row-wise Adagrad already runs);
+//                     n = sqrtf(ss) ; k = c / (n + 1e-6f) ; if (k < 1.f) g[d] = g[d] * k       (clip_grad_norm_, per row)
+// Row-wise Adagrad and partial row-wise Adam then sum the squares of the clipped (and decayed) gradient themselves: a
+// second reduction, not k^2 * ss.  Clipping does not change which rows a call names -- the mark rule depends on the
+// decay alone -- and a slot whose momentum or v index lies outside its array is still untouched.  clip_row is the one
+// spelling, so a row looked up once in a call gets the same bits from all three folds.
 #include "ce_common.h"
 
 namespace ce {
@@ -163,15 +176,66 @@ __device__ __forceinline__ float adam_delta(float lr, float eps, float m, float 
   return lr * q;
 }
 
+// Gradient clipping (the ce_*_clip entries, the CLIP = true instantiations), of a row's folded gradient
+// in its lane group's registers, BEFORE everything that reads it (the decay's h, the sums of squares, the moments, the
+// step).  Every lane of the group must be here: the norm's reduction shuffles across it.  c > 0, +inf included.
+//   CE_CLIP_VALUE:    per element g = g < -c ? -c : (g > c ? c : g)  (a NaN stays a NaN, as torch.clamp);
+//   CE_CLIP_ROW_NORM: ss = the group's lane_sq_sum<WT> (xor tree, widest stride first) ; n = sqrtf(ss) ;
+//                     k = c / (n + 1e-6f) ; if (k < 1.f) g = g * k per element  (clip_grad_norm_, the row its own parameter).
+// Chunks past rowlen hold zeros and keep them.  This is the ONE spelling: update_row and sorted_apply_row both call it.
+struct RowClip {
+  float c = 0.f;
+  int mode = CE_CLIP_NONE;
+};
+__device__ __forceinline__ float clip_value(float g, float c) { return g < -c ? -c : (g > c ? c : g); }
+__device__ __forceinline__ f32x4 clip_value(f32x4 g, float c) {
+  return f32x4{clip_value(g.x, c), clip_value(g.y, c), clip_value(g.z, c), clip_value(g.w, c)};
+}
+template <typename WT, typename VT, int NCH>
+__device__ __forceinline__ void clip_row(VT (&g)[NCH], RowClip k, int G) {
+#pragma clang fp contract(off)
+  if (k.mode == CE_CLIP_VALUE) {                             // (uniform)
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) g[c] = clip_value(g[c], k.c);
+  } else if (k.mode == CE_CLIP_ROW_NORM) {
+    float ss = lane_sq_sum<WT, NCH>(g);
+    for (int off = G >> 1; off > 0; off >>= 1) ss = ss + __shfl_xor(ss, off, G);
+    const float n = sqrtf(ss);
+    const float scale = k.c / (n + 1e-6f);
+    // `if (scale < 1.f) g = g * scale`, as a select per chunk: lane groups of one wave differ in `scale`, and a branch
+    // would hold a saved exec mask in two scalar registers that k_sorted_fold does not have
+    const bool shrink = scale < 1.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const VT t = g[c] * scale;
+      g[c] = shrink ? t : g[c];
+    }
+  }
+}
+
 //   ROWV (with ADAM: partial row-wise Adam, an fp32 table of rows w | m; the second moment is momentum[r], one fp32 per
 //   table row as in adagrad, and r outside it: nothing happens, no decay either), h the gradient after the decay:
 //     ss = sum of the group's lane_sq_sum<float> of h (xor tree, widest stride first) ;
 //     v' = v[r] + omb2 * (ss / D - v[r]) (lane 0 writes) ; m' = m + omb1 * (h - m) ; w' = w - lr * (m' / (sqrtf(v') + eps))
-template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false>
+//   CLIP (then WD as well: the decay's mode is read at run time, and CE_WD_NONE is the decoupled form with f = 1, which
+//   multiplies exactly): clip_row on a copy of g, then the WD update of that copy -- in every arm the clip stands in
+//   front of the decay, and everything behind it is the code the unclipped instantiation runs.
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false,
+          bool CLIP = false>
 __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64_t step_key, int64_t s,
-                                           const VT (&g)[NCH], int gl, int G, bool adagrad, float f = 1.f) {
+                                           const VT (&g)[NCH], int gl, int G, bool adagrad, float f = 1.f,
+                                           RowClip clip = RowClip{}) {
 #pragma clang fp contract(off)
   using T = Act<WT, VT>;
+  if constexpr (CLIP) {
+    static_assert(WD, "the clipped instantiations take the decay as a run-time mode");
+    VT cg[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) cg[c] = g[c];
+    clip_row<WT, VT, NCH>(cg, clip, G);
+    update_row<VT, WT, NCH, STOCH, ADAM, true, ROWV, false>(a, lr, step_key, s, cg, gl, G, adagrad, f);
+    return;
+  }
   const bool l2 = WD && a.wd_mode == CE_WD_L2;               // uniform
   static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
   static_assert(!ROWV || ADAM, "a row-wise second moment: Adam only");
@@ -381,12 +445,13 @@ struct ApplyArgs {
   float* acc;                // [num_rows, D], zero outside a call
   uint8_t* flags;            // [num_rows], zero outside a call
   uint32_t num_rows;
+  RowClip clip;              // the CLIP = true instantiations only
 };
 
 // a wave reads 64 flags at once, and a lane group per flagged slot reads acc, updates the row and writes acc and the
 // flag back to zero
 template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH, bool ADAM = false, bool WD = false,
-          bool ROWV = false>
+          bool ROWV = false, bool CLIP = false>
 __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
   const LaneGroup l = lane_group(a.u.g_log2);
   VT* A = (VT*)a.acc;
@@ -400,7 +465,7 @@ __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
       const int64_t s = base + i;
       VT g[NCH];
       load_row(g, A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
-      update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD, f);
+      update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV, CLIP>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD, f, a.clip);
       zero_row<VT, NCH>(A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
     });
     if (flagged) a.flags[mine] = 0;
@@ -439,7 +504,9 @@ struct SortedArgs {
   float lr;
   float eps;
   float wd;                    // weight decay (the WD = true instantiations): CE_WD_L2 or CE_WD_DECOUPLED
-  int32_t wd_mode;
+  int32_t wd_mode;             // (the CLIP = true instantiations: CE_WD_NONE as well, with wd = 0)
+  float clip;                  // gradient clipping (the CLIP = true instantiations): CE_CLIP_VALUE or CE_CLIP_ROW_NORM
+  int32_t clip_mode;
 };
 
 // first position of the run of `row` that holds position p (rows ascending, rows[p] == row): gallop back, then bisect
@@ -465,11 +532,17 @@ __device__ __forceinline__ int64_t run_start(const int32_t* __restrict__ rows, i
 struct SortedDecay {
   float wd = 0.f, f = 1.f;     // CE_WD_L2's factor of w in h; CE_WD_DECOUPLED's factor of w (decay_factor of the float lr)
   int l2 = 0;
+  RowClip clip;                // the CLIP = true instantiations: the threshold and the mode, parked like the rest
 };
 __device__ __forceinline__ float parked(float x) {
   float v;
   asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(x));
   return v;
+}
+__device__ __forceinline__ int64_t parked(int64_t x) {
+  const uint32_t lo = __float_as_uint(parked(__uint_as_float((uint32_t)x)));
+  const uint32_t hi = __float_as_uint(parked(__uint_as_float((uint32_t)((uint64_t)x >> 32))));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 __device__ __forceinline__ SortedDecay sorted_decay(const SortedArgs& a, bool park) {
   SortedDecay d;
@@ -483,14 +556,37 @@ __device__ __forceinline__ SortedDecay sorted_decay(const SortedArgs& a, bool pa
   }
   return d;
 }
+// the same for a clipped launch: the decay's values (CE_WD_NONE: wd = 0, so f = 1 and l2 = 0) and the clip's two
+__device__ __forceinline__ SortedDecay sorted_decay_clip(const SortedArgs& a, bool park) {
+  SortedDecay d = sorted_decay(a, park);
+  d.clip.c = a.clip;
+  d.clip.mode = a.clip_mode;
+  if (park) {
+    d.clip.c = parked(d.clip.c);
+    d.clip.mode = __float_as_int(parked(__int_as_float(d.clip.mode)));
+  }
+  return d;
+}
 
 // the update of one row by its lane group: g = the row's whole gradient of the step (zero in chunks past rowlen).
 // WD: the decayed update, its terms spelled as update_row spells them (the row read once, before the reduction; f is
 // decay_factor of the float lr) -- a row looked up once gets the bits of the atomic forms.
-template <typename VT, typename WT, int NCH, bool WD = false>
+// CLIP (then WD as well, as in update_row): clip_row on a copy of g, then the WD update of that copy.
+template <typename VT, typename WT, int NCH, bool WD = false, bool CLIP = false>
 __device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s, const VT (&g)[NCH], int gl, int G,
                                                  SortedDecay d = SortedDecay{}) {
   using T = Act<WT, VT>;
+  if constexpr (CLIP) {
+    static_assert(WD, "the clipped instantiations take the decay as a run-time mode");
+    VT cg[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) cg[c] = g[c];
+    // the mode comes back out of its parked register only here, so the branch on it is a scalar one: a branch on a
+    // vector register would hold a saved exec mask in two more scalars across clip_row
+    clip_row<WT, VT, NCH>(cg, RowClip{d.clip.c, __builtin_amdgcn_readfirstlane(d.clip.mode)}, G);
+    sorted_apply_row<VT, WT, NCH, true, false>(a, s, cg, gl, G, d);
+    return;
+  }
   typename T::V* W = (typename T::V*)a.weight;
   if constexpr (WD) {
 #pragma clang fp contract(off)
@@ -545,11 +641,12 @@ __device__ __forceinline__ void sorted_apply_row(const SortedArgs& a, int64_t s,
 
 // one wave per 64 consecutive sorted positions (grid-stride): every lane finds out whether its position starts a chunk,
 // the chunk heads are handed to the wave's lane groups in rounds (the walk for_each_flagged wraps, written out)
-template <typename VT, typename AT, typename WT, int NCH, bool WD = false>
+template <typename VT, typename AT, typename WT, int NCH, bool WD = false, bool CLIP = false>
 __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
   using TA = Act<AT, VT>;
   SortedDecay dec;
-  if constexpr (WD) dec = sorted_decay(a, true);
+  if constexpr (CLIP) dec = sorted_decay_clip(a, true);
+  else if constexpr (WD) dec = sorted_decay(a, true);
   const int G = 1 << a.g_log2;
   const int lane = threadIdx.x & 63;
   const int q = lane >> a.g_log2;
@@ -560,7 +657,11 @@ __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
   const typename TA::V* GO = (const typename TA::V*)a.grad_out;
   VT* P = (VT*)a.partials;
   const int32_t* __restrict__ rows = a.rows_sorted;
-  for (int64_t base = wave * 64; base < a.nnz; base += nwaves * 64) {
+  // the walk's stride: a clipped launch parks it too -- it lives across everything, `base` is a vector value anyway,
+  // and its two scalar registers are the two the clip's branches need
+  int64_t stride = nwaves * 64;
+  if constexpr (CLIP) stride = parked(stride);
+  for (int64_t base = wave * 64; base < a.nnz; base += stride) {
     const int64_t mine = base + lane;
     bool head = false;
     if (mine < a.nnz) {
@@ -613,7 +714,7 @@ __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
         }
       }
       if (first && !more) {
-        sorted_apply_row<VT, WT, NCH, WD>(a, (int64_t)row, g, gl, G, dec);
+        sorted_apply_row<VT, WT, NCH, WD, CLIP>(a, (int64_t)row, g, gl, G, dec);
       } else {
         const int64_t prow = 2 * (p >> 6) + (first ? 1 : 0);
 #pragma unroll
@@ -627,10 +728,11 @@ __global__ __launch_bounds__(256) void k_sorted_fold(SortedArgs a) {
 }
 
 // the runs of more than one chunk: the head of such a run adds its partial rows in ascending chunk order and applies
-template <typename VT, typename WT, int NCH, bool WD = false>
+template <typename VT, typename WT, int NCH, bool WD = false, bool CLIP = false>
 __global__ __launch_bounds__(256) void k_sorted_combine(SortedArgs a) {
   SortedDecay dec;
-  if constexpr (WD) dec = sorted_decay(a, false);
+  if constexpr (CLIP) dec = sorted_decay_clip(a, false);
+  else if constexpr (WD) dec = sorted_decay(a, false);
   const int G = 1 << a.g_log2;
   const int lane = threadIdx.x & 63;
   const int q = lane >> a.g_log2;
@@ -669,7 +771,7 @@ __global__ __launch_bounds__(256) void k_sorted_combine(SortedArgs a) {
           if (idx < a.rowlen) g[c] = g[c] + P[(2 * (t >> 6)) * a.rowlen + idx];
         }
       }
-      sorted_apply_row<VT, WT, NCH, WD>(a, (int64_t)row, g, gl, G, dec);
+      sorted_apply_row<VT, WT, NCH, WD, CLIP>(a, (int64_t)row, g, gl, G, dec);
     }
   }
 }
@@ -804,10 +906,12 @@ struct CompactArgs {
   const int32_t* list;       // [cap]: list[u] = the u-th flagged slot
   const int32_t* n_list;     // U, written by k_compact_emit
   int32_t adagrad;
+  RowClip clip;              // the CLIP = true instantiations only
 };
 
 // one lane group per list entry (grid-stride over u < U; the grid is sized by cap)
-template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false>
+template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false,
+          bool CLIP = false>
 __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   const int G = 1 << a.u.g_log2;
   const int gl = threadIdx.x & (G - 1);
@@ -821,7 +925,8 @@ __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
     VT g[NCH];
     load_row(g, A + u * a.u.rowlen, gl, G, a.u.rowlen);
-    update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad, f);
+    update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV, CLIP>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad, f,
+                                                         a.clip);
     zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
   }
 }
@@ -932,7 +1037,11 @@ struct UpdateCall {
   // the ce_*_wd entries: weight decay (decay() false: the call is the covered entry's, kernels and all)
   float wd = 0.f;
   int32_t wd_mode = CE_WD_NONE;
+  // the ce_*_clip entries: gradient clipping (clipped() false: the call is the covered entry's, kernels and all)
+  float clip = 0.f;
+  int32_t clip_mode = CE_CLIP_NONE;
   bool decay() const { return wd_mode != CE_WD_NONE && wd != 0.f; }
+  bool clipped() const { return clip_mode != CE_CLIP_NONE; }
   bool w16() const { return weight_dtype != CE_ACT_F32; }
   bool adagrad() const { return optimizer == CE_OPT_ROWWISE_ADAGRAD; }
   bool adam() const { return optimizer == kOptAdam || optimizer == kOptPartialAdam; }
@@ -958,8 +1067,9 @@ static UpdateArgs update_args(const UpdateCall& c, const RowGeom& r, const unsig
   u.beta2 = c.beta2;
   u.omb1 = (float)(1.0 - c.beta1);
   u.omb2 = (float)(1.0 - c.beta2);
-  u.wd = c.wd;
-  u.wd_mode = c.wd_mode;
+  // (a clipped launch reads the decay's mode at run time: a call without decay is CE_WD_NONE with wd = 0 there)
+  u.wd = c.decay() ? c.wd : 0.f;
+  u.wd_mode = c.decay() ? c.wd_mode : CE_WD_NONE;
   return u;
 }
 
@@ -971,9 +1081,24 @@ static int wd_check(float wd, int32_t wd_mode) {
   return CE_OK;
 }
 
-// f(std::true_type) for a call that decays, f(std::false_type) -- the instantiations from before the decay -- otherwise
-template <typename F> static inline void for_decay(bool decay, F&& f) {
-  if (decay) f(std::true_type{}); else f(std::false_type{});
+// the two checks the ce_*_clip entries add, directly behind the decay's (also for nnz == 0); every other entry passes
+// 0 / CE_CLIP_NONE
+static int clip_check(float clip, int32_t clip_mode) {
+  CE_REQUIRE(clip_mode == CE_CLIP_NONE || clip_mode == CE_CLIP_VALUE || clip_mode == CE_CLIP_ROW_NORM, CE_ERR_INVALID,
+             "unknown grad_clip_mode %d (CE_CLIP_NONE / CE_CLIP_VALUE / CE_CLIP_ROW_NORM)", (int)clip_mode);
+  CE_REQUIRE(clip_mode == CE_CLIP_NONE || clip > 0.f, CE_ERR_INVALID, "grad_clip must be > 0");
+  return CE_OK;
+}
+
+// which instantiations a call launches: a clipped call the CLIP ones (decay or not: they read its mode at run time), a
+// call that decays the WD ones, every other call the instantiations from before the decay
+template <bool W, bool C> struct UpdateKind {
+  static constexpr bool WD = W, CLIP = C;
+};
+template <typename F> static inline void for_decay(bool decay, bool clipped, F&& f) {
+  if (clipped) f(UpdateKind<true, true>{});
+  else if (decay) f(UpdateKind<true, false>{});
+  else f(UpdateKind<false, false>{});
 }
 
 // How the entries' checks differ -- everything else is the same conditions in the same order.
@@ -1071,28 +1196,31 @@ static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const SlotL
   a.acc = ws.acc;
   a.flags = ws.flags;
   a.num_rows = (uint32_t)c.num_rows;
+  a.clip = RowClip{c.clip, c.clip_mode};
   const dim3 g(grid_for(cdiv(c.num_rows, 64), 4)), b(256);
   const bool ada = c.adagrad(), st = c.stochastic();
-  for_decay(c.decay(), [&](auto d) {
-    constexpr bool WD = decltype(d)::value;
+  for_decay(c.decay(), c.clipped(), [&](auto d) {
+    constexpr bool WD = decltype(d)::WD, CL = decltype(d)::CLIP;
     if (c.rowv())
       for_vec_lanes(r.nch, [&](auto l) {
-        hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD, true>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD, true, CL>), g, b, 0, s,
+                           a);
       });
     else if (c.adam())
       for_vec_lanes(r.nch, [&](auto l) {
-        hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD, false, CL>), g, b, 0, s,
+                           a);
       });
     else for_table(c.weight_dtype, r, [&](auto l, auto w) {
       using VT = typename decltype(l)::VT;
       using WT = typename decltype(w)::AT;
       constexpr int N = decltype(l)::NCH;
       if constexpr (std::is_same<WT, float>::value)
-        hipLaunchKernelGGL((k_rows_apply<VT, float, N, true, false, false, WD>), g, b, 0, s, a);
-      else if (ada && st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, true, false, WD>), g, b, 0, s, a);
-      else if (ada) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, false, false, WD>), g, b, 0, s, a);
-      else if (st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, true, false, WD>), g, b, 0, s, a);
-      else hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, false, false, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_rows_apply<VT, float, N, true, false, false, WD, false, CL>), g, b, 0, s, a);
+      else if (ada && st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, true, false, WD, false, CL>), g, b, 0, s, a);
+      else if (ada) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, true, false, false, WD, false, CL>), g, b, 0, s, a);
+      else if (st) hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, true, false, WD, false, CL>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_rows_apply<VT, WT, N, false, false, false, WD, false, CL>), g, b, 0, s, a);
     });
   });
   CE_LAUNCH_CHECK();
@@ -1115,27 +1243,28 @@ static int launch_compact_apply(const UpdateCall& c, const RowGeom& r, const Com
   a.list = ws.list;
   a.n_list = ws.n_list;
   a.adagrad = c.adagrad();
+  a.clip = RowClip{c.clip, c.clip_mode};
   const dim3 g(grid_for(ws.cap, 256 >> r.g_log2)), b(256);
-  for_decay(c.decay(), [&](auto d) {
-    constexpr bool WD = decltype(d)::value;
+  for_decay(c.decay(), c.clipped(), [&](auto d) {
+    constexpr bool WD = decltype(d)::WD, CL = decltype(d)::CLIP;
     if (c.rowv())
       for_vec_lanes(r.nch, [&](auto l) {
-        hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD, true>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD, true, CL>), g, b, 0, s, a);
       });
     else if (c.adam())
       for_vec_lanes(r.nch, [&](auto l) {
-        hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD, false, CL>), g, b, 0, s, a);
       });
     else for_table(c.weight_dtype, r, [&](auto l, auto w) {
       using VT = typename decltype(l)::VT;
       using WT = typename decltype(w)::AT;
       constexpr int N = decltype(l)::NCH;
       if constexpr (std::is_same<WT, float>::value)
-        hipLaunchKernelGGL((k_compact_apply<VT, float, N, false, false, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_compact_apply<VT, float, N, false, false, WD, false, CL>), g, b, 0, s, a);
       else if (c.stochastic())
-        hipLaunchKernelGGL((k_compact_apply<VT, WT, N, true, false, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_compact_apply<VT, WT, N, true, false, WD, false, CL>), g, b, 0, s, a);
       else
-        hipLaunchKernelGGL((k_compact_apply<VT, WT, N, false, false, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_compact_apply<VT, WT, N, false, false, WD, false, CL>), g, b, 0, s, a);
     });
   });
   CE_LAUNCH_CHECK();
@@ -1316,6 +1445,8 @@ static int adam_check(const UpdateCall& c, int32_t accumulator, RowGeom& r) {
              "unknown accumulator %d (CE_ACC_CACHE / CE_ACC_STEP)", (int)accumulator);
   int rc = wd_check(c.wd, c.wd_mode);       // (the ce_*_adam_wd entries: the entries without decay pass 0 / CE_WD_NONE)
   if (rc) return rc;
+  rc = clip_check(c.clip, c.clip_mode);     // (the ce_*_clip entries: the others pass 0 / CE_CLIP_NONE)
+  if (rc) return rc;
   CE_REQUIRE(c.beta1 >= 0.0 && c.beta1 < 1.0 && c.beta2 >= 0.0 && c.beta2 < 1.0, CE_ERR_INVALID,
              "beta1 and beta2 must lie in [0, 1)");
   CE_REQUIRE(c.eps >= 0.f, CE_ERR_INVALID, "eps must be >= 0");
@@ -1346,7 +1477,7 @@ struct RowMoment {
 static UpdateCall adam_call(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act,
                             double beta1, double beta2, float lr, const float* lr_dev, float eps, int64_t* step,
                             void* workspace, size_t workspace_bytes, float wd = 0.f, int32_t wd_mode = CE_WD_NONE,
-                            const RowMoment* rv = nullptr) {
+                            const RowMoment* rv = nullptr, RowClip clip = RowClip{}) {
   UpdateCall c{weight, CE_ACT_F32, num_rows, dim, nnz, grad_out, act, rv ? rv->row_of_slot : nullptr,
                rv ? rv->v : nullptr, rv ? rv->v_rows : 0, lr_dev ? 0.f : lr, eps,
                rv ? kOptPartialAdam : kOptAdam, CE_ROUND_NEAREST, 0, workspace, workspace_bytes, lr_dev};
@@ -1355,6 +1486,8 @@ static UpdateCall adam_call(float* weight, int64_t num_rows, int32_t dim, int64_
   c.beta2 = beta2;
   c.wd = wd;
   c.wd_mode = wd_mode;
+  c.clip = clip.c;
+  c.clip_mode = clip.mode;
   return c;
 }
 
@@ -1372,13 +1505,15 @@ static int lrdev_dispatch(UpdateCall c, int32_t accumulator, Fp32&& fp32, W16&& 
   return fp32(c);
 }
 
-// a ce_*_wd update call: the accumulator code, the two decay checks, then the covered entry as lrdev_dispatch picks it
-// (lr_dev == NULL: the learning rate by value)
+// a ce_*_wd / ce_*_clip update call: the accumulator code, the two decay checks, the two clip checks (a _wd call
+// carries 0 / CE_CLIP_NONE), then the covered entry as lrdev_dispatch picks it (lr_dev == NULL: the learning rate by value)
 template <typename Fp32, typename W16, typename Compact>
 static int wd_dispatch(UpdateCall c, int32_t accumulator, Fp32&& fp32, W16&& w16, Compact&& compact) {
   CE_REQUIRE(accumulator == CE_ACC_CACHE || accumulator == CE_ACC_STEP, CE_ERR_INVALID,
              "unknown accumulator %d (CE_ACC_CACHE / CE_ACC_STEP)", (int)accumulator);
   int rc = wd_check(c.wd, c.wd_mode);
+  if (rc) return rc;
+  rc = clip_check(c.clip, c.clip_mode);
   if (rc) return rc;
   if (accumulator == CE_ACC_STEP) return compact(c);
   if (c.weight_dtype != CE_ACT_F32) return w16(c);
@@ -1552,20 +1687,24 @@ extern "C" size_t ce_bag_backward_update_sorted_workspace(int64_t num_rows, int6
   return carve_sorted(nullptr, nnz, dim).bytes;
 }
 
-// ce_bag_backward_update_sorted (weight_decay 0, CE_WD_NONE) and ce_bag_backward_update_sorted_wd are this one function
+// ce_bag_backward_update_sorted (weight_decay 0, CE_WD_NONE), ce_bag_backward_update_sorted_wd (grad_clip 0, CE_CLIP_NONE)
+// and ce_bag_backward_update_sorted_clip are this one function
 static int update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, const int64_t* indices,
                          int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
                          int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
                          int64_t hook_features, const void* grad_out, int32_t act_dtype, const int32_t* row_of_slot,
                          float* momentum, int64_t momentum_rows, float lr, float eps, float weight_decay,
-                         int32_t weight_decay_mode, int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
-                         size_t workspace_bytes, ce_stream_t stream) {
+                         int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int32_t optimizer,
+                         int32_t rounding, uint64_t seed, void* workspace, size_t workspace_bytes, ce_stream_t stream) {
   // everything that can be refused, from the arguments alone: no launch, no HIP call before the last check
   {
     int rc = wd_check(weight_decay, weight_decay_mode);
     if (rc) return rc;
+    rc = clip_check(grad_clip, grad_clip_mode);
+    if (rc) return rc;
   }
   const bool decay = weight_decay_mode != CE_WD_NONE && weight_decay != 0.f;
+  const bool clipped = grad_clip_mode != CE_CLIP_NONE;
   CE_REQUIRE_ACT(act_dtype);
   CE_REQUIRE(weight_dtype == CE_ACT_F32 || weight_dtype == CE_ACT_BF16 || weight_dtype == CE_ACT_F16, CE_ERR_INVALID,
              "unknown weight_dtype %d (CE_ACT_F32 / CE_ACT_BF16 / CE_ACT_F16)", (int)weight_dtype);
@@ -1640,28 +1779,31 @@ static int update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, i
   a.adagrad = optimizer == CE_OPT_ROWWISE_ADAGRAD;
   a.lr = lr;
   a.eps = eps;
-  a.wd = weight_decay;
-  a.wd_mode = weight_decay_mode;
+  // (a clipped launch reads the decay's mode at run time: a call without decay is CE_WD_NONE with wd = 0 there)
+  a.wd = decay ? weight_decay : 0.f;
+  a.wd_mode = decay ? weight_decay_mode : CE_WD_NONE;
+  a.clip = grad_clip;
+  a.clip_mode = grad_clip_mode;
   const dim3 g(grid_for(cdiv(nnz, 64), 4)), b(256);
-  for_decay(decay, [&](auto d) {
-    constexpr bool WD = decltype(d)::value;
+  for_decay(decay, clipped, [&](auto d) {
+    constexpr bool WD = decltype(d)::WD, CL = decltype(d)::CLIP;
     if (w16) {
       for_w16(r.nch, weight_dtype, [&](auto l, auto w) {
         using WT = typename decltype(w)::AT;
         constexpr int N = decltype(l)::NCH;
         for_act(act_dtype, [&](auto at) {
-          hipLaunchKernelGGL((k_sorted_fold<f32x4, typename decltype(at)::AT, WT, N, WD>), g, b, 0, s, a);
+          hipLaunchKernelGGL((k_sorted_fold<f32x4, typename decltype(at)::AT, WT, N, WD, CL>), g, b, 0, s, a);
         });
-        hipLaunchKernelGGL((k_sorted_combine<f32x4, WT, N, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_sorted_combine<f32x4, WT, N, WD, CL>), g, b, 0, s, a);
       });
     } else {
       for_lanes(r.vec, r.nch, [&](auto l) {
         using VT = typename decltype(l)::VT;
         constexpr int N = decltype(l)::NCH;
         for_act(act_dtype, [&](auto at) {
-          hipLaunchKernelGGL((k_sorted_fold<VT, typename decltype(at)::AT, float, N, WD>), g, b, 0, s, a);
+          hipLaunchKernelGGL((k_sorted_fold<VT, typename decltype(at)::AT, float, N, WD, CL>), g, b, 0, s, a);
         });
-        hipLaunchKernelGGL((k_sorted_combine<VT, float, N, WD>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_sorted_combine<VT, float, N, WD, CL>), g, b, 0, s, a);
       });
     }
   });
@@ -1679,8 +1821,8 @@ extern "C" int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype,
                                              size_t workspace_bytes, ce_stream_t stream) {
   return update_sorted(weight, weight_dtype, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                        include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype, row_of_slot,
-                       momentum, momentum_rows, lr, eps, 0.f, CE_WD_NONE, optimizer, rounding, seed, workspace,
-                       workspace_bytes, stream);
+                       momentum, momentum_rows, lr, eps, 0.f, CE_WD_NONE, 0.f, CE_CLIP_NONE, optimizer, rounding, seed,
+                       workspace, workspace_bytes, stream);
 }
 
 extern "C" int ce_bag_backward_update_sorted_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -1694,12 +1836,53 @@ extern "C" int ce_bag_backward_update_sorted_wd(void* weight, int32_t weight_dty
                                                 size_t workspace_bytes, ce_stream_t stream) {
   return update_sorted(weight, weight_dtype, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
                        include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype, row_of_slot,
-                       momentum, momentum_rows, lr, eps, weight_decay, weight_decay_mode, optimizer, rounding, seed,
-                       workspace, workspace_bytes, stream);
+                       momentum, momentum_rows, lr, eps, weight_decay, weight_decay_mode, 0.f, CE_CLIP_NONE, optimizer,
+                       rounding, seed, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ce_bag_backward_update_sorted_clip(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                                  const int64_t* indices, int64_t nnz, const void* offsets,
+                                                  int32_t offsets_are_i64, int64_t num_bags,
+                                                  int32_t include_last_offset, const float* per_sample_weights,
+                                                  int32_t mode, int64_t hook_features, const void* grad_out,
+                                                  int32_t act_dtype, const int32_t* row_of_slot, float* momentum,
+                                                  int64_t momentum_rows, float lr, float eps, float weight_decay,
+                                                  int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                                  int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                                  size_t workspace_bytes, ce_stream_t stream) {
+  return update_sorted(weight, weight_dtype, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                       include_last_offset, per_sample_weights, mode, hook_features, grad_out, act_dtype, row_of_slot,
+                       momentum, momentum_rows, lr, eps, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode,
+                       optimizer, rounding, seed, workspace, workspace_bytes, stream);
 }
 
 // ---- weight decay for the atomic updates: the pair of ce_bag_backward_update_lrdev / _src_lrdev with the learning
 // rate in Adam's convention (lr_dev == NULL: by value) and the decay behind eps
+
+// ce_bag_backward_update_wd (grad_clip 0, CE_CLIP_NONE) and ce_bag_backward_update_clip are one function; the _src
+// pair likewise
+extern "C" int ce_bag_backward_update_clip(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                           const int64_t* indices, int64_t nnz, const void* offsets,
+                                           int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                           const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                           const void* grad_out, int32_t act_dtype, const uint64_t* presorted,
+                                           const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                           const float* lr_dev, float eps, float weight_decay,
+                                           int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                           int32_t optimizer, int32_t rounding, uint64_t seed, int32_t accumulator,
+                                           void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
+               momentum_rows, lr_dev ? 0.f : lr, eps, optimizer, rounding, seed, workspace, workspace_bytes, lr_dev};
+  c.wd = weight_decay;
+  c.wd_mode = weight_decay_mode;
+  c.clip = grad_clip;
+  c.clip_mode = grad_clip_mode;
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, presorted};
+  return wd_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_slots(u, L, stream); },
+                     [&](const UpdateCall& u) { return update_w16_slots(u, L, stream); },
+                     [&](const UpdateCall& u) { return update_compact_slots(u, L, stream); });
+}
 
 extern "C" int ce_bag_backward_update_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
                                          const int64_t* indices, int64_t nnz, const void* offsets,
@@ -1710,15 +1893,30 @@ extern "C" int ce_bag_backward_update_wd(void* weight, int32_t weight_dtype, int
                                          const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
                                          int32_t optimizer, int32_t rounding, uint64_t seed, int32_t accumulator,
                                          void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  return ce_bag_backward_update_clip(weight, weight_dtype, num_rows, dim, indices, nnz, offsets, offsets_are_i64,
+                                     num_bags, include_last_offset, per_sample_weights, mode, hook_features, grad_out,
+                                     act_dtype, presorted, row_of_slot, momentum, momentum_rows, lr, lr_dev, eps,
+                                     weight_decay, weight_decay_mode, 0.f, CE_CLIP_NONE, optimizer, rounding, seed,
+                                     accumulator, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ce_bag_backward_update_src_clip(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                               int64_t nnz, const void* grad_out, int32_t act_dtype,
+                                               const uint64_t* src_keys, const int32_t* row_of_slot, float* momentum,
+                                               int64_t momentum_rows, float lr, const float* lr_dev, float eps,
+                                               float weight_decay, int32_t weight_decay_mode, float grad_clip,
+                                               int32_t grad_clip_mode, int32_t optimizer, int32_t rounding,
+                                               uint64_t seed, int32_t accumulator, void* workspace,
+                                               size_t workspace_bytes, ce_stream_t stream) {
   UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
                momentum_rows, lr_dev ? 0.f : lr, eps, optimizer, rounding, seed, workspace, workspace_bytes, lr_dev};
   c.wd = weight_decay;
   c.wd_mode = weight_decay_mode;
-  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
-                      hook_features, presorted};
-  return wd_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_slots(u, L, stream); },
-                     [&](const UpdateCall& u) { return update_w16_slots(u, L, stream); },
-                     [&](const UpdateCall& u) { return update_compact_slots(u, L, stream); });
+  c.clip = grad_clip;
+  c.clip_mode = grad_clip_mode;
+  return wd_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_src(u, src_keys, stream); },
+                     [&](const UpdateCall& u) { return update_w16_src(u, src_keys, stream); },
+                     [&](const UpdateCall& u) { return update_compact_src(u, src_keys, stream); });
 }
 
 extern "C" int ce_bag_backward_update_src_wd(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -1728,13 +1926,10 @@ extern "C" int ce_bag_backward_update_src_wd(void* weight, int32_t weight_dtype,
                                              float weight_decay, int32_t weight_decay_mode, int32_t optimizer,
                                              int32_t rounding, uint64_t seed, int32_t accumulator, void* workspace,
                                              size_t workspace_bytes, ce_stream_t stream) {
-  UpdateCall c{weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, row_of_slot, momentum,
-               momentum_rows, lr_dev ? 0.f : lr, eps, optimizer, rounding, seed, workspace, workspace_bytes, lr_dev};
-  c.wd = weight_decay;
-  c.wd_mode = weight_decay_mode;
-  return wd_dispatch(c, accumulator, [&](const UpdateCall& u) { return adagrad_fp32_src(u, src_keys, stream); },
-                     [&](const UpdateCall& u) { return update_w16_src(u, src_keys, stream); },
-                     [&](const UpdateCall& u) { return update_compact_src(u, src_keys, stream); });
+  return ce_bag_backward_update_src_clip(weight, weight_dtype, num_rows, dim, nnz, grad_out, act_dtype, src_keys,
+                                         row_of_slot, momentum, momentum_rows, lr, lr_dev, eps, weight_decay,
+                                         weight_decay_mode, 0.f, CE_CLIP_NONE, optimizer, rounding, seed, accumulator,
+                                         workspace, workspace_bytes, stream);
 }
 
 // ---- Adam on an Adam-layout table (rows w | m | v)
@@ -1752,9 +1947,9 @@ static int adam_slots(float* weight, int64_t num_rows, int32_t dim, const int64_
                       int32_t act_dtype, const uint64_t* presorted, double beta1, double beta2, float lr,
                       const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode, int64_t* step,
                       int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream,
-                      const RowMoment* rv = nullptr) {
+                      const RowMoment* rv = nullptr, RowClip clip = RowClip{}) {
   const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
-                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, rv);
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, rv, clip);
   const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
                       hook_features, presorted};
   RowGeom r;
@@ -1776,9 +1971,10 @@ static int adam_slots(float* weight, int64_t num_rows, int32_t dim, const int64_
 static int adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act_dtype,
                     const uint64_t* src_keys, double beta1, double beta2, float lr, const float* lr_dev, float eps,
                     float weight_decay, int32_t weight_decay_mode, int64_t* step, int32_t accumulator, void* workspace,
-                    size_t workspace_bytes, ce_stream_t stream, const RowMoment* rv = nullptr) {
+                    size_t workspace_bytes, ce_stream_t stream, const RowMoment* rv = nullptr,
+                    RowClip clip = RowClip{}) {
   const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
-                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, rv);
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, rv, clip);
   RowGeom r;
   int rc = adam_check(c, accumulator, r);
   if (rc) return rc;
@@ -1864,4 +2060,61 @@ extern "C" int ce_bag_backward_pradam_src(float* weight, int64_t num_rows, int32
   const RowMoment rv{row_of_slot, v, v_rows};
   return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, weight_decay,
                   weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, &rv);
+}
+
+// ---- gradient clipping for the Adam entries: the _wd / pradam lists with `grad_clip, grad_clip_mode`
+// directly behind weight_decay_mode
+
+extern "C" int ce_bag_backward_adam_clip(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                         int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                         int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                         int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                         const uint64_t* presorted, double beta1, double beta2, float lr,
+                                         const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
+                                         float grad_clip, int32_t grad_clip_mode, int64_t* step, int32_t accumulator,
+                                         void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  return adam_slots(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                    per_sample_weights, mode, hook_features, grad_out, act_dtype, presorted, beta1, beta2, lr, lr_dev, eps,
+                    weight_decay, weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, nullptr,
+                    RowClip{grad_clip, grad_clip_mode});
+}
+
+extern "C" int ce_bag_backward_adam_src_clip(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                             const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                             double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                                             float weight_decay, int32_t weight_decay_mode, float grad_clip,
+                                             int32_t grad_clip_mode, int64_t* step, int32_t accumulator,
+                                             void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, weight_decay,
+                  weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, nullptr,
+                  RowClip{grad_clip, grad_clip_mode});
+}
+
+extern "C" int ce_bag_backward_pradam_clip(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                           int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                           int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                           int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                           const uint64_t* presorted, const int32_t* row_of_slot, float* v,
+                                           int64_t v_rows, double beta1, double beta2, float lr, const float* lr_dev,
+                                           float eps, float weight_decay, int32_t weight_decay_mode, float grad_clip,
+                                           int32_t grad_clip_mode, int64_t* step, int32_t accumulator, void* workspace,
+                                           size_t workspace_bytes, ce_stream_t stream) {
+  const RowMoment rv{row_of_slot, v, v_rows};
+  return adam_slots(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset,
+                    per_sample_weights, mode, hook_features, grad_out, act_dtype, presorted, beta1, beta2, lr, lr_dev, eps,
+                    weight_decay, weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, &rv,
+                    RowClip{grad_clip, grad_clip_mode});
+}
+
+extern "C" int ce_bag_backward_pradam_src_clip(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                               const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                               const int32_t* row_of_slot, float* v, int64_t v_rows, double beta1,
+                                               double beta2, float lr, const float* lr_dev, float eps,
+                                               float weight_decay, int32_t weight_decay_mode, float grad_clip,
+                                               int32_t grad_clip_mode, int64_t* step, int32_t accumulator,
+                                               void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  const RowMoment rv{row_of_slot, v, v_rows};
+  return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, weight_decay,
+                  weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, &rv,
+                  RowClip{grad_clip, grad_clip_mode});
 }

@@ -153,11 +153,14 @@ class _BagFn(torch.autograd.Function):
             with torch.no_grad():
                 ws = fused.workspace(R, nnz, dim, weight.device)
                 lr_t = isinstance(fused.lr, torch.Tensor)
-                # weight decay: the ce_*_wd pair, the decay and its mode directly behind eps; without it today's entries
-                decay = fused.weight_decay != 0.0
+                # weight decay: the ce_*_wd pair, the decay and its mode directly behind eps; without it today's entries.
+                # Gradient clipping: the ce_*_clip entries, the clip and its mode directly behind the decay's
+                clip = fused.grad_clip is not None
+                decay = fused.weight_decay != 0.0 or clip
                 tail = (float(fused.betas[0]), float(fused.betas[1]), 0.0 if lr_t else float(fused.lr),
                         ptr(fused.lr) if lr_t else None, float(fused.eps)) + \
                     ((float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) if decay else ()) + \
+                    (fused.clip_args() if clip else ()) + \
                     (ptr(fused.step), _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws),
                      ws.numel(), stream_ptr())
                 if fused.layout == "partial_rowwise_adam":
@@ -165,19 +168,22 @@ class _BagFn(torch.autograd.Function):
                     # moment, one fp32 per table row, is named by row_of_slot, v, v_rows in front of beta1
                     v = fused.exp_avg_sq
                     tail = (ptr(fused.row_of_slot), ptr(v), v.numel()) + tail[:5] + \
-                        (float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + tail[-5:]
+                        (float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + \
+                        (fused.clip_args() if clip else ()) + tail[-5:]
                     if src:
-                        check(lib.ce_bag_backward_pradam_src(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys),
-                                                             *tail))
+                        fn = lib.ce_bag_backward_pradam_src_clip if clip else lib.ce_bag_backward_pradam_src
+                        check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                     else:
-                        check(lib.ce_bag_backward_pradam(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64,
-                                                         num_bags, int(include_last), ptr(psw), mode, hook_features,
-                                                         ptr(grad_out), act, ptr(pre), *tail))
+                        fn = lib.ce_bag_backward_pradam_clip if clip else lib.ce_bag_backward_pradam
+                        check(fn(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags,
+                                 int(include_last), ptr(psw), mode, hook_features, ptr(grad_out), act, ptr(pre), *tail))
                 elif src:
-                    fn = lib.ce_bag_backward_adam_src_wd if decay else lib.ce_bag_backward_adam_src
+                    fn = lib.ce_bag_backward_adam_src_clip if clip else \
+                        (lib.ce_bag_backward_adam_src_wd if decay else lib.ce_bag_backward_adam_src)
                     check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                 else:
-                    fn = lib.ce_bag_backward_adam_wd if decay else lib.ce_bag_backward_adam
+                    fn = lib.ce_bag_backward_adam_clip if clip else \
+                        (lib.ce_bag_backward_adam_wd if decay else lib.ce_bag_backward_adam)
                     check(fn(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last),
                              ptr(psw), mode, hook_features, ptr(grad_out), act, ptr(pre), *tail))
             return (None,) * 14
@@ -192,7 +198,8 @@ class _BagFn(torch.autograd.Function):
             raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
         # (deterministic SGD WITH weight decay is ce_bag_backward_update_sorted_wd, which reads `act` in place like the
         # other update entries: no upcast there, so `act` goes on describing the buffer that is handed over)
-        fp32_only = (fused.deterministic and fused.weight_decay == 0.0) if sgd else (sparse and not rowwise)
+        clip = (rowwise or sgd) and fused.grad_clip is not None
+        fp32_only = (fused.deterministic and fused.weight_decay == 0.0 and not clip) if sgd else (sparse and not rowwise)
         if fp32_only and act != _lib.CE_ACT_F32:
             grad_out = grad_out.float()
         slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
@@ -200,24 +207,26 @@ class _BagFn(torch.autograd.Function):
         # a tensor learning rate goes to the ce_*_lrdev entries, whose kernels read it when they run (nothing here
         # does); a float to the by-value entries.  What the tensor form does not take was refused before the forward.
         lr_dev = (rowwise or sgd) and isinstance(fused.lr, torch.Tensor)
-        if (rowwise or sgd) and fused.weight_decay != 0.0:
+        if (rowwise or sgd) and (fused.weight_decay != 0.0 or clip):
             # weight decay: the ce_*_wd entries -- the sorted one for deterministic=True (fp32 SGD has
             # no other), else the atomic pair with either accumulator.  What they do not take was refused before the
             # forward (check_weight_decay_path).  Without decay nothing below has changed.
+            # Gradient clipping: the ce_*_clip entries that cover those three, with the clip and its
+            # mode behind the decay's (check_grad_clip_path); without a clip the _wd entries as before.
             with torch.no_grad():
                 w16 = weight.dtype in _lib.W16_DTYPES
                 wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
                 mom = fused.momentum if rowwise else None
                 head = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel())
                 decay = (float(fused.eps) if rowwise else 0.0, float(fused.weight_decay),
-                         WEIGHT_DECAY_MODES[fused.weight_decay_mode],
-                         _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
+                         WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + (fused.clip_args() if clip else ()) + \
+                        (_lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
                          _lib.CE_ROUND_STOCHASTIC if w16 and fused.rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
                          int(fused.seed) & (2 ** 64 - 1))
                 if fused.deterministic:
                     ws = _workspace_sorted(fused, R, nnz, dim, weight.device)
-                    check(lib.ce_bag_backward_update_sorted_wd(*wd, *slots_args, act, *head, float(fused.lr), *decay,
-                                                               ptr(ws), ws.numel(), stream_ptr()))
+                    fn = lib.ce_bag_backward_update_sorted_clip if clip else lib.ce_bag_backward_update_sorted_wd
+                    check(fn(*wd, *slots_args, act, *head, float(fused.lr), *decay, ptr(ws), ws.numel(), stream_ptr()))
                     return (None,) * 14
                 if fused.accumulator == "step":
                     ws, acc = fused.workspace_step(R, nnz, dim, weight.device), _lib.CE_ACC_STEP
@@ -227,9 +236,11 @@ class _BagFn(torch.autograd.Function):
                 tail = head + (0.0 if lr_dev else float(fused.lr), ptr(fused.lr) if lr_dev else None) + decay + \
                     (acc, ptr(ws), ws.numel(), stream_ptr())
                 if src:
-                    check(lib.ce_bag_backward_update_src_wd(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
+                    fn = lib.ce_bag_backward_update_src_clip if clip else lib.ce_bag_backward_update_src_wd
+                    check(fn(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
                 else:
-                    check(lib.ce_bag_backward_update_wd(*wd, *slots_args, act, ptr(pre), *tail))
+                    fn = lib.ce_bag_backward_update_clip if clip else lib.ce_bag_backward_update_wd
+                    check(fn(*wd, *slots_args, act, ptr(pre), *tail))
             return (None,) * 14
         if (rowwise or sgd) and fused.accumulator == "step":
             # the atomic update with an accumulator of min(nnz, rows) rows (ce_bag_backward_update_compact*): mark, an
@@ -688,7 +699,68 @@ class _WeightDecay:
         self.weight_decay_mode = weight_decay_mode
 
 
-class FusedSGD(_CheckedLr, _WeightDecay):
+GRAD_CLIP_MODES = ("value", "row_norm")
+_GRAD_CLIP_CODES = {"value": _lib.CE_CLIP_VALUE, "row_norm": _lib.CE_CLIP_ROW_NORM}
+
+
+def check_grad_clip(grad_clip, grad_clip_mode) -> Optional[float]:
+    """grad_clip: None (no clipping) or a number > 0, +inf included (a tensor, zero, a negative one or a NaN is a
+    ValueError); grad_clip_mode: "value" (every element of a row's folded gradient is clamped to [-grad_clip, grad_clip]:
+    torch.nn.utils.clip_grad_value_) or "row_norm" (a row's folded gradient is scaled by grad_clip / (its 2-norm + 1e-6)
+    where that is below 1: clip_grad_norm_ with every row its own parameter).  Returns the threshold as a float, or
+    None."""
+    if grad_clip_mode not in GRAD_CLIP_MODES:
+        raise ValueError(f"grad_clip_mode={grad_clip_mode!r}: 'value' or 'row_norm'")
+    if grad_clip is None:
+        return None
+    if isinstance(grad_clip, torch.Tensor):
+        raise ValueError("grad_clip is a float: only the learning rate may live in device memory")
+    c = float(grad_clip)
+    if not c > 0.0:
+        raise ValueError(f"grad_clip={grad_clip!r}: must be > 0 (None: no clipping)")
+    return c
+
+
+def check_grad_clip_path(optimizer: str, table_dtype, grad_clip: Optional[float], deterministic: bool = False, lr=None,
+                         mode: Optional[str] = None) -> None:
+    """Refusals of grad_clip is not None: those of check_weight_decay_path, for the same reasons (the clip needs the
+    per-row pass the decay needs).  Host logic only -- it is asked before the forward, so that nothing is refused
+    after a kernel has run."""
+    if grad_clip is None:
+        return
+    if mode == "max":
+        raise NotImplementedError("grad_clip with mode='max': that update has no per-row pass")
+    if isinstance(lr, torch.Tensor) and deterministic:
+        raise NotImplementedError("grad_clip with a tensor learning rate and deterministic=True: the sorted updates "
+                                  "take a float")
+    if optimizer == "sgd" and table_dtype == torch.float32 and not deterministic:
+        raise NotImplementedError("grad_clip with fused SGD on an fp32 table: the atomic scatter has no per-row pass "
+                                  "that could clip a row's folded gradient -- set deterministic=True (the sorted update)")
+
+
+def refuse_grad_clip(who: Optional[str], grad_clip) -> None:
+    """the sharded and table-wise modules: their owner-side update is ce_rows_axpy, which has no clip"""
+    if who and grad_clip is not None:
+        raise NotImplementedError(f"grad_clip is not implemented for {who}: its owner-side update is ce_rows_axpy, "
+                                  "which has no per-row clip")
+
+
+class _GradClip:
+    """`grad_clip` / `grad_clip_mode` of the fused switches: checked on every set_grad_clip.  The clip
+    acts on a row's folded gradient of the step before everything else reads it -- the decay, the sums of squares, the
+    moments, the step."""
+    grad_clip, grad_clip_mode = None, "value"
+
+    def set_grad_clip(self, grad_clip: Optional[float] = None, grad_clip_mode: str = "value") -> None:
+        self.grad_clip = check_grad_clip(grad_clip, grad_clip_mode)
+        self.grad_clip_mode = grad_clip_mode
+
+    def clip_args(self) -> tuple:
+        """(grad_clip, grad_clip_mode) as the ce_*_clip entries take them"""
+        return (float(self.grad_clip), _GRAD_CLIP_CODES[self.grad_clip_mode])
+
+
+class FusedSGD(_CheckedLr, _WeightDecay, _GradClip):
     """Switch for the fused backward+SGD path of one embedding module.
 
     lr=None disables fusion (the module behaves exactly like nn.EmbeddingBag under
@@ -700,14 +772,19 @@ class FusedSGD(_CheckedLr, _WeightDecay):
     with deterministic=True and not with mode='max'.
     weight_decay, weight_decay_mode ("l2": w -= lr (g + wd w); "decoupled": w = w (1 - lr wd) - lr g), lazy: the rows a
     step looks up decay once, in that step.  A 16-bit table with either accumulator; an fp32 table
-    with deterministic=True only (the atomic scatter has no per-row pass); not with mode='max'."""
+    with deterministic=True only (the atomic scatter has no per-row pass); not with mode='max'.
+    grad_clip, grad_clip_mode ("value" / "row_norm"; check_grad_clip): the row's folded gradient is
+    clipped before the decay and the step see it.  Where the decay is taken, and nowhere else."""
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, deterministic: bool = False,
-                 accumulator: str = "cache", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
+                 accumulator: str = "cache", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2",
+                 grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
         check_accumulator("sgd", None, accumulator, bool(deterministic))
         check_lr_path(check_lr(lr), bool(deterministic))
         self.set_weight_decay(weight_decay, weight_decay_mode)
         check_weight_decay_path("sgd", None, self.weight_decay, bool(deterministic), lr)
+        self.set_grad_clip(grad_clip, grad_clip_mode)
+        check_grad_clip_path("sgd", None, self.grad_clip, bool(deterministic), lr)
         self._ws_sorted = None
         self.lr = lr
         self.deterministic = deterministic
@@ -726,7 +803,7 @@ class FusedSGD(_CheckedLr, _WeightDecay):
         return _cached_bytes(self, "_ws", lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz), device, zero=False)
 
 
-class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay):
+class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay, _GradClip):
     """Switch for the fused backward + exact row-wise Adagrad update of one embedding module (FBGEMM's
     EXACT_ROWWISE_ADAGRAD; weight_decay_mode "l2" / "decoupled" are its L2 / DECOUPLE).  Per step and per UNIQUE row r the step looks up, with g the sum of the
     row's gradient rows in the batch:  m[r] += sum(g * g) / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps).
@@ -750,16 +827,21 @@ class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay):
 
     weight_decay, weight_decay_mode, lazy (the rows a step looks up decay once, in that step):
     "l2": h = g + weight_decay * w takes the place of g everywhere, in sum(h * h) / D too; "decoupled": w is scaled by
-    1 - lr * weight_decay first.  Every path above takes it."""
+    1 - lr * weight_decay first.  Every path above takes it.
+
+    grad_clip, grad_clip_mode ("value" / "row_norm"; check_grad_clip): g is clipped first, and the
+    decay's h, sum(h * h) / D and the step all see the clipped g.  Every path above takes it."""
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, eps: float = 1e-8,
                  momentum: Optional[torch.Tensor] = None, row_of_slot: Optional[torch.Tensor] = None,
                  deterministic: bool = False, accumulator: str = "cache", *, weight_decay: float = 0.0,
-                 weight_decay_mode: str = "l2"):
+                 weight_decay_mode: str = "l2", grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
         check_accumulator("rowwise_adagrad", None, accumulator, bool(deterministic))
         check_lr_path(check_lr(lr), bool(deterministic))
         self.set_weight_decay(weight_decay, weight_decay_mode)
         check_weight_decay_path("rowwise_adagrad", None, self.weight_decay, bool(deterministic), lr)
+        self.set_grad_clip(grad_clip, grad_clip_mode)
+        check_grad_clip_path("rowwise_adagrad", None, self.grad_clip, bool(deterministic), lr)
         self.lr = lr
         self.deterministic = bool(deterministic)
         self.accumulator = accumulator
@@ -800,7 +882,7 @@ class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay):
         return _cached_bytes(self, "_ws", need, device, zero=True)
 
 
-class FusedAdam(_CheckedLr, _WeightDecay):
+class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
     """Switch for the fused backward + Adam update of one embedding module whose table carries its moments: the weight
     the kernels see is [rows, 3 * D] fp32, every row w | m | v.  torch.optim.SparseAdam's arithmetic,
     per step and per UNIQUE row the step looks up, g the sum of the row's gradient rows in the batch, t the step count:
@@ -817,6 +899,9 @@ class FusedAdam(_CheckedLr, _WeightDecay):
     "l2" is torch.optim.Adam(weight_decay=) -- g + weight_decay * w feeds both moments --, "decoupled" torch.optim.AdamW
     -- w is scaled by 1 - lr * weight_decay (lr, not the bias-corrected step size) first.
 
+    grad_clip, grad_clip_mode ("value" / "row_norm"; check_grad_clip): g is clipped first -- the decay
+    and both moments see the clipped g --, as clip_grad_value_ / a per-row clip_grad_norm_ before optimizer.step().
+
     layout="partial_rowwise_adam" (FBGEMM's PARTIAL_ROWWISE_ADAM): the weight is [rows, 2 * D], every row
     w | m, and the second moment is ONE fp32 per table row -- exp_avg_sq, [v_rows] fp32 on the weight's device, indexed by
     row_of_slot[slot] (int32 [rows]; None: by slot), as FusedRowwiseAdagrad's momentum is:
@@ -829,20 +914,23 @@ class FusedAdam(_CheckedLr, _WeightDecay):
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  accumulator: str = "step", step: Optional[torch.Tensor] = None, deterministic: bool = False, *,
                  weight_decay: float = 0.0, weight_decay_mode: str = "l2", layout: str = "adam",
-                 exp_avg_sq: Optional[torch.Tensor] = None, row_of_slot: Optional[torch.Tensor] = None):
+                 exp_avg_sq: Optional[torch.Tensor] = None, row_of_slot: Optional[torch.Tensor] = None,
+                 grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
         if layout not in ("adam", "partial_rowwise_adam"):
             raise ValueError(f"layout={layout!r}: 'adam' or 'partial_rowwise_adam'")
         self.layout, self.span = layout, _lib.LAYOUT_SPAN[layout]
         self.exp_avg_sq, self.row_of_slot = exp_avg_sq, row_of_slot        # (the partial layout only)
         self.lr = lr
-        self.set(betas, eps, accumulator, deterministic, weight_decay=weight_decay, weight_decay_mode=weight_decay_mode)
+        self.set(betas, eps, accumulator, deterministic, weight_decay=weight_decay, weight_decay_mode=weight_decay_mode,
+                 grad_clip=grad_clip, grad_clip_mode=grad_clip_mode)
         self.step = step
         self._ws_step, self._ws_step_key = None, None
         self._ws = None
 
     def set(self, betas, eps: float, accumulator: str, deterministic: bool = False, *, weight_decay: float = 0.0,
-            weight_decay_mode: str = "l2") -> None:
+            weight_decay_mode: str = "l2", grad_clip: Optional[float] = None, grad_clip_mode: str = "value") -> None:
         wd = check_weight_decay(weight_decay, weight_decay_mode)
+        clip = check_grad_clip(grad_clip, grad_clip_mode)
         if deterministic:
             raise NotImplementedError("fused Adam with deterministic=True: the sorted fold has no Adam form")
         b1, b2 = (float(b) for b in betas)
@@ -854,6 +942,7 @@ class FusedAdam(_CheckedLr, _WeightDecay):
             raise ValueError(f"accumulator={accumulator!r}: 'cache' or 'step'")
         self.betas, self.eps, self.accumulator = (b1, b2), float(eps), accumulator
         self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
+        self.grad_clip, self.grad_clip_mode = clip, grad_clip_mode
 
     def check(self, weight: torch.Tensor) -> None:
         """refusals that must come before any kernel of the step has run"""
@@ -941,6 +1030,8 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
             raise NotImplementedError("accumulator='step' with mode='max'")
         check_weight_decay_path("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
                                 fused_sgd.weight_decay, bool(fused_sgd.deterministic), fused_sgd.lr, mode)
+        check_grad_clip_path("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
+                             fused_sgd.grad_clip, bool(fused_sgd.deterministic), fused_sgd.lr, mode)
         if isinstance(fused_sgd.lr, torch.Tensor):
             # asked again here: .lr, .deterministic and the weight can all change after the switch was built
             check_lr_path(check_lr(fused_sgd.lr), bool(fused_sgd.deterministic), mode)

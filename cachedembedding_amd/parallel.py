@@ -32,7 +32,8 @@ from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
 from .cached_embedding import CachedEmbeddingBag
-from .functional import _MODES, FORWARD_FROM_KEYS, SrcKeys, check_weight_decay, refuse_weight_decay
+from .functional import (_MODES, FORWARD_FROM_KEYS, SrcKeys, check_grad_clip, check_weight_decay, refuse_grad_clip,
+                         refuse_weight_decay)
 
 
 def get_partition(embedding_dim: int, rank: int, world_size: int) -> Tuple[int, int, bool]:
@@ -577,9 +578,12 @@ class RowwiseShardedEmbeddingBag(nn.Module):
     def weight(self):
         return self.cache_weight_mgr.weight
 
-    def set_fused_sgd(self, lr: Optional[float], *, weight_decay: float = 0.0, weight_decay_mode: str = "l2"):
+    def set_fused_sgd(self, lr: Optional[float], *, weight_decay: float = 0.0, weight_decay_mode: str = "l2",
+                      grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
         refuse_weight_decay("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
                             check_weight_decay(weight_decay, weight_decay_mode))
+        refuse_grad_clip("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
+                         check_grad_clip(grad_clip, grad_clip_mode))
         if isinstance(lr, torch.Tensor):
             raise NotImplementedError("a tensor learning rate is not implemented for the row-wise sharded embedding "
                                       "(RowwiseShardedEmbeddingBag / GraphedShardedWindow): its owner-side update "
@@ -587,10 +591,13 @@ class RowwiseShardedEmbeddingBag(nn.Module):
         self._lr[0] = lr
 
     def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8, *, weight_decay: float = 0.0,
-                                  weight_decay_mode: str = "l2"):
+                                  weight_decay_mode: str = "l2", grad_clip: Optional[float] = None,
+                                  grad_clip_mode: str = "value"):
         """Refused: the owner-side update of the row exchange is SGD only (GraphedShardedWindow replays it too)."""
         refuse_weight_decay("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
                             check_weight_decay(weight_decay, weight_decay_mode))
+        refuse_grad_clip("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
+                         check_grad_clip(grad_clip, grad_clip_mode))
         if lr is not None:
             raise NotImplementedError("fused row-wise Adagrad is not implemented for the row-wise sharded embedding "
                                       "(RowwiseShardedEmbeddingBag / GraphedShardedWindow); use set_fused_sgd(lr)")

@@ -142,6 +142,13 @@ def parse_args(argv=None):
     p.add_argument("--embed_weight_decay_mode", choices=("l2", "decoupled"), default="l2",
                    help="l2: the decay joins the gradient (torch.optim.Adam / Adagrad / SGD weight_decay, FBGEMM L2); "
                         "decoupled: the row is scaled by 1 - lr * decay first (torch.optim.AdamW, FBGEMM DECOUPLE)")
+    p.add_argument("--embed_grad_clip", type=float, default=None,
+                   help="gradient clipping of the embedding's fused update (--adagrad, --adam or --fused_sgd): a row's "
+                        "folded gradient of the step is clipped before the decay and the optimizer see it; the dense "
+                        "part is not touched.  --fused_sgd on an fp32 table has no per-row pass and refuses it")
+    p.add_argument("--embed_grad_clip_mode", choices=("value", "row_norm"), default="value",
+                   help="value: every element is clamped to [-clip, clip] (torch clip_grad_value_, FBGEMM max_gradient); "
+                        "row_norm: a row is scaled down to the 2-norm clip (clip_grad_norm_, every row its own parameter)")
     p.add_argument("--fold_hook", action="store_true", help="write [B,F,D] from the gather kernel")
     p.add_argument("--window_keys", action="store_true",
                    help="the window's cache op also groups every batch's slots by row (source-row keys): the forward "
@@ -389,12 +396,14 @@ def make_optimizer(model, args, device, world: int):
     lr = args.learning_rate if lr_t is None else lr_t
     groups = [{"params": list(model.dense_modules.parameters()), "lr": args.learning_rate * world, "lr_scale": world}]
     if args.adam:
-        embed.set_fused_adam(lr, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc, **_decay(args))
+        embed.set_fused_adam(lr, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc,
+                             **_decay(args), **_clip(args))
         return torch.optim.Adam(groups, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps), None
     if args.adagrad:
-        embed.set_fused_rowwise_adagrad(lr, deterministic=args.adagrad_deterministic, accumulator=acc, **_decay(args))
+        embed.set_fused_rowwise_adagrad(lr, deterministic=args.adagrad_deterministic, accumulator=acc, **_decay(args),
+                                        **_clip(args))
     elif args.fused_sgd:
-        embed.set_fused_sgd(lr, accumulator=acc, **_decay(args))
+        embed.set_fused_sgd(lr, accumulator=acc, **_decay(args), **_clip(args))
     else:
         groups.insert(0, {"params": list(model.sparse_modules.parameters()), "lr": args.learning_rate, "lr_scale": 1})
     if lr_t is not None:
@@ -426,12 +435,12 @@ class LrChange:
         acc = "step" if args.step_accumulator else "cache"
         if args.adam:
             self.embed.set_fused_adam(new, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc,
-                                      **_decay(args))
+                                      **_decay(args), **_clip(args))
         elif args.adagrad:
             self.embed.set_fused_rowwise_adagrad(new, deterministic=args.adagrad_deterministic, accumulator=acc,
-                                                 **_decay(args))
+                                                 **_decay(args), **_clip(args))
         elif args.fused_sgd:
-            self.embed.set_fused_sgd(new, accumulator=acc, **_decay(args))
+            self.embed.set_fused_sgd(new, accumulator=acc, **_decay(args), **_clip(args))
 
 
 class _GraphedStep:
@@ -655,6 +664,11 @@ def _decay(args) -> dict:
     return {"weight_decay": args.embed_weight_decay, "weight_decay_mode": args.embed_weight_decay_mode}
 
 
+def _clip(args) -> dict:
+    """the keywords every set_fused_* takes for --embed_grad_clip / --embed_grad_clip_mode"""
+    return {"grad_clip": args.embed_grad_clip, "grad_clip_mode": args.embed_grad_clip_mode}
+
+
 def check_embed_weight_decay(args):
     """--embed_weight_decay: refused here, before a device is touched, with the library's own refusals"""
     from cachedembedding_amd.functional import check_weight_decay, check_weight_decay_path
@@ -667,6 +681,20 @@ def check_embed_weight_decay(args):
     table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
     check_weight_decay_path("adam" if args.adam else "rowwise_adagrad" if args.adagrad else "sgd", table, wd,
                             bool(args.adagrad_deterministic))
+
+
+def check_embed_grad_clip(args):
+    """--embed_grad_clip: refused here, before a device is touched, with the library's own refusals"""
+    from cachedembedding_amd.functional import check_grad_clip, check_grad_clip_path
+    clip = check_grad_clip(args.embed_grad_clip, args.embed_grad_clip_mode)
+    if clip is None:
+        return
+    if not (args.adagrad or args.adam or args.fused_sgd):
+        raise ValueError("--embed_grad_clip clips a row's gradient inside a fused update: pass --adagrad, --adam or "
+                         "--fused_sgd")
+    table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
+    check_grad_clip_path("adam" if args.adam else "rowwise_adagrad" if args.adagrad else "sgd", table, clip,
+                         bool(args.adagrad_deterministic))
 
 
 def check_step_accumulator(args):
@@ -691,6 +719,7 @@ def main(argv=None):
     if args.step_accumulator:
         check_step_accumulator(args)
     check_embed_weight_decay(args)
+    check_embed_grad_clip(args)
     if args.change_lr and args.graph_step and args.adagrad_deterministic:
         raise NotImplementedError("--graph_step --change_lr keeps the learning rate in a device tensor, which the "
                                   "sorted update (--adagrad_deterministic) does not read")

@@ -779,6 +779,98 @@ int ce_bag_backward_pradam_src(float* weight, int64_t num_rows, int32_t dim, int
                                int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
                                ce_stream_t stream);
 
+/* Gradient clipping for the fused updates (additions to API 6): per value and per row norm.  Seven entries; each is an
+ * existing argument list with `float grad_clip, int32_t grad_clip_mode` directly behind `weight_decay_mode`:
+ *   ce_bag_backward_update_clip         the list of ce_bag_backward_update_wd
+ *   ce_bag_backward_update_src_clip     the list of ce_bag_backward_update_src_wd
+ *   ce_bag_backward_update_sorted_clip  the list of ce_bag_backward_update_sorted_wd
+ *   ce_bag_backward_adam_clip           the list of ce_bag_backward_adam_wd
+ *   ce_bag_backward_adam_src_clip       the list of ce_bag_backward_adam_src_wd
+ *   ce_bag_backward_pradam_clip         the list of ce_bag_backward_pradam
+ *   ce_bag_backward_pradam_src_clip     the list of ce_bag_backward_pradam_src
+ * The workspaces and their zero-fill contract are those of the covered entries; so are the refusals, their codes,
+ * messages and order, capture-safety, no host synchronisation, no allocation.
+ *
+ * g is the row's folded gradient of the call -- after per-sample weights, the mean scaling and the fold over the row's
+ * lookups: what the covered entry's update starts from.  The clip acts on g FIRST, and everything that used g then uses
+ * the clipped g: the L2 decay's h = g + wd * w, row-wise Adagrad's sum h^2 / dim, Adam's m' and v', partial row-wise
+ * Adam's ss, the step -- the order of torch (clip_grad_* before optimizer.step()) and of FBGEMM (max_gradient).  fp32
+ * with contraction off, every operation rounded on its own; c = grad_clip, a float by value:
+ *   CE_CLIP_NONE      the covered entry's update, by the covered entry's kernels: its bits (grad_clip is not looked at)
+ *   CE_CLIP_VALUE     per element:  g = g < -c ? -c : (g > c ? c : g)          (a NaN stays a NaN, as torch.clamp)
+ *   CE_CLIP_ROW_NORM  ss = sum_d g[d]^2, per lane as row-wise Adagrad sums the squares for the table's type (an Adam
+ *                     layout: the fp32 table's), then the xor tree across the row's lane group, widest stride first;
+ *                     n = sqrtf(ss) ; k = c / (n + 1e-6f) ; if (k < 1.f) g[d] = g[d] * k    (clip_grad_norm_, every
+ *                     row its own parameter)
+ * Row-wise Adagrad and partial row-wise Adam then form their own sum of squares from the clipped (and decayed) gradient:
+ * a second reduction, not k^2 * ss.  Clipping does not change which rows a call names: the mark rule depends on the
+ * decay alone, a row with g = 0 stays a no-op for SGD and Adagrad without decay, and a slot whose momentum / v index
+ * lies outside its array is still not touched.  A row looked up once in a call gets the same bits from CE_ACC_CACHE,
+ * CE_ACC_STEP and the sorted entry.  grad_clip = +inf changes nothing (through the clipped kernels).
+ * Refusals: an unknown grad_clip_mode, then -- with a mode other than CE_CLIP_NONE -- a grad_clip that is not > 0 (zero,
+ * negative, NaN; +inf is taken) are CE_ERR_INVALID.  The two checks stand directly behind the weight-decay checks and
+ * also apply for nnz == 0.  CE_OPT_SGD on an fp32 table stays CE_ERR_UNSUPPORTED in the two atomic entries (that scatter
+ * has no per-row pass): fp32 SGD with clipping exists through the sorted entry only.
+ * Not built: a global (whole-table) norm, FBGEMM's COUNTER / COWCLIP, a threshold read from device memory, clipping in
+ * ce_rows_axpy. */
+#define CE_CLIP_NONE 0
+#define CE_CLIP_VALUE 1
+#define CE_CLIP_ROW_NORM 2
+int ce_bag_backward_update_clip(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                const uint64_t* presorted, const int32_t* row_of_slot, float* momentum,
+                                int64_t momentum_rows, float lr, const float* lr_dev, float eps, float weight_decay,
+                                int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int32_t optimizer,
+                                int32_t rounding, uint64_t seed, int32_t accumulator, void* workspace,
+                                size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_update_src_clip(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim, int64_t nnz,
+                                    const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                    const int32_t* row_of_slot, float* momentum, int64_t momentum_rows, float lr,
+                                    const float* lr_dev, float eps, float weight_decay, int32_t weight_decay_mode,
+                                    float grad_clip, int32_t grad_clip_mode, int32_t optimizer, int32_t rounding,
+                                    uint64_t seed, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                    ce_stream_t stream);
+int ce_bag_backward_update_sorted_clip(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
+                                       const int64_t* indices, int64_t nnz, const void* offsets,
+                                       int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
+                                       const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                       const void* grad_out, int32_t act_dtype, const int32_t* row_of_slot,
+                                       float* momentum, int64_t momentum_rows, float lr, float eps, float weight_decay,
+                                       int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                       int32_t optimizer, int32_t rounding, uint64_t seed, void* workspace,
+                                       size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_adam_clip(float* weight, int64_t num_rows, int32_t dim,
+                              const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                              int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                              int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                              const uint64_t* presorted, double beta1, double beta2, float lr, const float* lr_dev,
+                              float eps, float weight_decay, int32_t weight_decay_mode, float grad_clip,
+                              int32_t grad_clip_mode, int64_t* step, int32_t accumulator, void* workspace,
+                              size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_adam_src_clip(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                  const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                  double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                                  float weight_decay, int32_t weight_decay_mode, float grad_clip,
+                                  int32_t grad_clip_mode, int64_t* step, int32_t accumulator, void* workspace,
+                                  size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_pradam_clip(float* weight, int64_t num_rows, int32_t dim,
+                                const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                const uint64_t* presorted, const int32_t* row_of_slot, float* v, int64_t v_rows,
+                                double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                                float weight_decay, int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                ce_stream_t stream);
+int ce_bag_backward_pradam_src_clip(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                    const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                    const int32_t* row_of_slot, float* v, int64_t v_rows, double beta1, double beta2,
+                                    float lr, const float* lr_dev, float eps, float weight_decay,
+                                    int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int64_t* step,
+                                    int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+
 /* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
  * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
  * A row of `dim` elements is 16 + dim bytes:
