@@ -7,8 +7,9 @@ include/ce_api.h).  There is no CPU fallback: the import fails if the library is
 from ._lib import CeError, LIB_PATH  # noqa: F401
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable  # noqa: F401
 from .cached_embedding import CachedEmbeddingBag  # noqa: F401
-from .functional import (FusedAdam, FusedRowwiseAdagrad, FusedSGD, SrcKeys, dequantize_rows, embedding_bag,  # noqa: F401
-                         quantize_rows)
+from .functional import (FusedAdagrad, FusedAdam, FusedRowwiseAdagrad, FusedSGD, SrcKeys,  # noqa: F401
+                         dequantize_rows, embedding_bag, quantize_rows)
 
 __all__ = ["CachedEmbeddingBag", "CachedParamMgr", "EvictionStrategy", "HostTable", "embedding_bag",
-           "FusedSGD", "FusedRowwiseAdagrad", "FusedAdam", "SrcKeys", "CeError", "LIB_PATH", "quantize_rows", "dequantize_rows"]
+           "FusedSGD", "FusedRowwiseAdagrad", "FusedAdam", "FusedAdagrad", "SrcKeys", "CeError", "LIB_PATH", "quantize_rows",
+           "dequantize_rows"]

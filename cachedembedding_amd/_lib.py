@@ -134,6 +134,8 @@ _SORTED_CLIP_TAIL = [c_void_p, c_void_p, c_int64, c_float, c_float] + _WD + _CLI
     [c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
 _ADAM_CLIP_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD + _CLIP + \
     [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
+# element-wise Adagrad: the clipped Adam tail with lr_decay in the betas' place
+_ELEMENTWISE_TAIL = _KEYS + [c_double] + _ADAM_CLIP_TAIL[3:]
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -236,6 +238,14 @@ SIGNATURES = {
     "ce_bag_backward_adam_src_clip": (c_int, _SRC + _ACT + _ADAM_CLIP_TAIL),
     "ce_bag_backward_pradam_clip": (c_int, _BAG + _ACT + _KEYS + _ROW_MOMENT + _ADAM_CLIP_TAIL[1:]),
     "ce_bag_backward_pradam_src_clip": (c_int, _SRC + _ACT + _KEYS + _ROW_MOMENT + _ADAM_CLIP_TAIL[1:]),
+    # element-wise Adagrad (rows w | h of 2 * dim fp32, h the per-element sums of squares): the partial row-wise Adam
+    # forwards' lists; the fill's list with init_acc in front of threads
+    "ce_host_fill_uniform_adagrad": (c_int, [c_void_p, c_int64, c_int32, c_float, c_float, c_uint64, c_float, c_int]),
+    "ce_bag_forward_adagrad": (c_int, _BAG + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_adagrad": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    "ce_bag_backward_adagrad_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ce_bag_backward_adagrad": (c_int, _BAG + _ACT + _ELEMENTWISE_TAIL),
+    "ce_bag_backward_adagrad_src": (c_int, _SRC + _ACT + _ELEMENTWISE_TAIL),
     # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
     "ce_q8_row_bytes": (c_size_t, [c_int32]),
     "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),
@@ -466,13 +476,16 @@ def check_quant_bits(bits) -> int:
 # the Adam layout (fused_optimizer="adam"): an fp32 table whose rows carry their moments, [N, 3 * D] = w | m | v
 # partial row-wise Adam (fused_optimizer="partial_rowwise_adam"): [N, 2 * D] = w | m, the second moment one fp32 per row
 # in device memory
-LAYOUTS = (None, "adam", "partial_rowwise_adam")
-LAYOUT_SPAN = {None: 1, "adam": 3, "partial_rowwise_adam": 2}      # row parts of D floats
+# element-wise Adagrad (fused_optimizer="adagrad"): [N, 2 * D] = w | h, h the per-element sums of squared gradients
+# 
+LAYOUTS = (None, "adam", "partial_rowwise_adam", "adagrad")
+LAYOUT_SPAN = {None: 1, "adam": 3, "partial_rowwise_adam": 2, "adagrad": 2}      # row parts of D floats
+LAYOUT_NAMES = "None, 'adam', 'partial_rowwise_adam' or 'adagrad'"
 
 
 def check_layout(layout):
     if layout not in LAYOUTS:
-        raise ValueError(f"layout={layout!r}: None, 'adam' or 'partial_rowwise_adam'")
+        raise ValueError(f"layout={layout!r}: {LAYOUT_NAMES}")
     return layout
 
 
@@ -485,9 +498,13 @@ def check_adam_dim(dim: int) -> None:
 
 
 def check_adam_table(dim: int, table_dtype, layout: str = "adam") -> None:
-    """what fused_optimizer="adam" / "partial_rowwise_adam" needs of the table: fp32 rows (no 16-bit, no quantized
-    table) and the dim rule"""
+    """what fused_optimizer="adam" / "partial_rowwise_adam" / "adagrad" needs of the table: fp32 rows (no 16-bit, no
+    quantized table) and the dim rule"""
     if quant_bits_of(table_dtype) or table_code(table_dtype) != CE_ACT_F32:
+        if layout == "adagrad":
+            raise NotImplementedError(f"fused_optimizer={layout!r} with table_dtype={table_dtype}: a table whose rows "
+                                      "carry their Adagrad state is an fp32 table (a 16-bit state or table is not "
+                                      "implemented)")
         raise NotImplementedError(f"fused_optimizer={layout!r} with table_dtype={table_dtype}: the Adam layout is an "
                                   "fp32 table (16-bit moments or tables are not implemented)")
     check_adam_dim(dim)

@@ -53,13 +53,18 @@ class HostTable:
     needs D % 8 == 0 and D <= 1024: its rows are whole 16-byte units, the bytes of an fp32 [N, D / 2] table."""
 
     def __init__(self, tensor: torch.Tensor, host_ptr: int, dev_ptr: int, registered: bool, quant_bits: int = 0,
-                 layout: Optional[str] = None):
+                 layout: Optional[str] = None, init_acc: float = 0.0):
         self.tensor = tensor
         # "adam": an fp32 table whose rows carry their Adam moments, [N, 3 * D] = w | m | v (DESIGN.md 3.11); None: rows
         # of elements (or quantized rows, quant_bits)
         self.layout = _lib.check_layout(layout)
         # "partial_rowwise_adam": [N, 2 * D] = w | m, the second moment is not the table's (DESIGN.md 3.13)
         self.span = _lib.LAYOUT_SPAN[layout]
+        # "adagrad": [N, 2 * D] = w | h, h the per-element sums of squared gradients (DESIGN.md 3.15); init_acc is what
+        # fill_uniform_ / set_weight_ start every h element at (torch's initial_accumulator_value)
+        if not float(init_acc) >= 0.0 or (init_acc != 0.0 and layout != "adagrad"):
+            raise ValueError(f"init_acc={init_acc!r}: must be >= 0, and 0 for every layout but 'adagrad'")
+        self.init_acc = float(init_acc)
         assert layout is None or (tensor.dtype == torch.float32 and tensor.shape[1] % self.span == 0 and not quant_bits)
         # 8 / 4: the rows are q8 / q4 rows (torch.uint8 storage either way; uint8 alone means q8), 0: they are elements
         self.quant_bits = quant_bits or (8 if tensor.dtype == _lib.Q8 else 0)
@@ -77,12 +82,12 @@ class HostTable:
 
     @classmethod
     def allocate(cls, num_embeddings: int, dim: int, threads=0, dtype: torch.dtype = torch.float32,
-                 layout: Optional[str] = None) -> "HostTable":
+                 layout: Optional[str] = None, init_acc: float = 0.0) -> "HostTable":
         if not isinstance(threads, int):              # allocate(N, D, dtype)
             threads, dtype = 0, threads
         if _lib.check_layout(layout) is not None:
-            # [N, 3 * D] (adam) or [N, 2 * D] (partial_rowwise_adam) fp32: the rows' w parts are filled by fill_uniform_ /
-            # set_weight_, the moments start at zero
+            # [N, 3 * D] (adam) or [N, 2 * D] (partial_rowwise_adam, adagrad) fp32: the rows' w parts are filled by
+            # fill_uniform_ / set_weight_, the moments start at zero (adagrad: the sums of squares at init_acc)
             span = _lib.LAYOUT_SPAN[layout]
             _lib.check_adam_table(dim, dtype, layout)
             _lib.require_gpu()
@@ -92,7 +97,8 @@ class HostTable:
             carr = (ctypes.c_float * n).from_address(hp.value)
             carr._ce_block = _PinnedBlock(hp.value)
             t = torch.from_numpy(np.ctypeslib.as_array(carr))
-            return cls(t.view(num_embeddings, span * dim), hp.value, dp.value, registered=False, layout=layout)
+            return cls(t.view(num_embeddings, span * dim), hp.value, dp.value, registered=False, layout=layout,
+                       init_acc=init_acc)
         if dtype == _lib.Q8 or dtype == _lib.Q4:
             # a row-wise quantized table: [N, 16 + D] (q8) or [N, 16 + D / 2] (q4, spelled torch.quint4x2) uint8, whole
             # rows (filled by quantize_from)
@@ -162,10 +168,11 @@ class HostTable:
         return self
 
     def set_weight_(self, w: torch.Tensor) -> "HostTable":
-        """an Adam-layout table: the w parts = `w` ([N, D], cast to fp32), the moments zero"""
+        """an Adam-layout table: the w parts = `w` ([N, D], cast to fp32), the moments zero (an Adagrad-layout table:
+        every h element init_acc)"""
         assert self.layout is not None and tuple(w.shape) == (self.tensor.shape[0], self.tensor.shape[1] // self.span)
         d = w.shape[1]
-        self.tensor.zero_()
+        self.tensor.fill_(self.init_acc)
         self.tensor[:, :d].copy_(w.detach().to("cpu", torch.float32))
         return self
 
@@ -173,7 +180,7 @@ class HostTable:
         """an Adam-layout table: the m parts = `exp_avg` ([N, D]) and, for rows w | m | v, the v parts = `exp_avg_sq`;
         the w parts are not touched"""
         n, d = self.tensor.shape[0], self.tensor.shape[1] // self.span
-        assert self.layout is not None and tuple(exp_avg.shape) == (n, d)
+        assert self.layout in ("adam", "partial_rowwise_adam") and tuple(exp_avg.shape) == (n, d)
         assert (exp_avg_sq is not None) == (self.span == 3)
         self.tensor[:, d:2 * d].copy_(exp_avg.detach().to("cpu", torch.float32))
         if exp_avg_sq is not None:
@@ -181,7 +188,24 @@ class HostTable:
             self.tensor[:, 2 * d:].copy_(exp_avg_sq.detach().to("cpu", torch.float32))
         return self
 
-    def fill_uniform_(self, lo: float, hi: float, seed: int, threads: int = 0):
+    def set_state_sum_(self, state_sum: torch.Tensor) -> "HostTable":
+        """an Adagrad-layout table: the h parts = `state_sum` ([N, D], cast to fp32); the w parts are not touched"""
+        n, d = self.tensor.shape[0], self.tensor.shape[1] // self.span
+        assert self.layout == "adagrad" and tuple(state_sum.shape) == (n, d)
+        self.tensor[:, d:].copy_(state_sum.detach().to("cpu", torch.float32))
+        return self
+
+    def fill_uniform_(self, lo: float, hi: float, seed: int, threads: int = 0, init_acc: Optional[float] = None):
+        if init_acc is not None:                      # (an Adagrad-layout table: the value every h element starts at)
+            if not float(init_acc) >= 0.0 or (init_acc != 0.0 and self.layout != "adagrad"):
+                raise ValueError(f"init_acc={init_acc!r}: must be >= 0, and 0 for every layout but 'adagrad'")
+            self.init_acc = float(init_acc)
+        if self.layout == "adagrad":
+            # row r's w part = row r of the plain fp32 fill of the same seed; every h element init_acc
+            check(lib.ce_host_fill_uniform_adagrad(ctypes.c_void_p(self.host_ptr), self.tensor.shape[0],
+                                                   self.tensor.shape[1] // 2, lo, hi, seed, self.init_acc,
+                                                   threads or _default_threads()))
+            return self
         if self.layout is not None:
             # row r's w part = row r of the plain fp32 fill of the same seed; zero moments
             fill = lib.ce_host_fill_uniform_adam if self.layout == "adam" else lib.ce_host_fill_uniform_pradam
@@ -236,7 +260,7 @@ class CachedParamMgr(torch.nn.Module):
         # a q8 table's rows are 16 + D bytes wide, a q4 table's 16 + D / 2; embedding_dim keeps meaning D
         self.embedding_dim = (2 * (self._row_width - _lib.CE_Q4_HEADER_BYTES) if self.quant_bits == 4
                               else self._row_width - _lib.CE_Q8_HEADER_BYTES) if q8 else self._row_width
-        if self.layout is not None:                   # rows w | m | v of 3 * D floats, or w | m of 2 * D: D keeps meaning D
+        if self.layout is not None:                   # rows w | m | v of 3 * D floats, or w | m, w | h of 2 * D: D keeps meaning D
             self.embedding_dim = self._row_width // self._table.span
         # what the library is told a row is: fp32 elements (a 16-bit row of D elements = D / 2 of them, a q8 row
         # (16 + D) / 4 and a q4 row (16 + D / 2) / 4 of them, bit for bit)

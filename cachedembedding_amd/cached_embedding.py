@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
-from .functional import (FusedAdam, FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_grad_clip,
+from .functional import (FusedAdagrad, FusedAdam, FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_grad_clip,
                          check_grad_clip_path, check_lr, check_lr_path, check_weight_decay, check_weight_decay_path,
                          embedding_bag, refuse_grad_clip, refuse_weight_decay)
 
@@ -46,6 +46,9 @@ def _refuse_q8_update(module, what: str, lr) -> None:
 
 def _refuse_adam_layout(module, what: str, lr) -> None:
     layout = getattr(module, "fused_optimizer", None)
+    if lr is not None and layout == "adagrad":
+        raise NotImplementedError(f"{what}(lr) on an Adagrad-layout module (fused_optimizer={layout!r}): its rows carry "
+                                  "Adagrad's sums of squares, set_fused_adagrad(lr) is its fused update")
     if lr is not None and layout is not None:
         raise NotImplementedError(f"{what}(lr) on an Adam-layout module (fused_optimizer={layout!r}): its rows carry "
                                   "Adam's moments, set_fused_adam(lr) is its fused update")
@@ -64,7 +67,8 @@ class CachedEmbeddingBag(nn.Module):
                  evict_strategy: EvictionStrategy = EvictionStrategy.DATASET, *, cuda_row_num: Optional[int] = None,
                  init_seed: int = 1024, strict: bool = True, output_dtype: Optional[torch.dtype] = None,
                  table_dtype: Optional[torch.dtype] = None, _table: Optional[HostTable] = None,
-                 _idx_map: Optional[torch.Tensor] = None, fused_optimizer: Optional[str] = None):
+                 _idx_map: Optional[torch.Tensor] = None, fused_optimizer: Optional[str] = None,
+                 initial_accumulator_value: float = 0.0):
         super().__init__()
         # fused_optimizer="adam" (addition): the host table AND the cache hold rows w | m | v of 3 * D floats -- Adam's
         # moments live where the table lives and travel with the rows through eviction and admission;
@@ -73,16 +77,28 @@ class CachedEmbeddingBag(nn.Module):
         # 2 * D floats -- the first moment travels with the row --, and the second moment is one fp32 per host-table row
         # in device memory (`.exp_avg_sq`, [N]), fed by the mean of the row's squared gradient.  Everything else is the
         # Adam layout's: set_fused_adam(lr), an fp32 table only, the same refusals.
+        # fused_optimizer="adagrad" (addition; torch.optim.Adagrad, FBGEMM's EXACT_ADAGRAD): rows w | h of
+        # 2 * D floats, h the per-element sums of squared gradients, every element initial_accumulator_value at first
+        # (`.state_sum`, [N, D]); set_fused_adagrad(lr) applies the update inside backward.  The table rules and the
+        # refusals are the Adam layouts'.
         if fused_optimizer not in _lib.LAYOUTS:
-            raise ValueError(f"fused_optimizer={fused_optimizer!r}: None, 'adam' or 'partial_rowwise_adam'")
+            raise ValueError(f"fused_optimizer={fused_optimizer!r}: {_lib.LAYOUT_NAMES}")
+        if not float(initial_accumulator_value) >= 0.0:
+            raise ValueError(f"initial_accumulator_value={initial_accumulator_value!r}: must be >= 0")
+        if initial_accumulator_value != 0.0 and fused_optimizer != "adagrad":
+            raise ValueError(f"initial_accumulator_value={initial_accumulator_value!r} needs fused_optimizer='adagrad': "
+                             "no other layout has an accumulator in its rows")
         self.fused_optimizer = fused_optimizer
+        self.initial_accumulator_value = float(initial_accumulator_value)
         adam = fused_optimizer is not None
+        elem = fused_optimizer == "adagrad"
         if adam:
             _lib.check_adam_table(embedding_dim, table_dtype, fused_optimizer)
             for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
                              ("sparse=True", bool(sparse))):
                 if on:
-                    raise NotImplementedError(f"{what} with an Adam-layout table (fused_optimizer={fused_optimizer!r})")
+                    raise NotImplementedError(f"{what} with an {'Adagrad' if elem else 'Adam'}-layout table "
+                                              f"(fused_optimizer={fused_optimizer!r})")
         # output_dtype (addition): dtype of the pooled output and of the gradient coming back -- None / torch.float32,
         # torch.bfloat16 or torch.float16 (functional.embedding_bag(output_dtype=...)).  `dtype` is the TABLE's dtype.
         if dtype not in (None, torch.float32):
@@ -146,20 +162,22 @@ class CachedEmbeddingBag(nn.Module):
         self.fused_sgd = FusedSGD(None)
         self.fused_adagrad = FusedRowwiseAdagrad(None)
         self.fused_adam = None
+        self.fused_elementwise_adagrad = None
 
         if _table is not None:
             table = _table
             assert table.tensor.dtype == (torch.uint8 if q8 else self.table_dtype) and table.quant_bits == bits \
                 and table.tensor.shape[0] == num_embeddings and table.layout == fused_optimizer
         elif adam:
-            table = HostTable.allocate(num_embeddings, embedding_dim, layout=fused_optimizer)
+            table = HostTable.allocate(num_embeddings, embedding_dim, layout=fused_optimizer,
+                                       init_acc=self.initial_accumulator_value)
             if _weight is None:
                 table.fill_uniform_(-1.0 / num_embeddings, 1.0 / num_embeddings, init_seed)
-                if padding_idx is not None:
-                    table.tensor[padding_idx].zero_()
+                if padding_idx is not None:                 # (the w part: the moments are zero, Adagrad's h stays)
+                    table.tensor[padding_idx, :embedding_dim].zero_()
             else:
                 assert tuple(_weight.shape) == (num_embeddings, embedding_dim)
-                table.set_weight_(_weight)                  # zero moments
+                table.set_weight_(_weight)                  # zero moments (Adagrad's h: the initial value)
         elif q8:
             w = _weight.detach()
             if w.dtype == torch.uint8:                      # already q8 / q4 rows: pinned in place
@@ -195,7 +213,11 @@ class CachedEmbeddingBag(nn.Module):
             self.eval()
         if w16:
             self.set_weight_rounding(self.weight_rounding, self.weight_rounding_seed)
-        if adam:
+        if elem:
+            # the step count lr_decay reads: on the device, so that a replayed graph counts on
+            self.adagrad_step = torch.zeros(1, dtype=torch.int64, device=self.cache_weight_mgr.device)
+            self.fused_elementwise_adagrad = FusedAdagrad(None, step=self.adagrad_step)
+        elif adam:
             # the step count Adam's bias correction reads: on the device, so that a replayed graph counts on
             self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.cache_weight_mgr.device)
             mgr = self.cache_weight_mgr
@@ -216,7 +238,7 @@ class CachedEmbeddingBag(nn.Module):
         return w[:, :self.embedding_dim] if self.fused_optimizer is not None else w
 
     def _adam_part(self, k: int, name: str) -> torch.Tensor:
-        if self.fused_optimizer is None:
+        if self.fused_optimizer in (None, "adagrad"):
             raise AttributeError(f"{name} exists on a module built with fused_optimizer='adam' or "
                                  "'partial_rowwise_adam'")
         d = self.embedding_dim
@@ -236,12 +258,36 @@ class CachedEmbeddingBag(nn.Module):
             return self.cache_weight_mgr.exp_avg_sq
         return self._adam_part(2, "exp_avg_sq")
 
+    @property
+    def state_sum(self) -> torch.Tensor:
+        """Adagrad's per-element sums of squared gradients (torch.optim.Adagrad's state["sum"]), the [N, D] view of the
+        host table's h parts, in row space like `.weight`; current after flush()"""
+        if self.fused_optimizer != "adagrad":
+            raise AttributeError("state_sum exists on a module built with fused_optimizer='adagrad'")
+        return self.cache_weight_mgr.weight[:, self.embedding_dim:]
+
+    def load_adagrad_state(self, state_sum: torch.Tensor, step: int) -> None:
+        """Restore Adagrad's state, as read from `.state_sum` / `.adagrad_step` of a module with the same id -> row map:
+        state_sum [N, D], step the step count.  Flushes first, then writes the host table's h parts and sets the step
+        count; the weights are not touched."""
+        if self.fused_optimizer != "adagrad":
+            raise ValueError("load_adagrad_state needs a module built with fused_optimizer='adagrad'")
+        n, d = self.num_embeddings, self.embedding_dim
+        if tuple(state_sum.shape) != (n, d):
+            raise ValueError(f"state_sum must be [{n}, {d}] (got {tuple(state_sum.shape)})")
+        if int(step) < 0:
+            raise ValueError(f"step={step!r}: must be >= 0")
+        self.flush()
+        self.cache_weight_mgr.writeback_wait()              # (the write-backs of the worker transport have landed)
+        self.cache_weight_mgr._table.set_state_sum_(state_sum)
+        self.adagrad_step.fill_(int(step))
+
     def load_adam_state(self, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int) -> None:
         """Restore Adam's state, as read from `.exp_avg` / `.exp_avg_sq` / `.adam_step` of a module with the same layout
         and the same id -> row map: exp_avg [N, D]; exp_avg_sq [N, D] (Adam layout) or [N] (partial row-wise Adam); step
         the step count.  Flushes first, then writes the host table's moment parts (the partial layout: the device
         tensor) and sets the step count; the weights are not touched."""
-        if self.fused_optimizer is None:
+        if self.fused_optimizer in (None, "adagrad"):
             raise ValueError("load_adam_state needs a module built with fused_optimizer='adam' or 'partial_rowwise_adam'")
         n, d = self.num_embeddings, self.embedding_dim
         partial = self.fused_optimizer == "partial_rowwise_adam"
@@ -362,7 +408,7 @@ class CachedEmbeddingBag(nn.Module):
         "row_norm"; functional.check_grad_clip): the row's folded gradient is clipped before the decay and the moments
         see it -- clip_grad_value_ / a per-row clip_grad_norm_ in front of optimizer.step().  Exclusive with
         set_fused_sgd / set_fused_rowwise_adagrad: an Adam-layout module refuses those."""
-        if self.fused_optimizer is None:
+        if self.fused_optimizer in (None, "adagrad"):
             raise ValueError("set_fused_adam needs a module built with fused_optimizer='adam' (or 'partial_rowwise_adam'): "
                              "Adam's moments live in the rows of the table")
         if isinstance(lr, torch.Tensor):
@@ -375,6 +421,31 @@ class CachedEmbeddingBag(nn.Module):
                             weight_decay_mode=weight_decay_mode, grad_clip=clip,           # implemented)
                             grad_clip_mode=grad_clip_mode)
         self.fused_adam.lr = lr
+
+    def set_fused_adagrad(self, lr: Union[float, torch.Tensor, None], eps: float = 1e-10, lr_decay: float = 0.0,
+                          accumulator: str = "step", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2",
+                          grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
+        """Apply element-wise Adagrad (torch.optim.Adagrad's arithmetic on the rows a step looks up; FBGEMM's
+        EXACT_ADAGRAD) to the cache rows inside backward.  Needs a module built with fused_optimizer="adagrad": the sums
+        of squared gradients are part of every row, in the host table and in the cache, `.state_sum` after flush(); the
+        step count lr_decay reads is `.adagrad_step` (device).  lr=None turns the update off (state and step count are
+        kept; a backward is then a RuntimeError).  lr may be a tensor, as in set_fused_sgd.  accumulator, weight_decay
+        ("l2": torch.optim.Adagrad(weight_decay=); "decoupled": w is scaled by 1 - clr * weight_decay first, clr the
+        decayed rate) and grad_clip as in set_fused_adam (functional.FusedAdagrad).  Exclusive with the other
+        set_fused_*: an Adagrad-layout module refuses those, every other module refuses this."""
+        if self.fused_optimizer != "adagrad":
+            raise ValueError("set_fused_adagrad needs a module built with fused_optimizer='adagrad': Adagrad's sums of "
+                             "squares live in the rows of the table")
+        if isinstance(lr, torch.Tensor):
+            check_lr(lr)
+        elif lr is not None and not float(lr) >= 0.0:
+            raise ValueError(f"lr={lr!r}: must be >= 0")
+        wd = _checked_weight_decay(self, "adagrad", lr, False, weight_decay, weight_decay_mode)
+        clip = _checked_grad_clip(self, "adagrad", lr, False, grad_clip, grad_clip_mode)
+        self.fused_elementwise_adagrad.set(eps, lr_decay, accumulator, weight_decay=wd,
+                                           weight_decay_mode=weight_decay_mode, grad_clip=clip,
+                                           grad_clip_mode=grad_clip_mode)
+        self.fused_elementwise_adagrad.lr = lr
 
     def set_weight_rounding(self, rounding: str = "stochastic", seed: int = 0):
         """How the fused updates round a row of a 16-bit table: "nearest" (round-to-nearest-even) or "stochastic" (the
@@ -400,6 +471,8 @@ class CachedEmbeddingBag(nn.Module):
     def _fused(self):
         if self.fused_adam is not None:                     # an Adam-layout table: the forward needs the object too
             return self.fused_adam
+        if self.fused_elementwise_adagrad is not None:      # an Adagrad-layout table: likewise
+            return self.fused_elementwise_adagrad
         return self.fused_adagrad if self.fused_adagrad.lr is not None else self.fused_sgd
 
     def forward(self, input: torch.Tensor, offsets: Optional[torch.Tensor] = None,

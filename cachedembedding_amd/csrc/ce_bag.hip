@@ -1882,6 +1882,22 @@ extern "C" int ce_bag_forward_src_keys_pradam(const float* weight, int64_t num_r
                          (hipStream_t)stream);
 }
 
+// ---- forward from an element-wise Adagrad table (rows w | h of 2 * dim fp32): the row is two parts
+// wide and the forward reads the first, which is all PartialAdamRow says -- the same kernels, checks and order
+extern "C" int ce_bag_forward_adagrad(const float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                      int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                      int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                      int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream) {
+  return ce_bag_forward_pradam(weight, num_rows, dim, indices, nnz, offsets, offsets_are_i64, num_bags,
+                               include_last_offset, per_sample_weights, mode, hook_features, out, act_dtype, stream);
+}
+
+extern "C" int ce_bag_forward_src_keys_adagrad(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                               const uint64_t* src_keys, void* out, int32_t act_dtype,
+                                               ce_stream_t stream) {
+  return ce_bag_forward_src_keys_pradam(weight, num_rows, dim, nnz, src_keys, out, act_dtype, stream);
+}
+
 extern "C" int64_t ce_bag_presort_len(int64_t nnz) { return nnz <= 0 ? 0 : padded_keys(nnz); }
 
 // the refusals of a window's bag layout, and the BagParams the presort kernel reads it from

@@ -21,7 +21,9 @@
 // Adam (ce_bag_backward_adam*) is a third arithmetic of update_row on an fp32 table whose rows carry
 // their own moments (w | m | v): the two atomic folds above, unchanged, hand it the same folded gradient.  Partial
 // row-wise Adam (ce_bag_backward_pradam*) is a fourth: rows w | m, the second moment one fp32 per table
-// row where row-wise Adagrad keeps its momentum, fed by the mean of the row's squared gradient.
+// row where row-wise Adagrad keeps its momentum, fed by the mean of the row's squared gradient.  Element-wise Adagrad
+// (ce_bag_backward_adagrad*; torch.optim.Adagrad, FBGEMM's EXACT_ADAGRAD) is a fifth: rows w | h, h the
+// per-element sums of squared gradients, the rate lr / (1 + (t - 1) lr_decay) formed on the device from the step count.
 // Gradient clipping (the ce_*_clip entries, the CLIP = true instantiations) acts on a row's folded
 // gradient g -- what update_row / sorted_apply_row receive -- FIRST, and everything that used g then uses the clipped g:
 // the L2 decay's h = g + wd * w, row-wise Adagrad's sum h^2 / D, Adam's m' and v', partial row-wise Adam's ss, the step
@@ -57,7 +59,13 @@ struct UpdateArgs {
   float eps;
   const float* lr_dev;                // non-NULL (the ce_*_lrdev entries): the learning rate is *lr_dev, `lr` is not read
   // Adam only (`weight` is then [num_rows, 3 * D]: w | m | v; `counter` is the caller's step count)
-  double beta1, beta2;
+  // element-wise Adagrad (`weight` is [num_rows, 2 * D]: w | h; `counter` is the caller's step count) has no betas:
+  // its lr_decay lies where beta1 does, so that every other kernel's arguments stay where they were
+  union {
+    double beta1;
+    double lr_decay;
+  };
+  double beta2;
   float omb1, omb2;                   // (float)(1.0 - beta): the fp64 difference, rounded once
   // weight decay (the ce_*_wd entries, the WD = true instantiations): CE_WD_L2 or CE_WD_DECOUPLED
   float wd;
@@ -80,6 +88,19 @@ __device__ __forceinline__ float adam_step_size(const UpdateArgs& a) {
 // lr * c_t): uniform like the learning rate -- and read from *lr_dev with it, so a replayed graph follows a schedule in
 // the decay as well -- so a kernel works it out once per thread, at its top.  The L2 form does not look at it.
 __device__ __forceinline__ float decay_factor(float lr, float wd) { return (float)(1.0 - (double)lr * (double)wd); }
+
+// Element-wise Adagrad's rate: clr_d = lr / (1 + (t - 1) * lr_decay) in fp64, t the step count as the
+// call's first launch left it.  The step is (float)clr_d and the decoupled decay's factor (float)(1.0 - clr_d * wd), so
+// a replayed graph follows a schedule and the step count in both.  Uniform: once per thread, at the kernel's top.
+__device__ __forceinline__ double adagrad_rate(const UpdateArgs& a) {
+#pragma clang fp contract(off)
+  const double t = (double)*a.counter;
+  return (double)learning_rate(a) / (1.0 + (t - 1.0) * a.lr_decay);
+}
+__device__ __forceinline__ float adagrad_decay_factor(double clr, float wd) {
+#pragma clang fp contract(off)
+  return (float)(1.0 - clr * (double)wd);
+}
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -220,8 +241,12 @@ __device__ __forceinline__ void clip_row(VT (&g)[NCH], RowClip k, int G) {
 //   CLIP (then WD as well: the decay's mode is read at run time, and CE_WD_NONE is the decoupled form with f = 1, which
 //   multiplies exactly): clip_row on a copy of g, then the WD update of that copy -- in every arm the clip stands in
 //   front of the decay, and everything behind it is the code the unclipped instantiation runs.
+//   ELEM (element-wise Adagrad, torch.optim.Adagrad; DESIGN.md 3.15: an fp32 table of rows w | s, vector lanes; lr is
+//   (float)adagrad_rate, f adagrad_decay_factor; `adagrad` is not looked at), h the gradient after the decay, per element:
+//     s' = s + h * h ; w' = w - lr * (h / (sqrtf(s') + eps))
+//   every operation rounded on its own; no reduction, no state outside the row; w and s read once and written once.
 template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false,
-          bool CLIP = false>
+          bool CLIP = false, bool ELEM = false>
 __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64_t step_key, int64_t s,
                                            const VT (&g)[NCH], int gl, int G, bool adagrad, float f = 1.f,
                                            RowClip clip = RowClip{}) {
@@ -233,12 +258,34 @@ __device__ __forceinline__ void update_row(const UpdateArgs& a, float lr, uint64
 #pragma unroll
     for (int c = 0; c < NCH; ++c) cg[c] = g[c];
     clip_row<WT, VT, NCH>(cg, clip, G);
-    update_row<VT, WT, NCH, STOCH, ADAM, true, ROWV, false>(a, lr, step_key, s, cg, gl, G, adagrad, f);
+    update_row<VT, WT, NCH, STOCH, ADAM, true, ROWV, false, ELEM>(a, lr, step_key, s, cg, gl, G, adagrad, f);
     return;
   }
   const bool l2 = WD && a.wd_mode == CE_WD_L2;               // uniform
   static_assert(!STOCH || (sizeof(WT) == 2 && sizeof(VT) == 16), "stochastic rounding: a 16-bit table, vector lanes");
   static_assert(!ROWV || ADAM, "a row-wise second moment: Adam only");
+  static_assert(!ELEM || (!ADAM && !ROWV), "element-wise Adagrad: an arithmetic of its own, no moments");
+  if constexpr (ELEM) {
+    static_assert(std::is_same<WT, float>::value && sizeof(VT) == 16 && !STOCH,
+                  "element-wise Adagrad: an fp32 table, vector lanes");
+    f32x4* R = (f32x4*)a.weight + s * 2 * (int64_t)a.rowlen;      // w: [0, rowlen), the sums of squares behind it
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int idx = gl + c * G;
+      if (idx >= a.rowlen) continue;
+      f32x4 gc = g[c];
+      f32x4 w = R[idx], h = R[a.rowlen + idx];
+      if constexpr (WD) {
+        if (l2) gc = gc + w * a.wd; else w = w * f;
+      }
+      h = h + gc * gc;                           // (elementwise, each operation rounded: contraction is off)
+      w = w - f32x4{adam_delta(lr, a.eps, gc.x, h.x), adam_delta(lr, a.eps, gc.y, h.y), adam_delta(lr, a.eps, gc.z, h.z),
+                    adam_delta(lr, a.eps, gc.w, h.w)};
+      R[idx] = w;
+      R[a.rowlen + idx] = h;
+    }
+    return;
+  }
   if constexpr (ADAM && ROWV) {
     static_assert(std::is_same<WT, float>::value && sizeof(VT) == 16 && !STOCH, "Adam: an fp32 table, vector lanes");
     f32x4* R = (f32x4*)a.weight + s * 2 * (int64_t)a.rowlen;      // w: [0, rowlen), m: [rowlen, 2 rowlen)
@@ -451,13 +498,15 @@ struct ApplyArgs {
 // a wave reads 64 flags at once, and a lane group per flagged slot reads acc, updates the row and writes acc and the
 // flag back to zero
 template <typename VT, typename WT, int NCH, bool ADAGRAD, bool STOCH, bool ADAM = false, bool WD = false,
-          bool ROWV = false, bool CLIP = false>
+          bool ROWV = false, bool CLIP = false, bool ELEM = false>
 __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
   const LaneGroup l = lane_group(a.u.g_log2);
   VT* A = (VT*)a.acc;
   const uint64_t key = step_key<STOCH>(a.u);
-  const float lr = ADAM ? adam_step_size(a.u) : learning_rate(a.u);
-  const float f = WD ? decay_factor(learning_rate(a.u), a.u.wd) : 1.f;
+  const float lr = ELEM ? (float)adagrad_rate(a.u) : (ADAM ? adam_step_size(a.u) : learning_rate(a.u));
+  const float f = !WD ? 1.f
+                      : (ELEM ? adagrad_decay_factor(adagrad_rate(a.u), a.u.wd)
+                              : decay_factor(learning_rate(a.u), a.u.wd));
   for (int64_t base = l.wave * 64; base < (int64_t)a.num_rows; base += l.nwaves * 64) {
     const int64_t mine = base + l.lane;
     const bool flagged = mine < (int64_t)a.num_rows && a.flags[mine] != 0;
@@ -465,7 +514,7 @@ __global__ __launch_bounds__(256) void k_rows_apply(ApplyArgs a) {
       const int64_t s = base + i;
       VT g[NCH];
       load_row(g, A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
-      update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV, CLIP>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD, f, a.clip);
+      update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV, CLIP, ELEM>(a.u, lr, key, s, g, l.gl, l.G, ADAGRAD, f, a.clip);
       zero_row<VT, NCH>(A + s * a.u.rowlen, l.gl, l.G, a.u.rowlen);
     });
     if (flagged) a.flags[mine] = 0;
@@ -911,7 +960,7 @@ struct CompactArgs {
 
 // one lane group per list entry (grid-stride over u < U; the grid is sized by cap)
 template <typename VT, typename WT, int NCH, bool STOCH, bool ADAM = false, bool WD = false, bool ROWV = false,
-          bool CLIP = false>
+          bool CLIP = false, bool ELEM = false>
 __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   const int G = 1 << a.u.g_log2;
   const int gl = threadIdx.x & (G - 1);
@@ -920,13 +969,15 @@ __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
   VT* A = (VT*)a.acc;
   const int64_t n = *a.n_list;
   const uint64_t key = step_key<STOCH>(a.u);
-  const float lr = ADAM ? adam_step_size(a.u) : learning_rate(a.u);
-  const float f = WD ? decay_factor(learning_rate(a.u), a.u.wd) : 1.f;
+  const float lr = ELEM ? (float)adagrad_rate(a.u) : (ADAM ? adam_step_size(a.u) : learning_rate(a.u));
+  const float f = !WD ? 1.f
+                      : (ELEM ? adagrad_decay_factor(adagrad_rate(a.u), a.u.wd)
+                              : decay_factor(learning_rate(a.u), a.u.wd));
   for (int64_t u = grp; u < n; u += ngrp) {          // group-uniform
     VT g[NCH];
     load_row(g, A + u * a.u.rowlen, gl, G, a.u.rowlen);
-    update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV, CLIP>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad, f,
-                                                         a.clip);
+    update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV, CLIP, ELEM>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad,
+                                                               f, a.clip);
     zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
   }
 }
@@ -1011,6 +1062,7 @@ static CompactWs carve_compact(void* ws, int64_t num_rows, int64_t nnz, int32_t 
 
 constexpr int32_t kOptAdam = 2;       // beside CE_OPT_*: library-internal, no `optimizer` argument takes it
 constexpr int32_t kOptPartialAdam = 3;   // partial row-wise Adam (rows w | m, the second moment in `momentum`): likewise
+constexpr int32_t kOptElemAdagrad = 4;   // element-wise Adagrad (rows w | h, the sums of squares in the row): likewise
 
 // the arguments every update entry has (the fp32 Adagrad entries: CE_ACT_F32, CE_OPT_ROWWISE_ADAGRAD, CE_ROUND_NEAREST)
 struct UpdateCall {
@@ -1034,6 +1086,8 @@ struct UpdateCall {
   // takes the place of the workspace's counter
   unsigned long long* step = nullptr;
   double beta1 = 0.0, beta2 = 0.0;
+  // the ce_bag_backward_adagrad* entries (optimizer = kOptElemAdagrad, an fp32 table of rows w | h): `step` as for Adam
+  double lr_decay = 0.0;
   // the ce_*_wd entries: weight decay (decay() false: the call is the covered entry's, kernels and all)
   float wd = 0.f;
   int32_t wd_mode = CE_WD_NONE;
@@ -1046,6 +1100,9 @@ struct UpdateCall {
   bool adagrad() const { return optimizer == CE_OPT_ROWWISE_ADAGRAD; }
   bool adam() const { return optimizer == kOptAdam || optimizer == kOptPartialAdam; }
   bool rowv() const { return optimizer == kOptPartialAdam; }     // (then adam() holds as well)
+  bool elem() const { return optimizer == kOptElemAdagrad; }
+  // the state travels in the row and the caller's step count is counted: a row that is merely flagged changes
+  bool in_row() const { return adam() || elem(); }
   bool stochastic() const { return rounding == CE_ROUND_STOCHASTIC; }
 };
 
@@ -1063,7 +1120,7 @@ static UpdateArgs update_args(const UpdateCall& c, const RowGeom& r, const unsig
   u.lr = c.lr;
   u.eps = c.eps;
   u.lr_dev = c.lr_dev;
-  u.beta1 = c.beta1;
+  if (c.elem()) u.lr_decay = c.lr_decay; else u.beta1 = c.beta1;
   u.beta2 = c.beta2;
   u.omb1 = (float)(1.0 - c.beta1);
   u.omb2 = (float)(1.0 - c.beta2);
@@ -1172,7 +1229,7 @@ struct SlotLookups {
 // merely flagged changes) or, L == NULL, the row halves of `keys` (an uncovered lookup's key is all ones already)
 static void launch_mark_call(const UpdateCall& c, const SlotLookups* L, const void* keys, int64_t n, uint8_t* flags,
                              unsigned long long* counter, hipStream_t s) {
-  if (L && (c.adam() || c.decay()))
+  if (L && (c.in_row() || c.decay()))
     hipLaunchKernelGGL(k_mark_slots_covered, dim3(grid_for(n, 256)), dim3(256), 0, s, L->indices, n,
                        (uint32_t)c.num_rows, L->offsets, (int)L->off64, L->num_bags, (int)L->include_last, flags, counter);
   else
@@ -1186,7 +1243,7 @@ template <typename Scatter>
 static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const SlotLookups* L, const void* keys, int64_t n,
                               hipStream_t s, Scatter&& scatter) {
   const ApplyWs ws = carve_apply(c.workspace, c.num_rows, c.dim, c.w16());
-  unsigned long long* counter = c.adam() ? c.step : ws.counter;
+  unsigned long long* counter = c.in_row() ? c.step : ws.counter;
   launch_mark_call(c, L, keys, n, ws.flags, counter, s);
   CE_LAUNCH_CHECK();
   int rc = scatter(ws.acc);
@@ -1201,7 +1258,12 @@ static int update_cache_sized(const UpdateCall& c, const RowGeom& r, const SlotL
   const bool ada = c.adagrad(), st = c.stochastic();
   for_decay(c.decay(), c.clipped(), [&](auto d) {
     constexpr bool WD = decltype(d)::WD, CL = decltype(d)::CLIP;
-    if (c.rowv())
+    if (c.elem())
+      for_vec_lanes(r.nch, [&](auto l) {
+        hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, false, WD, false, CL, true>), g, b,
+                           0, s, a);
+      });
+    else if (c.rowv())
       for_vec_lanes(r.nch, [&](auto l) {
         hipLaunchKernelGGL((k_rows_apply<f32x4, float, decltype(l)::NCH, false, false, true, WD, true, CL>), g, b, 0, s,
                            a);
@@ -1238,7 +1300,7 @@ static int launch_compact_scan(int64_t num_rows, const CompactWs& ws, hipStream_
 
 static int launch_compact_apply(const UpdateCall& c, const RowGeom& r, const CompactWs& ws, hipStream_t s) {
   CompactArgs a{};
-  a.u = update_args(c, r, c.adam() ? c.step : ws.counter);
+  a.u = update_args(c, r, c.in_row() ? c.step : ws.counter);
   a.acc = ws.acc;
   a.list = ws.list;
   a.n_list = ws.n_list;
@@ -1247,7 +1309,12 @@ static int launch_compact_apply(const UpdateCall& c, const RowGeom& r, const Com
   const dim3 g(grid_for(ws.cap, 256 >> r.g_log2)), b(256);
   for_decay(c.decay(), c.clipped(), [&](auto d) {
     constexpr bool WD = decltype(d)::WD, CL = decltype(d)::CLIP;
-    if (c.rowv())
+    if (c.elem())
+      for_vec_lanes(r.nch, [&](auto l) {
+        hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, false, WD, false, CL, true>), g, b, 0,
+                           s, a);
+      });
+    else if (c.rowv())
       for_vec_lanes(r.nch, [&](auto l) {
         hipLaunchKernelGGL((k_compact_apply<f32x4, float, decltype(l)::NCH, false, true, WD, true, CL>), g, b, 0, s, a);
       });
@@ -1372,7 +1439,7 @@ static int compact_slots_run(const UpdateCall& c, const RowGeom& r, const SlotLo
              "hook_features must divide num_bags");
   hipStream_t s = (hipStream_t)stream;
   const CompactWs ws = carve_compact(c.workspace, c.num_rows, c.nnz, c.dim);
-  launch_mark_call(c, &L, nullptr, c.nnz, ws.flags, c.adam() ? c.step : (c.w16() ? ws.counter : nullptr), s);
+  launch_mark_call(c, &L, nullptr, c.nnz, ws.flags, c.in_row() ? c.step : (c.w16() ? ws.counter : nullptr), s);
   rc = launch_compact_scan(c.num_rows, ws, s);
   if (rc) return rc;
   // segment-sorted keys hold the rows themselves: with them the scatter never reads `indices`, so only they are remapped
@@ -1409,7 +1476,7 @@ static int compact_src_run(const UpdateCall& c, const RowGeom& r, const uint64_t
   hipStream_t s = (hipStream_t)stream;
   const CompactWs ws = carve_compact(c.workspace, c.num_rows, c.nnz, c.dim);
   const int64_t total = ce_bag_presort_len(c.nnz);
-  launch_mark_call(c, nullptr, src_keys, total, ws.flags, c.adam() ? c.step : (c.w16() ? ws.counter : nullptr), s);
+  launch_mark_call(c, nullptr, src_keys, total, ws.flags, c.in_row() ? c.step : (c.w16() ? ws.counter : nullptr), s);
   rc = launch_compact_scan(c.num_rows, ws, s);
   if (rc) return rc;
   hipLaunchKernelGGL(k_compact_remap_keys, dim3(grid_for(total, 256)), dim3(256), 0, s,
@@ -1449,6 +1516,7 @@ static int adam_check(const UpdateCall& c, int32_t accumulator, RowGeom& r) {
   if (rc) return rc;
   CE_REQUIRE(c.beta1 >= 0.0 && c.beta1 < 1.0 && c.beta2 >= 0.0 && c.beta2 < 1.0, CE_ERR_INVALID,
              "beta1 and beta2 must lie in [0, 1)");
+  CE_REQUIRE(c.lr_decay >= 0.0, CE_ERR_INVALID, "lr_decay must be >= 0");       // (a NaN fails it; Adam passes 0)
   CE_REQUIRE(c.eps >= 0.f, CE_ERR_INVALID, "eps must be >= 0");
   CE_REQUIRE(c.lr_dev || c.lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
   CE_REQUIRE_ACT(c.act);
@@ -1940,6 +2008,37 @@ extern "C" size_t ce_bag_backward_adam_workspace(int64_t num_rows, int64_t nnz, 
   return adam_workspace(num_rows, nnz, dim, accumulator);
 }
 
+// the body of every entry whose table carries its state in the row (Adam, partial row-wise Adam, element-wise Adagrad):
+// the check, then either accumulator's pipeline
+static int in_row_slots(const UpdateCall& c, const SlotLookups& L, int32_t accumulator, ce_stream_t stream) {
+  RowGeom r;
+  int rc = adam_check(c, accumulator, r);
+  if (rc) return rc;
+  if (accumulator == CE_ACC_STEP) return compact_slots_run(c, r, L, stream);
+  if (L.num_bags == 0 || c.nnz == 0) return CE_OK;
+  CE_REQUIRE(L.indices && L.offsets, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(L.num_bags > 0 && L.num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "sizes out of range");
+  CE_REQUIRE(L.mode == CE_MODE_SUM || (L.mode == CE_MODE_MEAN && !L.psw), CE_ERR_INVALID,
+             "mode must be sum, or mean without per_sample_weights");
+  CE_REQUIRE(L.hookF >= 0 && (L.hookF == 0 || L.num_bags % L.hookF == 0), CE_ERR_INVALID,
+             "hook_features must divide num_bags");
+  return update_cache_sized(c, r, &L, nullptr, c.nnz, (hipStream_t)stream, [&](float* acc) {
+    return scatter_slots(acc, c.num_rows, c, L, L.indices, L.presorted, stream);
+  });
+}
+
+static int in_row_src(const UpdateCall& c, const uint64_t* src_keys, int32_t accumulator, ce_stream_t stream) {
+  RowGeom r;
+  int rc = adam_check(c, accumulator, r);
+  if (rc) return rc;
+  if (accumulator == CE_ACC_STEP) return compact_src_run(c, r, src_keys, stream);
+  if (c.nnz == 0) return CE_OK;
+  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
+  return update_cache_sized(c, r, nullptr, src_keys, ce_bag_presort_len(c.nnz), (hipStream_t)stream, [&](float* acc) {
+    return ce_bag_backward_dense_src_act(acc, c.num_rows, c.dim, c.nnz, c.grad_out, c.act, src_keys, stream);
+  });
+}
+
 // ce_bag_backward_adam (weight_decay 0, CE_WD_NONE) and ce_bag_backward_adam_wd are one function; the _src pair likewise
 static int adam_slots(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
                       const void* offsets, int32_t offsets_are_i64, int64_t num_bags, int32_t include_last_offset,
@@ -1952,20 +2051,7 @@ static int adam_slots(float* weight, int64_t num_rows, int32_t dim, const int64_
                                  workspace, workspace_bytes, weight_decay, weight_decay_mode, rv, clip);
   const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
                       hook_features, presorted};
-  RowGeom r;
-  int rc = adam_check(c, accumulator, r);
-  if (rc) return rc;
-  if (accumulator == CE_ACC_STEP) return compact_slots_run(c, r, L, stream);
-  if (num_bags == 0 || nnz == 0) return CE_OK;
-  CE_REQUIRE(indices && offsets, CE_ERR_INVALID, "null pointer");
-  CE_REQUIRE(num_bags > 0 && num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "sizes out of range");
-  CE_REQUIRE(mode == CE_MODE_SUM || (mode == CE_MODE_MEAN && !per_sample_weights), CE_ERR_INVALID,
-             "mode must be sum, or mean without per_sample_weights");
-  CE_REQUIRE(hook_features >= 0 && (hook_features == 0 || num_bags % hook_features == 0), CE_ERR_INVALID,
-             "hook_features must divide num_bags");
-  return update_cache_sized(c, r, &L, nullptr, nnz, (hipStream_t)stream, [&](float* acc) {
-    return scatter_slots(acc, num_rows, c, L, indices, presorted, stream);
-  });
+  return in_row_slots(c, L, accumulator, stream);
 }
 
 static int adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out, int32_t act_dtype,
@@ -1975,15 +2061,7 @@ static int adam_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, c
                     RowClip clip = RowClip{}) {
   const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
                                  workspace, workspace_bytes, weight_decay, weight_decay_mode, rv, clip);
-  RowGeom r;
-  int rc = adam_check(c, accumulator, r);
-  if (rc) return rc;
-  if (accumulator == CE_ACC_STEP) return compact_src_run(c, r, src_keys, stream);
-  if (nnz == 0) return CE_OK;
-  CE_REQUIRE(src_keys, CE_ERR_INVALID, "null pointer");
-  return update_cache_sized(c, r, nullptr, src_keys, ce_bag_presort_len(nnz), (hipStream_t)stream, [&](float* acc) {
-    return ce_bag_backward_dense_src_act(acc, num_rows, dim, nnz, grad_out, act_dtype, src_keys, stream);
-  });
+  return in_row_src(c, src_keys, accumulator, stream);
 }
 
 extern "C" int ce_bag_backward_adam(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
@@ -2117,4 +2195,50 @@ extern "C" int ce_bag_backward_pradam_src_clip(float* weight, int64_t num_rows, 
   return adam_src(weight, num_rows, dim, nnz, grad_out, act_dtype, src_keys, beta1, beta2, lr, lr_dev, eps, weight_decay,
                   weight_decay_mode, step, accumulator, workspace, workspace_bytes, stream, &rv,
                   RowClip{grad_clip, grad_clip_mode});
+}
+
+// ---- element-wise Adagrad on a table of rows w | h: the clipped Adam entries' lists with lr_decay in
+// the betas' place; decay and clip are in from the start.  The accumulators are [., dim] as for any fp32 table, so the
+// workspace is the Adam entries'.
+
+static UpdateCall adagrad_call(float* weight, int64_t num_rows, int32_t dim, int64_t nnz, const void* grad_out,
+                               int32_t act, double lr_decay, float lr, const float* lr_dev, float eps, float wd,
+                               int32_t wd_mode, RowClip clip, int64_t* step, void* workspace, size_t workspace_bytes) {
+  UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act, 0.0, 0.0, lr, lr_dev, eps, step, workspace,
+                           workspace_bytes, wd, wd_mode, nullptr, clip);
+  c.optimizer = kOptElemAdagrad;
+  c.lr_decay = lr_decay;
+  return c;
+}
+
+extern "C" size_t ce_bag_backward_adagrad_workspace(int64_t num_rows, int64_t nnz, int32_t dim, int32_t accumulator) {
+  return ce_bag_backward_adam_workspace(num_rows, nnz, dim, accumulator);
+}
+
+extern "C" int ce_bag_backward_adagrad(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices, int64_t nnz,
+                                       const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                       int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                       int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                       const uint64_t* presorted, double lr_decay, float lr, const float* lr_dev,
+                                       float eps, float weight_decay, int32_t weight_decay_mode, float grad_clip,
+                                       int32_t grad_clip_mode, int64_t* step, int32_t accumulator, void* workspace,
+                                       size_t workspace_bytes, ce_stream_t stream) {
+  const UpdateCall c = adagrad_call(weight, num_rows, dim, nnz, grad_out, act_dtype, lr_decay, lr, lr_dev, eps,
+                                    weight_decay, weight_decay_mode, RowClip{grad_clip, grad_clip_mode}, step, workspace,
+                                    workspace_bytes);
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, presorted};
+  return in_row_slots(c, L, accumulator, stream);
+}
+
+extern "C" int ce_bag_backward_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                           const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                           double lr_decay, float lr, const float* lr_dev, float eps, float weight_decay,
+                                           int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                           int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                                           ce_stream_t stream) {
+  const UpdateCall c = adagrad_call(weight, num_rows, dim, nnz, grad_out, act_dtype, lr_decay, lr, lr_dev, eps,
+                                    weight_decay, weight_decay_mode, RowClip{grad_clip, grad_clip_mode}, step, workspace,
+                                    workspace_bytes);
+  return in_row_src(c, src_keys, accumulator, stream);
 }

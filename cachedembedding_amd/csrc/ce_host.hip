@@ -261,10 +261,11 @@ extern "C" int ce_host_fill_uniform(float* dst, int64_t n, float lo, float hi, u
 }
 
 // a table whose rows carry optimizer state (rows of parts * dim floats, the w part first): the w part of row r = row r
-// of the fill above, the parts behind it zero
+// of the fill above, every element of the parts behind it `state` (zero: Adam's moments)
 static int fill_uniform_parts(float* dst, int64_t n_rows, int32_t dim, int parts, float lo, float hi, uint64_t seed,
-                              int threads) {
+                              int threads, float state = 0.f) {
   CE_REQUIRE(dst && n_rows >= 0, CE_ERR_INVALID, "bad arguments");
+  CE_REQUIRE(state >= 0.f, CE_ERR_INVALID, "init_acc must be >= 0");
   CE_REQUIRE_ADAM_DIM(dim);
   const float span = hi - lo;
   parallel_for(n_rows, threads, [=](int64_t a, int64_t b) {
@@ -275,7 +276,8 @@ static int fill_uniform_parts(float* dst, int64_t n_rows, int32_t dim, int parts
         const float u = (float)(x >> 40) * (1.0f / 16777216.0f);   // as ce_host_fill_uniform
         row[d] = lo + span * u;
       }
-      memset(row + dim, 0, (size_t)dim * 4 * (size_t)(parts - 1));
+      if (state == 0.f) memset(row + dim, 0, (size_t)dim * 4 * (size_t)(parts - 1));
+      else std::fill(row + dim, row + (int64_t)parts * dim, state);
     }
   });
   return CE_OK;
@@ -291,6 +293,12 @@ extern "C" int ce_host_fill_uniform_adam(float* dst, int64_t n_rows, int32_t dim
 extern "C" int ce_host_fill_uniform_pradam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed,
                                            int threads) {
   return fill_uniform_parts(dst, n_rows, dim, 2, lo, hi, seed, threads);
+}
+
+// an element-wise Adagrad table: rows w | h of 2 * dim floats, every h = init_acc (torch's initial_accumulator_value)
+extern "C" int ce_host_fill_uniform_adagrad(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed,
+                                            float init_acc, int threads) {
+  return fill_uniform_parts(dst, n_rows, dim, 2, lo, hi, seed, threads, init_acc);
 }
 
 // round-to-nearest-even casts of a finite or non-finite fp32 value, in integer arithmetic (host code)

@@ -71,8 +71,8 @@ class _BagFn(torch.autograd.Function):
         _lib.require_gpu()
         w16 = weight.dtype in _lib.W16_DTYPES
         assert weight.is_cuda and (w16 or weight.dtype == torch.float32) and weight.is_contiguous()
-        # the weight is then [rows, 3 * D]: w | m | v, or [rows, 2 * D]: w | m (3.13)
-        adam = isinstance(fused, FusedAdam)
+        # the weight is then [rows, 3 * D]: w | m | v, or [rows, 2 * D]: w | m (3.13) or w | h (3.15)
+        adam = isinstance(fused, _IN_ROW)
         partial = adam and fused.layout == "partial_rowwise_adam"
         if psw is not None and ctx.needs_input_grad[3] and fused is not None and fused.lr is not None:
             # d loss / d per_sample_weights[j] = <grad_out[bag of j], weight[indices[j]]> needs the rows as the forward
@@ -110,7 +110,9 @@ class _BagFn(torch.autograd.Function):
             check(fn(ptr(weight), _lib.ACT_DTYPES[weight.dtype], weight.shape[0], dim, *args))
         elif adam:
             # the fp32 kernels with the Adam row type: the w part of every row, the rows three times as far apart
-            if partial:
+            if fused.layout == "adagrad":
+                fn = lib.ce_bag_forward_src_keys_adagrad if from_keys else lib.ce_bag_forward_adagrad
+            elif partial:
                 fn = lib.ce_bag_forward_src_keys_pradam if from_keys else lib.ce_bag_forward_pradam
             else:
                 fn = lib.ce_bag_forward_src_keys_adam if from_keys else lib.ce_bag_forward_adam
@@ -132,7 +134,11 @@ class _BagFn(torch.autograd.Function):
         weight = ctx.weight
         mode, include_last, hook_features, sparse, fused, num_bags = ctx.args
         grad_out = grad_out.contiguous()
-        adam = isinstance(fused, FusedAdam)
+        adam = isinstance(fused, _IN_ROW)
+        if isinstance(fused, FusedAdagrad) and fused.lr is None:
+            raise RuntimeError("backward through an Adagrad-layout table with no fused Adagrad set: an autograd gradient "
+                               "in slot space over 2 * D columns means nothing (set_fused_adagrad(lr) first, or run the "
+                               "forward under torch.no_grad())")
         if adam and fused.lr is None:
             raise RuntimeError("backward through an Adam-layout table with no fused Adam set: an autograd gradient in "
                                f"slot space over {getattr(fused, 'span', 3)} * D columns means nothing (set_fused_adam(lr) first, or run the "
@@ -157,6 +163,22 @@ class _BagFn(torch.autograd.Function):
                 # Gradient clipping: the ce_*_clip entries, the clip and its mode directly behind the decay's
                 clip = fused.grad_clip is not None
                 decay = fused.weight_decay != 0.0 or clip
+                if fused.layout == "adagrad":
+                    # element-wise Adagrad (ce_bag_backward_adagrad*): one entry, decay and clip always in its list
+                    # (weight_decay 0 and CE_CLIP_NONE: the kernels without them), lr_decay where Adam has its betas
+                    tail = (float(fused.lr_decay), 0.0 if lr_t else float(fused.lr), ptr(fused.lr) if lr_t else None,
+                            float(fused.eps), float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + \
+                        (fused.clip_args() if clip else (0.0, _lib.CE_CLIP_NONE)) + \
+                        (ptr(fused.step), _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws),
+                         ws.numel(), stream_ptr())
+                    if src:
+                        check(lib.ce_bag_backward_adagrad_src(ptr(weight), R, dim, nnz, ptr(grad_out), act,
+                                                              ptr(pre.keys), *tail))
+                    else:
+                        check(lib.ce_bag_backward_adagrad(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64,
+                                                          num_bags, int(include_last), ptr(psw), mode, hook_features,
+                                                          ptr(grad_out), act, ptr(pre), *tail))
+                    return (None,) * 14
                 tail = (float(fused.betas[0]), float(fused.betas[1]), 0.0 if lr_t else float(fused.lr),
                         ptr(fused.lr) if lr_t else None, float(fused.eps)) + \
                     ((float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) if decay else ()) + \
@@ -976,11 +998,87 @@ class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
         return _cached_bytes(self, "_ws", need, device, zero=True)
 
 
+class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
+    """Switch for the fused backward + element-wise Adagrad update (torch.optim.Adagrad; FBGEMM's EXACT_ADAGRAD) of one
+    embedding module whose table carries its state: the weight the kernels see is [rows, 2 * D] fp32, every row w | h, h
+    the per-element sums of squared gradients.  Per step and per UNIQUE row the step looks up, g the sum
+    of the row's gradient rows in the batch, t the step count:
+        clr = lr / (1 + (t - 1) lr_decay) ;  h += g g ;  w -= clr * g / (sqrt(h) + eps)
+    Rows no lookup names keep both parts.  FusedRowwiseAdagrad keeps ONE sum per row and is an approximation of this.
+    Handing this object to embedding_bag is what says the weight has the layout, so the forward needs it too; lr=None
+    leaves the forward working and makes a backward a RuntimeError.  The defaults are torch.optim.Adagrad's.
+
+    step, accumulator and a tensor lr: as for FusedAdam -- the step count is ONE int64 on the weight's device which the
+    first kernel of every backward adds 1 to, so a replayed graph follows it, and a tensor lr, in clr.
+
+    weight_decay, weight_decay_mode, lazy (the rows a step looks up decay once, in that step): "l2" is
+    torch.optim.Adagrad(weight_decay=) -- g + weight_decay * w takes the place of g --, "decoupled" scales w by
+    1 - clr * weight_decay first.  grad_clip, grad_clip_mode (check_grad_clip): g is clipped first."""
+
+    deterministic = False                                   # (the sorted fold has no form for rows that carry state)
+    rounding, seed = "nearest", 0
+    layout, span = "adagrad", 2
+
+    def __init__(self, lr: Union[float, torch.Tensor, None] = None, eps: float = 1e-10, lr_decay: float = 0.0,
+                 accumulator: str = "step", step: Optional[torch.Tensor] = None, *, weight_decay: float = 0.0,
+                 weight_decay_mode: str = "l2", grad_clip: Optional[float] = None, grad_clip_mode: str = "value",
+                 deterministic: bool = False):
+        self.lr = lr
+        self.set(eps, lr_decay, accumulator, deterministic, weight_decay=weight_decay,
+                 weight_decay_mode=weight_decay_mode, grad_clip=grad_clip, grad_clip_mode=grad_clip_mode)
+        self.step = step
+        self._ws_step, self._ws_step_key = None, None
+        self._ws = None
+
+    def set(self, eps: float, lr_decay: float, accumulator: str, deterministic: bool = False, *,
+            weight_decay: float = 0.0, weight_decay_mode: str = "l2", grad_clip: Optional[float] = None,
+            grad_clip_mode: str = "value") -> None:
+        wd = check_weight_decay(weight_decay, weight_decay_mode)
+        clip = check_grad_clip(grad_clip, grad_clip_mode)
+        if deterministic:
+            raise NotImplementedError("fused Adagrad with deterministic=True: the sorted fold has no form for rows that "
+                                      "carry their state")
+        if not float(eps) >= 0.0:
+            raise ValueError(f"eps={eps!r}: must be >= 0")
+        if not float(lr_decay) >= 0.0:
+            raise ValueError(f"lr_decay={lr_decay!r}: must be >= 0")
+        if accumulator not in ACCUMULATORS:
+            raise ValueError(f"accumulator={accumulator!r}: 'cache' or 'step'")
+        self.eps, self.lr_decay, self.accumulator = float(eps), float(lr_decay), accumulator
+        self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
+        self.grad_clip, self.grad_clip_mode = clip, grad_clip_mode
+
+    def check(self, weight: torch.Tensor) -> None:
+        """refusals that must come before any kernel of the step has run"""
+        if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] % 2 != 0:
+            raise NotImplementedError("FusedAdagrad needs an fp32 weight of Adagrad-layout rows, [rows, 2 * "
+                                      f"embedding_dim] (got {tuple(weight.shape)} {weight.dtype})")
+        _lib.check_adam_dim(weight.shape[1] // 2)
+        if self.lr is None:
+            return
+        if not isinstance(self.lr, torch.Tensor) and not float(self.lr) >= 0.0:
+            raise ValueError(f"lr={self.lr!r}: must be >= 0")
+        st = self.step
+        if st is None or not st.is_cuda or st.dtype != torch.int64 or st.numel() != 1 or st.device != weight.device:
+            raise ValueError("fused Adagrad needs its step count: one int64 element on the weight's device")
+
+    def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
+        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again
+        if self.accumulator == "step":
+            return _workspace_step(self, num_rows, nnz, dim, device)
+        need = lib.ce_bag_backward_adagrad_workspace(num_rows, nnz, dim, _lib.CE_ACC_CACHE)
+        return _cached_bytes(self, "_ws", need, device, zero=True)
+
+
+# the switches that say the weight's rows carry optimizer state behind their w part (span parts of D floats)
+_IN_ROW = (FusedAdam, FusedAdagrad)
+
+
 def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional[torch.Tensor] = None,
                   max_norm: Optional[float] = None, norm_type: float = 2.0, scale_grad_by_freq: bool = False,
                   mode: str = "mean", sparse: bool = False, per_sample_weights: Optional[torch.Tensor] = None,
                   include_last_offset: bool = False, padding_idx: Optional[int] = None, *,
-                  hook_features: int = 0, fused_sgd: Union[FusedSGD, FusedRowwiseAdagrad, FusedAdam, None] = None,
+                  hook_features: int = 0, fused_sgd: Union[FusedSGD, FusedRowwiseAdagrad, FusedAdam, FusedAdagrad, None] = None,
                   presorted: Union[torch.Tensor, SrcKeys, None] = None, masked_indices: bool = False,
                   out: Optional[torch.Tensor] = None, output_dtype: Optional[torch.dtype] = None,
                   quant_bits: int = 8) -> torch.Tensor:
@@ -994,8 +1092,9 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     # round once on the store and read the 16-bit gradient in place.  out= must then have that dtype.
     _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
     q8 = weight.dtype == _lib.Q8
-    adam = isinstance(fused_sgd, FusedAdam)
+    adam = isinstance(fused_sgd, _IN_ROW)
     if adam:
+        # (FusedAdagrad: [R, 2 * D] rows w | h -- the same refusals)
         # an Adam-layout table ([R, 3 * D] fp32 rows w | m | v; the FusedAdam object is what says so): what it does not
         # take is refused here, before any kernel has run
         fused_sgd.check(weight)
@@ -1004,7 +1103,8 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
                           per_sample_weights is not None and per_sample_weights.requires_grad
                           and torch.is_grad_enabled())):
             if on:
-                raise NotImplementedError(f"{what} with an Adam-layout table")
+                raise NotImplementedError(f"{what} with an {'Adagrad' if fused_sgd.layout == 'adagrad' else 'Adam'}"
+                                          "-layout table")
         if isinstance(fused_sgd.lr, torch.Tensor) and check_lr(fused_sgd.lr).device != weight.device:
             raise ValueError(f"the learning-rate tensor is on {fused_sgd.lr.device}, the weight on "
                              f"{weight.device}: the kernels read it from device memory")

@@ -124,6 +124,12 @@ def parse_args(argv=None):
                         "CachedEmbeddingBag(fused_optimizer='partial_rowwise_adam')): the first moment travels in the "
                         "row, the second moment is one fp32 per table row in device memory -- rows of 2 * D floats "
                         "instead of 3 * D")
+    p.add_argument("--adagrad_elementwise", action="store_true",
+                   help="element-wise Adagrad for the embedding, fused into its backward (torch.optim.Adagrad's "
+                        "arithmetic, FBGEMM's EXACT_ADAGRAD: one sum of squares per ELEMENT, carried in the row -- "
+                        "CachedEmbeddingBag(fused_optimizer='adagrad') + set_fused_adagrad; rows of 2 * D floats), "
+                        "torch.optim.Adagrad for the dense part.  One process, an fp32 table, without --use_tablewise; "
+                        "not with --adagrad, --adam, --adam_partial_rowwise or --fused_sgd")
     p.add_argument("--adam_beta1", type=float, default=0.9, help="with --adam: beta1 of both Adams")
     p.add_argument("--adam_beta2", type=float, default=0.999, help="with --adam: beta2 of both Adams")
     p.add_argument("--eps", type=float, default=1e-8, help="with --adam: eps of both Adams")
@@ -194,7 +200,9 @@ _TABLE_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
 
 
 def _fused_optimizer(args) -> Optional[str]:
-    """the layout --adam builds the table with"""
+    """the layout --adam / --adagrad_elementwise builds the table with"""
+    if args.adagrad_elementwise:
+        return "adagrad"
     if not args.adam:
         return None
     return "partial_rowwise_adam" if args.adam_partial_rowwise else "adam"
@@ -399,7 +407,9 @@ def make_optimizer(model, args, device, world: int):
         embed.set_fused_adam(lr, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc,
                              **_decay(args), **_clip(args))
         return torch.optim.Adam(groups, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps), None
-    if args.adagrad:
+    if args.adagrad_elementwise:
+        embed.set_fused_adagrad(lr, accumulator=acc, **_decay(args), **_clip(args))
+    elif args.adagrad:
         embed.set_fused_rowwise_adagrad(lr, deterministic=args.adagrad_deterministic, accumulator=acc, **_decay(args),
                                         **_clip(args))
     elif args.fused_sgd:
@@ -407,8 +417,9 @@ def make_optimizer(model, args, device, world: int):
     else:
         groups.insert(0, {"params": list(model.sparse_modules.parameters()), "lr": args.learning_rate, "lr_scale": 1})
     if lr_t is not None:
-        return DenseStep(groups[0]["params"], lr_t, adagrad=args.adagrad), lr_t
-    return (torch.optim.Adagrad(groups) if args.adagrad else torch.optim.SGD(groups)), None
+        return DenseStep(groups[0]["params"], lr_t, adagrad=args.adagrad or args.adagrad_elementwise), lr_t
+    adagrad = args.adagrad or args.adagrad_elementwise
+    return (torch.optim.Adagrad(groups) if adagrad else torch.optim.SGD(groups)), None
 
 
 class LrChange:
@@ -436,6 +447,8 @@ class LrChange:
         if args.adam:
             self.embed.set_fused_adam(new, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc,
                                       **_decay(args), **_clip(args))
+        elif args.adagrad_elementwise:
+            self.embed.set_fused_adagrad(new, accumulator=acc, **_decay(args), **_clip(args))
         elif args.adagrad:
             self.embed.set_fused_rowwise_adagrad(new, deterministic=args.adagrad_deterministic, accumulator=acc,
                                                  **_decay(args), **_clip(args))
@@ -507,7 +520,8 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None, lr_
     embed = model.sparse_modules.embed
     layout = None
     if args.window_keys:
-        if not ((args.fused_sgd or args.adagrad or args.adam) and args.fold_hook) or world > 1:
+        if not ((args.fused_sgd or args.adagrad or args.adam or args.adagrad_elementwise) and args.fold_hook) \
+                or world > 1:
             raise ValueError("--window_keys needs --fused_sgd (or --adagrad, or --adam) --fold_hook (one process)")
         F = model.sparse_modules.sparse_feature_num
         offsets = torch.arange(F * args.batch_size + 1, dtype=torch.int32, device=device)     # one id per bag (KJT lengths = 1)
@@ -519,7 +533,8 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None, lr_
     train.window = win
     graphed = None
     train.graph_captures = 0
-    if args.graph_step and (world > 1 or not ((args.fused_sgd or args.adagrad or args.adam) and args.fold_hook)):
+    if args.graph_step and (world > 1 or not ((args.fused_sgd or args.adagrad or args.adam or args.adagrad_elementwise)
+                                              and args.fold_hook)):
         raise ValueError("--graph_step needs --fused_sgd (or --adagrad) --fold_hook and one process (DDP's bucket hooks "
                          "and the sparse "
                          "COO gradient of the unfused path are not captured)")
@@ -675,11 +690,12 @@ def check_embed_weight_decay(args):
     wd = check_weight_decay(args.embed_weight_decay, args.embed_weight_decay_mode)
     if not wd:
         return
-    if not (args.adagrad or args.adam or args.fused_sgd):
+    if not (args.adagrad or args.adam or args.fused_sgd or args.adagrad_elementwise):
         raise ValueError("--embed_weight_decay decays the rows inside a fused update: pass --adagrad, --adam or "
                          "--fused_sgd")
     table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
-    check_weight_decay_path("adam" if args.adam else "rowwise_adagrad" if args.adagrad else "sgd", table, wd,
+    in_row = args.adam or args.adagrad_elementwise             # (the state travels in the row: the Adam entries' rules)
+    check_weight_decay_path("adam" if in_row else "rowwise_adagrad" if args.adagrad else "sgd", table, wd,
                             bool(args.adagrad_deterministic))
 
 
@@ -689,19 +705,20 @@ def check_embed_grad_clip(args):
     clip = check_grad_clip(args.embed_grad_clip, args.embed_grad_clip_mode)
     if clip is None:
         return
-    if not (args.adagrad or args.adam or args.fused_sgd):
+    if not (args.adagrad or args.adam or args.fused_sgd or args.adagrad_elementwise):
         raise ValueError("--embed_grad_clip clips a row's gradient inside a fused update: pass --adagrad, --adam or "
                          "--fused_sgd")
     table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
-    check_grad_clip_path("adam" if args.adam else "rowwise_adagrad" if args.adagrad else "sgd", table, clip,
+    in_row = args.adam or args.adagrad_elementwise
+    check_grad_clip_path("adam" if in_row else "rowwise_adagrad" if args.adagrad else "sgd", table, clip,
                          bool(args.adagrad_deterministic))
 
 
 def check_step_accumulator(args):
     """--step_accumulator: refused here, before a device is touched, with the library's own refusals"""
     from cachedembedding_amd.functional import check_accumulator
-    if args.adam:
-        return                                      # (both accumulators serve Adam)
+    if args.adam or args.adagrad_elementwise:
+        return                                      # (both accumulators serve the updates whose state is in the row)
     if not (args.adagrad or args.fused_sgd):
         raise ValueError("--step_accumulator sizes the accumulator of a fused update: pass --adagrad, or --fused_sgd "
                          "with a 16-bit --table_dtype")
@@ -745,6 +762,19 @@ def main(argv=None):
                                       "classes do not take a q4 table)")
     if args.adam_partial_rowwise and not args.adam:
         raise ValueError("--adam_partial_rowwise chooses the layout of --adam: pass --adam with it")
+    if args.adagrad_elementwise:
+        if args.adagrad or args.adam or args.fused_sgd:
+            raise ValueError("--adagrad_elementwise takes the place of --adagrad, of --adam and of --fused_sgd: pass one "
+                             "of them")
+        if world > 1 or args.use_tablewise:
+            raise NotImplementedError("--adagrad_elementwise is implemented for one process without --use_tablewise "
+                                      "(the sharded classes do not take a table whose rows carry optimizer state)")
+        if args.table_dtype != "fp32":
+            raise NotImplementedError("--adagrad_elementwise needs --table_dtype fp32: the rows carry fp32 sums of "
+                                      "squares")
+        if args.use_sparse_embed_grad:
+            raise NotImplementedError("--adagrad_elementwise with --use_sparse_embed_grad: the fused update hands torch "
+                                      "no gradient")
     if args.adam:
         if args.adagrad or args.fused_sgd:
             raise ValueError("--adam takes the place of --adagrad and of --fused_sgd: pass one of them")

@@ -871,6 +871,72 @@ int ce_bag_backward_pradam_src_clip(float* weight, int64_t num_rows, int32_t dim
                                     int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int64_t* step,
                                     int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
+/* Element-wise Adagrad with its state carried in the row, layout `adagrad` (additions to API 6; torch.optim.Adagrad,
+ * FBGEMM's EXACT_ADAGRAD).  Row-wise Adagrad (ce_bag_backward_rowwise_adagrad*) keeps ONE sum of squares per row; this
+ * is the optimizer it approximates, with one per element, and a state as large as the table travels in the row as
+ * Adam's moments do.  An fp32 table only.  A row of `dim` elements is 2 * dim floats:
+ *   w[0 .. dim) | h[dim .. 2 dim)                             (weights, sums of squared gradients)
+ * The dim rule and the alignment are the Adam layout's (dim % 4 == 0, 4 <= dim <= 1024, the table 16-byte aligned;
+ * vector lanes only; the cache op is driven with embedding_dim = 2 * dim).  `weight` is [num_rows, 2 * dim] in every
+ * entry below; `dim` stays D.
+ *
+ * ce_host_fill_uniform_adagrad is ce_host_fill_uniform_pradam with every h element = init_acc (torch's
+ * initial_accumulator_value) instead of zero: the same w parts, a result that does not depend on `threads`.
+ * init_acc < 0 or NaN is CE_ERR_INVALID, before the dim rule (CE_ERR_UNSUPPORTED).
+ *
+ * ce_bag_forward_adagrad / ce_bag_forward_src_keys_adagrad take the lists of ce_bag_forward_pradam /
+ * _src_keys_pradam and ARE those entries: a row two parts wide whose first part is read.  Bit-equal to the fp32
+ * sibling's result over a contiguous copy of the w parts; the same refusals in the same order.
+ *
+ * ce_bag_backward_adagrad / ce_bag_backward_adagrad_src take the lists of ce_bag_backward_adam_clip / _adam_src_clip
+ * with `double lr_decay` in place of `double beta1, double beta2`: decay and clip are in from the start.  lr / lr_dev,
+ * `step`, the accumulators, the workspace (ce_bag_backward_adagrad_workspace = ce_bag_backward_adam_workspace) and its
+ * zero-fill contract, the mark rule, capture safety, no host synchronisation and no allocation are the Adam entries'.
+ * The arithmetic, fp32 with every operation rounded on its own (no contraction), for every UNIQUE row the call names, g
+ * its folded gradient of the call, t the step count after the call's first launch added 1, lr the by-value rate or
+ * *lr_dev as read when the kernels run:
+ *     clr_d = (double)lr / (1.0 + (double)(t - 1) * lr_decay)                            fp64, on the device
+ *     clr   = (float)clr_d
+ *     g     = clip(g)                                                                    as in the _clip entries, first
+ *     h  = g                                                                             no decay
+ *     h  = g + weight_decay * w                                                          CE_WD_L2
+ *     w  = w * f, h = g ; f = (float)(1.0 - clr_d * (double)weight_decay)                CE_WD_DECOUPLED
+ *     s' = s + h * h                                                                     per element
+ *     w' = w - clr * (h / (sqrtf(s') + eps))                                             per element
+ *   With lr_decay == 0, clr == lr and f is the _wd entries' factor.  A replayed graph follows *lr_dev and *step in both
+ *   clr and f.
+ *   - Rows no covered lookup names keep w and s bit for bit.  Lookups outside [0, num_rows) and lookups no bag covers
+ *     take no part and flag nothing.  A row named only by zero-weight lookups has g = 0: without decay s + 0 and w - 0
+ *     leave its bits as they were.  eps == 0 on a zero state gives NaN (0 / 0), as in torch.  Given the same folded
+ *     gradient both accumulators write the same bits: no reduction across lanes outside the row-norm clip.
+ *   - Refused before the first launch, in the Adam entries' order: step == NULL first; then the accumulator code, the
+ *     decay's and the clip's checks; lr_decay < 0 or NaN, eps < 0, lr < 0 (CE_ERR_INVALID); act_dtype; the dim rule
+ *     (CE_ERR_UNSUPPORTED); null pointers, sizes, alignment, workspace.  nnz == 0 (or num_bags == 0) returns after the
+ *     checks with no launch: it does not count a step.
+ * Not built: 16-bit state or tables, the sorted (deterministic) fold, a scalar lane form. */
+int ce_host_fill_uniform_adagrad(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed,
+                                 float init_acc, int threads);
+int ce_bag_forward_adagrad(const float* weight, int64_t num_rows, int32_t dim,
+                           const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                           int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                           int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
+int ce_bag_forward_src_keys_adagrad(const float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                    const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+size_t ce_bag_backward_adagrad_workspace(int64_t num_rows, int64_t nnz, int32_t dim, int32_t accumulator);
+int ce_bag_backward_adagrad(float* weight, int64_t num_rows, int32_t dim,
+                            const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                            int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                            int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                            const uint64_t* presorted, double lr_decay, float lr, const float* lr_dev, float eps,
+                            float weight_decay, int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                            int64_t* step, int32_t accumulator, void* workspace, size_t workspace_bytes,
+                            ce_stream_t stream);
+int ce_bag_backward_adagrad_src(float* weight, int64_t num_rows, int32_t dim, int64_t nnz,
+                                const void* grad_out, int32_t act_dtype, const uint64_t* src_keys,
+                                double lr_decay, float lr, const float* lr_dev, float eps, float weight_decay,
+                                int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int64_t* step,
+                                int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+
 /* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
  * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
  * A row of `dim` elements is 16 + dim bytes:
