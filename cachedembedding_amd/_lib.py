@@ -136,6 +136,11 @@ _ADAM_CLIP_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD
     [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
 # element-wise Adagrad: the clipped Adam tail with lr_decay in the betas' place
 _ELEMENTWISE_TAIL = _KEYS + [c_double] + _ADAM_CLIP_TAIL[3:]
+# the sorted (deterministic) in-row updates: the clipped lists without the keys and without the accumulator --
+# beta1, beta2 (or lr_decay), lr, lr_dev, eps, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode, step, workspace,
+# workspace_bytes, stream
+_ADAM_SORTED_TAIL = _ADAM_CLIP_TAIL[1:11] + _ADAM_CLIP_TAIL[12:]
+_ELEMENTWISE_SORTED_TAIL = [c_double] + _ADAM_SORTED_TAIL[2:]
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -246,6 +251,11 @@ SIGNATURES = {
     "ce_bag_backward_adagrad_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
     "ce_bag_backward_adagrad": (c_int, _BAG + _ACT + _ELEMENTWISE_TAIL),
     "ce_bag_backward_adagrad_src": (c_int, _SRC + _ACT + _ELEMENTWISE_TAIL),
+    # the deterministic, accumulator-free updates of the three in-row layouts: slots + offsets, no keys, no accumulator
+    "ce_bag_backward_in_row_sorted_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
+    "ce_bag_backward_adam_sorted": (c_int, _BAG + _ACT + _ADAM_SORTED_TAIL),
+    "ce_bag_backward_pradam_sorted": (c_int, _BAG + _ACT + _ROW_MOMENT + _ADAM_SORTED_TAIL),
+    "ce_bag_backward_adagrad_sorted": (c_int, _BAG + _ACT + _ELEMENTWISE_SORTED_TAIL),
     # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
     "ce_q8_row_bytes": (c_size_t, [c_int32]),
     "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),

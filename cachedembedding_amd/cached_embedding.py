@@ -402,7 +402,10 @@ class CachedEmbeddingBag(nn.Module):
         table and in the cache, `.exp_avg` / `.exp_avg_sq` after flush(); the step count is `.adam_step` (device).
         lr=None turns the update off (moments and step count are kept; a backward is then a RuntimeError).  lr may be
         a tensor, as in set_fused_sgd.  accumulator: "step" (default) or "cache" -- the size of the fp32 accumulator the
-        step's gradient is folded into; both write the same bits given the same folded gradient.  weight_decay with
+        step's gradient is folded into; both write the same bits given the same folded gradient -- or "sorted": no
+        accumulator and no atomics, the step's lookups sorted by slot and every row's gradient folded in lookup order,
+        so that two runs of a job agree bit for bit whatever the cache holds (this, not
+        deterministic=True, is the switch of the deterministic fold here).  weight_decay with
         weight_decay_mode "l2" is torch.optim.Adam(weight_decay=), with "decoupled" torch.optim.AdamW, both lazy: the
         rows a step looks up decay once, at that step (functional.FusedAdam).  grad_clip / grad_clip_mode ("value" or
         "row_norm"; functional.check_grad_clip): the row's folded gradient is clipped before the decay and the moments
@@ -417,8 +420,8 @@ class CachedEmbeddingBag(nn.Module):
             raise ValueError(f"lr={lr!r}: must be >= 0")
         wd = _checked_weight_decay(self, "adam", lr, False, weight_decay, weight_decay_mode)
         clip = _checked_grad_clip(self, "adam", lr, False, grad_clip, grad_clip_mode)
-        self.fused_adam.set(betas, eps, accumulator, deterministic, weight_decay=wd,       # (deterministic=True: not
-                            weight_decay_mode=weight_decay_mode, grad_clip=clip,           # implemented)
+        self.fused_adam.set(betas, eps, accumulator, deterministic, weight_decay=wd,       # (deterministic=True: refused;
+                            weight_decay_mode=weight_decay_mode, grad_clip=clip,           # accumulator="sorted")
                             grad_clip_mode=grad_clip_mode)
         self.fused_adam.lr = lr
 
@@ -429,7 +432,8 @@ class CachedEmbeddingBag(nn.Module):
         EXACT_ADAGRAD) to the cache rows inside backward.  Needs a module built with fused_optimizer="adagrad": the sums
         of squared gradients are part of every row, in the host table and in the cache, `.state_sum` after flush(); the
         step count lr_decay reads is `.adagrad_step` (device).  lr=None turns the update off (state and step count are
-        kept; a backward is then a RuntimeError).  lr may be a tensor, as in set_fused_sgd.  accumulator, weight_decay
+        kept; a backward is then a RuntimeError).  lr may be a tensor, as in set_fused_sgd.  accumulator ("sorted"
+        included: the deterministic fold), weight_decay
         ("l2": torch.optim.Adagrad(weight_decay=); "decoupled": w is scaled by 1 - clr * weight_decay first, clr the
         decayed rate) and grad_clip as in set_fused_adam (functional.FusedAdagrad).  Exclusive with the other
         set_fused_*: an Adagrad-layout module refuses those, every other module refuses this."""

@@ -37,6 +37,9 @@
 // second reduction, not k^2 * ss.  Clipping does not change which rows a call names -- the mark rule depends on the
 // decay alone -- and a slot whose momentum or v index lies outside its array is still untouched.  clip_row is the one
 // spelling, so a row looked up once in a call gets the same bits from all three folds.
+// The three in-row arithmetics have the deterministic fold as well (ce_bag_backward_adam_sorted / _pradam_sorted /
+// _adagrad_sorted): k_in_row_fold folds every chunk into a partial row, k_in_row_apply hands a row's
+// whole gradient to update_row -- no copy of the update there.
 #include "ce_common.h"
 
 namespace ce {
@@ -979,6 +982,151 @@ __global__ __launch_bounds__(256) void k_compact_apply(CompactArgs a) {
     update_row<VT, WT, NCH, STOCH, ADAM, WD, ROWV, CLIP, ELEM>(a.u, lr, key, (int64_t)a.list[u], g, gl, G, a.adagrad,
                                                                f, a.clip);
     zero_row<VT, NCH>(A + u * a.u.rowlen, gl, G, a.u.rowlen);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Deterministic, accumulator-free form for the tables that carry their state in the row (ce_bag_backward_adam_sorted /
+// _pradam_sorted / _adagrad_sorted).  The fold is 3.5's, to the letter: the sort, chunks of
+// CE_SORTED_CHUNK positions counted from the start of the run, each folded sequentially from zero, the partial rows
+// added in ascending chunk order.  The update is update_row's -- the arms the atomic forms run -- so a row gets the bits
+// of CE_ACC_CACHE / CE_ACC_STEP given the same folded gradient.  The work is split differently from 3.5's pair:
+//   1. k_count_step: the caller's step count += 1, the call's first launch;
+//   2. sorted_rows(covered_only): a lookup no bag covers heads nothing, as k_mark_slots_covered flags nothing for it;
+//   3. k_in_row_fold ONLY folds: every chunk, the only chunk of a short run included, goes to a partial row;
+//   4. k_in_row_apply: the head of every run adds its partial rows and calls update_row once.
+// k_sorted_fold folds AND applies, and at NCH = 4 it holds every scalar register there is; the in-row arms bring more
+// uniforms (the step size, omb1, omb2, eps, f, the clip).  Here no kernel holds both sets.  The price: the chunk that
+// starts at sorted position p takes partial row p -- nnz rows of D floats, where 3.5 needs 2 * ceil(nnz / 64) -- and a
+// row looked up once pays one write and one read of D floats.  The partial rows are D floats wide whatever the layout.
+
+__global__ void k_count_step(unsigned long long* step) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *step = *step + 1;
+}
+
+struct InRowSortedArgs {
+  UpdateArgs u;                // k_in_row_apply only
+  const void* grad_out;        // of AT
+  float* partials;             // [nnz, D]: row p = the chunk that starts at sorted position p
+  const int32_t* rows_sorted;
+  const int32_t* lookup_sorted;
+  const int32_t* bag_of;
+  const void* offsets;
+  const float* psw;
+  int64_t nnz;
+  int64_t num_bags;
+  int32_t num_rows;
+  int32_t rowlen, g_log2, off64, include_last, mode, hookF, hookB;
+  RowClip clip;                // the CLIP = true instantiations of k_in_row_apply only
+};
+
+// k_sorted_fold's walk and fold loop; every chunk is written to its partial row and nothing is applied
+template <typename AT, int NCH>
+__global__ __launch_bounds__(256) void k_in_row_fold(InRowSortedArgs a) {
+  using VT = f32x4;
+  using TA = Act<AT, VT>;
+  const int G = 1 << a.g_log2;
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> a.g_log2;
+  const int gl = lane & (G - 1);
+  const int ngw = 64 >> a.g_log2;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const typename TA::V* GO = (const typename TA::V*)a.grad_out;
+  VT* P = (VT*)a.partials;
+  const int32_t* __restrict__ rows = a.rows_sorted;
+  for (int64_t base = wave * 64; base < a.nnz; base += nwaves * 64) {
+    const int64_t mine = base + lane;
+    bool head = false;
+    if (mine < a.nnz) {
+      const int32_t row = rows[mine];
+      // ignored and uncovered lookups carry the key num_rows and lie behind every valid row: they start nothing
+      if ((uint32_t)row < (uint32_t)a.num_rows)
+        head = ((mine - run_start(rows, mine, row)) & (CE_SORTED_CHUNK - 1)) == 0;
+    }
+    unsigned long long m = __ballot(head);
+    while (m) {
+      unsigned long long mm = m;
+      for (int k = 0; k < q; ++k) mm &= mm - 1;          // this group's chunk: the q-th lowest head
+      for (int k = 0; k < ngw; ++k) m &= m - 1;
+      if (mm == 0) continue;
+      const int64_t p = base + (__ffsll((long long)mm) - 1);
+      const int32_t row = rows[p];
+      VT g[NCH];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) g[c] = vzero<VT>();
+      const int64_t end = p + CE_SORTED_CHUNK < a.nnz ? p + CE_SORTED_CHUNK : a.nnz;
+      for (int64_t t = p; t < end && rows[t] == row; ++t) {
+        const int32_t j = a.lookup_sorted[t];
+        const int64_t bag = a.bag_of[j];
+        if (bag < 0 || bag >= a.num_bags) continue;        // (covered_only: no such lookup carries a valid row)
+        float sc = a.psw ? a.psw[j] : 1.f;
+        if (a.mode == CE_MODE_MEAN) {
+          const int64_t lo = a.off64 ? ((const int64_t*)a.offsets)[bag] : ((const int32_t*)a.offsets)[bag];
+          const int64_t hi = (a.include_last || bag + 1 < a.num_bags)
+                                 ? (a.off64 ? ((const int64_t*)a.offsets)[bag + 1] : ((const int32_t*)a.offsets)[bag + 1])
+                                 : a.nnz;
+          if (hi - lo > 1) sc = sc / (float)(hi - lo);
+        }
+        int64_t orow = bag;
+        if (a.hookF) {
+          const int64_t f = bag / a.hookB;
+          orow = (bag - f * a.hookB) * a.hookF + f;
+        }
+        {
+#pragma clang fp contract(off)      // the specification: the term s_j g_j is rounded before it is added
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            const int idx = gl + c * G;
+            if (idx < a.rowlen) {
+              const VT v = TA::up(GO[orow * a.rowlen + idx]);
+              g[c] = (sc == 1.f) ? g[c] + v : g[c] + v * sc;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int idx = gl + c * G;
+        if (idx < a.rowlen) P[p * a.rowlen + idx] = g[c];
+      }
+    }
+  }
+}
+
+// the head of every run of a valid row adds the run's partial rows in ascending chunk order and updates the row once
+template <int NCH, bool ADAM, bool WD, bool ROWV, bool CLIP, bool ELEM>
+__global__ __launch_bounds__(256) void k_in_row_apply(InRowSortedArgs a) {
+  using VT = f32x4;
+  const LaneGroup l = lane_group(a.g_log2);
+  const VT* P = (const VT*)a.partials;
+  const int32_t* __restrict__ rows = a.rows_sorted;
+  const float lr = ELEM ? (float)adagrad_rate(a.u) : adam_step_size(a.u);
+  const float f = !WD ? 1.f
+                      : (ELEM ? adagrad_decay_factor(adagrad_rate(a.u), a.u.wd)
+                              : decay_factor(learning_rate(a.u), a.u.wd));
+  for (int64_t base = l.wave * 64; base < a.nnz; base += l.nwaves * 64) {
+    const int64_t mine = base + l.lane;
+    bool head = false;
+    if (mine < a.nnz) {
+      const int32_t row = rows[mine];
+      head = (uint32_t)row < (uint32_t)a.num_rows && (mine == 0 || rows[mine - 1] != row);
+    }
+    for_each_flagged(head, l, [=](int i) {
+      const int64_t p = base + i;
+      const int32_t row = rows[p];
+      VT g[NCH];
+      load_row(g, P + p * a.rowlen, l.gl, l.G, a.rowlen);
+      for (int64_t t = p + CE_SORTED_CHUNK; t < a.nnz && rows[t] == row; t += CE_SORTED_CHUNK) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int idx = l.gl + c * l.G;
+          if (idx < a.rowlen) g[c] = g[c] + P[t * a.rowlen + idx];
+        }
+      }
+      update_row<VT, float, NCH, false, ADAM, WD, ROWV, CLIP, ELEM>(a.u, lr, 0, (int64_t)row, g, l.gl, l.G, false, f,
+                                                                    a.clip);
+    });
   }
 }
 
@@ -2241,4 +2389,145 @@ extern "C" int ce_bag_backward_adagrad_src(float* weight, int64_t num_rows, int3
                                     weight_decay, weight_decay_mode, RowClip{grad_clip, grad_clip_mode}, step, workspace,
                                     workspace_bytes);
   return in_row_src(c, src_keys, accumulator, stream);
+}
+
+// ---- deterministic, accumulator-free updates of the in-row layouts: count the step, sort, fold,
+// apply.  The lists are those of ce_bag_backward_adam_clip / _pradam_clip / _adagrad without `presorted` and
+// `accumulator`.
+
+extern "C" size_t ce_bag_backward_in_row_sorted_workspace(int64_t num_rows, int64_t nnz, int32_t dim) {
+  (void)num_rows;
+  if (nnz < 0 || nnz >= (int64_t)INT32_MAX || dim <= 0) return 0;
+  const int64_t n = nnz < 1 ? 1 : nnz;
+  return al256(sorted_rows_bytes(n)) + al256((size_t)n * (size_t)dim * 4);
+}
+
+// Everything the three entries refuse, from the arguments alone, before the first launch and before any HIP call; the
+// order is the header's.  Then: the step, the sort, the fold, the apply.
+static int in_row_sorted(const UpdateCall& c, const SlotLookups& L, ce_stream_t stream) {
+  CE_REQUIRE(c.step, CE_ERR_INVALID, "step: null device pointer");
+  int rc = wd_check(c.wd, c.wd_mode);
+  if (rc) return rc;
+  rc = clip_check(c.clip, c.clip_mode);
+  if (rc) return rc;
+  CE_REQUIRE(c.beta1 >= 0.0 && c.beta1 < 1.0 && c.beta2 >= 0.0 && c.beta2 < 1.0, CE_ERR_INVALID,
+             "beta1 and beta2 must lie in [0, 1)");
+  CE_REQUIRE(c.lr_decay >= 0.0, CE_ERR_INVALID, "lr_decay must be >= 0");       // (a NaN fails it; Adam passes 0)
+  CE_REQUIRE(c.eps >= 0.f, CE_ERR_INVALID, "eps must be >= 0");
+  CE_REQUIRE(c.lr_dev || c.lr >= 0.f, CE_ERR_INVALID, "lr must be >= 0");
+  CE_REQUIRE_ACT(c.act);
+  CE_REQUIRE(c.weight && c.grad_out && c.workspace, CE_ERR_INVALID, "null pointer");
+  CE_REQUIRE(!c.rowv() || (c.momentum && c.momentum_rows > 0), CE_ERR_INVALID,
+             "partial row-wise Adam needs its second moment: v, v_rows > 0");
+  CE_REQUIRE(c.dim > 0, CE_ERR_INVALID, "dim must be positive");
+  CE_REQUIRE(c.num_rows > 0 && c.num_rows < (int64_t)INT32_MAX, CE_ERR_INVALID, "num_rows out of range");
+  CE_REQUIRE(c.nnz >= 0 && c.nnz < (int64_t)INT32_MAX, CE_ERR_INVALID, "nnz out of range");
+  CE_REQUIRE(L.num_bags >= 0 && L.num_bags < (int64_t)INT32_MAX - 64, CE_ERR_INVALID, "num_bags out of range");
+  CE_REQUIRE(L.mode == CE_MODE_SUM || L.mode == CE_MODE_MEAN, CE_ERR_UNSUPPORTED, "mode must be sum or mean");
+  CE_REQUIRE(L.hookF >= 0 && L.hookF < (int64_t)INT32_MAX && (L.hookF == 0 || L.num_bags % L.hookF == 0),
+             CE_ERR_INVALID, "hook_features must divide num_bags");
+  CE_REQUIRE(al16(c.weight) && (((uintptr_t)c.step) & 7) == 0 && act_aligned(c.grad_out, c.act), CE_ERR_INVALID,
+             "an in-row table must be 16-byte aligned, step 8-byte aligned and grad_out on the vector boundary");
+  CE_REQUIRE((((uintptr_t)c.workspace) & 255) == 0, CE_ERR_INVALID, "workspace must be 256-byte aligned");
+  CE_REQUIRE(c.workspace_bytes >= ce_bag_backward_in_row_sorted_workspace(c.num_rows, c.nnz, c.dim), CE_ERR_INVALID,
+             "workspace too small");
+  CE_REQUIRE_ADAM_DIM(c.dim);
+  RowGeom r;
+  rc = row_geometry(c.dim, true, r);
+  if (rc) return rc;
+  if (L.num_bags == 0 || c.nnz == 0) return CE_OK;
+  CE_REQUIRE(L.indices && L.offsets, CE_ERR_INVALID, "null pointer");
+
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_count_step, dim3(1), dim3(64), 0, s, c.step);
+  char* sort_ws = (char*)c.workspace;
+  float* partials = (float*)(sort_ws + al256(sorted_rows_bytes(c.nnz)));
+  SortedRows sr{};
+  rc = sorted_rows(L.indices, c.nnz, c.num_rows, L.offsets, L.off64, L.num_bags, L.include_last, sort_ws, s, sr, true);
+  if (rc) return rc;
+  InRowSortedArgs a{};
+  a.u = update_args(c, r, c.step);
+  a.grad_out = c.grad_out;
+  a.partials = partials;
+  a.rows_sorted = sr.rows;
+  a.lookup_sorted = sr.lookups;
+  a.bag_of = sr.bag_of;
+  a.offsets = L.offsets;
+  a.psw = L.psw;
+  a.nnz = c.nnz;
+  a.num_bags = L.num_bags;
+  a.num_rows = (int32_t)c.num_rows;
+  a.rowlen = r.rowlen;
+  a.g_log2 = r.g_log2;
+  a.off64 = L.off64;
+  a.include_last = L.include_last;
+  a.mode = L.mode;
+  a.hookF = (int)L.hookF;
+  a.hookB = L.hookF ? (int)(L.num_bags / L.hookF) : 0;
+  a.clip = RowClip{c.clip, c.clip_mode};
+  const dim3 g(grid_for(cdiv(c.nnz, 64), 4)), b(256);
+  for_vec_lanes(r.nch, [&](auto l) {
+    constexpr int N = decltype(l)::NCH;
+    for_act(c.act, [&](auto at) {
+      hipLaunchKernelGGL((k_in_row_fold<typename decltype(at)::AT, N>), g, b, 0, s, a);
+    });
+    for_decay(c.decay(), c.clipped(), [&](auto d) {
+      constexpr bool WD = decltype(d)::WD, CL = decltype(d)::CLIP;
+      if (c.elem()) hipLaunchKernelGGL((k_in_row_apply<N, false, WD, false, CL, true>), g, b, 0, s, a);
+      else if (c.rowv()) hipLaunchKernelGGL((k_in_row_apply<N, true, WD, true, CL, false>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_in_row_apply<N, true, WD, false, CL, false>), g, b, 0, s, a);
+    });
+  });
+  CE_LAUNCH_CHECK();
+  return CE_OK;
+}
+
+extern "C" int ce_bag_backward_adam_sorted(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                           int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                           int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                           int64_t hook_features, const void* grad_out, int32_t act_dtype, double beta1,
+                                           double beta2, float lr, const float* lr_dev, float eps, float weight_decay,
+                                           int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                           int64_t* step, void* workspace, size_t workspace_bytes, ce_stream_t stream) {
+  const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, nullptr,
+                                 RowClip{grad_clip, grad_clip_mode});
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, nullptr};
+  return in_row_sorted(c, L, stream);
+}
+
+extern "C" int ce_bag_backward_pradam_sorted(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                             int64_t nnz, const void* offsets, int32_t offsets_are_i64, int64_t num_bags,
+                                             int32_t include_last_offset, const float* per_sample_weights, int32_t mode,
+                                             int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                             const int32_t* row_of_slot, float* v, int64_t v_rows, double beta1,
+                                             double beta2, float lr, const float* lr_dev, float eps, float weight_decay,
+                                             int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                             int64_t* step, void* workspace, size_t workspace_bytes,
+                                             ce_stream_t stream) {
+  const RowMoment rv{row_of_slot, v, v_rows};
+  const UpdateCall c = adam_call(weight, num_rows, dim, nnz, grad_out, act_dtype, beta1, beta2, lr, lr_dev, eps, step,
+                                 workspace, workspace_bytes, weight_decay, weight_decay_mode, &rv,
+                                 RowClip{grad_clip, grad_clip_mode});
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, nullptr};
+  return in_row_sorted(c, L, stream);
+}
+
+extern "C" int ce_bag_backward_adagrad_sorted(float* weight, int64_t num_rows, int32_t dim, const int64_t* indices,
+                                              int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                              int64_t num_bags, int32_t include_last_offset,
+                                              const float* per_sample_weights, int32_t mode, int64_t hook_features,
+                                              const void* grad_out, int32_t act_dtype, double lr_decay, float lr,
+                                              const float* lr_dev, float eps, float weight_decay,
+                                              int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                              int64_t* step, void* workspace, size_t workspace_bytes,
+                                              ce_stream_t stream) {
+  const UpdateCall c = adagrad_call(weight, num_rows, dim, nnz, grad_out, act_dtype, lr_decay, lr, lr_dev, eps,
+                                    weight_decay, weight_decay_mode, RowClip{grad_clip, grad_clip_mode}, step, workspace,
+                                    workspace_bytes);
+  const SlotLookups L{indices, offsets, offsets_are_i64, num_bags, include_last_offset, per_sample_weights, mode,
+                      hook_features, nullptr};
+  return in_row_sorted(c, L, stream);
 }

@@ -135,6 +135,7 @@ class _BagFn(torch.autograd.Function):
         mode, include_last, hook_features, sparse, fused, num_bags = ctx.args
         grad_out = grad_out.contiguous()
         adam = isinstance(fused, _IN_ROW)
+        partial = adam and fused.layout == "partial_rowwise_adam"
         if isinstance(fused, FusedAdagrad) and fused.lr is None:
             raise RuntimeError("backward through an Adagrad-layout table with no fused Adagrad set: an autograd gradient "
                                "in slot space over 2 * D columns means nothing (set_fused_adagrad(lr) first, or run the "
@@ -163,6 +164,25 @@ class _BagFn(torch.autograd.Function):
                 # Gradient clipping: the ce_*_clip entries, the clip and its mode directly behind the decay's
                 clip = fused.grad_clip is not None
                 decay = fused.weight_decay != 0.0 or clip
+                if fused.accumulator == "sorted":
+                    # the deterministic fold (ce_bag_backward_*_sorted): always from slots + offsets --
+                    # presorted keys of either kind are not needed and ignored --, decay and clip always in the list
+                    rate = (0.0 if lr_t else float(fused.lr), ptr(fused.lr) if lr_t else None, float(fused.eps),
+                            float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + \
+                        (fused.clip_args() if clip else (0.0, _lib.CE_CLIP_NONE)) + \
+                        (ptr(fused.step), ptr(ws), ws.numel(), stream_ptr())
+                    lookups = (ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last),
+                               ptr(psw), mode, hook_features, ptr(grad_out), act)
+                    if fused.layout == "adagrad":
+                        check(lib.ce_bag_backward_adagrad_sorted(*lookups, float(fused.lr_decay), *rate))
+                    elif partial:
+                        v = fused.exp_avg_sq
+                        check(lib.ce_bag_backward_pradam_sorted(*lookups, ptr(fused.row_of_slot), ptr(v), v.numel(),
+                                                                float(fused.betas[0]), float(fused.betas[1]), *rate))
+                    else:
+                        check(lib.ce_bag_backward_adam_sorted(*lookups, float(fused.betas[0]), float(fused.betas[1]),
+                                                              *rate))
+                    return (None,) * 14
                 if fused.layout == "adagrad":
                     # element-wise Adagrad (ce_bag_backward_adagrad*): one entry, decay and clip always in its list
                     # (weight_decay 0 and CE_CLIP_NONE: the kernels without them), lr_decay where Adam has its betas
@@ -611,6 +631,9 @@ def _workspace_w16(self, num_rows: int, dim: int, device) -> torch.Tensor:
 
 
 ACCUMULATORS = ("cache", "step")
+# the in-row layouts (FusedAdam, FusedAdagrad) also take "sorted": the deterministic fold, which has no accumulator
+# 
+IN_ROW_ACCUMULATORS = ACCUMULATORS + ("sorted",)
 
 
 def check_accumulator(optimizer: str, table_dtype, accumulator: str, deterministic: bool = False,
@@ -704,6 +727,13 @@ def refuse_weight_decay(who: Optional[str], weight_decay) -> None:
     if who and weight_decay:
         raise NotImplementedError(f"weight_decay is not implemented for {who}: its owner-side update is ce_rows_axpy, "
                                   "which has no per-row decay")
+
+
+def _workspace_in_row_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
+    """workspace of ce_bag_backward_adam_sorted / _pradam_sorted / _adagrad_sorted (sort arrays, one partial row per
+    lookup): nothing in it needs initialising"""
+    need = lib.ce_bag_backward_in_row_sorted_workspace(num_rows, nnz, dim)
+    return _cached_bytes(self, "_ws_sorted", need, device, zero=False)
 
 
 def _workspace_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
@@ -915,7 +945,9 @@ class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
 
     step: ONE int64 on the weight's device, zero before the first step; the first kernel of every backward adds 1 to it
     (a replayed graph counts on).  accumulator: "step" (the default: an fp32 accumulator of min(lookups of the step,
-    rows) rows) or "cache" (one row per row of the weight).  lr may be a tensor, as for FusedSGD (check_lr).
+    rows) rows), "cache" (one row per row of the weight) or "sorted" (no accumulator and no atomics -- the
+    step's lookups are sorted by slot and a row's gradient is folded in lookup order, so two runs of a job agree bit for
+    bit; presorted keys are not needed and ignored).  lr may be a tensor, as for FusedSGD (check_lr), "sorted" included.
 
     weight_decay, weight_decay_mode, lazy like the moments (the rows a step looks up decay once, in that step):
     "l2" is torch.optim.Adam(weight_decay=) -- g + weight_decay * w feeds both moments --, "decoupled" torch.optim.AdamW
@@ -930,7 +962,7 @@ class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
         v[r] += (1 - beta2) (mean_d (g_d g_d) - v[r]) ;  w -= lr c_t * m / (sqrt(v[r]) + eps)
     A slot whose row_of_slot lies outside [0, v_rows) is left alone."""
 
-    deterministic = False                                   # (the sorted fold has no Adam form)
+    deterministic = False                                   # (the sorted fold is accumulator="sorted" here)
     rounding, seed = "nearest", 0
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -948,20 +980,22 @@ class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
         self.step = step
         self._ws_step, self._ws_step_key = None, None
         self._ws = None
+        self._ws_sorted = None
 
     def set(self, betas, eps: float, accumulator: str, deterministic: bool = False, *, weight_decay: float = 0.0,
             weight_decay_mode: str = "l2", grad_clip: Optional[float] = None, grad_clip_mode: str = "value") -> None:
         wd = check_weight_decay(weight_decay, weight_decay_mode)
         clip = check_grad_clip(grad_clip, grad_clip_mode)
         if deterministic:
-            raise NotImplementedError("fused Adam with deterministic=True: the sorted fold has no Adam form")
+            raise NotImplementedError("fused Adam with deterministic=True: the deterministic (sorted) fold of an "
+                                      "Adam-layout table is accumulator='sorted'")
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas={tuple(betas)!r}: both must lie in [0, 1)")
         if not float(eps) >= 0.0:
             raise ValueError(f"eps={eps!r}: must be >= 0")
-        if accumulator not in ACCUMULATORS:
-            raise ValueError(f"accumulator={accumulator!r}: 'cache' or 'step'")
+        if accumulator not in IN_ROW_ACCUMULATORS:
+            raise ValueError(f"accumulator={accumulator!r}: 'cache', 'step' or 'sorted'")
         self.betas, self.eps, self.accumulator = (b1, b2), float(eps), accumulator
         self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
         self.grad_clip, self.grad_clip_mode = clip, grad_clip_mode
@@ -991,7 +1025,10 @@ class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
                                  "device")
 
     def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
-        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again
+        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again ("sorted": nothing
+        # in it needs initialising)
+        if self.accumulator == "sorted":
+            return _workspace_in_row_sorted(self, num_rows, nnz, dim, device)
         if self.accumulator == "step":
             return _workspace_step(self, num_rows, nnz, dim, device)
         need = lib.ce_bag_backward_adam_workspace(num_rows, nnz, dim, _lib.CE_ACC_CACHE)
@@ -1008,14 +1045,14 @@ class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
     Handing this object to embedding_bag is what says the weight has the layout, so the forward needs it too; lr=None
     leaves the forward working and makes a backward a RuntimeError.  The defaults are torch.optim.Adagrad's.
 
-    step, accumulator and a tensor lr: as for FusedAdam -- the step count is ONE int64 on the weight's device which the
+    step, accumulator ("sorted" included: the deterministic fold) and a tensor lr: as for FusedAdam -- the step count is ONE int64 on the weight's device which the
     first kernel of every backward adds 1 to, so a replayed graph follows it, and a tensor lr, in clr.
 
     weight_decay, weight_decay_mode, lazy (the rows a step looks up decay once, in that step): "l2" is
     torch.optim.Adagrad(weight_decay=) -- g + weight_decay * w takes the place of g --, "decoupled" scales w by
     1 - clr * weight_decay first.  grad_clip, grad_clip_mode (check_grad_clip): g is clipped first."""
 
-    deterministic = False                                   # (the sorted fold has no form for rows that carry state)
+    deterministic = False                                   # (the sorted fold is accumulator="sorted" here)
     rounding, seed = "nearest", 0
     layout, span = "adagrad", 2
 
@@ -1029,6 +1066,7 @@ class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
         self.step = step
         self._ws_step, self._ws_step_key = None, None
         self._ws = None
+        self._ws_sorted = None
 
     def set(self, eps: float, lr_decay: float, accumulator: str, deterministic: bool = False, *,
             weight_decay: float = 0.0, weight_decay_mode: str = "l2", grad_clip: Optional[float] = None,
@@ -1036,14 +1074,14 @@ class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
         wd = check_weight_decay(weight_decay, weight_decay_mode)
         clip = check_grad_clip(grad_clip, grad_clip_mode)
         if deterministic:
-            raise NotImplementedError("fused Adagrad with deterministic=True: the sorted fold has no form for rows that "
-                                      "carry their state")
+            raise NotImplementedError("fused Adagrad with deterministic=True: the deterministic (sorted) fold of an "
+                                      "Adagrad-layout table is accumulator='sorted'")
         if not float(eps) >= 0.0:
             raise ValueError(f"eps={eps!r}: must be >= 0")
         if not float(lr_decay) >= 0.0:
             raise ValueError(f"lr_decay={lr_decay!r}: must be >= 0")
-        if accumulator not in ACCUMULATORS:
-            raise ValueError(f"accumulator={accumulator!r}: 'cache' or 'step'")
+        if accumulator not in IN_ROW_ACCUMULATORS:
+            raise ValueError(f"accumulator={accumulator!r}: 'cache', 'step' or 'sorted'")
         self.eps, self.lr_decay, self.accumulator = float(eps), float(lr_decay), accumulator
         self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
         self.grad_clip, self.grad_clip_mode = clip, grad_clip_mode
@@ -1063,7 +1101,10 @@ class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
             raise ValueError("fused Adagrad needs its step count: one int64 element on the weight's device")
 
     def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
-        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again
+        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again ("sorted": nothing
+        # in it needs initialising)
+        if self.accumulator == "sorted":
+            return _workspace_in_row_sorted(self, num_rows, nnz, dim, device)
         if self.accumulator == "step":
             return _workspace_step(self, num_rows, nnz, dim, device)
         need = lib.ce_bag_backward_adagrad_workspace(num_rows, nnz, dim, _lib.CE_ACC_CACHE)

@@ -136,6 +136,11 @@ def parse_args(argv=None):
     p.add_argument("--adagrad_deterministic", action="store_true",
                    help="with --adagrad: fold a row's gradient in lookup order over the step's sorted lookups instead "
                         "of by atomics -- bit-reproducible, and without the [cache rows, D] fp32 accumulator")
+    p.add_argument("--embed_sorted_update", action="store_true",
+                   help="with --adam, --adam_partial_rowwise or --adagrad_elementwise: fold a row's gradient in lookup "
+                        "order over the step's sorted lookups instead of by atomics (accumulator='sorted') -- two runs "
+                        "of a job agree bit for bit; the rate is read from device memory, so --graph_step --change_lr "
+                        "work with it.  --adagrad has --adagrad_deterministic for this; not with --step_accumulator")
     p.add_argument("--step_accumulator", action="store_true",
                    help="with --adagrad, or with a 16-bit --table_dtype and --fused_sgd: the fused update's fp32 "
                         "accumulator has a row per lookup of a step at most instead of one per cache row "
@@ -393,11 +398,30 @@ class DenseStep:
         torch._foreach_sub_(self.params, torch._foreach_mul(grads, self.lr))
 
 
+def _accumulator(args) -> str:
+    """accumulator= of the embedding's fused update ("sorted": the in-row layouts' deterministic fold)"""
+    if args.embed_sorted_update:
+        return "sorted"
+    return "step" if args.step_accumulator else "cache"
+
+
+def check_embed_sorted_update(args):
+    """--embed_sorted_update: refused here, before a device is touched"""
+    if not args.embed_sorted_update:
+        return
+    if not (args.adam or args.adam_partial_rowwise or args.adagrad_elementwise):
+        raise ValueError("--embed_sorted_update is the deterministic fold of the updates whose state is in the row: pass "
+                         "--adam, --adam_partial_rowwise or --adagrad_elementwise (--adagrad has "
+                         "--adagrad_deterministic for this)")
+    if args.step_accumulator:
+        raise ValueError("--embed_sorted_update has no accumulator: not with --step_accumulator")
+
+
 def make_optimizer(model, args, device, world: int):
     """(optimizer, lr tensor or None): the embedding's fused update is switched on and the optimizer of everything else
     built.  --graph_step --change_lr: both read the rate from one device tensor (DenseStep, set_fused_*(tensor))."""
     embed = model.sparse_modules.embed
-    acc = "step" if args.step_accumulator else "cache"
+    acc = _accumulator(args)
     lr_t = None
     if args.change_lr and args.graph_step:
         lr_t = torch.full((1,), args.learning_rate, dtype=torch.float32, device=device)
@@ -443,7 +467,7 @@ class LrChange:
             return
         for g in self.optimizer.param_groups:
             g["lr"] = new * g.get("lr_scale", 1)
-        acc = "step" if args.step_accumulator else "cache"
+        acc = _accumulator(args)
         if args.adam:
             self.embed.set_fused_adam(new, betas=(args.adam_beta1, args.adam_beta2), eps=args.eps, accumulator=acc,
                                       **_decay(args), **_clip(args))
@@ -733,6 +757,7 @@ def main(argv=None):
         raise ValueError("--adagrad_deterministic chooses how --adagrad folds the gradient: pass --adagrad as well")
     if args.adagrad_deterministic and args.table_dtype != "fp32" and args.weight_rounding == "stochastic":
         raise NotImplementedError("--adagrad_deterministic rounds a 16-bit table to nearest: pass --weight_rounding nearest")
+    check_embed_sorted_update(args)
     if args.step_accumulator:
         check_step_accumulator(args)
     check_embed_weight_decay(args)

@@ -458,7 +458,9 @@ int ce_bag_backward_update_src_w16(void* weight, int32_t weight_dtype, int64_t n
  * from one call to the next).  No host synchronisation, no allocation, launch shapes fixed by the arguments
  * (capture-safe).  Everything that can be refused -- null pointers, sizes beyond 2^31, unknown dtype / optimizer /
  * rounding codes, stochastic rounding, a 16-bit table's dim rule or alignment, a workspace that is too small -- is
- * refused before the first launch. */
+ * refused before the first launch.
+ * The tables that carry their state in the row (Adam, partial row-wise Adam, element-wise Adagrad) have this fold in
+ * entries of their own: ce_bag_backward_adam_sorted / _pradam_sorted / _adagrad_sorted, further down. */
 #define CE_SORTED_CHUNK 64
 size_t ce_bag_backward_update_sorted_workspace(int64_t num_rows, int64_t nnz, int32_t dim);
 int ce_bag_backward_update_sorted(void* weight, int32_t weight_dtype, int64_t num_rows, int32_t dim,
@@ -615,7 +617,7 @@ int ce_bag_backward_update_src_lrdev(void* weight, int32_t weight_dtype, int64_t
  *     a workspace that is too small; then, for a call with lookups, what the covered pipeline refuses (null indices /
  *     offsets / keys, mean with per-sample weights, hook_features that does not divide num_bags).
  *   - nnz == 0 (or num_bags == 0) returns after those checks with no launch: it does not count a step.
- * Not built: 16-bit moments or tables, the sorted (deterministic) fold.  Weight decay (L2 as torch.optim.Adam's,
+ * Not built: 16-bit moments or tables.  The sorted (deterministic) fold: ce_bag_backward_adam_sorted below.  Weight decay (L2 as torch.optim.Adam's,
  * decoupled as torch.optim.AdamW's): ce_bag_backward_adam_wd / _adam_src_wd below. */
 int ce_host_fill_uniform_adam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed, int threads);
 int ce_bag_forward_adam(const float* weight, int64_t num_rows, int32_t dim,
@@ -755,7 +757,7 @@ int ce_bag_backward_adam_src_wd(float* weight, int64_t num_rows, int32_t dim, in
  *   - Refused before the first launch: what ce_bag_backward_adam_wd refuses, in its order, and v == NULL or
  *     v_rows <= 0 (CE_ERR_INVALID) directly behind its null-pointer check.  nnz == 0 (or num_bags == 0) returns after
  *     the checks with no launch: it does not count a step.
- * Not built: 16-bit moments or tables, the sorted (deterministic) fold, a scalar lane form. */
+ * Not built: 16-bit moments or tables, a scalar lane form.  (The sorted fold: ce_bag_backward_pradam_sorted.) */
 int ce_host_fill_uniform_pradam(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed, int threads);
 int ce_bag_forward_pradam(const float* weight, int64_t num_rows, int32_t dim,
                           const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
@@ -913,7 +915,7 @@ int ce_bag_backward_pradam_src_clip(float* weight, int64_t num_rows, int32_t dim
  *     decay's and the clip's checks; lr_decay < 0 or NaN, eps < 0, lr < 0 (CE_ERR_INVALID); act_dtype; the dim rule
  *     (CE_ERR_UNSUPPORTED); null pointers, sizes, alignment, workspace.  nnz == 0 (or num_bags == 0) returns after the
  *     checks with no launch: it does not count a step.
- * Not built: 16-bit state or tables, the sorted (deterministic) fold, a scalar lane form. */
+ * Not built: 16-bit state or tables, a scalar lane form.  (The sorted fold: ce_bag_backward_adagrad_sorted.) */
 int ce_host_fill_uniform_adagrad(float* dst, int64_t n_rows, int32_t dim, float lo, float hi, uint64_t seed,
                                  float init_acc, int threads);
 int ce_bag_forward_adagrad(const float* weight, int64_t num_rows, int32_t dim,
@@ -936,6 +938,64 @@ int ce_bag_backward_adagrad_src(float* weight, int64_t num_rows, int32_t dim, in
                                 double lr_decay, float lr, const float* lr_dev, float eps, float weight_decay,
                                 int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int64_t* step,
                                 int32_t accumulator, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+
+/* Deterministic, accumulator-free updates of the three in-row layouts (additions to API 6): what
+ * ce_bag_backward_update_sorted is to SGD and row-wise Adagrad, for the Adam layout (rows w | m | v), partial row-wise
+ * Adam (rows w | m, v per table row) and element-wise Adagrad (rows w | h).  Bit-reproducible, no atomics, a workspace
+ * proportional to the call's lookups.
+ *   ce_bag_backward_adam_sorted     the list of ce_bag_backward_adam_clip   without `presorted` and `accumulator`
+ *   ce_bag_backward_pradam_sorted   the list of ce_bag_backward_pradam_clip without `presorted` and `accumulator`
+ *   ce_bag_backward_adagrad_sorted  the list of ce_bag_backward_adagrad     without `presorted` and `accumulator`
+ * Decay and clip are always in the list; weight_decay 0 / CE_WD_NONE and CE_CLIP_NONE select the kernels without them.
+ *   - The fold is ce_bag_backward_update_sorted's, CE_SORTED_CHUNK = 64: the lookups stably sorted by slot; a run of
+ *     n <= 64 lookups folded strictly in lookup order in fp32 from zero, g = (...((s_0 g_0) + s_1 g_1) + ...), the term
+ *     the gradient row itself for s_j == 1 and otherwise the product rounded before it is added; s_j the per-sample
+ *     weight, 1 / len for mean (both together: their quotient); a 16-bit grad_out upcast exactly; a longer run cut into
+ *     chunks of 64 positions counted from the start of the run, each folded from zero, the partial rows added in
+ *     ascending chunk order.  Nothing depends on the grid, on the slot a row sits in or on timing.
+ *   - Which rows: the atomic in-row entries' rule.  A row is updated once per call iff a lookup that a bag covers names
+ *     it, zero weights or not (such a row decays, its moments decay towards zero).  Lookups outside [0, num_rows) and
+ *     lookups no bag covers head nothing; a row only they name keeps every part bit for bit.  Partial row-wise Adam: a
+ *     slot whose row_of_slot lies outside [0, v_rows) is left alone.
+ *   - The update of a row from its folded gradient is the atomic entries' -- clip, decay, moments or sums of squares, w
+ *     -- by the same device function: given the same folded gradient a row gets the bits of CE_ACC_CACHE / CE_ACC_STEP.
+ *   - The call's first launch adds 1 to *step; the step size, the decayed Adagrad rate and the decoupled factor are
+ *     formed on the device from lr or *lr_dev and *step, so a captured call that is replayed follows the count and a
+ *     schedule.  One stream, no host synchronisation, no allocation, launch shapes fixed by the arguments; nothing in
+ *     the workspace needs initialising, and no state passes from call to call except the table, v and *step.
+ *   - ce_bag_backward_in_row_sorted_workspace(num_rows, nnz, dim): 256-byte aligned, independent of num_rows; the sort's
+ *     arrays and one partial row of dim floats per lookup (0 for nnz < 0, nnz >= 2^31 - 1 or dim <= 0).
+ *   - Refused before the first launch and before any HIP call, the table untouched, in this order: step == NULL; the
+ *     decay's checks; the clip's checks; betas outside [0, 1), or lr_decay < 0 or NaN; eps < 0; lr < 0 (by value only);
+ *     act_dtype; null pointers (weight, grad_out, workspace; v for partial row-wise Adam); sizes (dim <= 0, num_rows,
+ *     nnz, num_bags); mode other than sum / mean (CE_ERR_UNSUPPORTED); hook_features; alignment (table 16 bytes, step 8,
+ *     grad_out on its vector boundary, workspace 256) and the workspace's size; the dim rule, dim % 4 == 0 and
+ *     4 <= dim <= 1024 (CE_ERR_UNSUPPORTED).  nnz == 0 or num_bags == 0 then returns with no launch and counts no step;
+ *     otherwise indices == NULL or offsets == NULL is CE_ERR_INVALID.
+ * Not built: a form from source-row keys, 16-bit tables or moments, stochastic rounding, mode max, scalar lanes. */
+size_t ce_bag_backward_in_row_sorted_workspace(int64_t num_rows, int64_t nnz, int32_t dim);
+int ce_bag_backward_adam_sorted(float* weight, int64_t num_rows, int32_t dim,
+                                const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                double beta1, double beta2, float lr, const float* lr_dev, float eps,
+                                float weight_decay, int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode,
+                                int64_t* step, void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_pradam_sorted(float* weight, int64_t num_rows, int32_t dim,
+                                  const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                  int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                  int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                  const int32_t* row_of_slot, float* v, int64_t v_rows, double beta1, double beta2,
+                                  float lr, const float* lr_dev, float eps, float weight_decay,
+                                  int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int64_t* step,
+                                  void* workspace, size_t workspace_bytes, ce_stream_t stream);
+int ce_bag_backward_adagrad_sorted(float* weight, int64_t num_rows, int32_t dim,
+                                   const int64_t* indices, int64_t nnz, const void* offsets, int32_t offsets_are_i64,
+                                   int64_t num_bags, int32_t include_last_offset, const float* per_sample_weights,
+                                   int32_t mode, int64_t hook_features, const void* grad_out, int32_t act_dtype,
+                                   double lr_decay, float lr, const float* lr_dev, float eps, float weight_decay,
+                                   int32_t weight_decay_mode, float grad_clip, int32_t grad_clip_mode, int64_t* step,
+                                   void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
 /* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
  * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
