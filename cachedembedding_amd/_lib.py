@@ -92,55 +92,51 @@ class CeCallStats(Structure):
     ]
 
 
-# name -> (restype, argtypes); mirrors include/ce_api.h declaration by declaration
-# the pieces the ce_bag_* declarations are made of --
-# table, num_rows, dim | indices, nnz | offsets, offsets_are_i64, num_bags, include_last_offset
-_TABLE = [c_void_p, c_int64, c_int32]
-_LOOKUPS = _TABLE + [c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32]
-# ... per_sample_weights, mode, hook_features, out / grad_out: the slots + offsets entries
-_BAG = _LOOKUPS + [c_void_p, c_int32, c_int64, c_void_p]
-# table, num_rows, dim, nnz, grad_out: the backward entries that walk source-row keys
-_SRC = _TABLE + [c_int64, c_void_p]
+# name -> (restype, argtypes); mirrors include/ce_api.h declaration by declaration (tests/test_abi.py compares the two
+# parameter by parameter).  The groups the ce_bag_* declarations are made of, each written once and in the order the
+# lists have them -- functional._fused_update_call builds the argument tuples from the same ones:
+_ROWS = [c_int64, c_int32]                      # num_rows, dim
+_TABLE = [c_void_p] + _ROWS                     # the table in front of them
+_TABLE_W16 = [c_void_p, c_int32] + _ROWS        # ... with its CE_ACT_* code: the entries a 16-bit table goes to
+# indices, nnz, offsets, offsets_are_i64, num_bags, include_last_offset
+_SLOTS = [c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32]
+_POOL = [c_void_p, c_int32, c_int64, c_void_p]  # per_sample_weights, mode, hook_features, out / grad_out
+_LOOKUPS = _TABLE + _SLOTS
+_BAG = _LOOKUPS + _POOL                         # the slots + offsets entries
+_BAG_W16 = _TABLE_W16 + _SLOTS + _POOL
+_SRC_WALK = [c_int64, c_void_p]                 # nnz, grad_out: the backward entries that walk source-row keys
+_SRC = _TABLE + _SRC_WALK
+_SRC_W16 = _TABLE_W16 + _SRC_WALK
 _ACT = [c_int32]                # act_dtype, right behind the out / grad_out it describes
 _KEYS = [c_void_p]              # presorted / source-row keys
+_ROW_STATE = [c_void_p, c_void_p, c_int64]      # row_of_slot, momentum (partial row-wise Adam: v), its rows
+_RATE = [c_float, c_float]                      # lr, eps
+_RATE_DEV = [c_void_p, c_float]                 # lr as ONE fp32 in device memory, eps
+_RATE_BOTH = [c_float, c_void_p, c_float]       # lr, lr_dev, eps
+_BETAS = [c_double, c_double]                   # beta1, beta2
+_LR_DECAY = [c_double]                          # element-wise Adagrad: lr_decay where Adam has its betas
+_WD = [c_float, c_int32]                        # weight_decay, weight_decay_mode: directly behind eps
+_CLIP = [c_float, c_int32]                      # grad_clip, grad_clip_mode: directly behind weight_decay_mode
+_OPT = [c_int32, c_int32, c_uint64]             # optimizer, rounding, seed
+_STEP = [c_void_p]                              # the in-row layouts' step count on the device
+_ACC = [c_int32]                                # accumulator (CE_ACC_*)
 _STREAM = [c_void_p]
-# keys, row_of_slot, momentum, momentum_rows, lr, eps, workspace, workspace_bytes, stream
-_ADAGRAD_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_size_t] + _STREAM
-_W16 = [c_void_p, c_int32]      # the 16-bit table and its CE_ACT_* code
-_W16_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_float, c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
-# keys, row_of_slot, momentum, momentum_rows, lr (device pointer), eps, optimizer, rounding, seed, accumulator, workspace,
-# workspace_bytes, stream
-_LRDEV_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int32, c_int32, c_uint64, c_int32, c_void_p,
-                       c_size_t] + _STREAM
-# keys, beta1, beta2, lr, lr_dev, eps, step, accumulator, workspace, workspace_bytes, stream
-_ADAM_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
-# weight decay: `weight_decay, weight_decay_mode` directly behind eps --
-# keys, row_of_slot, momentum, momentum_rows, lr, lr_dev, eps, weight_decay, weight_decay_mode, optimizer, rounding, seed,
-# accumulator, workspace, workspace_bytes, stream
-_WD = [c_float, c_int32]
-_UPDATE_WD_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_float] + _WD + \
-    [c_int32, c_int32, c_uint64, c_int32, c_void_p, c_size_t] + _STREAM
-# row_of_slot, momentum, momentum_rows, lr, eps, weight_decay, weight_decay_mode, optimizer, rounding, seed, workspace, ...
-_SORTED_WD_TAIL = [c_void_p, c_void_p, c_int64, c_float, c_float] + _WD + \
-    [c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
-_ADAM_WD_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD + \
-    [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
-_ROW_MOMENT = [c_void_p, c_void_p, c_int64]      # row_of_slot, v, v_rows (partial row-wise Adam), behind the keys
-# gradient clipping: `grad_clip, grad_clip_mode` directly behind weight_decay_mode
-_CLIP = [c_float, c_int32]
-_UPDATE_CLIP_TAIL = _KEYS + [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_float] + _WD + _CLIP + \
-    [c_int32, c_int32, c_uint64, c_int32, c_void_p, c_size_t] + _STREAM
-_SORTED_CLIP_TAIL = [c_void_p, c_void_p, c_int64, c_float, c_float] + _WD + _CLIP + \
-    [c_int32, c_int32, c_uint64, c_void_p, c_size_t] + _STREAM
-_ADAM_CLIP_TAIL = _KEYS + [c_double, c_double, c_float, c_void_p, c_float] + _WD + _CLIP + \
-    [c_void_p, c_int32, c_void_p, c_size_t] + _STREAM
-# element-wise Adagrad: the clipped Adam tail with lr_decay in the betas' place
-_ELEMENTWISE_TAIL = _KEYS + [c_double] + _ADAM_CLIP_TAIL[3:]
-# the sorted (deterministic) in-row updates: the clipped lists without the keys and without the accumulator --
-# beta1, beta2 (or lr_decay), lr, lr_dev, eps, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode, step, workspace,
-# workspace_bytes, stream
-_ADAM_SORTED_TAIL = _ADAM_CLIP_TAIL[1:11] + _ADAM_CLIP_TAIL[12:]
-_ELEMENTWISE_SORTED_TAIL = [c_double] + _ADAM_SORTED_TAIL[2:]
+_WS = [c_void_p, c_size_t] + _STREAM            # workspace, workspace_bytes, stream
+# row-wise Adagrad and SGD with a per-row pass, behind the lookups and their act_dtype: the sorted entries take no keys
+_ADAGRAD_TAIL = _KEYS + _ROW_STATE + _RATE + _WS
+_UPDATE_SORTED_TAIL = _ROW_STATE + _RATE + _OPT + _WS
+_UPDATE_TAIL = _KEYS + _UPDATE_SORTED_TAIL
+_LRDEV_TAIL = _KEYS + _ROW_STATE + _RATE_DEV + _OPT + _ACC + _WS
+_UPDATE_WD_TAIL = _KEYS + _ROW_STATE + _RATE_BOTH + _WD + _OPT + _ACC + _WS
+_UPDATE_CLIP_TAIL = _KEYS + _ROW_STATE + _RATE_BOTH + _WD + _CLIP + _OPT + _ACC + _WS
+_SORTED_WD_TAIL = _ROW_STATE + _RATE + _WD + _OPT + _WS
+_SORTED_CLIP_TAIL = _ROW_STATE + _RATE + _WD + _CLIP + _OPT + _WS
+# the in-row layouts behind their moments (beta1, beta2 or lr_decay), which stand behind the keys -- partial row-wise
+# Adam: behind keys and row state; the sorted entries: no keys, no accumulator
+_IN_ROW_TAIL = _RATE_BOTH + _STEP + _ACC + _WS
+_IN_ROW_WD_TAIL = _RATE_BOTH + _WD + _STEP + _ACC + _WS
+_IN_ROW_CLIP_TAIL = _RATE_BOTH + _WD + _CLIP + _STEP + _ACC + _WS
+_IN_ROW_SORTED_TAIL = _RATE_BOTH + _WD + _CLIP + _STEP + _WS
 # the window presort: slots, nnz_per_batch, n_batches, num_rows | offsets, offsets_are_i64, offsets_batch_stride,
 # num_bags, include_last_offset, hook_features
 _WINDOW = [c_void_p, c_int64, c_int64, c_int64]
@@ -194,68 +190,68 @@ SIGNATURES = {
     # 16-bit table: weight, weight_dtype in front; the update's tail = keys, row_of_slot, momentum, momentum_rows, lr,
     # eps, optimizer, rounding, seed, workspace, workspace_bytes, stream
     "ce_host_fill_uniform_w16": (c_int, [c_void_p, c_int64, c_float, c_float, c_uint64, c_int32, c_int]),
-    "ce_bag_forward_w16": (c_int, _W16 + _BAG[1:] + _ACT + _STREAM),
-    "ce_bag_forward_src_keys_w16": (c_int, _W16 + [c_int64, c_int32, c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    "ce_bag_forward_w16": (c_int, _BAG_W16 + _ACT + _STREAM),
+    "ce_bag_forward_src_keys_w16": (c_int, _TABLE_W16 + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
     "ce_bag_backward_w16_workspace": (c_size_t, [c_int64, c_int32]),
-    "ce_bag_backward_update_w16": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL),
-    "ce_bag_backward_update_src_w16": (c_int, _W16 + _SRC[1:] + _ACT + _W16_TAIL),
+    "ce_bag_backward_update_w16": (c_int, _BAG_W16 + _ACT + _UPDATE_TAIL),
+    "ce_bag_backward_update_src_w16": (c_int, _SRC_W16 + _ACT + _UPDATE_TAIL),
     # the deterministic, accumulator-free update: the w16 update's arguments without the presorted keys
     "ce_bag_backward_update_sorted_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
-    "ce_bag_backward_update_sorted": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL[1:]),
+    "ce_bag_backward_update_sorted": (c_int, _BAG_W16 + _ACT + _UPDATE_SORTED_TAIL),
     # the atomic updates with a step-sized accumulator: the w16 update's arguments, weight_dtype may be CE_ACT_F32
     "ce_bag_backward_update_compact_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
-    "ce_bag_backward_update_compact": (c_int, _W16 + _BAG[1:] + _ACT + _W16_TAIL),
-    "ce_bag_backward_update_compact_src": (c_int, _W16 + _SRC[1:] + _ACT + _W16_TAIL),
+    "ce_bag_backward_update_compact": (c_int, _BAG_W16 + _ACT + _UPDATE_TAIL),
+    "ce_bag_backward_update_compact_src": (c_int, _SRC_W16 + _ACT + _UPDATE_TAIL),
     # the learning rate as ONE fp32 in device memory, read by the kernels when they run: the _act / _w16 lists with lr a
     # pointer; the update pair also takes the accumulator (CE_ACC_*) behind the seed and covers the cache-sized fp32
     # Adagrad, the cache-sized 16-bit and the step-sized entries
     "ce_bag_backward_sgd_lrdev": (c_int, _BAG + _ACT + [c_void_p] + _KEYS + _STREAM),
     "ce_bag_backward_sgd_src_lrdev": (c_int, _SRC + _ACT + [c_void_p] + _KEYS + [c_void_p] + _STREAM),
-    "ce_bag_backward_update_lrdev": (c_int, _W16 + _BAG[1:] + _ACT + _LRDEV_TAIL),
-    "ce_bag_backward_update_src_lrdev": (c_int, _W16 + _SRC[1:] + _ACT + _LRDEV_TAIL),
+    "ce_bag_backward_update_lrdev": (c_int, _BAG_W16 + _ACT + _LRDEV_TAIL),
+    "ce_bag_backward_update_src_lrdev": (c_int, _SRC_W16 + _ACT + _LRDEV_TAIL),
     # the Adam-layout table (rows w | m | v of 3 * dim fp32): the fp32 forwards' lists; the update's tail = keys, beta1,
     # beta2, lr, lr_dev, eps, step, accumulator, workspace, workspace_bytes, stream
     "ce_host_fill_uniform_adam": (c_int, [c_void_p, c_int64, c_int32, c_float, c_float, c_uint64, c_int]),
     "ce_bag_forward_adam": (c_int, _BAG + _ACT + _STREAM),
     "ce_bag_forward_src_keys_adam": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
     "ce_bag_backward_adam_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
-    "ce_bag_backward_adam": (c_int, _BAG + _ACT + _ADAM_TAIL),
-    "ce_bag_backward_adam_src": (c_int, _SRC + _ACT + _ADAM_TAIL),
+    "ce_bag_backward_adam": (c_int, _BAG + _ACT + _KEYS + _BETAS + _IN_ROW_TAIL),
+    "ce_bag_backward_adam_src": (c_int, _SRC + _ACT + _KEYS + _BETAS + _IN_ROW_TAIL),
     # weight decay (L2 / decoupled, lazy) for the fused updates: the covered lists with the decay behind eps
-    "ce_bag_backward_update_wd": (c_int, _W16 + _BAG[1:] + _ACT + _UPDATE_WD_TAIL),
-    "ce_bag_backward_update_src_wd": (c_int, _W16 + _SRC[1:] + _ACT + _UPDATE_WD_TAIL),
-    "ce_bag_backward_update_sorted_wd": (c_int, _W16 + _BAG[1:] + _ACT + _SORTED_WD_TAIL),
-    "ce_bag_backward_adam_wd": (c_int, _BAG + _ACT + _ADAM_WD_TAIL),
-    "ce_bag_backward_adam_src_wd": (c_int, _SRC + _ACT + _ADAM_WD_TAIL),
+    "ce_bag_backward_update_wd": (c_int, _BAG_W16 + _ACT + _UPDATE_WD_TAIL),
+    "ce_bag_backward_update_src_wd": (c_int, _SRC_W16 + _ACT + _UPDATE_WD_TAIL),
+    "ce_bag_backward_update_sorted_wd": (c_int, _BAG_W16 + _ACT + _SORTED_WD_TAIL),
+    "ce_bag_backward_adam_wd": (c_int, _BAG + _ACT + _KEYS + _BETAS + _IN_ROW_WD_TAIL),
+    "ce_bag_backward_adam_src_wd": (c_int, _SRC + _ACT + _KEYS + _BETAS + _IN_ROW_WD_TAIL),
     # partial row-wise Adam (rows w | m of 2 * dim fp32, the second moment one fp32 per table row): the Adam layout's
     # lists; the update's = the _adam_wd lists with row_of_slot, v, v_rows behind the keys
     "ce_host_fill_uniform_pradam": (c_int, [c_void_p, c_int64, c_int32, c_float, c_float, c_uint64, c_int]),
     "ce_bag_forward_pradam": (c_int, _BAG + _ACT + _STREAM),
     "ce_bag_forward_src_keys_pradam": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
     "ce_bag_backward_pradam_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
-    "ce_bag_backward_pradam": (c_int, _BAG + _ACT + _KEYS + _ROW_MOMENT + _ADAM_WD_TAIL[1:]),
-    "ce_bag_backward_pradam_src": (c_int, _SRC + _ACT + _KEYS + _ROW_MOMENT + _ADAM_WD_TAIL[1:]),
+    "ce_bag_backward_pradam": (c_int, _BAG + _ACT + _KEYS + _ROW_STATE + _BETAS + _IN_ROW_WD_TAIL),
+    "ce_bag_backward_pradam_src": (c_int, _SRC + _ACT + _KEYS + _ROW_STATE + _BETAS + _IN_ROW_WD_TAIL),
     # gradient clipping (per value / per row norm) for the fused updates: the covered lists with the clip behind the decay
-    "ce_bag_backward_update_clip": (c_int, _W16 + _BAG[1:] + _ACT + _UPDATE_CLIP_TAIL),
-    "ce_bag_backward_update_src_clip": (c_int, _W16 + _SRC[1:] + _ACT + _UPDATE_CLIP_TAIL),
-    "ce_bag_backward_update_sorted_clip": (c_int, _W16 + _BAG[1:] + _ACT + _SORTED_CLIP_TAIL),
-    "ce_bag_backward_adam_clip": (c_int, _BAG + _ACT + _ADAM_CLIP_TAIL),
-    "ce_bag_backward_adam_src_clip": (c_int, _SRC + _ACT + _ADAM_CLIP_TAIL),
-    "ce_bag_backward_pradam_clip": (c_int, _BAG + _ACT + _KEYS + _ROW_MOMENT + _ADAM_CLIP_TAIL[1:]),
-    "ce_bag_backward_pradam_src_clip": (c_int, _SRC + _ACT + _KEYS + _ROW_MOMENT + _ADAM_CLIP_TAIL[1:]),
+    "ce_bag_backward_update_clip": (c_int, _BAG_W16 + _ACT + _UPDATE_CLIP_TAIL),
+    "ce_bag_backward_update_src_clip": (c_int, _SRC_W16 + _ACT + _UPDATE_CLIP_TAIL),
+    "ce_bag_backward_update_sorted_clip": (c_int, _BAG_W16 + _ACT + _SORTED_CLIP_TAIL),
+    "ce_bag_backward_adam_clip": (c_int, _BAG + _ACT + _KEYS + _BETAS + _IN_ROW_CLIP_TAIL),
+    "ce_bag_backward_adam_src_clip": (c_int, _SRC + _ACT + _KEYS + _BETAS + _IN_ROW_CLIP_TAIL),
+    "ce_bag_backward_pradam_clip": (c_int, _BAG + _ACT + _KEYS + _ROW_STATE + _BETAS + _IN_ROW_CLIP_TAIL),
+    "ce_bag_backward_pradam_src_clip": (c_int, _SRC + _ACT + _KEYS + _ROW_STATE + _BETAS + _IN_ROW_CLIP_TAIL),
     # element-wise Adagrad (rows w | h of 2 * dim fp32, h the per-element sums of squares): the partial row-wise Adam
     # forwards' lists; the fill's list with init_acc in front of threads
     "ce_host_fill_uniform_adagrad": (c_int, [c_void_p, c_int64, c_int32, c_float, c_float, c_uint64, c_float, c_int]),
     "ce_bag_forward_adagrad": (c_int, _BAG + _ACT + _STREAM),
     "ce_bag_forward_src_keys_adagrad": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
     "ce_bag_backward_adagrad_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
-    "ce_bag_backward_adagrad": (c_int, _BAG + _ACT + _ELEMENTWISE_TAIL),
-    "ce_bag_backward_adagrad_src": (c_int, _SRC + _ACT + _ELEMENTWISE_TAIL),
+    "ce_bag_backward_adagrad": (c_int, _BAG + _ACT + _KEYS + _LR_DECAY + _IN_ROW_CLIP_TAIL),
+    "ce_bag_backward_adagrad_src": (c_int, _SRC + _ACT + _KEYS + _LR_DECAY + _IN_ROW_CLIP_TAIL),
     # the deterministic, accumulator-free updates of the three in-row layouts: slots + offsets, no keys, no accumulator
     "ce_bag_backward_in_row_sorted_workspace": (c_size_t, [c_int64, c_int64, c_int32]),
-    "ce_bag_backward_adam_sorted": (c_int, _BAG + _ACT + _ADAM_SORTED_TAIL),
-    "ce_bag_backward_pradam_sorted": (c_int, _BAG + _ACT + _ROW_MOMENT + _ADAM_SORTED_TAIL),
-    "ce_bag_backward_adagrad_sorted": (c_int, _BAG + _ACT + _ELEMENTWISE_SORTED_TAIL),
+    "ce_bag_backward_adam_sorted": (c_int, _BAG + _ACT + _BETAS + _IN_ROW_SORTED_TAIL),
+    "ce_bag_backward_pradam_sorted": (c_int, _BAG + _ACT + _ROW_STATE + _BETAS + _IN_ROW_SORTED_TAIL),
+    "ce_bag_backward_adagrad_sorted": (c_int, _BAG + _ACT + _LR_DECAY + _IN_ROW_SORTED_TAIL),
     # the 8-bit row-wise quantized table (q8): rows of 16 + dim bytes; forward only
     "ce_q8_row_bytes": (c_size_t, [c_int32]),
     "ce_host_quantize_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int]),

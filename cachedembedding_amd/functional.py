@@ -135,7 +135,6 @@ class _BagFn(torch.autograd.Function):
         mode, include_last, hook_features, sparse, fused, num_bags = ctx.args
         grad_out = grad_out.contiguous()
         adam = isinstance(fused, _IN_ROW)
-        partial = adam and fused.layout == "partial_rowwise_adam"
         if isinstance(fused, FusedAdagrad) and fused.lr is None:
             raise RuntimeError("backward through an Adagrad-layout table with no fused Adagrad set: an autograd gradient "
                                "in slot space over 2 * D columns means nothing (set_fused_adagrad(lr) first, or run the "
@@ -151,182 +150,33 @@ class _BagFn(torch.autograd.Function):
         gw = None
         pre = ctx.presorted
         src = isinstance(pre, SrcKeys)
-        if adam:
-            # Adam inside backward (ce_bag_backward_adam*): either accumulator's fold, then one apply pass that updates
-            # w, m and v of every row the step looked up; the step count lives on the device (fused.step)
-            act = _lib.ACT_DTYPES.get(grad_out.dtype)
-            if act is None:
-                raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
-            with torch.no_grad():
-                ws = fused.workspace(R, nnz, dim, weight.device)
-                lr_t = isinstance(fused.lr, torch.Tensor)
-                # weight decay: the ce_*_wd pair, the decay and its mode directly behind eps; without it today's entries.
-                # Gradient clipping: the ce_*_clip entries, the clip and its mode directly behind the decay's
-                clip = fused.grad_clip is not None
-                decay = fused.weight_decay != 0.0 or clip
-                if fused.accumulator == "sorted":
-                    # the deterministic fold (ce_bag_backward_*_sorted): always from slots + offsets --
-                    # presorted keys of either kind are not needed and ignored --, decay and clip always in the list
-                    rate = (0.0 if lr_t else float(fused.lr), ptr(fused.lr) if lr_t else None, float(fused.eps),
-                            float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + \
-                        (fused.clip_args() if clip else (0.0, _lib.CE_CLIP_NONE)) + \
-                        (ptr(fused.step), ptr(ws), ws.numel(), stream_ptr())
-                    lookups = (ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last),
-                               ptr(psw), mode, hook_features, ptr(grad_out), act)
-                    if fused.layout == "adagrad":
-                        check(lib.ce_bag_backward_adagrad_sorted(*lookups, float(fused.lr_decay), *rate))
-                    elif partial:
-                        v = fused.exp_avg_sq
-                        check(lib.ce_bag_backward_pradam_sorted(*lookups, ptr(fused.row_of_slot), ptr(v), v.numel(),
-                                                                float(fused.betas[0]), float(fused.betas[1]), *rate))
-                    else:
-                        check(lib.ce_bag_backward_adam_sorted(*lookups, float(fused.betas[0]), float(fused.betas[1]),
-                                                              *rate))
-                    return (None,) * 14
-                if fused.layout == "adagrad":
-                    # element-wise Adagrad (ce_bag_backward_adagrad*): one entry, decay and clip always in its list
-                    # (weight_decay 0 and CE_CLIP_NONE: the kernels without them), lr_decay where Adam has its betas
-                    tail = (float(fused.lr_decay), 0.0 if lr_t else float(fused.lr), ptr(fused.lr) if lr_t else None,
-                            float(fused.eps), float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + \
-                        (fused.clip_args() if clip else (0.0, _lib.CE_CLIP_NONE)) + \
-                        (ptr(fused.step), _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws),
-                         ws.numel(), stream_ptr())
-                    if src:
-                        check(lib.ce_bag_backward_adagrad_src(ptr(weight), R, dim, nnz, ptr(grad_out), act,
-                                                              ptr(pre.keys), *tail))
-                    else:
-                        check(lib.ce_bag_backward_adagrad(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64,
-                                                          num_bags, int(include_last), ptr(psw), mode, hook_features,
-                                                          ptr(grad_out), act, ptr(pre), *tail))
-                    return (None,) * 14
-                tail = (float(fused.betas[0]), float(fused.betas[1]), 0.0 if lr_t else float(fused.lr),
-                        ptr(fused.lr) if lr_t else None, float(fused.eps)) + \
-                    ((float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) if decay else ()) + \
-                    (fused.clip_args() if clip else ()) + \
-                    (ptr(fused.step), _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE, ptr(ws),
-                     ws.numel(), stream_ptr())
-                if fused.layout == "partial_rowwise_adam":
-                    # partial row-wise Adam (ce_bag_backward_pradam*): one entry with or without decay; the second
-                    # moment, one fp32 per table row, is named by row_of_slot, v, v_rows in front of beta1
-                    v = fused.exp_avg_sq
-                    tail = (ptr(fused.row_of_slot), ptr(v), v.numel()) + tail[:5] + \
-                        (float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + \
-                        (fused.clip_args() if clip else ()) + tail[-5:]
-                    if src:
-                        fn = lib.ce_bag_backward_pradam_src_clip if clip else lib.ce_bag_backward_pradam_src
-                        check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
-                    else:
-                        fn = lib.ce_bag_backward_pradam_clip if clip else lib.ce_bag_backward_pradam
-                        check(fn(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags,
-                                 int(include_last), ptr(psw), mode, hook_features, ptr(grad_out), act, ptr(pre), *tail))
-                elif src:
-                    fn = lib.ce_bag_backward_adam_src_clip if clip else \
-                        (lib.ce_bag_backward_adam_src_wd if decay else lib.ce_bag_backward_adam_src)
-                    check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
-                else:
-                    fn = lib.ce_bag_backward_adam_clip if clip else \
-                        (lib.ce_bag_backward_adam_wd if decay else lib.ce_bag_backward_adam)
-                    check(fn(ptr(weight), R, dim, ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last),
-                             ptr(psw), mode, hook_features, ptr(grad_out), act, ptr(pre), *tail))
-            return (None,) * 14
-        rowwise = isinstance(fused, FusedRowwiseAdagrad) and fused.lr is not None
-        sgd = not rowwise and fused is not None and fused.lr is not None
-        # the hot paths -- row-wise Adagrad, fused SGD by atomics, the dense gradient -- read grad_out as it comes
-        # (fp32, bf16 or fp16: what autograd delivers for an output of that dtype) through the ce_*_act entries, from
-        # source-row keys or from slots + offsets (ptr(None) = 0: no presorted keys / no owner ranges).  Deterministic
-        # SGD and the two sparse=True forms have fp32 entries only and take the exact upcast of a 16-bit gradient.
+        # the update entries -- the in-row layouts' (Adam, partial row-wise Adam, element-wise Adagrad), row-wise Adagrad,
+        # fused SGD -- and the dense gradient read grad_out as it comes (fp32, bf16 or fp16: what autograd delivers for
+        # an output of that dtype), from source-row keys or from slots + offsets
         act = _lib.ACT_DTYPES.get(grad_out.dtype)
         if act is None:
             raise NotImplementedError(f"gradient of dtype {grad_out.dtype}: fp32, bf16 and fp16 are implemented")
-        # (deterministic SGD WITH weight decay is ce_bag_backward_update_sorted_wd, which reads `act` in place like the
-        # other update entries: no upcast there, so `act` goes on describing the buffer that is handed over)
+        update = fused is not None and fused.lr is not None
+        rowwise = update and isinstance(fused, FusedRowwiseAdagrad)
+        sgd = update and not rowwise and not adam
+        # deterministic fp32 SGD without decay or clip (ce_bag_backward_sgd_sorted) and the two sparse=True forms read
+        # fp32 only and take the exact upcast of a 16-bit gradient; every other entry reads `act` in place
         clip = (rowwise or sgd) and fused.grad_clip is not None
-        fp32_only = (fused.deterministic and fused.weight_decay == 0.0 and not clip) if sgd else (sparse and not rowwise)
+        fp32_only = (fused.deterministic and fused.weight_decay == 0.0 and not clip) if sgd else \
+            (sparse and not rowwise and not adam)
         if fp32_only and act != _lib.CE_ACT_F32:
             grad_out = grad_out.float()
         slots_args = (ptr(indices), nnz, ptr(offsets), off64, num_bags, int(include_last), ptr(psw), mode,
                       hook_features, ptr(grad_out))
-        # a tensor learning rate goes to the ce_*_lrdev entries, whose kernels read it when they run (nothing here
-        # does); a float to the by-value entries.  What the tensor form does not take was refused before the forward.
-        lr_dev = (rowwise or sgd) and isinstance(fused.lr, torch.Tensor)
-        if (rowwise or sgd) and (fused.weight_decay != 0.0 or clip):
-            # weight decay: the ce_*_wd entries -- the sorted one for deterministic=True (fp32 SGD has
-            # no other), else the atomic pair with either accumulator.  What they do not take was refused before the
-            # forward (check_weight_decay_path).  Without decay nothing below has changed.
-            # Gradient clipping: the ce_*_clip entries that cover those three, with the clip and its
-            # mode behind the decay's (check_grad_clip_path); without a clip the _wd entries as before.
+        if update:
+            # the optimizer's step inside backward: it sees grad=None for the cache parameter
+            entry, args = _fused_update_call(fused, weight, dim, slots_args, nnz, grad_out, act, pre)
             with torch.no_grad():
-                w16 = weight.dtype in _lib.W16_DTYPES
-                wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
-                mom = fused.momentum if rowwise else None
-                head = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel())
-                decay = (float(fused.eps) if rowwise else 0.0, float(fused.weight_decay),
-                         WEIGHT_DECAY_MODES[fused.weight_decay_mode]) + (fused.clip_args() if clip else ()) + \
-                        (_lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
-                         _lib.CE_ROUND_STOCHASTIC if w16 and fused.rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
-                         int(fused.seed) & (2 ** 64 - 1))
-                if fused.deterministic:
-                    ws = _workspace_sorted(fused, R, nnz, dim, weight.device)
-                    fn = lib.ce_bag_backward_update_sorted_clip if clip else lib.ce_bag_backward_update_sorted_wd
-                    check(fn(*wd, *slots_args, act, *head, float(fused.lr), *decay, ptr(ws), ws.numel(), stream_ptr()))
-                    return (None,) * 14
-                if fused.accumulator == "step":
-                    ws, acc = fused.workspace_step(R, nnz, dim, weight.device), _lib.CE_ACC_STEP
-                else:
-                    ws = fused.workspace_w16(R, dim, weight.device) if w16 else fused.workspace(R, dim, weight.device)
-                    acc = _lib.CE_ACC_CACHE
-                tail = head + (0.0 if lr_dev else float(fused.lr), ptr(fused.lr) if lr_dev else None) + decay + \
-                    (acc, ptr(ws), ws.numel(), stream_ptr())
-                if src:
-                    fn = lib.ce_bag_backward_update_src_clip if clip else lib.ce_bag_backward_update_src_wd
-                    check(fn(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
-                else:
-                    fn = lib.ce_bag_backward_update_clip if clip else lib.ce_bag_backward_update_wd
-                    check(fn(*wd, *slots_args, act, ptr(pre), *tail))
-            return (None,) * 14
-        if (rowwise or sgd) and fused.accumulator == "step":
-            # the atomic update with an accumulator of min(nnz, rows) rows (ce_bag_backward_update_compact*): mark, an
-            # ordered compaction of the flagged slots, the slots / keys renumbered, the same dense backward, one apply
-            # pass over the list.  fp32 tables (row-wise Adagrad) and 16-bit tables alike, from slots + offsets, from
-            # presorted keys and from source-row keys; what it does not take was refused before the forward.
-            with torch.no_grad():
-                ws = fused.workspace_step(R, nnz, dim, weight.device)
-                wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
-                # (an fp32 table is never rounded, whatever fused.rounding says)
-                w16 = weight.dtype in _lib.W16_DTYPES
-                tail = _update_tail(fused, rowwise, fused.rounding if w16 else "nearest", ws, _lib.CE_ACC_STEP)
-                if src:
-                    fn = lib.ce_bag_backward_update_src_lrdev if lr_dev else lib.ce_bag_backward_update_compact_src
-                    check(fn(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
-                else:
-                    fn = lib.ce_bag_backward_update_lrdev if lr_dev else lib.ce_bag_backward_update_compact
-                    check(fn(*wd, *slots_args, act, ptr(pre), *tail))
-            return (None,) * 14
-        if rowwise and fused.deterministic:
-            # bit-reproducible row-wise Adagrad without the [rows, D] accumulator (ce_bag_backward_update_sorted): fp32
-            # and 16-bit tables (rounded to nearest: stochastic rounding was refused before the forward), always from
-            # slots + offsets -- presorted keys of either kind are not needed and ignored
-            with torch.no_grad():
-                ws = fused.workspace_sorted(R, nnz, dim, weight.device)
-                check(lib.ce_bag_backward_update_sorted(ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim, *slots_args,
-                                                        act, *_update_tail(fused, True, fused.rounding, ws)))
+                check(getattr(lib, entry)(*args))
             return (None,) * 14
         if weight.dtype in _lib.W16_DTYPES:
-            # 16-bit table (the combinations it does not take were refused in embedding_bag, before the forward)
-            wd = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
-            if rowwise or sgd:
-                # mark + the dense backward into an fp32 accumulator + one apply pass that rounds every row once
-                with torch.no_grad():
-                    ws = fused.workspace_w16(R, dim, weight.device)
-                    tail = _update_tail(fused, rowwise, fused.rounding, ws, _lib.CE_ACC_CACHE)
-                    if src:
-                        fn = lib.ce_bag_backward_update_src_lrdev if lr_dev else lib.ce_bag_backward_update_src_w16
-                        check(fn(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
-                    else:
-                        fn = lib.ce_bag_backward_update_lrdev if lr_dev else lib.ce_bag_backward_update_w16
-                        check(fn(*wd, *slots_args, act, ptr(pre), *tail))
-                return (None,) * 14
-            # no fused optimizer: the dense gradient is accumulated in fp32 and cast once to the parameter's dtype
+            # a 16-bit table (sparse=True was refused in embedding_bag, before the forward): the dense gradient is
+            # accumulated in fp32 and cast once to the parameter's dtype
             g32 = torch.zeros(R, dim, device=weight.device, dtype=torch.float32)
             if src:
                 check(lib.ce_bag_backward_dense_src_act(ptr(g32), R, dim, nnz, ptr(grad_out), act, ptr(pre.keys),
@@ -334,43 +184,7 @@ class _BagFn(torch.autograd.Function):
             else:
                 check(lib.ce_bag_backward_dense_act(ptr(g32), R, dim, *slots_args, act, ptr(pre), stream_ptr()))
             return (g32.to(weight.dtype),) + (None,) * 13
-        if rowwise:
-            # exact row-wise Adagrad inside backward (ce_bag_adagrad.hip): the optimizer sees grad=None
-            with torch.no_grad():
-                ws = fused.workspace(R, dim, weight.device)
-                mom = fused.momentum
-                if lr_dev:
-                    # the cache-sized fp32 update behind the entry that covers it (CE_ACT_F32, CE_ACC_CACHE)
-                    wd = (ptr(weight), _lib.CE_ACT_F32, R, dim)
-                    tail = _update_tail(fused, True, "nearest", ws, _lib.CE_ACC_CACHE)
-                    if src:
-                        check(lib.ce_bag_backward_update_src_lrdev(*wd, nnz, ptr(grad_out), act, ptr(pre.keys), *tail))
-                    else:
-                        check(lib.ce_bag_backward_update_lrdev(*wd, *slots_args, act, ptr(pre), *tail))
-                    return (None,) * 14
-                tail = (ptr(fused.row_of_slot), ptr(mom), mom.numel(), float(fused.lr), float(fused.eps), ptr(ws),
-                        ws.numel(), stream_ptr())
-                if src:
-                    check(lib.ce_bag_backward_rowwise_adagrad_src_act(ptr(weight), R, dim, nnz, ptr(grad_out), act,
-                                                                      ptr(pre.keys), *tail))
-                else:
-                    check(lib.ce_bag_backward_rowwise_adagrad_act(ptr(weight), R, dim, *slots_args, act, ptr(pre),
-                                                                  *tail))
-        elif sgd:
-            # K13+K14 in one pass; the optimizer sees grad=None for the cache parameter
-            with torch.no_grad():
-                if fused.deterministic:
-                    ws = fused.workspace(R, nnz, weight.device)
-                    check(lib.ce_bag_backward_sgd_sorted(ptr(weight), R, dim, *slots_args, float(fused.lr), ptr(ws),
-                                                         ws.numel(), stream_ptr()))
-                elif src:
-                    fn = lib.ce_bag_backward_sgd_src_lrdev if lr_dev else lib.ce_bag_backward_sgd_src_act
-                    check(fn(ptr(weight), R, dim, nnz, ptr(grad_out), act, _lr_arg(fused), ptr(pre.keys),
-                             ptr(pre.ranges), stream_ptr()))
-                else:
-                    fn = lib.ce_bag_backward_sgd_lrdev if lr_dev else lib.ce_bag_backward_sgd_act
-                    check(fn(ptr(weight), R, dim, *slots_args, act, _lr_arg(fused), ptr(pre), stream_ptr()))
-        elif sparse and COALESCED_SPARSE_GRAD and nnz > 0 and not torch.cuda.is_current_stream_capturing():
+        if sparse and COALESCED_SPARSE_GRAD and nnz > 0 and not torch.cuda.is_current_stream_capturing():
             # sparse=True (scripts/kaggle.sh:71 --use_sparse_embed_grad): the COO gradient is handed over COALESCED --
             # unique rows (ce_dedupe_bucket_rows), ascending, each with the sum of its lookups' gradient rows (the dense
             # backward kernel over the unique positions) -- so torch.optim.SGD's grad.coalesce() (a sort of every lookup
@@ -524,11 +338,6 @@ def check_lr(lr):
     return lr
 
 
-def _lr_arg(fused):
-    """the learning-rate argument of a C entry: the device address of a tensor (ce_*_lrdev), else the float"""
-    return ptr(fused.lr) if isinstance(fused.lr, torch.Tensor) else float(fused.lr)
-
-
 class _CheckedLr:
     """`lr` of FusedSGD / FusedRowwiseAdagrad: check_lr runs on every assignment, a direct one included"""
 
@@ -541,17 +350,117 @@ class _CheckedLr:
         self._lr = check_lr(value)
 
 
-def _update_tail(fused, rowwise: bool, rounding: str, ws: torch.Tensor, accumulator: Optional[int] = None) -> tuple:
-    """what the ce_bag_backward_update_* entries take behind the lookups: row_of_slot, momentum and its length, lr, eps,
-    optimizer, rounding, seed, workspace, stream.  `rounding` is the caller's: the entries do not agree on when
-    fused.rounding counts.  A tensor learning rate: the tail of the ce_*_lrdev pair instead -- lr as a device address
-    and `accumulator` (CE_ACC_*: which of the entries it covers the call is) behind the seed."""
-    mom = fused.momentum if rowwise else None
+# the in-row layouts' entries, ce_bag_backward_<stem>[_src]<suffix> and ce_bag_backward_<stem>_sorted: the suffix by what
+# the list holds behind eps -- 0: nothing, 1: the decay, 2: the decay and the clip -- and the least the layout's lists hold
+_IN_ROW_ENTRIES = {"adam": ("adam", ("", "_wd", "_clip"), 0),
+                   "partial_rowwise_adam": ("pradam", (None, "", "_clip"), 1),
+                   "adagrad": ("adagrad", (None, None, ""), 2)}
+# the ce_bag_backward_update_* entries that walk keys, by what they take beyond the plain list: (from slots + offsets,
+# from source-row keys)
+_UPDATE_ENTRIES = {"clip": ("ce_bag_backward_update_clip", "ce_bag_backward_update_src_clip"),
+                   "wd": ("ce_bag_backward_update_wd", "ce_bag_backward_update_src_wd"),
+                   "lrdev": ("ce_bag_backward_update_lrdev", "ce_bag_backward_update_src_lrdev"),
+                   "compact": ("ce_bag_backward_update_compact", "ce_bag_backward_update_compact_src"),
+                   "w16": ("ce_bag_backward_update_w16", "ce_bag_backward_update_src_w16")}
+
+
+def _decay(fused) -> tuple:
+    """weight_decay, weight_decay_mode as the lists that hold a decay take them"""
+    return (float(fused.weight_decay), WEIGHT_DECAY_MODES[fused.weight_decay_mode])
+
+
+def _fused_update_call(fused, weight, dim: int, slots: tuple, nnz: int, grad_out, act: int, pre) -> tuple:
+    """The one place that says which C entry applies `fused` (a switch whose lr is set) inside the backward, with which
+    arguments and on which workspace: (entry, args) -- a name of _lib.SIGNATURES and its complete positional list.
+    slots: the slots + offsets lookups up to grad_out; act: grad_out's CE_ACT_*; pre: None, presorted keys or SrcKeys.
+    A list is made of groups, each written once and in the order every list has them (_lib.py declares the same ones):
+        table | lookups (`walk`: slots + offsets, or source-row keys) and act | keys | row state | moments | rate |
+        decay | clip | optimizer, rounding, seed | step | accumulator | workspace, its bytes, stream
+    tests/golden/update_dispatch.json pins every list."""
+    R, dev = weight.shape[0], weight.device
+    src = isinstance(pre, SrcKeys)
+    # the lookups as the entry walks them, with the dtype of grad_out; the keys behind them (a sorted entry takes slots +
+    # offsets and no keys, whatever `pre` is)
+    walk = (nnz, ptr(grad_out), act) if src else (*slots, act)
+    keys = ptr(pre.keys) if src else ptr(pre)
+    # the rate.  lr: a float, or -- the ce_*_lrdev entries -- the address of ONE fp32 in device memory that the kernels
+    # read when they run; lr_both: `lr, lr_dev` of the entries that take it both ways, the other one 0 / NULL.  What a
+    # tensor learning rate does not go with was refused before the forward.
     lr_dev = isinstance(fused.lr, torch.Tensor)
-    return (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel(), _lr_arg(fused),
-            float(fused.eps) if rowwise else 0.0, _lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
-            _lib.CE_ROUND_STOCHASTIC if rounding == "stochastic" else _lib.CE_ROUND_NEAREST,
-            int(fused.seed) & (2 ** 64 - 1)) + ((accumulator,) if lr_dev else ()) + (ptr(ws), ws.numel(), stream_ptr())
+    lr = ptr(fused.lr) if lr_dev else float(fused.lr)
+    lr_both = (0.0, lr) if lr_dev else (lr, None)
+    clip = fused.grad_clip is not None
+    decay = clip or fused.weight_decay != 0.0
+    if isinstance(fused, _IN_ROW):
+        # one fold, then one apply pass over the rows the step looked up; the step count lives on the device.  The
+        # workspace follows fused.accumulator: _ws ("cache"), _ws_step ("step") or _ws_sorted ("sorted")
+        stem, suffixes, least = _IN_ROW_ENTRIES[fused.layout]
+        by_sort = fused.accumulator == "sorted"
+        holds = 2 if by_sort else max(least, 2 if clip else 1 if decay else 0)
+        ws = fused.workspace(R, nnz, dim, dev)
+        # (partial row-wise Adam: the second moment, one fp32 per table row, is named like row-wise Adagrad's momentum)
+        state = ()
+        if fused.layout == "partial_rowwise_adam":
+            state = (ptr(fused.row_of_slot), ptr(fused.exp_avg_sq), fused.exp_avg_sq.numel())
+        moments = (float(fused.lr_decay),) if fused.layout == "adagrad" else (float(fused.betas[0]), float(fused.betas[1]))
+        decay_part = _decay(fused) if holds >= 1 else ()
+        clip_part = () if holds < 2 else fused.clip_args() if clip else (0.0, _lib.CE_CLIP_NONE)
+        if by_sort:
+            return f"ce_bag_backward_{stem}_sorted", \
+                (ptr(weight), R, dim, *slots, act, *state, *moments, *lr_both, float(fused.eps), *decay_part, *clip_part,
+                 ptr(fused.step), ptr(ws), ws.numel(), stream_ptr())
+        return f"ce_bag_backward_{stem}{'_src' if src else ''}{suffixes[holds]}", \
+            (ptr(weight), R, dim, *walk, keys, *state, *moments, *lr_both, float(fused.eps), *decay_part, *clip_part,
+             ptr(fused.step), _lib.CE_ACC_STEP if fused.accumulator == "step" else _lib.CE_ACC_CACHE,
+             ptr(ws), ws.numel(), stream_ptr())
+    rowwise = isinstance(fused, FusedRowwiseAdagrad)
+    w16 = weight.dtype in _lib.W16_DTYPES
+    by_step = fused.accumulator == "step"
+    if not (rowwise or w16 or decay or by_step):
+        # fused SGD on an fp32 table folds straight into the rows (K13 + K14 in one pass): no row state, no accumulator
+        if fused.deterministic:
+            ws = fused.workspace(R, nnz, dev)
+            return "ce_bag_backward_sgd_sorted", (ptr(weight), R, dim, *slots, lr, ptr(ws), ws.numel(), stream_ptr())
+        if src:
+            return "ce_bag_backward_sgd_src_lrdev" if lr_dev else "ce_bag_backward_sgd_src_act", \
+                (ptr(weight), R, dim, *walk, lr, keys, ptr(pre.ranges), stream_ptr())
+        return "ce_bag_backward_sgd_lrdev" if lr_dev else "ce_bag_backward_sgd_act", \
+            (ptr(weight), R, dim, *walk, lr, keys, stream_ptr())
+    # row-wise Adagrad, and SGD where it has a per-row pass (DESIGN.md 3.4 - 3.7, 3.12, 3.14).  The workspace first: the
+    # sorted fold's arrays, the step-sized accumulator, or the cache-sized one of the table's dtype
+    if fused.deterministic:
+        ws = _workspace_sorted(fused, R, nnz, dim, dev)
+    elif by_step:
+        ws = fused.workspace_step(R, nnz, dim, dev)
+    else:
+        ws = fused.workspace_w16(R, dim, dev) if w16 else fused.workspace(R, dim, dev)
+    mom = fused.momentum if rowwise else None
+    state = (ptr(fused.row_of_slot), ptr(mom), 0 if mom is None else mom.numel())
+    eps = float(fused.eps) if rowwise else 0.0
+    # what the call needs beyond the plain list picks the entry: a clip, a decay, the learning rate from device memory,
+    # the step-sized accumulator, a 16-bit table
+    kind = "clip" if clip else "wd" if decay else "" if fused.deterministic else "lrdev" if lr_dev else \
+        "compact" if by_step else "w16" if w16 else None
+    if kind is None:
+        # exact row-wise Adagrad on an fp32 table, cache-sized accumulator, lr by value: the first pair, the short list
+        return "ce_bag_backward_rowwise_adagrad_src_act" if src else "ce_bag_backward_rowwise_adagrad_act", \
+            (ptr(weight), R, dim, *walk, keys, *state, lr, eps, ptr(ws), ws.numel(), stream_ptr())
+    table = (ptr(weight), _lib.ACT_DTYPES[weight.dtype], R, dim)
+    # an fp32 table is never rounded, whatever fused.rounding says (the plain sorted entry is handed it as it is set)
+    stochastic = fused.rounding == "stochastic" and (w16 or kind == "")
+    optimizer = (_lib.CE_OPT_ROWWISE_ADAGRAD if rowwise else _lib.CE_OPT_SGD,
+                 _lib.CE_ROUND_STOCHASTIC if stochastic else _lib.CE_ROUND_NEAREST, int(fused.seed) & (2 ** 64 - 1))
+    decay_part = _decay(fused) if decay else ()
+    clip_part = fused.clip_args() if clip else ()
+    if fused.deterministic:
+        # bit-reproducible, no accumulator: ce_bag_backward_update_sorted[_wd | _clip], the learning rate a float
+        return "ce_bag_backward_update_sorted" + (kind and "_" + kind), \
+            (*table, *slots, act, *state, lr, eps, *decay_part, *clip_part, *optimizer, ptr(ws), ws.numel(), stream_ptr())
+    # the _wd / _clip lists take the learning rate both ways; they and the _lrdev list say which accumulator `ws` is
+    rate = (*lr_both, eps) if decay else (lr, eps)
+    acc = (_lib.CE_ACC_STEP if by_step else _lib.CE_ACC_CACHE,) if decay or lr_dev else ()
+    return _UPDATE_ENTRIES[kind][src], \
+        (*table, *walk, keys, *state, *rate, *decay_part, *clip_part, *optimizer, *acc, ptr(ws), ws.numel(), stream_ptr())
 
 
 _DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
@@ -1165,14 +1074,15 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
             if on:
                 raise NotImplementedError(f"{what} with a {name} table: it is forward only")
     elif not adam and fused_sgd is not None and fused_sgd.lr is not None:
-        check_accumulator("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
-                          fused_sgd.accumulator, bool(fused_sgd.deterministic), fused_sgd.rounding)
+        optimizer = "rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd"
+        check_accumulator(optimizer, weight.dtype, fused_sgd.accumulator, bool(fused_sgd.deterministic),
+                          fused_sgd.rounding)
         if fused_sgd.accumulator == "step" and mode == "max":
             raise NotImplementedError("accumulator='step' with mode='max'")
-        check_weight_decay_path("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
-                                fused_sgd.weight_decay, bool(fused_sgd.deterministic), fused_sgd.lr, mode)
-        check_grad_clip_path("rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd", weight.dtype,
-                             fused_sgd.grad_clip, bool(fused_sgd.deterministic), fused_sgd.lr, mode)
+        check_weight_decay_path(optimizer, weight.dtype, fused_sgd.weight_decay, bool(fused_sgd.deterministic),
+                                fused_sgd.lr, mode)
+        check_grad_clip_path(optimizer, weight.dtype, fused_sgd.grad_clip, bool(fused_sgd.deterministic), fused_sgd.lr,
+                             mode)
         if isinstance(fused_sgd.lr, torch.Tensor):
             # asked again here: .lr, .deterministic and the weight can all change after the switch was built
             check_lr_path(check_lr(fused_sgd.lr), bool(fused_sgd.deterministic), mode)

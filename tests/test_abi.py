@@ -56,6 +56,54 @@ def test_every_declared_symbol_is_exported_and_bound():
         assert getattr(_lib.lib, n) is not None
 
 
+_C_SCALARS = {"float": ctypes.c_float, "double": ctypes.c_double, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+              "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
+
+
+def _ctype_matches(c_type: str, ctype) -> bool:
+    """one C parameter or return type (its name stripped) against one ctypes type: a pointer of any kind and
+    ce_stream_t are c_void_p, a POINTER(...) or -- a returned string -- c_char_p; a scalar is its own ctypes type"""
+    c_type = re.sub(r"\bconst\b", "", c_type).strip()
+    if c_type.endswith("*") or c_type == "ce_stream_t":
+        return ctype is ctypes.c_void_p or isinstance(ctype, type(ctypes.POINTER(ctypes.c_int))) or \
+            (ctype is ctypes.c_char_p and c_type.replace(" ", "") == "char*")
+    return c_type in _C_SCALARS and ctype is _C_SCALARS[c_type]
+
+
+def header_prototypes(prefix="ce_"):
+    """{name: (return type, [parameter types])} of every function include/ce_api.h declares whose name starts with
+    `prefix`, the types as the header spells them, without the parameters' names"""
+    body = re.sub(r"/\*.*?\*/|//[^\n]*", "", HEADER, flags=re.S)
+    body = re.sub(r"^[ \t]*#.*$", "", body, flags=re.M)                  # (no macro of the header spans lines)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(%s[a-z0-9_]+)\s*\(([^()]*)\)\s*;" % prefix, body):
+        params = [p.strip() for p in params.split(",")] if params.strip() not in ("", "void") else []
+        # `const float* grad_out` -> `const float*`: the last identifier of a parameter is its name
+        protos[name] = (ret.strip(), [re.sub(r"\s*\b\w+$", "", p) for p in params])
+    return protos
+
+
+def test_signatures_match_the_header_parameter_by_parameter():
+    """every entry of _lib.SIGNATURES -- the 80 ce_bag_* ones the fused updates go through, and the rest, which the same
+    rule reads without exceptions -- against its prototype: the return type and each parameter, in order.  No entry is
+    left out: a prototype this rule cannot read is a failure."""
+    from cachedembedding_amd import _lib
+    protos = header_prototypes()
+    bound = set(_lib.SIGNATURES)
+    assert set(protos) == bound, sorted(set(protos) ^ bound)
+    assert len([n for n in bound if n.startswith("ce_bag_")]) >= 80
+    wrong = []
+    for name in sorted(bound):
+        ret, params = protos[name]
+        restype, argtypes = _lib.SIGNATURES[name]
+        if not _ctype_matches(ret, restype):
+            wrong.append((name, "returns", ret, restype))
+        if len(params) != len(argtypes):
+            wrong.append((name, "parameters", len(params), len(argtypes)))
+        wrong += [(name, i, p, a) for i, (p, a) in enumerate(zip(params, argtypes)) if not _ctype_matches(p, a)]
+    assert not wrong, wrong
+
+
 def test_product_library_has_no_test_hooks_and_few_switches():
     """the fault / delay injection the worker tests need is compiled only into libce_hip_testhooks.so
     (-DCE_TEST_HOOKS); the product library carries neither the switches' names nor more than 20 environment switches
