@@ -14,27 +14,55 @@ import torch.nn as nn
 
 from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
-from .functional import (FusedAdagrad, FusedAdam, FusedRowwiseAdagrad, FusedSGD, check_accumulator, check_grad_clip,
-                         check_grad_clip_path, check_lr, check_lr_path, check_weight_decay, check_weight_decay_path,
-                         embedding_bag, refuse_grad_clip, refuse_weight_decay)
+from .functional import (FusedAdagrad, FusedAdam, FusedRowwiseAdagrad, FusedSGD, _at_least_0, _refuse_for_table,
+                         check_accumulator, check_grad_clip, check_grad_clip_path, check_lr, check_lr_path,
+                         check_weight_decay, check_weight_decay_path, embedding_bag, refuse_grad_clip,
+                         refuse_weight_decay)
 
 
-def _checked_weight_decay(module, optimizer: str, lr, deterministic: bool, weight_decay, weight_decay_mode) -> float:
-    """the checked decay of a set_fused_* call, with everything it is refused for known at that point"""
+def _checked_decay_and_clip(module, optimizer: str, lr, deterministic: bool, weight_decay, weight_decay_mode, grad_clip,
+                            grad_clip_mode) -> tuple:
+    """the checked decay (a float) and clip (a float or None) of a set_fused_* call, with everything they are refused
+    for known at that point; the module's table and mode are looked at only for one that is switched on"""
+    who = getattr(module, "_no_weight_decay", None)
     wd = check_weight_decay(weight_decay, weight_decay_mode)
-    refuse_weight_decay(getattr(module, "_no_weight_decay", None), wd)
+    refuse_weight_decay(who, wd)
     if lr is not None and wd:
         check_weight_decay_path(optimizer, module.table_dtype, wd, bool(deterministic), lr, module.mode)
-    return wd
-
-
-def _checked_grad_clip(module, optimizer: str, lr, deterministic: bool, grad_clip, grad_clip_mode):
-    """the checked clip of a set_fused_* call (a float or None), with everything it is refused for known at that point"""
     clip = check_grad_clip(grad_clip, grad_clip_mode)
-    refuse_grad_clip(getattr(module, "_no_weight_decay", None), clip)
+    refuse_grad_clip(who, clip)
     if lr is not None and clip is not None:
         check_grad_clip_path(optimizer, module.table_dtype, clip, bool(deterministic), lr, module.mode)
-    return clip
+    return wd, clip
+
+
+def _checked_by_accumulator(module, setter: str, optimizer: str, lr, deterministic, accumulator: str, *decay_and_clip):
+    """what set_fused_sgd and set_fused_rowwise_adagrad refuse alike, in this order; the checked (decay, clip)"""
+    _refuse_q8_update(module, setter, lr)
+    _refuse_adam_layout(module, setter, lr)
+    checked = _checked_decay_and_clip(module, optimizer, lr, deterministic, *decay_and_clip)
+    if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
+        check_lr_path(check_lr(lr), bool(deterministic), module.mode)
+    if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
+        check_accumulator(optimizer, module.table_dtype, accumulator, bool(deterministic), module.weight_rounding)
+    return checked
+
+
+def _checked_in_row(module, optimizer: str, lr, *per_row) -> tuple:
+    """what set_fused_adam and set_fused_adagrad refuse alike behind their layout check; the checked (decay, clip)"""
+    if isinstance(lr, torch.Tensor):
+        check_lr(lr)
+    elif lr is not None:
+        _at_least_0("lr", lr)
+    return _checked_decay_and_clip(module, optimizer, lr, False, *per_row)
+
+
+def _set_by_accumulator(switch, lr, deterministic, accumulator: str, wd, weight_decay_mode, clip, grad_clip_mode):
+    switch.lr = lr
+    switch.deterministic = deterministic
+    switch.accumulator = accumulator
+    switch.set_weight_decay(wd, weight_decay_mode)
+    switch.set_grad_clip(clip, grad_clip_mode)
 
 
 def _refuse_q8_update(module, what: str, lr) -> None:
@@ -83,8 +111,7 @@ class CachedEmbeddingBag(nn.Module):
         # refusals are the Adam layouts'.
         if fused_optimizer not in _lib.LAYOUTS:
             raise ValueError(f"fused_optimizer={fused_optimizer!r}: {_lib.LAYOUT_NAMES}")
-        if not float(initial_accumulator_value) >= 0.0:
-            raise ValueError(f"initial_accumulator_value={initial_accumulator_value!r}: must be >= 0")
+        _at_least_0("initial_accumulator_value", initial_accumulator_value)
         if initial_accumulator_value != 0.0 and fused_optimizer != "adagrad":
             raise ValueError(f"initial_accumulator_value={initial_accumulator_value!r} needs fused_optimizer='adagrad': "
                              "no other layout has an accumulator in its rows")
@@ -94,11 +121,8 @@ class CachedEmbeddingBag(nn.Module):
         elem = fused_optimizer == "adagrad"
         if adam:
             _lib.check_adam_table(embedding_dim, table_dtype, fused_optimizer)
-            for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
-                             ("sparse=True", bool(sparse))):
-                if on:
-                    raise NotImplementedError(f"{what} with an {'Adagrad' if elem else 'Adam'}-layout table "
-                                              f"(fused_optimizer={fused_optimizer!r})")
+            _refuse_for_table(f"an {'Adagrad' if elem else 'Adam'}-layout table (fused_optimizer={fused_optimizer!r})",
+                              mode, max_norm, sparse, None)
         # output_dtype (addition): dtype of the pooled output and of the gradient coming back -- None / torch.float32,
         # torch.bfloat16 or torch.float16 (functional.embedding_bag(output_dtype=...)).  `dtype` is the TABLE's dtype.
         if dtype not in (None, torch.float32):
@@ -120,10 +144,7 @@ class CachedEmbeddingBag(nn.Module):
         w16 = self.table_dtype in _lib.W16_DTYPES
         if q8:
             (_lib.check_q4_dim if bits == 4 else _lib.check_q8_dim)(embedding_dim)
-            for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
-                             ("sparse=True", bool(sparse))):
-                if on:
-                    raise NotImplementedError(f"{what} with a {_quant_name(bits)} table: it is forward only")
+            _refuse_for_table(f"a {_quant_name(bits)} table: it is forward only", mode, max_norm, sparse, None)
             if _weight is None and _table is None:
                 raise NotImplementedError(f"a {_quant_name(bits)} table is built from trained rows, it cannot be "
                                           "initialised: CachedEmbeddingBag.from_pretrained(embeddings, "
@@ -131,10 +152,7 @@ class CachedEmbeddingBag(nn.Module):
                                           "of a trained module")
         if w16:
             _lib.check_w16_dim(embedding_dim)
-            for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None),
-                             ("sparse=True", bool(sparse))):
-                if on:
-                    raise NotImplementedError(f"{what} with a 16-bit table (table_dtype={table_dtype})")
+            _refuse_for_table(f"a 16-bit table (table_dtype={table_dtype})", mode, max_norm, sparse, None)
         self.set_output_dtype(self.table_dtype if (w16 and output_dtype is None) else output_dtype)
         self.weight_rounding, self.weight_rounding_seed = "stochastic", 0
         _lib.require_gpu()
@@ -335,23 +353,13 @@ class CachedEmbeddingBag(nn.Module):
         which is refused here, before the first step.
         grad_clip / grad_clip_mode ("value" or "row_norm"; functional.check_grad_clip): a row's folded gradient of the
         step is clipped before the decay and the step see it.  Taken where the decay is, refused where it is."""
-        _refuse_q8_update(self, "set_fused_sgd", lr)
-        _refuse_adam_layout(self, "set_fused_sgd", lr)
-        wd = _checked_weight_decay(self, "sgd", lr, deterministic, weight_decay, weight_decay_mode)
-        clip = _checked_grad_clip(self, "sgd", lr, deterministic, grad_clip, grad_clip_mode)
-        if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
-            check_lr_path(check_lr(lr), bool(deterministic), self.mode)
-        if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
-            check_accumulator("sgd", self.table_dtype, accumulator, bool(deterministic), self.weight_rounding)
+        wd, clip = _checked_by_accumulator(self, "set_fused_sgd", "sgd", lr, deterministic, accumulator, weight_decay,
+                                           weight_decay_mode, grad_clip, grad_clip_mode)
         if lr is not None and self.fused_adagrad.lr is not None:
             raise ValueError("fused row-wise Adagrad is set: set_fused_rowwise_adagrad(None) before set_fused_sgd(lr)")
         if lr is not None and deterministic and self.table_dtype != torch.float32:
             raise NotImplementedError("FusedSGD(deterministic=True) with a 16-bit table")
-        self.fused_sgd.lr = lr
-        self.fused_sgd.deterministic = deterministic
-        self.fused_sgd.accumulator = accumulator
-        self.fused_sgd.set_weight_decay(wd, weight_decay_mode)
-        self.fused_sgd.set_grad_clip(clip, grad_clip_mode)
+        _set_by_accumulator(self.fused_sgd, lr, deterministic, accumulator, wd, weight_decay_mode, clip, grad_clip_mode)
 
     def set_fused_rowwise_adagrad(self, lr: Union[float, torch.Tensor, None], eps: float = 1e-8,
                                   deterministic: bool = False, accumulator: str = "cache", *,
@@ -371,26 +379,16 @@ class CachedEmbeddingBag(nn.Module):
         lr may be a tensor, as in set_fused_sgd; not with deterministic=True.
         grad_clip / grad_clip_mode ("value" or "row_norm"; functional.check_grad_clip): the row's folded gradient is
         clipped first; the decay, the sum of squares and the step see the clipped one.  Every path above takes it."""
-        _refuse_q8_update(self, "set_fused_rowwise_adagrad", lr)
-        _refuse_adam_layout(self, "set_fused_rowwise_adagrad", lr)
-        wd = _checked_weight_decay(self, "rowwise_adagrad", lr, deterministic, weight_decay, weight_decay_mode)
-        clip = _checked_grad_clip(self, "rowwise_adagrad", lr, deterministic, grad_clip, grad_clip_mode)
-        if isinstance(lr, torch.Tensor):                       # (a float or None: nothing new is looked at)
-            check_lr_path(check_lr(lr), bool(deterministic), self.mode)
-        if lr is not None or accumulator != "step":            # (an unknown value is refused whatever lr is)
-            check_accumulator("rowwise_adagrad", self.table_dtype, accumulator, bool(deterministic),
-                              self.weight_rounding)
+        wd, clip = _checked_by_accumulator(self, "set_fused_rowwise_adagrad", "rowwise_adagrad", lr, deterministic,
+                                           accumulator, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode)
         if lr is not None and self.fused_sgd.lr is not None:
             raise ValueError("fused SGD is set: set_fused_sgd(None) before set_fused_rowwise_adagrad(lr)")
         mgr = self.cache_weight_mgr
         if lr is not None and getattr(mgr, "momentum1", None) is None:
             mgr.momentum1 = torch.zeros(mgr.num_embeddings, device=mgr.device, dtype=torch.float32)
-        self.fused_adagrad.lr = lr
+        _set_by_accumulator(self.fused_adagrad, lr, bool(deterministic), accumulator, wd, weight_decay_mode, clip,
+                            grad_clip_mode)
         self.fused_adagrad.eps = float(eps)
-        self.fused_adagrad.deterministic = bool(deterministic)
-        self.fused_adagrad.accumulator = accumulator
-        self.fused_adagrad.set_weight_decay(wd, weight_decay_mode)
-        self.fused_adagrad.set_grad_clip(clip, grad_clip_mode)
         self.fused_adagrad.momentum = getattr(mgr, "momentum1", None)
         self.fused_adagrad.row_of_slot = mgr.cached_idx_map
 
@@ -414,12 +412,7 @@ class CachedEmbeddingBag(nn.Module):
         if self.fused_optimizer in (None, "adagrad"):
             raise ValueError("set_fused_adam needs a module built with fused_optimizer='adam' (or 'partial_rowwise_adam'): "
                              "Adam's moments live in the rows of the table")
-        if isinstance(lr, torch.Tensor):
-            check_lr(lr)
-        elif lr is not None and not float(lr) >= 0.0:
-            raise ValueError(f"lr={lr!r}: must be >= 0")
-        wd = _checked_weight_decay(self, "adam", lr, False, weight_decay, weight_decay_mode)
-        clip = _checked_grad_clip(self, "adam", lr, False, grad_clip, grad_clip_mode)
+        wd, clip = _checked_in_row(self, "adam", lr, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode)
         self.fused_adam.set(betas, eps, accumulator, deterministic, weight_decay=wd,       # (deterministic=True: refused;
                             weight_decay_mode=weight_decay_mode, grad_clip=clip,           # accumulator="sorted")
                             grad_clip_mode=grad_clip_mode)
@@ -440,12 +433,7 @@ class CachedEmbeddingBag(nn.Module):
         if self.fused_optimizer != "adagrad":
             raise ValueError("set_fused_adagrad needs a module built with fused_optimizer='adagrad': Adagrad's sums of "
                              "squares live in the rows of the table")
-        if isinstance(lr, torch.Tensor):
-            check_lr(lr)
-        elif lr is not None and not float(lr) >= 0.0:
-            raise ValueError(f"lr={lr!r}: must be >= 0")
-        wd = _checked_weight_decay(self, "adagrad", lr, False, weight_decay, weight_decay_mode)
-        clip = _checked_grad_clip(self, "adagrad", lr, False, grad_clip, grad_clip_mode)
+        wd, clip = _checked_in_row(self, "adagrad", lr, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode)
         self.fused_elementwise_adagrad.set(eps, lr_decay, accumulator, weight_decay=wd,
                                            weight_decay_mode=weight_decay_mode, grad_clip=clip,
                                            grad_clip_mode=grad_clip_mode)
@@ -568,9 +556,7 @@ class CachedEmbeddingBag(nn.Module):
         bad = set(overrides) - {"cuda_row_num", "output_dtype", "warmup_ratio", "buffer_size", "strict"}
         if bad:
             raise TypeError(f"quantized() got unexpected overrides {sorted(bad)}")
-        for what, on in (("mode='max'", self.mode == "max"), ("max_norm", self.max_norm is not None)):
-            if on:
-                raise NotImplementedError(f"{what} with a {_quant_name(bits)} table: it is forward only")
+        _refuse_for_table(f"a {_quant_name(bits)} table: it is forward only", self.mode, self.max_norm, False, None)
         (_lib.check_q4_dim if bits == 4 else _lib.check_q8_dim)(self.embedding_dim)
         mgr = self.cache_weight_mgr
         self.flush()

@@ -338,16 +338,10 @@ def check_lr(lr):
     return lr
 
 
-class _CheckedLr:
-    """`lr` of FusedSGD / FusedRowwiseAdagrad: check_lr runs on every assignment, a direct one included"""
-
-    @property
-    def lr(self):
-        return self._lr
-
-    @lr.setter
-    def lr(self, value):
-        self._lr = check_lr(value)
+def _at_least_0(name: str, value) -> float:
+    if not float(value) >= 0.0:
+        raise ValueError(f"{name}={value!r}: must be >= 0")
+    return float(value)
 
 
 # the in-row layouts' entries, ce_bag_backward_<stem>[_src]<suffix> and ce_bag_backward_<stem>_sorted: the suffix by what
@@ -608,10 +602,25 @@ def check_weight_decay(weight_decay, weight_decay_mode) -> float:
         raise ValueError(f"weight_decay_mode={weight_decay_mode!r}: 'l2' or 'decoupled'")
     if isinstance(weight_decay, torch.Tensor):
         raise ValueError("weight_decay is a float: only the learning rate may live in device memory")
-    wd = float(weight_decay)
-    if not wd >= 0.0:
-        raise ValueError(f"weight_decay={weight_decay!r}: must be >= 0")
-    return wd
+    return _at_least_0("weight_decay", weight_decay)
+
+
+def _refuse_per_row_path(what: str, does: str, optimizer: str, table_dtype, deterministic: bool, lr, mode) -> None:
+    """The decay and the clip both need the update's per-row pass: what either of them, switched on, is refused for.
+    what: "weight_decay" or "grad_clip"; does: what the pass would do with a row."""
+    if mode == "max":
+        raise NotImplementedError(f"{what} with mode='max': that update has no per-row pass")
+    if isinstance(lr, torch.Tensor) and deterministic:
+        raise NotImplementedError(f"{what} with a tensor learning rate and deterministic=True: the sorted updates "
+                                  "take a float")
+    if optimizer == "sgd" and table_dtype == torch.float32 and not deterministic:
+        raise NotImplementedError(f"{what} with fused SGD on an fp32 table: the atomic scatter has no per-row pass "
+                                  f"that could {does} -- set deterministic=True (the sorted update)")
+
+
+def _refuse_owner_side(what: str, lacks: str, who: str) -> None:
+    raise NotImplementedError(f"{what} is not implemented for {who}: its owner-side update is ce_rows_axpy, "
+                              f"which has no per-row {lacks}")
 
 
 def check_weight_decay_path(optimizer: str, table_dtype, weight_decay: float, deterministic: bool = False, lr=None,
@@ -619,23 +628,14 @@ def check_weight_decay_path(optimizer: str, table_dtype, weight_decay: float, de
     """Refusals of weight_decay != 0 (optimizer: "sgd", "rowwise_adagrad" or "adam"; table_dtype: the weight's, None:
     not known yet -- what depends on it is asked again before the forward).  Host logic only -- it is asked before the
     forward, so that nothing is refused after a kernel has run."""
-    if not weight_decay:
-        return
-    if mode == "max":
-        raise NotImplementedError("weight_decay with mode='max': that update has no per-row pass")
-    if isinstance(lr, torch.Tensor) and deterministic:
-        raise NotImplementedError("weight_decay with a tensor learning rate and deterministic=True: the sorted updates "
-                                  "take a float")
-    if optimizer == "sgd" and table_dtype == torch.float32 and not deterministic:
-        raise NotImplementedError("weight_decay with fused SGD on an fp32 table: the atomic scatter has no per-row "
-                                  "pass that could decay a row once -- set deterministic=True (the sorted update)")
+    if weight_decay:
+        _refuse_per_row_path("weight_decay", "decay a row once", optimizer, table_dtype, deterministic, lr, mode)
 
 
 def refuse_weight_decay(who: Optional[str], weight_decay) -> None:
     """the sharded and table-wise modules: their owner-side update is ce_rows_axpy, which has no decay"""
     if who and weight_decay:
-        raise NotImplementedError(f"weight_decay is not implemented for {who}: its owner-side update is ce_rows_axpy, "
-                                  "which has no per-row decay")
+        _refuse_owner_side("weight_decay", "decay", who)
 
 
 def _workspace_in_row_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
@@ -649,15 +649,6 @@ def _workspace_sorted(self, num_rows: int, nnz: int, dim: int, device) -> torch.
     """workspace of ce_bag_backward_update_sorted* (sort arrays, partial rows): nothing in it needs initialising"""
     need = lib.ce_bag_backward_update_sorted_workspace(num_rows, nnz, dim)
     return _cached_bytes(self, "_ws_sorted", need, device, zero=False)
-
-
-class _WeightDecay:
-    """`weight_decay` / `weight_decay_mode` of the fused switches: checked on every set_weight_decay"""
-    weight_decay, weight_decay_mode = 0.0, "l2"
-
-    def set_weight_decay(self, weight_decay: float = 0.0, weight_decay_mode: str = "l2") -> None:
-        self.weight_decay = check_weight_decay(weight_decay, weight_decay_mode)
-        self.weight_decay_mode = weight_decay_mode
 
 
 GRAD_CLIP_MODES = ("value", "row_norm")
@@ -687,30 +678,38 @@ def check_grad_clip_path(optimizer: str, table_dtype, grad_clip: Optional[float]
     """Refusals of grad_clip is not None: those of check_weight_decay_path, for the same reasons (the clip needs the
     per-row pass the decay needs).  Host logic only -- it is asked before the forward, so that nothing is refused
     after a kernel has run."""
-    if grad_clip is None:
-        return
-    if mode == "max":
-        raise NotImplementedError("grad_clip with mode='max': that update has no per-row pass")
-    if isinstance(lr, torch.Tensor) and deterministic:
-        raise NotImplementedError("grad_clip with a tensor learning rate and deterministic=True: the sorted updates "
-                                  "take a float")
-    if optimizer == "sgd" and table_dtype == torch.float32 and not deterministic:
-        raise NotImplementedError("grad_clip with fused SGD on an fp32 table: the atomic scatter has no per-row pass "
-                                  "that could clip a row's folded gradient -- set deterministic=True (the sorted update)")
+    if grad_clip is not None:
+        _refuse_per_row_path("grad_clip", "clip a row's folded gradient", optimizer, table_dtype, deterministic, lr, mode)
 
 
 def refuse_grad_clip(who: Optional[str], grad_clip) -> None:
     """the sharded and table-wise modules: their owner-side update is ce_rows_axpy, which has no clip"""
     if who and grad_clip is not None:
-        raise NotImplementedError(f"grad_clip is not implemented for {who}: its owner-side update is ce_rows_axpy, "
-                                  "which has no per-row clip")
+        _refuse_owner_side("grad_clip", "clip", who)
 
 
-class _GradClip:
-    """`grad_clip` / `grad_clip_mode` of the fused switches: checked on every set_grad_clip.  The clip
-    acts on a row's folded gradient of the step before everything else reads it -- the decay, the sums of squares, the
-    moments, the step."""
+class _FusedSwitch:
+    """What the four switches share.  `optimizer`: the name the check_* functions know the switch by.  `lr`: check_lr
+    runs on every assignment, a direct one included.  `weight_decay` / `weight_decay_mode` and `grad_clip` /
+    `grad_clip_mode` are checked on every set_weight_decay / set_grad_clip; the clip acts on a
+    row's folded gradient of the step before everything else reads it -- the decay, the sums of squares, the moments, the
+    step.  The workspaces (the workspace* methods fill the slots a switch uses) start out empty."""
+    optimizer: str
+    weight_decay, weight_decay_mode = 0.0, "l2"
     grad_clip, grad_clip_mode = None, "value"
+    _ws = _ws16 = _ws_step = _ws_step_key = _ws_sorted = None
+
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        self._lr = check_lr(value)
+
+    def set_weight_decay(self, weight_decay: float = 0.0, weight_decay_mode: str = "l2") -> None:
+        self.weight_decay = check_weight_decay(weight_decay, weight_decay_mode)
+        self.weight_decay_mode = weight_decay_mode
 
     def set_grad_clip(self, grad_clip: Optional[float] = None, grad_clip_mode: str = "value") -> None:
         self.grad_clip = check_grad_clip(grad_clip, grad_clip_mode)
@@ -720,8 +719,22 @@ class _GradClip:
         """(grad_clip, grad_clip_mode) as the ce_*_clip entries take them"""
         return (float(self.grad_clip), _GRAD_CLIP_CODES[self.grad_clip_mode])
 
+    def _init_by_accumulator(self, lr, deterministic: bool, accumulator: str, weight_decay, weight_decay_mode,
+                             grad_clip, grad_clip_mode) -> None:
+        """FusedSGD's and FusedRowwiseAdagrad's constructors: what they refuse while the table is not known yet"""
+        check_accumulator(self.optimizer, None, accumulator, deterministic)
+        check_lr_path(check_lr(lr), deterministic)
+        self.set_weight_decay(weight_decay, weight_decay_mode)
+        check_weight_decay_path(self.optimizer, None, self.weight_decay, deterministic, lr)
+        self.set_grad_clip(grad_clip, grad_clip_mode)
+        check_grad_clip_path(self.optimizer, None, self.grad_clip, deterministic, lr)
+        self.lr, self.accumulator = lr, accumulator
 
-class FusedSGD(_CheckedLr, _WeightDecay, _GradClip):
+    workspace_w16 = _workspace_w16
+    workspace_step = _workspace_step
+
+
+class FusedSGD(_FusedSwitch):
     """Switch for the fused backward+SGD path of one embedding module.
 
     lr=None disables fusion (the module behaves exactly like nn.EmbeddingBag under
@@ -736,35 +749,23 @@ class FusedSGD(_CheckedLr, _WeightDecay, _GradClip):
     with deterministic=True only (the atomic scatter has no per-row pass); not with mode='max'.
     grad_clip, grad_clip_mode ("value" / "row_norm"; check_grad_clip): the row's folded gradient is
     clipped before the decay and the step see it.  Where the decay is taken, and nowhere else."""
+    optimizer = "sgd"
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, deterministic: bool = False,
                  accumulator: str = "cache", *, weight_decay: float = 0.0, weight_decay_mode: str = "l2",
                  grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
-        check_accumulator("sgd", None, accumulator, bool(deterministic))
-        check_lr_path(check_lr(lr), bool(deterministic))
-        self.set_weight_decay(weight_decay, weight_decay_mode)
-        check_weight_decay_path("sgd", None, self.weight_decay, bool(deterministic), lr)
-        self.set_grad_clip(grad_clip, grad_clip_mode)
-        check_grad_clip_path("sgd", None, self.grad_clip, bool(deterministic), lr)
-        self._ws_sorted = None
-        self.lr = lr
+        self._init_by_accumulator(lr, bool(deterministic), accumulator, weight_decay, weight_decay_mode, grad_clip,
+                                  grad_clip_mode)
         self.deterministic = deterministic
-        self.accumulator = accumulator
-        self._ws_step, self._ws_step_key = None, None
-        self._ws = None
         # a 16-bit table only: how the update rounds a row ("nearest" / "stochastic"), the seed of the random bits and
         # the host-table row of every slot they are drawn for (None: the slot itself)
         self.rounding, self.seed, self.row_of_slot = "stochastic", 0, None
-        self._ws16 = None
-
-    workspace_w16 = _workspace_w16
-    workspace_step = _workspace_step
 
     def workspace(self, num_rows: int, nnz: int, device) -> torch.Tensor:
         return _cached_bytes(self, "_ws", lib.ce_bag_backward_sgd_sorted_workspace(num_rows, nnz), device, zero=False)
 
 
-class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay, _GradClip):
+class FusedRowwiseAdagrad(_FusedSwitch):
     """Switch for the fused backward + exact row-wise Adagrad update of one embedding module (FBGEMM's
     EXACT_ROWWISE_ADAGRAD; weight_decay_mode "l2" / "decoupled" are its L2 / DECOUPLE).  Per step and per UNIQUE row r the step looks up, with g the sum of the
     row's gradient rows in the batch:  m[r] += sum(g * g) / D ;  W[r] -= lr * g / (sqrt(m[r]) + eps).
@@ -792,31 +793,19 @@ class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay, _GradClip):
 
     grad_clip, grad_clip_mode ("value" / "row_norm"; check_grad_clip): g is clipped first, and the
     decay's h, sum(h * h) / D and the step all see the clipped g.  Every path above takes it."""
+    optimizer = "rowwise_adagrad"
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, eps: float = 1e-8,
                  momentum: Optional[torch.Tensor] = None, row_of_slot: Optional[torch.Tensor] = None,
                  deterministic: bool = False, accumulator: str = "cache", *, weight_decay: float = 0.0,
                  weight_decay_mode: str = "l2", grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
-        check_accumulator("rowwise_adagrad", None, accumulator, bool(deterministic))
-        check_lr_path(check_lr(lr), bool(deterministic))
-        self.set_weight_decay(weight_decay, weight_decay_mode)
-        check_weight_decay_path("rowwise_adagrad", None, self.weight_decay, bool(deterministic), lr)
-        self.set_grad_clip(grad_clip, grad_clip_mode)
-        check_grad_clip_path("rowwise_adagrad", None, self.grad_clip, bool(deterministic), lr)
-        self.lr = lr
+        self._init_by_accumulator(lr, bool(deterministic), accumulator, weight_decay, weight_decay_mode, grad_clip,
+                                  grad_clip_mode)
         self.deterministic = bool(deterministic)
-        self.accumulator = accumulator
-        self._ws_step, self._ws_step_key = None, None
-        self._ws_sorted = None
         self.eps = float(eps)
         self.momentum = momentum
         self.row_of_slot = row_of_slot
-        self._ws = None
         self.rounding, self.seed = "stochastic", 0          # a 16-bit table only (see FusedSGD)
-        self._ws16 = None
-
-    workspace_w16 = _workspace_w16
-    workspace_step = _workspace_step
 
     def check(self, weight: torch.Tensor) -> None:
         """refusals that must come before any kernel of the step has run"""
@@ -843,7 +832,64 @@ class FusedRowwiseAdagrad(_CheckedLr, _WeightDecay, _GradClip):
         return _cached_bytes(self, "_ws", need, device, zero=True)
 
 
-class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
+class _InRowSwitch(_FusedSwitch):
+    """What FusedAdam and FusedAdagrad share: the table's rows carry the optimizer's state behind their w part (`span`
+    parts of D floats, `layout` says which), the step count is one int64 on the device, and the accumulator -- "sorted"
+    is the deterministic fold here -- picks the workspace."""
+    deterministic = False                                   # (the sorted fold is accumulator="sorted" here)
+    rounding, seed = "nearest", 0
+    _name: str                                              # "Adam" / "Adagrad", as the refusals spell it
+    _cache_workspace: str                                   # the library's size function of accumulator="cache"
+
+    def _set_head(self, deterministic: bool, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode) -> tuple:
+        """how every set() begins: the checked (decay, clip), and deterministic=True refused"""
+        wd = check_weight_decay(weight_decay, weight_decay_mode)
+        clip = check_grad_clip(grad_clip, grad_clip_mode)
+        if deterministic:
+            raise NotImplementedError(f"fused {self._name} with deterministic=True: the deterministic (sorted) fold of "
+                                      f"an {self._name}-layout table is accumulator='sorted'")
+        return wd, clip
+
+    def _set_tail(self, accumulator: str, wd: float, weight_decay_mode: str, clip, grad_clip_mode: str) -> None:
+        """how every set() ends: the last check, then the first store -- a refused set() changes nothing"""
+        if accumulator not in IN_ROW_ACCUMULATORS:
+            raise ValueError(f"accumulator={accumulator!r}: 'cache', 'step' or 'sorted'")
+        self.accumulator = accumulator
+        self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
+        self.grad_clip, self.grad_clip_mode = clip, grad_clip_mode
+
+    def check(self, weight: torch.Tensor) -> None:
+        """refusals that must come before any kernel of the step has run"""
+        if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] % self.span != 0:
+            raise NotImplementedError(f"Fused{self._name} needs an fp32 weight of {self._name}-layout rows, [rows, "
+                                      f"{self.span} * embedding_dim] (got {tuple(weight.shape)} {weight.dtype})")
+        _lib.check_adam_dim(weight.shape[1] // self.span)
+        if self.lr is None:
+            return
+        if not isinstance(self.lr, torch.Tensor):
+            _at_least_0("lr", self.lr)
+        st = self.step
+        if st is None or not st.is_cuda or st.dtype != torch.int64 or st.numel() != 1 or st.device != weight.device:
+            raise ValueError(f"fused {self._name} needs its step count: one int64 element on the weight's device")
+        if self.layout == "partial_rowwise_adam":
+            self.check_row_state(weight)                    # (FusedAdam's own)
+
+    def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
+        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again ("sorted": nothing
+        # in it needs initialising)
+        if self.accumulator == "sorted":
+            return _workspace_in_row_sorted(self, num_rows, nnz, dim, device)
+        if self.accumulator == "step":
+            return _workspace_step(self, num_rows, nnz, dim, device)
+        need = getattr(lib, self._cache_workspace)(num_rows, nnz, dim, _lib.CE_ACC_CACHE)
+        return _cached_bytes(self, "_ws", need, device, zero=True)
+
+
+# the switches that say the weight's rows carry optimizer state behind their w part (span parts of D floats)
+_IN_ROW = _InRowSwitch
+
+
+class FusedAdam(_InRowSwitch):
     """Switch for the fused backward + Adam update of one embedding module whose table carries its moments: the weight
     the kernels see is [rows, 3 * D] fp32, every row w | m | v.  torch.optim.SparseAdam's arithmetic,
     per step and per UNIQUE row the step looks up, g the sum of the row's gradient rows in the batch, t the step count:
@@ -870,9 +916,7 @@ class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
     row_of_slot[slot] (int32 [rows]; None: by slot), as FusedRowwiseAdagrad's momentum is:
         v[r] += (1 - beta2) (mean_d (g_d g_d) - v[r]) ;  w -= lr c_t * m / (sqrt(v[r]) + eps)
     A slot whose row_of_slot lies outside [0, v_rows) is left alone."""
-
-    deterministic = False                                   # (the sorted fold is accumulator="sorted" here)
-    rounding, seed = "nearest", 0
+    optimizer, _name, _cache_workspace = "adam", "Adam", "ce_bag_backward_adam_workspace"
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  accumulator: str = "step", step: Optional[torch.Tensor] = None, deterministic: bool = False, *,
@@ -887,64 +931,31 @@ class FusedAdam(_CheckedLr, _WeightDecay, _GradClip):
         self.set(betas, eps, accumulator, deterministic, weight_decay=weight_decay, weight_decay_mode=weight_decay_mode,
                  grad_clip=grad_clip, grad_clip_mode=grad_clip_mode)
         self.step = step
-        self._ws_step, self._ws_step_key = None, None
-        self._ws = None
-        self._ws_sorted = None
 
     def set(self, betas, eps: float, accumulator: str, deterministic: bool = False, *, weight_decay: float = 0.0,
             weight_decay_mode: str = "l2", grad_clip: Optional[float] = None, grad_clip_mode: str = "value") -> None:
-        wd = check_weight_decay(weight_decay, weight_decay_mode)
-        clip = check_grad_clip(grad_clip, grad_clip_mode)
-        if deterministic:
-            raise NotImplementedError("fused Adam with deterministic=True: the deterministic (sorted) fold of an "
-                                      "Adam-layout table is accumulator='sorted'")
+        wd, clip = self._set_head(deterministic, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode)
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas={tuple(betas)!r}: both must lie in [0, 1)")
-        if not float(eps) >= 0.0:
-            raise ValueError(f"eps={eps!r}: must be >= 0")
-        if accumulator not in IN_ROW_ACCUMULATORS:
-            raise ValueError(f"accumulator={accumulator!r}: 'cache', 'step' or 'sorted'")
-        self.betas, self.eps, self.accumulator = (b1, b2), float(eps), accumulator
-        self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
-        self.grad_clip, self.grad_clip_mode = clip, grad_clip_mode
+        eps = _at_least_0("eps", eps)
+        self._set_tail(accumulator, wd, weight_decay_mode, clip, grad_clip_mode)
+        self.betas, self.eps = (b1, b2), eps
 
-    def check(self, weight: torch.Tensor) -> None:
-        """refusals that must come before any kernel of the step has run"""
-        if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] % self.span != 0:
-            raise NotImplementedError(f"FusedAdam needs an fp32 weight of Adam-layout rows, [rows, {self.span} * "
-                                      f"embedding_dim] (got {tuple(weight.shape)} {weight.dtype})")
-        _lib.check_adam_dim(weight.shape[1] // self.span)
-        if self.lr is None:
-            return
-        if not isinstance(self.lr, torch.Tensor) and not float(self.lr) >= 0.0:
-            raise ValueError(f"lr={self.lr!r}: must be >= 0")
-        st = self.step
-        if st is None or not st.is_cuda or st.dtype != torch.int64 or st.numel() != 1 or st.device != weight.device:
-            raise ValueError("fused Adam needs its step count: one int64 element on the weight's device")
-        if self.layout == "partial_rowwise_adam":
-            v, ros = self.exp_avg_sq, self.row_of_slot
-            if v is None or v.dtype != torch.float32 or v.device != weight.device or not v.is_contiguous() or \
-                    v.numel() == 0:
-                raise ValueError("partial row-wise Adam needs exp_avg_sq: a contiguous fp32 tensor, one element per "
-                                 "table row, on the weight's device")
-            if ros is not None and (ros.dtype != torch.int32 or ros.device != weight.device or not ros.is_contiguous()
-                                    or ros.numel() < weight.shape[0]):
-                raise ValueError("row_of_slot: a contiguous int32 tensor of one element per row of the weight, on its "
-                                 "device")
-
-    def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
-        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again ("sorted": nothing
-        # in it needs initialising)
-        if self.accumulator == "sorted":
-            return _workspace_in_row_sorted(self, num_rows, nnz, dim, device)
-        if self.accumulator == "step":
-            return _workspace_step(self, num_rows, nnz, dim, device)
-        need = lib.ce_bag_backward_adam_workspace(num_rows, nnz, dim, _lib.CE_ACC_CACHE)
-        return _cached_bytes(self, "_ws", need, device, zero=True)
+    def check_row_state(self, weight: torch.Tensor) -> None:
+        """the partial layout's part of check(): the per-row second moment and its map"""
+        v, ros = self.exp_avg_sq, self.row_of_slot
+        if v is None or v.dtype != torch.float32 or v.device != weight.device or not v.is_contiguous() or \
+                v.numel() == 0:
+            raise ValueError("partial row-wise Adam needs exp_avg_sq: a contiguous fp32 tensor, one element per "
+                             "table row, on the weight's device")
+        if ros is not None and (ros.dtype != torch.int32 or ros.device != weight.device or not ros.is_contiguous()
+                                or ros.numel() < weight.shape[0]):
+            raise ValueError("row_of_slot: a contiguous int32 tensor of one element per row of the weight, on its "
+                             "device")
 
 
-class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
+class FusedAdagrad(_InRowSwitch):
     """Switch for the fused backward + element-wise Adagrad update (torch.optim.Adagrad; FBGEMM's EXACT_ADAGRAD) of one
     embedding module whose table carries its state: the weight the kernels see is [rows, 2 * D] fp32, every row w | h, h
     the per-element sums of squared gradients.  Per step and per UNIQUE row the step looks up, g the sum
@@ -961,8 +972,7 @@ class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
     torch.optim.Adagrad(weight_decay=) -- g + weight_decay * w takes the place of g --, "decoupled" scales w by
     1 - clr * weight_decay first.  grad_clip, grad_clip_mode (check_grad_clip): g is clipped first."""
 
-    deterministic = False                                   # (the sorted fold is accumulator="sorted" here)
-    rounding, seed = "nearest", 0
+    optimizer, _name, _cache_workspace = "adagrad", "Adagrad", "ce_bag_backward_adagrad_workspace"
     layout, span = "adagrad", 2
 
     def __init__(self, lr: Union[float, torch.Tensor, None] = None, eps: float = 1e-10, lr_decay: float = 0.0,
@@ -973,55 +983,89 @@ class FusedAdagrad(_CheckedLr, _WeightDecay, _GradClip):
         self.set(eps, lr_decay, accumulator, deterministic, weight_decay=weight_decay,
                  weight_decay_mode=weight_decay_mode, grad_clip=grad_clip, grad_clip_mode=grad_clip_mode)
         self.step = step
-        self._ws_step, self._ws_step_key = None, None
-        self._ws = None
-        self._ws_sorted = None
 
     def set(self, eps: float, lr_decay: float, accumulator: str, deterministic: bool = False, *,
             weight_decay: float = 0.0, weight_decay_mode: str = "l2", grad_clip: Optional[float] = None,
             grad_clip_mode: str = "value") -> None:
-        wd = check_weight_decay(weight_decay, weight_decay_mode)
-        clip = check_grad_clip(grad_clip, grad_clip_mode)
-        if deterministic:
-            raise NotImplementedError("fused Adagrad with deterministic=True: the deterministic (sorted) fold of an "
-                                      "Adagrad-layout table is accumulator='sorted'")
-        if not float(eps) >= 0.0:
-            raise ValueError(f"eps={eps!r}: must be >= 0")
-        if not float(lr_decay) >= 0.0:
-            raise ValueError(f"lr_decay={lr_decay!r}: must be >= 0")
-        if accumulator not in IN_ROW_ACCUMULATORS:
-            raise ValueError(f"accumulator={accumulator!r}: 'cache', 'step' or 'sorted'")
-        self.eps, self.lr_decay, self.accumulator = float(eps), float(lr_decay), accumulator
-        self.weight_decay, self.weight_decay_mode = wd, weight_decay_mode
-        self.grad_clip, self.grad_clip_mode = clip, grad_clip_mode
-
-    def check(self, weight: torch.Tensor) -> None:
-        """refusals that must come before any kernel of the step has run"""
-        if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] % 2 != 0:
-            raise NotImplementedError("FusedAdagrad needs an fp32 weight of Adagrad-layout rows, [rows, 2 * "
-                                      f"embedding_dim] (got {tuple(weight.shape)} {weight.dtype})")
-        _lib.check_adam_dim(weight.shape[1] // 2)
-        if self.lr is None:
-            return
-        if not isinstance(self.lr, torch.Tensor) and not float(self.lr) >= 0.0:
-            raise ValueError(f"lr={self.lr!r}: must be >= 0")
-        st = self.step
-        if st is None or not st.is_cuda or st.dtype != torch.int64 or st.numel() != 1 or st.device != weight.device:
-            raise ValueError("fused Adagrad needs its step count: one int64 element on the weight's device")
-
-    def workspace(self, num_rows: int, nnz: int, dim: int, device) -> torch.Tensor:
-        # zero-filled once; every call of the kernels leaves what must be zero zero-filled again ("sorted": nothing
-        # in it needs initialising)
-        if self.accumulator == "sorted":
-            return _workspace_in_row_sorted(self, num_rows, nnz, dim, device)
-        if self.accumulator == "step":
-            return _workspace_step(self, num_rows, nnz, dim, device)
-        need = lib.ce_bag_backward_adagrad_workspace(num_rows, nnz, dim, _lib.CE_ACC_CACHE)
-        return _cached_bytes(self, "_ws", need, device, zero=True)
+        wd, clip = self._set_head(deterministic, weight_decay, weight_decay_mode, grad_clip, grad_clip_mode)
+        eps, lr_decay = _at_least_0("eps", eps), _at_least_0("lr_decay", lr_decay)
+        self._set_tail(accumulator, wd, weight_decay_mode, clip, grad_clip_mode)
+        self.eps, self.lr_decay = eps, lr_decay
 
 
-# the switches that say the weight's rows carry optimizer state behind their w part (span parts of D floats)
-_IN_ROW = (FusedAdam, FusedAdagrad)
+def _refuse_for_table(table: str, mode, max_norm, sparse, per_sample_weights, more=()) -> None:
+    """What only a plain fp32 table takes: mode='max', max_norm, sparse=True, and -- listed last -- a gradient w.r.t.
+    per_sample_weights.  table: how the refusal names the table; more: the table kind's own rows, (what, is it on)."""
+    what = "mode='max'" if mode == "max" else "max_norm" if max_norm is not None else "sparse=True" if sparse else None
+    for row, on in more:
+        if on and what is None:
+            what = row
+    if what is None and per_sample_weights is not None and per_sample_weights.requires_grad and torch.is_grad_enabled():
+        what = "a gradient w.r.t. per_sample_weights"
+    if what is not None:
+        raise NotImplementedError(f"{what} with {table}")
+
+
+def _check_lr_device(lr: torch.Tensor, weight) -> None:
+    if lr.device != weight.device:
+        raise ValueError(f"the learning-rate tensor is on {lr.device}, the weight on {weight.device}: the kernels read "
+                         "it from device memory")
+
+
+def check_front(fused, weight: torch.Tensor, mode: str, max_norm, sparse, per_sample_weights, output_dtype,
+                quant_bits: int = 8):
+    """Everything embedding_bag refuses for its switch and its table, before any kernel has run -- a refusal inside
+    backward would leave the caller with an exception AND an updated table.  Host logic only.  Returns the output dtype
+    the call resolves to.  Of two refusals the earlier stage wins (DESIGN.md 3.18 lists the stages and says where a new
+    optimizer adds its rows); a switch is asked again here because its fields and the weight can change after it was
+    built or set."""
+    _lib.act_code(output_dtype)
+    update = fused is not None and fused.lr is not None
+    in_row = isinstance(fused, _IN_ROW)
+    if in_row:
+        # the switch is what says the rows carry state: [R, 3 * D] w | m | v, or [R, 2 * D] w | m or w | h
+        fused.check(weight)
+        _refuse_for_table(f"an {fused._name}-layout table", mode, max_norm, sparse, per_sample_weights)
+        if isinstance(fused.lr, torch.Tensor):
+            _check_lr_device(check_lr(fused.lr), weight)
+    if weight.dtype == _lib.Q8:
+        # a row-wise quantized table ([R, 16 + D] uint8 q8 rows, or [R, 16 + D / 2] q4 rows with quant_bits=4): forward
+        # only, the output defaults to fp32
+        name = "q4 (torch.quint4x2)" if _lib.check_quant_bits(quant_bits) == 4 else "q8 (torch.uint8)"
+        if weight.dim() != 2:
+            raise ValueError(f"a {name} weight is a [rows, 16 + embedding_dim{' / 2' if quant_bits == 4 else ''}] tensor")
+        (_lib.check_q4_dim if quant_bits == 4 else _lib.check_q8_dim)(_quant_dim(weight.shape[1], quant_bits))
+        _refuse_for_table(f"a {name} table: it is forward only", mode, max_norm, sparse, per_sample_weights,
+                          (("a fused SGD / row-wise Adagrad update (a quantized table is never updated)", update),))
+    elif update and not in_row:
+        # fused SGD and row-wise Adagrad: what depends on the table's dtype and on the mode
+        det = bool(fused.deterministic)
+        check_accumulator(fused.optimizer, weight.dtype, fused.accumulator, det, fused.rounding)
+        if fused.accumulator == "step" and mode == "max":
+            raise NotImplementedError("accumulator='step' with mode='max'")
+        check_weight_decay_path(fused.optimizer, weight.dtype, fused.weight_decay, det, fused.lr, mode)
+        check_grad_clip_path(fused.optimizer, weight.dtype, fused.grad_clip, det, fused.lr, mode)
+        if isinstance(fused.lr, torch.Tensor):
+            check_lr_path(check_lr(fused.lr), det, mode)
+            _check_lr_device(fused.lr, weight)
+    if weight.dtype in _lib.W16_DTYPES:
+        # a 16-bit table (bf16 / fp16 weight): rows up-converted exactly, fp32 sums, the output defaults to the
+        # weight's dtype
+        _lib.check_w16_dim(weight.shape[1])
+        sorted16 = update and fused.deterministic and fused.optimizer
+        _refuse_for_table(f"a 16-bit table ({weight.dtype})", mode, max_norm, sparse, per_sample_weights,
+                          (("FusedSGD(deterministic=True)", sorted16 == "sgd"),
+                           ("FusedRowwiseAdagrad(deterministic=True) with rounding='stochastic' (set rounding='nearest')",
+                            sorted16 == "rowwise_adagrad" and fused.rounding == "stochastic")))
+        if output_dtype is None:
+            output_dtype = weight.dtype
+    if mode not in _MODES and mode != "max":
+        raise NotImplementedError(f"mode={mode!r}: 'sum', 'mean' and 'max' are implemented")
+    if update and fused.optimizer == "rowwise_adagrad":
+        if mode == "max":
+            raise NotImplementedError("fused row-wise Adagrad with mode='max'")
+        fused.check(weight)
+    return torch.float32 if output_dtype is None else output_dtype
 
 
 def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional[torch.Tensor] = None,
@@ -1040,83 +1084,10 @@ def embedding_bag(indices: torch.Tensor, weight: torch.Tensor, offsets: Optional
     # output_dtype: None / torch.float32 (the default), torch.bfloat16 or torch.float16 -- the dtype of the pooled output
     # and hence of the gradient autograd hands back; the weight, the sums and every update stay fp32, the kernels
     # round once on the store and read the 16-bit gradient in place.  out= must then have that dtype.
-    _lib.act_code(output_dtype)               # anything else is refused before any kernel runs
+    output_dtype = check_front(fused_sgd, weight, mode, max_norm, sparse, per_sample_weights, output_dtype, quant_bits)
     q8 = weight.dtype == _lib.Q8
-    adam = isinstance(fused_sgd, _IN_ROW)
-    if adam:
-        # (FusedAdagrad: [R, 2 * D] rows w | h -- the same refusals)
-        # an Adam-layout table ([R, 3 * D] fp32 rows w | m | v; the FusedAdam object is what says so): what it does not
-        # take is refused here, before any kernel has run
-        fused_sgd.check(weight)
-        for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
-                         ("a gradient w.r.t. per_sample_weights",
-                          per_sample_weights is not None and per_sample_weights.requires_grad
-                          and torch.is_grad_enabled())):
-            if on:
-                raise NotImplementedError(f"{what} with an {'Adagrad' if fused_sgd.layout == 'adagrad' else 'Adam'}"
-                                          "-layout table")
-        if isinstance(fused_sgd.lr, torch.Tensor) and check_lr(fused_sgd.lr).device != weight.device:
-            raise ValueError(f"the learning-rate tensor is on {fused_sgd.lr.device}, the weight on "
-                             f"{weight.device}: the kernels read it from device memory")
-    if q8:
-        # a row-wise quantized table ([R, 16 + D] uint8 q8 rows, or [R, 16 + D / 2] q4 rows with quant_bits=4): forward
-        # only, the output defaults to fp32.  What it does not take is refused here, before any kernel has run.
-        name = "q4 (torch.quint4x2)" if _lib.check_quant_bits(quant_bits) == 4 else "q8 (torch.uint8)"
-        if weight.dim() != 2:
-            raise ValueError(f"a {name} weight is a [rows, 16 + embedding_dim{' / 2' if quant_bits == 4 else ''}] tensor")
-        (_lib.check_q4_dim if quant_bits == 4 else _lib.check_q8_dim)(_quant_dim(weight.shape[1], quant_bits))
-        for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
-                         ("a fused SGD / row-wise Adagrad update (a quantized table is never updated)",
-                          fused_sgd is not None and fused_sgd.lr is not None),
-                         ("a gradient w.r.t. per_sample_weights",
-                          per_sample_weights is not None and per_sample_weights.requires_grad
-                          and torch.is_grad_enabled())):
-            if on:
-                raise NotImplementedError(f"{what} with a {name} table: it is forward only")
-    elif not adam and fused_sgd is not None and fused_sgd.lr is not None:
-        optimizer = "rowwise_adagrad" if isinstance(fused_sgd, FusedRowwiseAdagrad) else "sgd"
-        check_accumulator(optimizer, weight.dtype, fused_sgd.accumulator, bool(fused_sgd.deterministic),
-                          fused_sgd.rounding)
-        if fused_sgd.accumulator == "step" and mode == "max":
-            raise NotImplementedError("accumulator='step' with mode='max'")
-        check_weight_decay_path(optimizer, weight.dtype, fused_sgd.weight_decay, bool(fused_sgd.deterministic),
-                                fused_sgd.lr, mode)
-        check_grad_clip_path(optimizer, weight.dtype, fused_sgd.grad_clip, bool(fused_sgd.deterministic), fused_sgd.lr,
-                             mode)
-        if isinstance(fused_sgd.lr, torch.Tensor):
-            # asked again here: .lr, .deterministic and the weight can all change after the switch was built
-            check_lr_path(check_lr(fused_sgd.lr), bool(fused_sgd.deterministic), mode)
-            if fused_sgd.lr.device != weight.device:
-                raise ValueError(f"the learning-rate tensor is on {fused_sgd.lr.device}, the weight on "
-                                 f"{weight.device}: the kernels read it from device memory")
-    if weight.dtype in _lib.W16_DTYPES:
-        # a 16-bit table (bf16 / fp16 weight): rows up-converted exactly, fp32 sums, the output defaults to the
-        # weight's dtype.  What it does not take is refused here, before any kernel has run.
-        _lib.check_w16_dim(weight.shape[1])
-        sgd16 = isinstance(fused_sgd, FusedSGD) and fused_sgd.lr is not None
-        det16 = isinstance(fused_sgd, FusedRowwiseAdagrad) and fused_sgd.lr is not None and fused_sgd.deterministic
-        for what, on in (("mode='max'", mode == "max"), ("max_norm", max_norm is not None), ("sparse=True", bool(sparse)),
-                         ("FusedSGD(deterministic=True)", sgd16 and fused_sgd.deterministic),
-                         ("FusedRowwiseAdagrad(deterministic=True) with rounding='stochastic' (set rounding='nearest')",
-                          det16 and fused_sgd.rounding == "stochastic"),
-                         ("a gradient w.r.t. per_sample_weights",
-                          per_sample_weights is not None and per_sample_weights.requires_grad
-                          and torch.is_grad_enabled())):
-            if on:
-                raise NotImplementedError(f"{what} with a 16-bit table ({weight.dtype})")
-        if output_dtype is None:
-            output_dtype = weight.dtype
-    if output_dtype is None:
-        output_dtype = torch.float32
     # masked_indices: the caller already replaced ignored lookups (padding) by -1 -- the kernels skip them; the
     # sparse=True backward then parks their (zero) gradient rows at index 0 so the COO tensor stays valid
-    if mode not in _MODES and mode != "max":
-        raise NotImplementedError(f"mode={mode!r}: 'sum', 'mean' and 'max' are implemented")
-    if isinstance(fused_sgd, FusedRowwiseAdagrad) and fused_sgd.lr is not None:
-        # fused_sgd may also carry the row-wise Adagrad switch; its refusals come before any kernel runs
-        if mode == "max":
-            raise NotImplementedError("fused row-wise Adagrad with mode='max'")
-        fused_sgd.check(weight)
     if per_sample_weights is not None:
         if mode != "sum":
             raise NotImplementedError("embedding_bag: per_sample_weights was not None. per_sample_weights is "

@@ -519,6 +519,15 @@ class _RowwiseFn(torch.autograd.Function):
         return (None,) * 9
 
 
+_ROWWISE_SHARDED = "the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)"
+
+
+def _refuse_decay_and_clip(weight_decay, weight_decay_mode, grad_clip, grad_clip_mode) -> None:
+    """both setters of the row-wise sharded module: the values are checked, then refused where they are switched on"""
+    refuse_weight_decay(_ROWWISE_SHARDED, check_weight_decay(weight_decay, weight_decay_mode))
+    refuse_grad_clip(_ROWWISE_SHARDED, check_grad_clip(grad_clip, grad_clip_mode))
+
+
 class RowwiseShardedEmbeddingBag(nn.Module):
     """Row-wise sharded cached EmbeddingBag: local batch in ([values, offsets] of B_loc samples),
     pooled [B_loc*F, D] (or [B_loc, F, D] with hook_features) out."""
@@ -580,27 +589,20 @@ class RowwiseShardedEmbeddingBag(nn.Module):
 
     def set_fused_sgd(self, lr: Optional[float], *, weight_decay: float = 0.0, weight_decay_mode: str = "l2",
                       grad_clip: Optional[float] = None, grad_clip_mode: str = "value"):
-        refuse_weight_decay("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
-                            check_weight_decay(weight_decay, weight_decay_mode))
-        refuse_grad_clip("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
-                         check_grad_clip(grad_clip, grad_clip_mode))
+        _refuse_decay_and_clip(weight_decay, weight_decay_mode, grad_clip, grad_clip_mode)
         if isinstance(lr, torch.Tensor):
-            raise NotImplementedError("a tensor learning rate is not implemented for the row-wise sharded embedding "
-                                      "(RowwiseShardedEmbeddingBag / GraphedShardedWindow): its owner-side update "
-                                      "takes a float")
+            raise NotImplementedError(f"a tensor learning rate is not implemented for {_ROWWISE_SHARDED}: its owner-side "
+                                      "update takes a float")
         self._lr[0] = lr
 
     def set_fused_rowwise_adagrad(self, lr: Optional[float], eps: float = 1e-8, *, weight_decay: float = 0.0,
                                   weight_decay_mode: str = "l2", grad_clip: Optional[float] = None,
                                   grad_clip_mode: str = "value"):
         """Refused: the owner-side update of the row exchange is SGD only (GraphedShardedWindow replays it too)."""
-        refuse_weight_decay("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
-                            check_weight_decay(weight_decay, weight_decay_mode))
-        refuse_grad_clip("the row-wise sharded embedding (RowwiseShardedEmbeddingBag / GraphedShardedWindow)",
-                         check_grad_clip(grad_clip, grad_clip_mode))
+        _refuse_decay_and_clip(weight_decay, weight_decay_mode, grad_clip, grad_clip_mode)
         if lr is not None:
-            raise NotImplementedError("fused row-wise Adagrad is not implemented for the row-wise sharded embedding "
-                                      "(RowwiseShardedEmbeddingBag / GraphedShardedWindow); use set_fused_sgd(lr)")
+            raise NotImplementedError(f"fused row-wise Adagrad is not implemented for {_ROWWISE_SHARDED}; use "
+                                      "set_fused_sgd(lr)")
 
     def plan_window(self, ids_list: Sequence[torch.Tensor]) -> List[BatchPlan]:
         return self.exchange.plan_window(ids_list)

@@ -708,6 +708,14 @@ def _clip(args) -> dict:
     return {"grad_clip": args.embed_grad_clip, "grad_clip_mode": args.embed_grad_clip_mode}
 
 
+def _fused_update(args) -> tuple:
+    """(the name the library's check_* functions know the chosen fused update by, the table's dtype).  The updates
+    whose state travels in the row (--adam, --adagrad_elementwise) go by the Adam entries' rules."""
+    table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
+    in_row = args.adam or args.adagrad_elementwise
+    return "adam" if in_row else "rowwise_adagrad" if args.adagrad else "sgd", table
+
+
 def check_embed_weight_decay(args):
     """--embed_weight_decay: refused here, before a device is touched, with the library's own refusals"""
     from cachedembedding_amd.functional import check_weight_decay, check_weight_decay_path
@@ -717,10 +725,7 @@ def check_embed_weight_decay(args):
     if not (args.adagrad or args.adam or args.fused_sgd or args.adagrad_elementwise):
         raise ValueError("--embed_weight_decay decays the rows inside a fused update: pass --adagrad, --adam or "
                          "--fused_sgd")
-    table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
-    in_row = args.adam or args.adagrad_elementwise             # (the state travels in the row: the Adam entries' rules)
-    check_weight_decay_path("adam" if in_row else "rowwise_adagrad" if args.adagrad else "sgd", table, wd,
-                            bool(args.adagrad_deterministic))
+    check_weight_decay_path(*_fused_update(args), wd, bool(args.adagrad_deterministic))
 
 
 def check_embed_grad_clip(args):
@@ -732,10 +737,7 @@ def check_embed_grad_clip(args):
     if not (args.adagrad or args.adam or args.fused_sgd or args.adagrad_elementwise):
         raise ValueError("--embed_grad_clip clips a row's gradient inside a fused update: pass --adagrad, --adam or "
                          "--fused_sgd")
-    table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
-    in_row = args.adam or args.adagrad_elementwise
-    check_grad_clip_path("adam" if in_row else "rowwise_adagrad" if args.adagrad else "sgd", table, clip,
-                         bool(args.adagrad_deterministic))
+    check_grad_clip_path(*_fused_update(args), clip, bool(args.adagrad_deterministic))
 
 
 def check_step_accumulator(args):
@@ -746,9 +748,7 @@ def check_step_accumulator(args):
     if not (args.adagrad or args.fused_sgd):
         raise ValueError("--step_accumulator sizes the accumulator of a fused update: pass --adagrad, or --fused_sgd "
                          "with a 16-bit --table_dtype")
-    table = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.table_dtype]
-    check_accumulator("rowwise_adagrad" if args.adagrad else "sgd", table, "step", bool(args.adagrad_deterministic),
-                      args.weight_rounding)
+    check_accumulator(*_fused_update(args), "step", bool(args.adagrad_deterministic), args.weight_rounding)
 
 
 def main(argv=None):

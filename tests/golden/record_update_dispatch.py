@@ -4,8 +4,9 @@
     python tests/golden/record_update_dispatch.py --repo <checkout with its own build> --commit <its hash> [--out F]
                                                   [--only OPTIMIZER[,OPTIMIZER]]
 
-It needs no GPU (update_dispatch_cases.py says how) and only what a checkout's `functional` module has had since the
-sorted in-row fold.  The cases: the full product of base_cases(), less what embedding_bag refuses before its forward,
+It needs no GPU (update_dispatch_cases.py says how).  The case builder asks `functional.check_front` what is refused
+before the forward, so --repo must be a checkout that has it: none older than the commit that gave the refusals one
+rule set.  The cases: the full product of base_cases(), less what embedding_bag refuses before its forward,
 then the smaller sweep (variants()) over the first case that reached each entry.  --only records the cases of the named
 optimizers again (a new optimizer's, say) and keeps every other record of the file as it is; the file names the commit
 each optimizer's records come from.

@@ -70,10 +70,10 @@ class Call(NamedTuple):
 
 def build(case: Case, F) -> Optional[Call]:
     """the inputs of `case` for the `functional` module F, or None where embedding_bag refuses the combination before
-    its forward (the switches' constructors, check_accumulator, check_lr_path, check_weight_decay_path,
-    check_grad_clip_path, the 16-bit table's and the source-row keys' refusals)"""
+    its forward (the switches' constructors, then F.check_front: the front of embedding_bag itself; the source-row
+    keys' refusals)"""
     v = case.variant
-    src, w16, det = case.lookups == "src", case.table != "fp32", case.path == "sorted"
+    src, det = case.lookups == "src", case.path == "sorted"
     mode = "mean" if v == "mean" else "sum"
     if (v == "ranges" and not src) or (src and v in ("mean", "psw")):
         return None
@@ -98,12 +98,10 @@ def build(case: Case, F) -> Optional[Call]:
                 fused = F.FusedRowwiseAdagrad(lr, EPS, t["momentum"], t.get("row_of_slot"), deterministic=det,
                                               accumulator="cache" if det else case.path, **kw)
             fused.rounding, fused.seed = case.rounding, SEED
-            F.check_accumulator(case.optimizer, DTYPES[case.table], fused.accumulator, det, fused.rounding)
-            F.check_weight_decay_path(case.optimizer, DTYPES[case.table], fused.weight_decay, det, fused.lr, mode)
-            F.check_grad_clip_path(case.optimizer, DTYPES[case.table], fused.grad_clip, det, fused.lr, mode)
-            F.check_lr_path(fused.lr, det, mode)
-            if w16 and det and (case.optimizer == "sgd" or fused.rounding == "stochastic"):
-                return None                      # embedding_bag's own refusals "... with a 16-bit table"
+            # (the switch's own state would have to be on a GPU: FusedRowwiseAdagrad.check is not what is asked here)
+            fused.check = lambda weight: None
+            F.check_front(fused, torch.empty(ROWS, DIM, dtype=DTYPES[case.table]), mode, None, False, None, None)
+            del fused.check
         else:
             t["step"] = torch.zeros(1, dtype=torch.int64)
             if case.optimizer == "adagrad":
