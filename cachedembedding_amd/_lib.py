@@ -264,6 +264,9 @@ SIGNATURES = {
     "ce_host_dequantize_q4": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int]),
     "ce_bag_forward_q4": (c_int, _BAG + _ACT + _STREAM),
     "ce_bag_forward_src_keys_q4": (c_int, _TABLE + [c_int64] + _KEYS + [c_void_p] + _ACT + _STREAM),
+    # the device-side quantizer of both formats: src, src_dtype, n_rows, dim, dst, first_bad, stream
+    "ce_quantize_rows_q8": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ce_quantize_rows_q4": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "ce_cache_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "ce_cache_create": (c_int, [POINTER(CeCacheConfig), c_void_p, POINTER(c_void_p)]),
     "ce_cache_destroy": (c_int, [c_void_p]),
@@ -286,6 +289,7 @@ SIGNATURES = {
     "ce_cache_history": (c_int64, [c_void_p, c_int64, POINTER(CeCallStats), c_int64]),
     "ce_cache_lookup_slots": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "ce_cache_flush": (c_int, [c_void_p, c_void_p]),
+    "ce_cache_install_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "ce_cache_set_protect_depth": (c_int, [c_void_p, c_int32]),
     "ce_cache_set_transport": (c_int, [c_void_p, c_int32]),
     "ce_cache_get_transport": (c_int32, [c_void_p]),

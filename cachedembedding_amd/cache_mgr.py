@@ -537,6 +537,22 @@ class CachedParamMgr(torch.nn.Module):
         check(lib.ce_cache_lookup_slots(self._handle, ptr(flat), flat.numel(), ptr(slots), stream_ptr()))
         return slots.view(ids.shape)
 
+    @torch.no_grad()
+    def install_rows(self, ids: torch.Tensor, packed: torch.Tensor) -> None:
+        """Rows refreshed in place, behind the cache (ce_cache_install_rows): packed[i] -- a row in the TABLE's format,
+        [n, row width] of the table's storage dtype on the GPU -- becomes the value of id ids[i] (1-D int64, on the GPU,
+        DISTINCT) in the host table and, where the row is resident, in its cache slot.  Nothing is admitted or evicted
+        and no map, counter or statistic moves.  Returns after the rows are in place.  An id outside
+        [0, num_embeddings): IndexError, nothing written."""
+        assert ids.is_cuda and ids.dim() == 1 and ids.dtype == torch.int64 and ids.is_contiguous()
+        assert packed.is_cuda and packed.is_contiguous() and packed.dtype == self._weight.dtype \
+            and tuple(packed.shape) == (ids.numel(), self._row_width)
+        with torch.cuda.device(self.device):
+            rc = lib.ce_cache_install_rows(self._handle, ptr(ids), ids.numel(), ptr(packed), stream_ptr())
+        if rc == _lib.CE_ERR_RANGE:
+            raise IndexError(_lib.last_error())
+        check(rc)
+
     # ------------------------------------------------------------------ A.7 flush
     @torch.no_grad()
     def flush(self):

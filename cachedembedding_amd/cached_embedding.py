@@ -16,8 +16,8 @@ from . import _lib
 from .cache_mgr import CachedParamMgr, EvictionStrategy, HostTable
 from .functional import (FusedAdagrad, FusedAdam, FusedRowwiseAdagrad, FusedSGD, _at_least_0, _refuse_for_table,
                          check_accumulator, check_grad_clip, check_grad_clip_path, check_lr, check_lr_path,
-                         check_weight_decay, check_weight_decay_path, embedding_bag, refuse_grad_clip,
-                         refuse_weight_decay)
+                         check_weight_decay, check_weight_decay_path, embedding_bag, quantize_rows_device,
+                         refuse_grad_clip, refuse_weight_decay)
 
 
 def _checked_decay_and_clip(module, optimizer: str, lr, deterministic: bool, weight_decay, weight_decay_mode, grad_clip,
@@ -84,6 +84,46 @@ def _refuse_adam_layout(module, what: str, lr) -> None:
 
 def _quant_name(bits: int) -> str:
     return "q4 (torch.quint4x2)" if bits == 4 else "q8 (torch.uint8)"
+
+
+def _refuse_sharded(module, what: str) -> None:
+    """refresh_rows / current_rows are a single-process module's: one message for world_size > 1 and for a module that a
+    sharded class owns (the table-wise class names itself in its shard modules' _no_weight_decay; they have no
+    world_size of their own).  The column-wise class on ONE rank is a single-process module, as for quantized()."""
+    who = getattr(module, "_no_weight_decay", None)
+    world = getattr(module, "world_size", None)
+    if (world or 1) > 1 or (who is not None and world is None):
+        raise NotImplementedError(f"{what} on {who or type(module).__name__} ({world or 1} rank"
+                                  f"{'s' if (world or 1) != 1 else ''}): rows are refreshed in, and read from, a "
+                                  "single-process CachedEmbeddingBag")
+
+
+def _check_row_ids(what: str, ids) -> None:
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or ids.dtype != torch.int64:
+        raise ValueError(f"{what} takes ids as a 1-D torch.int64 tensor")
+
+
+def _check_refresh_rows(module, ids, rows) -> None:
+    """what refresh_rows refuses before the GPU is asked for (rows=None: refresh_from, whose rows current_rows makes)"""
+    layout = getattr(module, "fused_optimizer", None)
+    if layout is not None:
+        raise NotImplementedError(f"refresh_rows on an in-row layout (fused_optimizer={layout!r}): a row there is weights "
+                                  "plus optimizer state, and new weights alone do not make one")
+    _refuse_sharded(module, "refresh_rows")
+    _check_row_ids("refresh_rows", ids)
+    if rows is None:
+        return
+    if not isinstance(rows, torch.Tensor) or rows.dtype not in _lib.ACT_DTYPES:
+        raise NotImplementedError("refresh_rows takes rows as a torch.float32, torch.bfloat16 or torch.float16 tensor")
+    if rows.dim() != 2 or tuple(rows.shape) != (ids.numel(), module.embedding_dim):
+        raise ValueError(f"refresh_rows needs [{ids.numel()}, {module.embedding_dim}] rows for {ids.numel()} ids of a "
+                         f"table with embedding_dim={module.embedding_dim} (got {tuple(rows.shape)})")
+
+
+def _check_current_rows(module, ids) -> None:
+    _lib.refuse_quantized("current_rows", getattr(module, "table_dtype", None))
+    _refuse_sharded(module, "current_rows")
+    _check_row_ids("current_rows", ids)
 
 
 class CachedEmbeddingBag(nn.Module):
@@ -520,6 +560,76 @@ class CachedEmbeddingBag(nn.Module):
 
     def flush(self):
         self.cache_weight_mgr.flush()
+
+    # -- rows refreshed in place ------------------------------------------
+    def refresh_rows(self, ids: torch.Tensor, rows: torch.Tensor) -> None:
+        """Give the rows of `ids` new values in place, behind the cache: ids 1-D int64, DISTINCT, on any device; rows
+        [n, D] fp32 / bf16 / fp16, on any device (moved to the GPU).  On a q8 / q4 module the rows are quantized on the
+        GPU (functional.quantize_rows_device: the bytes quantize_rows gives) -- a row holding a NaN or an infinity raises
+        and NOTHING is installed --, on an fp32 / bf16 / fp16 table they are cast to the table's dtype, to nearest.
+        Every live copy of a row gets the new value: the host row and, where the row is resident, its cache slot
+        (CachedParamMgr.install_rows); the cache stays as warm as it was -- nothing is admitted, evicted or counted.
+        Returns when the rows are in place.  Optimizer state kept outside the rows -- the row-wise Adagrad accumulator
+        `cache_weight_mgr.momentum1` -- is left alone.  Duplicate ids: ValueError; an id outside [0, num_embeddings):
+        IndexError, nothing written; n == 0: nothing happens.  Refused before the GPU is asked for: an in-row layout
+        (fused_optimizer=: a row there is weights plus state), the sharded classes, a wrong shape or dtype."""
+        _check_refresh_rows(self, ids, rows)
+        if ids.numel() == 0:
+            return
+        _lib.require_gpu()
+        mgr = self.cache_weight_mgr
+        with torch.no_grad(), torch.cuda.device(mgr.device):
+            ids_d = ids.detach().to(mgr.device).contiguous()
+            rows_d = rows.detach().to(mgr.device).contiguous()
+            if torch.unique(ids_d).numel() != ids_d.numel():
+                raise ValueError("refresh_rows needs distinct ids: with duplicates a row's new value is not defined")
+            bits = _lib.quant_bits_of(self.table_dtype)
+            packed = quantize_rows_device(rows_d, bits) if bits else rows_d.to(self.table_dtype)
+            mgr.install_rows(ids_d, packed)
+
+    def current_rows(self, ids: torch.Tensor) -> torch.Tensor:
+        """The present value of the rows of `ids` (1-D int64, any device), [n, D] in the table's dtype on the GPU, WITHOUT
+        a flush: a resident row is read from its cache slot, any other from the host table (through its device mapping)
+        once the write-backs of the worker transport have landed.  The cache is left as it is.  An in-row layout gives
+        the rows' w parts.  Not on a quantized table (dequantize_rows of `.weight` rows is its reading)."""
+        _check_current_rows(self, ids)
+        _lib.require_gpu()
+        mgr = self.cache_weight_mgr
+        with torch.no_grad(), torch.cuda.device(mgr.device):
+            ids_d = ids.detach().to(mgr.device).contiguous()
+            n = ids_d.numel()
+            out = torch.empty(n, mgr._row_width, dtype=mgr._weight.dtype, device=mgr.device)
+            if n:
+                if int(((ids_d < 0) | (ids_d >= self.num_embeddings)).sum().item()):
+                    raise IndexError(f"current_rows: an id is outside [0, {self.num_embeddings})")
+                mgr.writeback_wait()
+                mgr.wait_rows()                             # (deferred rows: the maps may name a slot whose row is still
+                slots = mgr._id_to_cached_cuda_id(ids_d)    #  travelling on the library's admission stream)
+                resident = slots >= 0
+                host_rows = ids_d if mgr._idx_map is None else mgr._idx_map[ids_d].long()
+                host_rows = torch.where(resident, torch.full_like(host_rows, -1), host_rows)     # (-1: a zero row)
+                _lib.check(_lib.lib.ce_host_rows_gather(mgr._table.dev_ptr, mgr.num_embeddings, mgr._lib_dim,
+                                                        _lib.ptr(host_rows), n, _lib.ptr(out), _lib.stream_ptr()))
+                out[resident] = mgr.cuda_cached_weight.data[slots[resident]]
+        return out[:, :self.embedding_dim].contiguous() if self.fused_optimizer is not None else out
+
+    def refresh_from(self, source: "CachedEmbeddingBag", ids: torch.Tensor) -> None:
+        """refresh_rows(ids, source.current_rows(ids)): the rows of `ids` as the module `source` -- the trainer -- holds
+        them now reach this (served) module, with no flush of either.  Both modules must have the same num_embeddings,
+        embedding_dim and id -> row map; quantized() carries the map over, so a module made by source.quantized()
+        qualifies."""
+        for name in ("num_embeddings", "embedding_dim"):
+            if getattr(source, name, None) != getattr(self, name):
+                raise ValueError(f"refresh_from needs a source with the same {name} ({getattr(self, name)}; the source "
+                                 f"has {getattr(source, name, None)})")
+        _check_refresh_rows(self, ids, None)
+        _check_current_rows(source, ids)
+        _lib.require_gpu()
+        mine, theirs = self.cache_weight_mgr._idx_map, source.cache_weight_mgr._idx_map
+        if (mine is None) != (theirs is None) or (mine is not None and not torch.equal(mine, theirs.to(mine.device))):
+            raise ValueError("refresh_from needs a source with the same id -> row map (idx_map): a module made by "
+                             "source.quantized() has it")
+        self.refresh_rows(ids, source.current_rows(ids))
 
     @classmethod
     def from_pretrained(cls, embeddings: torch.Tensor, freeze: bool = True, **kwargs) -> "CachedEmbeddingBag":

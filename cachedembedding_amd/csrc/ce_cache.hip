@@ -129,6 +129,7 @@ struct ce_cache {
   bool free_zero = false;
   long long free_reset_seq = 0;          // records up to this call number say nothing about the present
   bool deferred_rows = false;  // chained admission: calls do not make their stream wait for the rows (ce_cache_wait_rows)
+  unsigned long long* install_bad = nullptr;       // ce_cache_install_rows: ids out of range (device; made by ce_cache_create)
   // The one description of a prepare_ids call in flight, filled by record_call before the call's first launch and read
   // by everything behind it (select_and_stage, the second halves).  A call issued in two halves
   // (ce_cache_prepare_ids_begin / _finish) stays `active` in between.
@@ -316,6 +317,13 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
     set_error("hipEventCreate failed");
     return CE_ERR_HIP;
   }
+  if (hipMalloc((void**)&h->install_bad, sizeof(unsigned long long)) != hipSuccess) {
+    (void)hipEventDestroy(h->ev);
+    (void)hipHostFree(ring_host);
+    delete h;
+    set_error("hipMalloc(install counter) failed");
+    return CE_ERR_HIP;
+  }
   // empty-cache state of A.1
   const int64_t N = cfg->num_embeddings, C = cfg->cuda_row_num;
   (void)hipMemsetAsync(h->ws, 0, L.stage_idx, s);
@@ -332,6 +340,7 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
   if (e != hipSuccess) {
     set_error("cache state initialisation failed: %s", hipGetErrorString(e));
     (void)hipEventDestroy(h->ev);
+    (void)hipFree(h->install_bad);
     (void)hipHostFree(ring_host);
     delete h;
     return CE_ERR_HIP;
@@ -341,6 +350,7 @@ extern "C" int ce_cache_create(const ce_cache_config_t* cfg, ce_stream_t stream,
     int rc = ensure_writeback(h);
     if (rc) {
       (void)hipEventDestroy(h->ev);
+      (void)hipFree(h->install_bad);
       (void)hipHostFree(ring_host);
       delete h;
       return rc;
@@ -367,6 +377,7 @@ extern "C" int ce_cache_destroy(ce_cache_t* h) {
   if (h->stage_host) (void)hipHostFree(h->stage_host);
   if (h->list_host) (void)hipHostFree(h->list_host);
   if (h->ctl_host) (void)hipHostFree(h->ctl_host);
+  if (h->install_bad) (void)hipFree(h->install_bad);
   delete h;
   return CE_OK;
 }
@@ -1577,6 +1588,92 @@ extern "C" int ce_cache_flush(ce_cache_t* h, ce_stream_t stream) {
                      (long long)h->seq);
   CE_LAUNCH_CHECK();
   CE_HIP_CHECK(hipEventRecord(h->ev, s));
+  return CE_OK;
+}
+
+// ce_cache_install_rows: how many ids lie outside [0, N) (the pre-pass: nothing is written if any does)
+__global__ __launch_bounds__(256) void k_install_check(const int64_t* __restrict__ ids, int64_t n, int64_t N,
+                                                       unsigned long long* n_bad) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int bad = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    bad += (unsigned long long)ids[i] >= (unsigned long long)N;
+  bad = wave_sum(bad);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(n_bad, (unsigned long long)bad);
+}
+
+// ... and the install: one lane group per id; the payload goes to the host row and, where the row is resident, to its
+// slot.  idx_map as k_lookup applies it; the maps are only read.
+template <typename VT>
+__global__ __launch_bounds__(256) void k_install_rows(const int64_t* __restrict__ ids, int64_t n,
+                                                      const int32_t* __restrict__ idx_map,
+                                                      const int32_t* __restrict__ inverted, int64_t N,
+                                                      const VT* __restrict__ rows, VT* host, VT* cache, int rowlen,
+                                                      int g_log2) {
+  const int G = 1 << g_log2;
+  const int gl = threadIdx.x & (G - 1);
+  const int64_t gstride = ((int64_t)gridDim.x * blockDim.x) >> g_log2;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> g_log2; i < n; i += gstride) {
+    const int64_t id = ids[i];
+    if ((unsigned long long)id >= (unsigned long long)N) continue;     // (the pre-pass has refused the call already)
+    const int64_t row = idx_map ? idx_map[id] : id;
+    const int32_t slot = inverted[row];
+    const VT* src = rows + i * rowlen;
+    VT* to_host = host + row * rowlen;
+    VT* to_slot = cache + (int64_t)(slot >= 0 ? slot : 0) * rowlen;
+    for (int c = gl; c < rowlen; c += G) {
+      const VT v = src[c];
+      to_host[c] = v;
+      if (slot >= 0) to_slot[c] = v;
+    }
+  }
+}
+
+extern "C" int ce_cache_install_rows(ce_cache_t* h, const int64_t* ids, int64_t n, const void* rows,
+                                     ce_stream_t stream) {
+  CE_REQUIRE(h, CE_ERR_INVALID, "null handle");
+  CE_REQUIRE(n >= 0, CE_ERR_INVALID, "negative n");
+  CE_REQUIRE(!h->pend.active, CE_ERR_INVALID, "a cache op begun with ce_cache_prepare_ids_begin has not been finished");
+  if (n == 0) return CE_OK;
+  CE_REQUIRE(ids && rows, CE_ERR_INVALID, "null ids/rows");
+  CE_REQUIRE(!h->vec || al16(rows), CE_ERR_INVALID, "rows must keep the table's 16-byte alignment");
+  hipStream_t s = (hipStream_t)stream;
+  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+  if (s != nullptr) CE_HIP_CHECK(hipStreamIsCapturing(s, &cap_st));
+  CE_REQUIRE(cap_st != hipStreamCaptureStatusActive, CE_ERR_UNSUPPORTED,
+             "ce_cache_install_rows cannot be captured in a hipGraph (it reads a count back and waits for its kernels)");
+  int rc = before_call(h);
+  if (rc) return rc;
+  if (h->wb) {
+    // queued write-backs land first: one still on its way may carry an old copy of a row installed here and would land
+    // on top of it
+    rc = h->wb->wait_out(h->wb->out_issued);
+    if (rc) return rc;
+  }
+  rc = join_rows(h, s);
+  if (rc) return rc;
+  const ce_cache_config_t& c = h->cfg;
+  CE_HIP_CHECK(hipMemsetAsync(h->install_bad, 0, sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(k_install_check, dim3(grid_for(n, 256)), dim3(256), 0, s, ids, n, c.num_embeddings, h->install_bad);
+  CE_LAUNCH_CHECK();
+  unsigned long long n_bad = 0;
+  CE_HIP_CHECK(hipMemcpyAsync(&n_bad, h->install_bad, sizeof(n_bad), hipMemcpyDeviceToHost, s));
+  CE_HIP_CHECK(hipStreamSynchronize(s));
+  CE_REQUIRE(n_bad == 0, CE_ERR_RANGE, "%llu of the %lld ids are outside [0, %lld): no row was installed", n_bad,
+             (long long)n, (long long)c.num_embeddings);
+  const int gpb = 256 >> h->g_log2;
+  for_rows(h, [&](auto r) {
+    using VT = typename decltype(r)::VT;
+    hipLaunchKernelGGL((k_install_rows<VT>), dim3(grid_for(n, gpb)), dim3(256), 0, s, ids, n, c.idx_map,
+                       c.inverted_cached_idx, c.num_embeddings, (const VT*)rows, (VT*)c.host_weight_dev,
+                       (VT*)c.cache_weight, h->rowlen, h->g_log2);
+  });
+  CE_LAUNCH_CHECK();
+  CE_HIP_CHECK(hipStreamSynchronize(s));
+  // the previous write-back job's staging buffer may hold the old payload of a row the last call evicted: the next
+  // admission must not serve such a row from it (k_admit_probe / k_unpack_chained).  Every job has landed (above), so
+  // the host table is the up-to-date copy of all of them -- the rule of ce_cache_set_transport.
+  if (h->wb) h->wb->probe_floor = h->wb->out_issued + 1;
   return CE_OK;
 }
 

@@ -298,6 +298,47 @@ def quantize_rows(t: torch.Tensor, threads: int = 0, bits: int = 8) -> torch.Ten
     return q
 
 
+_NO_BAD_ROW = 2 ** 63 - 1                                   # INT64_MAX: what ce_quantize_rows_* leaves in first_bad
+
+
+def check_quantize_rows_device(t, bits: int = 8, out=None) -> int:
+    """what quantize_rows_device refuses before the GPU is asked for; the width of a quantized row, in bytes"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in _lib.ACT_DTYPES:
+        raise NotImplementedError("quantize_rows_device takes a 2-D torch.float32, torch.bfloat16 or torch.float16 "
+                                  "tensor")
+    (_lib.check_q4_dim if _lib.check_quant_bits(bits) == 4 else _lib.check_q8_dim)(t.shape[1])
+    if t.device.type != "cuda":
+        raise ValueError("quantize_rows_device takes rows that are on the GPU (quantize_rows quantizes on the host)")
+    width = (_lib.q4_row_bytes if bits == 4 else _lib.q8_row_bytes)(t.shape[1])
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != t.device
+                            or tuple(out.shape) != (t.shape[0], width) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous [{t.shape[0]}, {width}] torch.uint8 tensor on {t.device}")
+    return width
+
+
+def quantize_rows_device(t: torch.Tensor, bits: int = 8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """quantize_rows on the GPU: [n, D] fp32 / bf16 / fp16 rows in device memory -> [n, 16 + D] uint8 q8 rows (bits=4:
+    [n, 16 + D / 2] q4 rows) in device memory, byte for byte the rows quantize_rows gives (ce_quantize_rows_q8 / _q4).
+    A row holding a NaN or an infinity raises what quantize_rows raises, naming the same row (the first one); the other
+    rows of `out` are written by then.  Reads one int64 back, so it waits for the kernel."""
+    width = check_quantize_rows_device(t, bits, out)
+    src = t.detach().contiguous()
+    n, dim = src.shape
+    if out is None:
+        out = torch.empty(n, width, dtype=torch.uint8, device=src.device)
+    if n == 0:
+        return out
+    first_bad = torch.empty(1, dtype=torch.int64, device=src.device)
+    quantize = lib.ce_quantize_rows_q4 if bits == 4 else lib.ce_quantize_rows_q8
+    with torch.cuda.device(src.device):
+        check(quantize(ptr(src), _lib.ACT_DTYPES[src.dtype], n, dim, ptr(out), ptr(first_bad), stream_ptr()))
+        bad = int(first_bad.item())
+    if bad != _NO_BAD_ROW:
+        raise _lib.CeError(_lib.CE_ERR_INVALID, f"row {bad} holds a NaN or an infinity (or its range overflows fp32): "
+                                                "it cannot be quantized")
+    return out
+
+
 def dequantize_rows(q: torch.Tensor, dim: Optional[int] = None, threads: int = 0, bits: int = 8) -> torch.Tensor:
     """[N, 16 + dim] uint8 q8 rows -> [N, dim] fp32 on the CPU: fmaf(code, scale, bias), the value the kernels use.
     bits=4: [N, 16 + dim / 2] uint8 q4 rows (a uint8 tensor's width cannot tell the two apart)."""

@@ -60,6 +60,14 @@ def parse_args(argv=None):
                         "table is quantized to 8-bit rows (CachedEmbeddingBag.quantized()), the test set is evaluated "
                         "again through it, and test_auroc_q8 / test_accuracy_q8 / the two table sizes are printed as "
                         "one JSON line (and merged into --json_out)")
+    p.add_argument("--eval_q8_refresh", action="store_true",
+                   help="with --eval_acc, one process, no --use_tablewise: a served 8-bit copy of the table is built ONCE, "
+                        "before training (CachedEmbeddingBag.quantized()); the training loop marks the rows it looks up "
+                        "in a device bitmap, and every evaluation first brings the served copy up to date with "
+                        "served.refresh_from(trainer, marked ids) -- no flush, no rebuild, the served cache stays warm -- "
+                        "and evaluates through it too: val_aurocs_q8_refresh, test_auroc_q8_refresh, refreshed_rows_q8")
+    p.add_argument("--eval_q4_refresh", action="store_true",
+                   help="like --eval_q8_refresh (and beside it, if both are given) with the 4-bit table")
     p.add_argument("--eval_q4", action="store_true",
                    help="like --eval_q8 (and beside it, if both are given) with the 4-bit row-wise quantized table "
                         "(CachedEmbeddingBag.quantized(bits=4)): test_auroc_q4 / test_accuracy_q4 / table_bytes_q4")
@@ -566,9 +574,21 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None, lr_
     steady = {"t0": None, "done0": 0}
     model.train()
     start = time.time()
+    touched = getattr(train, "touched", None)
+
+    def ids_of(window):
+        """the window's id tensors, as every form of the cache op below is handed them; --eval_q8_refresh /
+        --eval_q4_refresh: they are also marked in the bitmap of the rows looked up since the last evaluation (a row is
+        updated only if it was looked up, so these are the rows a served copy has to be given again)"""
+        ids = [s[0] for s in window[1]]
+        if touched is not None:
+            for t in ids:
+                touched[t.reshape(-1).long()] = True
+        return ids
+
     cur = _window(data_iter, P, device, args, rank, world)
     if cur is not None and args.overlap_cache_op:
-        win.submit([s[0] for s in cur[1]])
+        win.submit(ids_of(cur))
     while cur is not None:
         dense_l, sparse_l, labels_l = cur
         nxt = None
@@ -576,9 +596,9 @@ def _train(model, optimizer, loader, args, device, rank, world, record=None, lr_
             slots = win.collect()
             nxt = _window(data_iter, P, device, args, rank, world)
             if nxt is not None:
-                win.submit([s[0] for s in nxt[1]])
+                win.submit(ids_of(nxt))
         else:
-            slots = win.prepare([s[0] for s in sparse_l])
+            slots = win.prepare(ids_of(cur))
         for k in range(len(dense_l)):
             sparse_l[k][0] = slots[k]
             keys_k = win.keys[k] if layout is not None else None
@@ -785,6 +805,13 @@ def main(argv=None):
         if world > 1 or args.use_tablewise:
             raise NotImplementedError("--eval_q4 is implemented for one process without --use_tablewise (the sharded "
                                       "classes do not take a q4 table)")
+    for flag, on in (("--eval_q8_refresh", args.eval_q8_refresh), ("--eval_q4_refresh", args.eval_q4_refresh)):
+        if on and not args.eval_acc:
+            raise ValueError(f"{flag} needs --eval_acc: it evaluates the validation and the test set once more, through "
+                             "the served quantized table")
+        if on and (world > 1 or args.use_tablewise):
+            raise NotImplementedError(f"{flag} is implemented for one process without --use_tablewise (rows are "
+                                      "refreshed in, and read from, a single-process CachedEmbeddingBag)")
     if args.adam_partial_rowwise and not args.adam:
         raise ValueError("--adam_partial_rowwise chooses the layout of --adam: pass --adam with it")
     if args.adagrad_elementwise:
@@ -885,6 +912,29 @@ def main(argv=None):
     results = {"val_aurocs": [], "val_accuracies": [], "test_auroc": None, "test_accuracy": None}   # TrainValTestResults
     main.results, main.model, main.val_loader, main.test_loader = results, model, val_loader, test_loader
     lr_change = LrChange(args, len(loader) * args.epochs, optimizer, embed, lr_tensor) if args.change_lr else None
+    # --eval_q8_refresh / --eval_q4_refresh: the served copies are built once, here, from the untrained table; from then
+    # on they only ever receive the rows the training loop marked (train.touched, one bool per id, on the device)
+    served = {bits: embed.quantized(bits=bits)
+              for bits, on in ((8, args.eval_q8_refresh), (4, args.eval_q4_refresh)) if on}
+    train.touched = torch.zeros(embed.num_embeddings, dtype=torch.bool, device=device) if served else None
+    main.served = served
+
+    def evaluate_served(loader_, stage, into):
+        """bring every served copy up to date with the rows marked since the last evaluation, then evaluate through it"""
+        ids = torch.nonzero(train.touched).view(-1)
+        train.touched.zero_()
+        sparse = model.sparse_modules
+        for bits, module in served.items():
+            module.refresh_from(embed, ids)
+            sparse.embed = module
+            try:
+                auroc, acc = _evaluate(model, loader_, f"{stage} (q{bits} table, refreshed)", args, device, rank, world)
+            finally:
+                sparse.embed = embed
+            into(bits, auroc, acc, int(ids.numel()))
+
+    for bits in served:
+        results.update({f"val_aurocs_q{bits}_refresh": [], f"refreshed_rows_q{bits}": []})
     for epoch in range(args.epochs):
         rec = []
         done, elapsed, loss = train(model, optimizer, loader, args, device, rank, world, record=rec,
@@ -893,6 +943,9 @@ def main(argv=None):
             auroc, acc = _evaluate(model, val_loader, "val", args, device, rank, world)
             results["val_aurocs"].append(auroc)
             results["val_accuracies"].append(acc)
+            if served:
+                evaluate_served(val_loader, "val", lambda bits, auroc_q, _acc, n: (
+                    results[f"val_aurocs_q{bits}_refresh"].append(auroc_q), results[f"refreshed_rows_q{bits}"].append(n)))
         if rank == 0:
             lookups = done * args.batch_size * len(sizes)
             q = max(1, len(rec) // 4)
@@ -937,6 +990,13 @@ def main(argv=None):
                               "val_batches": _evaluate.batches} if args.eval_acc else None)}, indent=1))
     if args.eval_acc:                                            # recsys/dlrm_main.py:365-369
         results["test_auroc"], results["test_accuracy"] = _evaluate(model, test_loader, "test", args, device, rank, world)
+        if served:
+            import json
+            evaluate_served(test_loader, "test", lambda bits, auroc_q, acc_q, n: (
+                results.update({f"test_auroc_q{bits}_refresh": auroc_q, f"test_accuracy_q{bits}_refresh": acc_q}),
+                results[f"refreshed_rows_q{bits}"].append(n)))
+            print(json.dumps({"script": "examples/dlrm_main.py", "test_auroc": results["test_auroc"]} | {
+                k: v for k, v in results.items() if k.endswith("_refresh") or k.startswith("refreshed_rows")}))
     for bits in [b for b, on in ((8, args.eval_q8), (4, args.eval_q4)) if on]:
         # serve what was trained at a quarter (q8) or a sixth (q4, D = 128) of the memory: the same dense weights over
         # the row-wise quantized copy of the table (a new pinned table and a cache of its own; the trained module is

@@ -998,7 +998,8 @@ int ce_bag_backward_adagrad_sorted(float* weight, int64_t num_rows, int32_t dim,
                                    void* workspace, size_t workspace_bytes, ce_stream_t stream);
 
 /* 8-bit row-wise quantized table, `q8` (additions to API 6): evaluation and serving only -- there is NO backward and
- * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and never written by a kernel.
+ * no update; a q8 table is built from trained rows (ce_host_quantize_q8) and written only by
+ * ce_cache_install_rows.
  * A row of `dim` elements is 16 + dim bytes:
  *   bytes 0..3 scale (fp32) | 4..7 bias (fp32) | 8..15 zero | 16..16+dim-1: dim codes, uint8
  * dim % 16 == 0, 16 <= dim <= 1024 and the table 16-byte aligned, so every row is a whole number of 16-byte units
@@ -1028,7 +1029,7 @@ int ce_bag_forward_src_keys_q8(const void* weight, int64_t num_rows, int32_t dim
                                const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
 
 /* 4-bit row-wise quantized table, `q4` (additions to API 6): q8 with 16 levels -- evaluation and serving only, no
- * backward, no update, never written by a kernel.  A row of `dim` elements is 16 + dim / 2 bytes:
+ * backward, no update, written only by ce_cache_install_rows.  A row of `dim` elements is 16 + dim / 2 bytes:
  *   bytes 0..3 scale (fp32) | 4..7 bias (fp32) | 8..15 zero | 16..16+dim/2-1: dim codes, two per byte
  * Element i is in code byte i / 2: the low nibble for even i, the high nibble for odd i.  The four elements
  * 4ch .. 4ch+3 of a lane's chunk ch are therefore one little-endian uint16 at code offset 2ch, nibble k of it is
@@ -1053,6 +1054,23 @@ int ce_bag_forward_q4(const void* weight, int64_t num_rows, int32_t dim,
                       int32_t mode, int64_t hook_features, void* out, int32_t act_dtype, ce_stream_t stream);
 int ce_bag_forward_src_keys_q4(const void* weight, int64_t num_rows, int32_t dim, int64_t nnz,
                                const uint64_t* src_keys, void* out, int32_t act_dtype, ce_stream_t stream);
+
+/* Device-side quantizer (additions to API 6): the rows ce_host_quantize_q8 / _q4 write, byte for byte -- scale, bias,
+ * the 8 zero bytes and the codes (both nibbles of every q4 byte) --, from rows that are in device memory already.
+ * src: [n_rows, dim] fp32, bf16 or fp16 (src_dtype: CE_ACT_*), device memory, 16-byte aligned (8 for a 16-bit source);
+ * dst: [n_rows, ce_q8_row_bytes(dim)] (ce_q4_row_bytes(dim)), device memory, 16-byte aligned.  first_bad: one device
+ * int64 -- the entry sets it to INT64_MAX on `stream`, the kernel lowers it (an ordinary global atomic minimum) to the
+ * smallest index of a row that holds a NaN or an infinity or whose range overflows fp32; such a row's destination is
+ * unspecified, every other row is written.  Asynchronous on `stream`; the entry does not read first_bad back.
+ * Refused before any launch, as the host entries refuse it: an unknown src_dtype, a negative n_rows, a null pointer, a
+ * misaligned one (CE_ERR_INVALID), the dim rule (CE_ERR_UNSUPPORTED); n_rows == 0 is CE_OK.
+ * The arithmetic is the quantizer's above, operation by operation: bias is the FIRST element equal to the minimum, in
+ * index order (the sign of a zero minimum follows it); both divisions are correctly rounded fp32, subnormal operands
+ * and quotients included; rintf rounds the ties to even. */
+int ce_quantize_rows_q8(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, void* dst, int64_t* first_bad,
+                        ce_stream_t stream);
+int ce_quantize_rows_q4(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, void* dst, int64_t* first_bad,
+                        ce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * CachedParamMgr [A.1-A.6]. Device state arrays are owned by the caller (so the Python
@@ -1212,6 +1230,20 @@ int ce_cache_lookup_slots(ce_cache_t* h, const int64_t* ids, int64_t n, int64_t*
 /* flush() [A.7]: every resident row is written back to the host table, maps emptied,
  * freq_cnter reset.  Asynchronous on `stream`. */
 int ce_cache_flush(ce_cache_t* h, ce_stream_t stream);
+
+/* Refresh rows in place, behind the cache (addition to API 6): rows[i] -- 4 * embedding_dim bytes in the TABLE's row
+ * format, which this entry never interprets (fp32, 16-bit, q8 and q4 tables alike) -- becomes the value of row
+ * idx_map[ids[i]] in EVERY live copy: the host row (through the table's device mapping) and, where the row is
+ * resident, its cache slot.  ids (id space) and rows are device memory; rows keeps the table's alignment.  ids must be
+ * distinct: with duplicates a row's copies are unspecified.
+ * It opens the way ce_cache_flush opens: a call begun with ce_cache_prepare_ids_begin is CE_ERR_INVALID; with the
+ * worker transport every queued write-back lands first (one still on its way may carry an old copy of a row being
+ * installed); `stream` waits for the rows of the chained admission.  Behind it the previous write-back job's staging
+ * buffer is no longer probed by the next admission (it may hold the old payload of a row evicted by the last call).
+ * An id outside [0, num_embeddings): CE_ERR_RANGE, nothing is written.  Admits nothing, evicts nothing, and touches no
+ * map, counter, stamp, statistic or history record.  SYNCHRONOUS: it returns after its kernels have finished, so the
+ * host table can be read straight away.  Refused inside a stream capture (CE_ERR_UNSUPPORTED). */
+int ce_cache_install_rows(ce_cache_t* h, const int64_t* ids, int64_t n, const void* rows, ce_stream_t stream);
 
 int ce_cache_set_protect_depth(ce_cache_t* h, int32_t depth);
 /* Switching away from / to CE_TRANSPORT_WORKER blocks until the queued write-backs have landed. */
